@@ -337,6 +337,25 @@ int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t
                             int64_t npts, const float* normals, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum,
                             uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream);
 
+/* ---- point normals (new: the reference reads them from a `--input_normals` file, src/compress_octree.py:142-144) ----------------
+ * The normals the D2 metrics need (pcc_d12_threshold_stats, utils/pc_metric.py) estimated from the cloud itself.  Definition:
+ *   - pts: (npts,3) int32, every coordinate in [0, 2^21) (the codec's voxelised clouds; other values give unspecified normals,
+ *     never an access outside the buffers); duplicates allowed; 1 <= npts < 2^31, 3 <= k <= 64;
+ *   - neighbourhood of point i: the k_eff = min(k, npts) points j with the smallest (|p_j - p_i|^2, j), exact integers,
+ *     lexicographic (i itself is a candidate like any other);
+ *   - M = k_eff * sum q q^T - (sum q)(sum q)^T over the neighbours, q = p_j - p_i, exact in int64;
+ *   - normal = unit eigenvector of the smallest eigenvalue of M, solved in double (cyclic Jacobi, fixed sweep count), stored
+ *     as float32; M == 0 (all neighbours coincide) gives exactly (0, 0, 1);
+ *   - otherwise the sign makes n . (p_i - o) >= 0, o = viewpoint or (viewpoint NULL) the centroid = exact int64 sums / npts;
+ *     a product of exactly 0 makes the first non-zero component of n positive.
+ * Arguments (device memory, on `stream`): viewpoint 3 doubles or NULL; normals (npts,3) float32; knn NULL or (npts,k) int32:
+ * row i = the neighbours of point i in the order above, columns >= k_eff hold -1; workspace: pcc_normals_workspace_bytes(npts,k)
+ * bytes.  No host synchronisation, no floating-point atomics: results are bit-reproducible.  pcc_normals_workspace_bytes
+ * returns 0 for an npts outside [1, 2^31).                                                                                     */
+size_t pcc_normals_workspace_bytes(int64_t npts, int32_t k);
+int pcc_estimate_normals(pcc_ctx* ctx, const int32_t* pts, int64_t npts, int32_t k, const double* viewpoint, float* normals,
+                         int32_t* knn, void* workspace, void* stream);
+
 /* ---- focal loss (src/utils/focal_loss.py:5-12) ------------------------------------------
  * Deterministic two-stage reduction (wavefront DPP/shuffle tree, fixed block order); result is a
  * single float32 written to out[0] (device).  `scratch` must hold pcc_focal_scratch_floats().   */

@@ -27,7 +27,7 @@ EXPORTS = [
     'pcc_network_workspace_bytes', 'pcc_network_out_dims', 'pcc_network_forward', 'pcc_network_forward_analysis',
     'pcc_network_forward_synthesis', 'pcc_network_forward_hyper_a', 'pcc_network_forward_hyper_s',
     'pcc_codec_workspace_bytes', 'pcc_codec_encode', 'pcc_codec_decode_hyper', 'pcc_codec_decode_main',
-    'pcc_profile_select', 'pcc_profile_read',
+    'pcc_profile_select', 'pcc_profile_read', 'pcc_normals_workspace_bytes', 'pcc_estimate_normals',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -115,6 +115,9 @@ def lib():
     L.pcc_d12_search_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_int64]
     L.pcc_d12_search_workspace_bytes.restype = sz
     L.pcc_d12_threshold_stats.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pcc_normals_workspace_bytes.argtypes = [C.c_int64, i32]
+    L.pcc_normals_workspace_bytes.restype = sz
+    L.pcc_estimate_normals.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

@@ -3,11 +3,13 @@
   python -m pcc_geo_cnn_v2_amd.compress_octree --input_files a.ply --output_files a.ply.bin \\
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
+         [--estimate_normals [--normals_k 16]]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
 `python -m torch.distributed.run --nproc-per-node N` the blocks are sharded over N GPUs and rank 0 writes
-the files.  `--num_filters` is accepted and ignored, like in the reference.
+the files.  `--num_filters` is accepted and ignored, like in the reference.  `--estimate_normals` is new: the
+normals of the D2 metrics come from the GPU (include/pcc_geo.h "point normals") instead of an `--input_normals` file.
 """
 import argparse
 import json
@@ -49,7 +51,10 @@ def _plan(args):
         raise AssertionError(f'unknown data_format {args.data_format}')
     if args.model_config not in ModelConfigType.keys():
         raise AssertionError(f'unknown model_config {args.model_config}: one of {list(ModelConfigType.keys())}')
-    with_normals = args.input_normals is not None
+    estimate = getattr(args, 'estimate_normals', False)
+    if estimate and args.input_normals is not None:
+        raise AssertionError('--estimate_normals and --input_normals are mutually exclusive')
+    with_normals = args.input_normals is not None or estimate
     # the reference's own default '--opt_metrics d1_psnr' is not in avail_opt_metrics, so its CLI asserts unless the flag is
     # given (compress_octree.py:37,154).  psnr is monotone in mse (pc_metric.py:55), so '<g>_psnr' is taken as '<g>_mse' here
     metrics = []
@@ -64,7 +69,7 @@ def _plan(args):
     n_in = len(args.input_files)
     if len(args.output_files) != per_cloud * n_in:
         raise AssertionError(f'{n_in} input file(s) x {per_cloud} metric(s) need {per_cloud * n_in} output files, got {len(args.output_files)}')
-    if per_cloud > 1 and len(args.input_normals or ()) * per_cloud != len(args.output_files):
+    if per_cloud > 1 and not estimate and len(args.input_normals or ()) * per_cloud != len(args.output_files):
         raise AssertionError('several optimisation metrics need one normals file per input file')
     if args.dec_files is not None and len(args.dec_files) != per_cloud * n_in:
         raise AssertionError(f'--dec_files: expected {per_cloud * n_in} paths, got {len(args.dec_files)}')
@@ -150,7 +155,11 @@ def compress(args):
     T.mark('context', sess.device)
 
     geometry = pc_io.load_points(args.input_files, batch_size=args.read_batch_size)
-    if with_normals:
+    if getattr(args, 'estimate_normals', False):
+        # once per cloud, before partitioning; every rank of a sharded run estimates from its own copy (deterministic: same bits)
+        geometry = [np.hstack((xyz, ops.estimate_normals(sess, xyz, k=args.normals_k))) for xyz in geometry]
+        T.mark('estimate_normals', sess.device)
+    elif with_normals:
         geometry = [np.hstack((xyz, pc_io.load_normals(path))) for xyz, path in zip(geometry, args.input_normals)]
     T.mark('ply_read')
     box, block_shape = _block_grid(args.resolution, args.octree_level, args.data_format)
@@ -200,6 +209,10 @@ def build_parser():
                         help='Output files. If input normals are provided, specify two output files per input file.')
     parser.add_argument('--input_normals', nargs='+',
                         help='Input normals. If provided, two output paths are needed for each input file for D1 and D2 optimization.')
+    parser.add_argument('--estimate_normals', default=False, action='store_true',
+                        help='Estimate the normals of each input cloud on the GPU instead of reading --input_normals (new; enables the '
+                             'd2_* metrics like a normals file does).')
+    parser.add_argument('--normals_k', type=int, default=16, help='Neighbours per point of --estimate_normals (3..64).')
     parser.add_argument('--dec_files', nargs='*',
                         help='Decoded files. Allows compression/decompression in a single execution.')
     parser.add_argument('--checkpoint_dir', help='Directory where to save/load model checkpoints.', required=True)

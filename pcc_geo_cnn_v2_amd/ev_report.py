@@ -8,7 +8,7 @@ utils/pc_metric.compute_metrics, the module the encoder itself uses for its `.en
 ev_experiment.py:158-162) carries over.
 
     python -m pcc_geo_cnn_v2_amd.ev_report --input_pc a.ply --decoded_pc a.ply.bin.ply --enc_pc a.ply.bin \\
-        --resolution 1024 [--input_norm a_n.ply] --output report_d1.json
+        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] --output report_d1.json
 """
 import argparse
 import json
@@ -23,10 +23,15 @@ from .utils.pc_metric import compute_metrics
 logger = logging.getLogger(__name__)
 
 
-def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None):
+def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, estimate_normals=False, normals_k=16):
+    if input_norm and estimate_normals:
+        raise AssertionError('--estimate_normals and --input_norm are mutually exclusive')
     p1 = pc_io.load_pc(input_pc)
     p2 = pc_io.load_pc(decoded_pc)
     n1 = pc_io.load_normals(input_norm) if input_norm else None
+    if estimate_normals:
+        from . import ops
+        n1 = ops.estimate_normals(ops.get_context(), p1, k=normals_k)
     if n1 is not None:
         assert len(n1) == len(p1), 'normals file must have one normal per input point'
     m = compute_metrics(np.asarray(p1, np.float64)[:, :3], np.asarray(p2, np.float64)[:, :3], resolution - 1, p1_n=n1)
@@ -45,10 +50,15 @@ def main():
     p.add_argument('--decoded_pc', required=True, help='Path to the decoded point cloud')
     p.add_argument('--enc_pc', required=True, help='Path to the compressed file (its size gives the rate)')
     p.add_argument('--input_norm', default=None, help='Path to input point cloud normals (enables D2)')
+    p.add_argument('--estimate_normals', default=False, action='store_true',
+                   help='Estimate the input normals on the GPU (enables D2 without --input_norm; new)')
+    p.add_argument('--normals_k', type=int, default=16, help='Neighbours per point of --estimate_normals (3..64)')
     p.add_argument('--resolution', type=int, required=True, help='Voxel grid resolution of the input (peak = resolution - 1)')
     p.add_argument('--output', required=True, help='Report JSON path')
     args = p.parse_args()
-    data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm)
+    if args.input_norm and args.estimate_normals:
+        p.error('--estimate_normals and --input_norm are mutually exclusive')
+    data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm, args.estimate_normals, args.normals_k)
     with open(args.output, 'w') as f:
         json.dump(data, f, sort_keys=True, indent=4)
     enc_metric = args.enc_pc + '.enc.metric.json'

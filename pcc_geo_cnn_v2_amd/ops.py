@@ -626,6 +626,67 @@ def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, cl
     return s_ab.cpu().numpy(), s_ba, n_b, tcount.cpu().numpy(), d2_ab.cpu().numpy(), d2_ba.cpu().numpy()
 
 
+NORMALS_COORD_LIMIT = 1 << 21        # include/pcc_geo.h "point normals": coordinates are integers in [0, 2^21)
+
+
+def _voxel_points(points):
+    """The input contract of estimate_normals, checked before anything reaches the GPU: an (N,3) cloud of integer coordinates in
+    [0, 2^21), 1 <= N < 2^31.  Returns an int32 array (numpy input) or an int32 contiguous device tensor (torch input)."""
+    if isinstance(points, torch.Tensor):
+        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
+            raise L.PccError(f'estimate_normals: points must be (N, 3) with N >= 1, got {tuple(points.shape)}')
+        if points.is_floating_point():
+            if not bool(torch.isfinite(points).all()) or not bool((points == torch.round(points)).all()):
+                raise L.PccError('estimate_normals: coordinates must be integers (voxelised cloud); got non-integer values')
+        elif points.dtype == torch.bool or points.is_complex():
+            raise L.PccError(f'estimate_normals: unsupported dtype {points.dtype}')
+        if bool((points < 0).any()) or bool((points >= NORMALS_COORD_LIMIT).any()):
+            raise L.PccError(f'estimate_normals: coordinates must lie in [0, {NORMALS_COORD_LIMIT})')
+        return points.to(torch.int32).contiguous()
+    a = np.asarray(points)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] == 0:
+        raise L.PccError(f'estimate_normals: points must be (N, 3) with N >= 1, got {a.shape}')
+    if a.shape[0] >= 1 << 31:
+        raise L.PccError('estimate_normals: at most 2^31 - 1 points per call')
+    if a.dtype.kind == 'f':
+        if not np.isfinite(a).all() or not np.array_equal(a, np.round(a)):
+            raise L.PccError('estimate_normals: coordinates must be integers (voxelised cloud); got non-integer values')
+    elif a.dtype.kind not in 'iu':
+        raise L.PccError(f'estimate_normals: unsupported dtype {a.dtype}')
+    if (a < 0).any() or (a >= NORMALS_COORD_LIMIT).any():
+        raise L.PccError(f'estimate_normals: coordinates must lie in [0, {NORMALS_COORD_LIMIT})')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def estimate_normals(ctx, points, k=16, viewpoint=None, return_knn=False):
+    """Point normals of a voxelised cloud (include/pcc_geo.h "point normals"): (N,3) float32 numpy array, oriented away from
+    `viewpoint` (3 numbers) or, by default, from the cloud's centroid.  points: (N,3) numpy array or device tensor of integer
+    coordinates in [0, 2^21).  return_knn=True also returns the (N, min(k, N)) int32 neighbour rows (nearest first, ties by
+    row index).  Deterministic: the same cloud gives the same bits on every call."""
+    k = int(k)
+    if not 3 <= k <= 64:
+        raise L.PccError(f'estimate_normals: k = {k} outside [3, 64]')
+    vp = None
+    if viewpoint is not None:
+        vp = np.asarray(viewpoint, np.float64).reshape(-1)
+        if vp.shape != (3,) or not np.isfinite(vp).all():
+            raise L.PccError(f'estimate_normals: viewpoint must be 3 finite numbers, got {viewpoint!r}')
+    pts = _voxel_points(points)
+    dev = ctx.device
+    pts_d = pts.to(dev) if isinstance(pts, torch.Tensor) else torch.from_numpy(pts).to(dev)
+    n = pts_d.shape[0]
+    vp_d = None if vp is None else torch.from_numpy(vp).to(dev)
+    normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    knn = torch.empty((n, k), dtype=torch.int32, device=dev) if return_knn else None
+    ws = torch.empty((L.lib().pcc_normals_workspace_bytes(n, k),), dtype=torch.uint8, device=dev)
+    L.check(L.lib().pcc_estimate_normals(ctx.handle, _ptr(pts_d), n, k, _ptr(vp_d), _ptr(normals), _ptr(knn), _ptr(ws), ctx.stream),
+            'pcc_estimate_normals')
+    out = normals.cpu().numpy()
+    if return_knn:
+        return out, knn[:, :min(k, n)].cpu().numpy()
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------

@@ -32,6 +32,14 @@ def validate_opt_metrics(opt_metrics, with_normals=False):
     assert with_normals or not needs_normals, f'{needs_normals[0] if needs_normals else None} not available without normals'
 
 
+def estimate_normals(ctx, points, k=16, viewpoint=None, return_knn=False):
+    """Normals for the D2 terms when the cloud comes without a normals file: ops.estimate_normals (HIP, include/pcc_geo.h
+    "point normals"), re-exported beside the metric code that consumes them.  Oriented away from the centroid (or `viewpoint`),
+    so that transfer_normals' averages do not cancel."""
+    from .. import ops
+    return ops.estimate_normals(ctx, points, k=k, viewpoint=viewpoint, return_knn=return_knn)
+
+
 def psnr(mse, max_energy):
     with np.errstate(divide='ignore'):
         return 10 * np.log10(max_energy / mse)
