@@ -356,6 +356,33 @@ size_t pcc_normals_workspace_bytes(int64_t npts, int32_t k);
 int pcc_estimate_normals(pcc_ctx* ctx, const int32_t* pts, int64_t npts, int32_t k, const double* viewpoint, float* normals,
                          int32_t* knn, void* workspace, void* stream);
 
+/* ---- cloud metrics (new: the whole-cloud D1 / D2 of src/utils/pc_metric.py:76-138 and pc_error's --hausdorff terms) -----------
+ * Nearest neighbours across two voxelised clouds and the distortion tally of utils/pc_metric.pair_tally on the GPU.  Definition:
+ *   - points: (n,3) int32, every coordinate in [0, 2^21) (other values give unspecified results, never an access outside the
+ *     buffers); duplicates allowed; 1 <= n < 2^31;
+ *   - nearest indexed point of a query q: the row j with the smallest (|p_j - q|^2, j), exact integers, lexicographic -- ties go
+ *     to the LOWEST row (the point-normals rule at k = 1; scipy's cKDTree may pick another of several equidistant points);
+ *   - tally (A = original, B = decoded, to_b[i] / to_a[j] the nearest rows across): float64[9] = N_B, D1_AB, D1_BA, D2_AB, D2_BA,
+ *     H1_AB, H1_BA, H2_AB, H2_BA.  D1_* = sums of the squared distances, exact in 128-bit integers and rounded once; H1_* = their
+ *     maxima.  With a_normals ((na,3) float64, NULL: the D2 / H2 slots are 0): the normal of decoded point j is the mean of
+ *     a_normals[i] over {i : to_b[i] == j}, summed in float64 in increasing i and divided by the count, or a_normals[to_a[j]] when
+ *     that set is empty (utils/pc_metric.transfer_normals); per point, v = ((g.x*n.x + g.y*n.y) + g.z*n.z)^2 in float64, every
+ *     operation rounded (no contraction), g = a_i - b_{to_b[i]} with the decoded point's normal (A->B) or g = b_j - a_{to_a[j]}
+ *     with a_normals[to_a[j]] (B->A); D2_* = sums of v in a fixed order that depends on the sizes only, H2_* = maxima of v.
+ * Index: pcc_cloud_index_bytes(n) bytes of device memory, written by pcc_cloud_index_build; it keeps a copy of the points and
+ * stays valid (and reusable by any number of queries) while the buffer lives.  pcc_cloud_nearest writes nn[i] (int32) and
+ * sqdist[i] (int64) for each of the nq query points (either output may be NULL).  pcc_cloud_distortion takes both indices (with
+ * their sizes), writes the 9 slots to `tally` (device) and, when non-NULL, to_b (na int32) and to_a (nb int32); workspace:
+ * pcc_cloud_distortion_workspace_bytes(na, nb) bytes.  No host synchronisation; floating-point values are summed in a fixed
+ * order, so the same inputs give the same bits on every call.  The *_bytes functions return 0 for a size outside [1, 2^31).   */
+size_t pcc_cloud_index_bytes(int64_t npts);
+int pcc_cloud_index_build(pcc_ctx* ctx, const int32_t* pts, int64_t npts, void* index, void* stream);
+int pcc_cloud_nearest(pcc_ctx* ctx, const void* index, int64_t npts, const int32_t* queries, int64_t nq, int32_t* nn, int64_t* sqdist,
+                      void* stream);
+size_t pcc_cloud_distortion_workspace_bytes(int64_t na, int64_t nb);
+int pcc_cloud_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const void* index_b, int64_t nb, const double* a_normals,
+                         double* tally, int32_t* to_b, int32_t* to_a, void* workspace, void* stream);
+
 /* ---- focal loss (src/utils/focal_loss.py:5-12) ------------------------------------------
  * Deterministic two-stage reduction (wavefront DPP/shuffle tree, fixed block order); result is a
  * single float32 written to out[0] (device).  `scratch` must hold pcc_focal_scratch_floats().   */

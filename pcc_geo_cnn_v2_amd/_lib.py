@@ -28,6 +28,7 @@ EXPORTS = [
     'pcc_network_forward_synthesis', 'pcc_network_forward_hyper_a', 'pcc_network_forward_hyper_s',
     'pcc_codec_workspace_bytes', 'pcc_codec_encode', 'pcc_codec_decode_hyper', 'pcc_codec_decode_main',
     'pcc_profile_select', 'pcc_profile_read', 'pcc_normals_workspace_bytes', 'pcc_estimate_normals',
+    'pcc_cloud_index_bytes', 'pcc_cloud_index_build', 'pcc_cloud_nearest', 'pcc_cloud_distortion_workspace_bytes', 'pcc_cloud_distortion',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -118,6 +119,13 @@ def lib():
     L.pcc_normals_workspace_bytes.argtypes = [C.c_int64, i32]
     L.pcc_normals_workspace_bytes.restype = sz
     L.pcc_estimate_normals.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp]
+    L.pcc_cloud_index_bytes.argtypes = [C.c_int64]
+    L.pcc_cloud_index_bytes.restype = sz
+    L.pcc_cloud_index_build.argtypes = [vp, vp, C.c_int64, vp, vp]
+    L.pcc_cloud_nearest.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
+    L.pcc_cloud_distortion_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    L.pcc_cloud_distortion_workspace_bytes.restype = sz
+    L.pcc_cloud_distortion.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

@@ -3,13 +3,15 @@
   python -m pcc_geo_cnn_v2_amd.compress_octree --input_files a.ply --output_files a.ply.bin \\
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
-         [--estimate_normals [--normals_k 16]]
+         [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
 `python -m torch.distributed.run --nproc-per-node N` the blocks are sharded over N GPUs and rank 0 writes
 the files.  `--num_filters` is accepted and ignored, like in the reference.  `--estimate_normals` is new: the
 normals of the D2 metrics come from the GPU (include/pcc_geo.h "point normals") instead of an `--input_normals` file.
+`--metrics_device gpu` is new: the whole-cloud metrics of the final candidate selection run on the GPU (include/pcc_geo.h "cloud
+metrics", neighbour ties to the lowest row) instead of scipy KD-trees; single process only.
 """
 import argparse
 import json
@@ -103,6 +105,15 @@ def _join_process_group():
     return rank, world, local
 
 
+def check_metrics_device(metrics_device, world):
+    """--metrics_device gpu runs the whole-cloud metrics of one process; the sharded (world > 1) metric path stays on the host."""
+    if metrics_device not in ('host', 'gpu'):
+        raise AssertionError(f'--metrics_device must be host or gpu, got {metrics_device!r}')
+    if metrics_device == 'gpu' and world > 1:
+        raise AssertionError(f'--metrics_device gpu is single-process only (world size {world}): the sharded metric path runs on the '
+                             'host, drop the flag or run on one GPU')
+
+
 def _block_grid(resolution, level, data_format):
     """Octree geometry: the bounding box of the whole cloud and the dense shape of one leaf block."""
     from .utils import pc_io
@@ -126,7 +137,10 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
     with open(target + '.enc.metric.json', 'w') as fh:
         # the reference's keys (floats) + the tag of the kernels that computed sigma-hat (a string: a tool that re-gzips the payload drops the
         # header comment, this file keeps it; readers of the reference's JSON iterate over known metric names)
-        json.dump(dict({name: float(val) for name, val in info['metrics'].items()}, codec_numerics=info['numerics_tag']), fh, sort_keys=True, indent=4)
+        record = dict({name: float(val) for name, val in info['metrics'].items()}, codec_numerics=info['numerics_tag'])
+        if getattr(args, 'metrics_device', 'host') != 'host':      # host mode writes exactly the keys it always wrote
+            record['metrics_device'] = args.metrics_device
+        json.dump(record, fh, sort_keys=True, indent=4)
     if decoded_path is not None:
         pc_io.write_df(decoded_path, pc_io.pa_to_df(info['blocks_full']))
     if args.debug:
@@ -149,6 +163,7 @@ def compress(args):
 
     clouds, with_normals = _plan(args)
     rank, world, local = _join_process_group()
+    check_metrics_device(getattr(args, 'metrics_device', 'host'), world)
     if args.debug and world > 1:
         raise AssertionError('--debug dumps every intermediate of every block: run it on one GPU')
     sess = ops.get_context(torch.device('cuda', local))        # what tf.Session is to the reference (compress_octree.py:84)
@@ -183,7 +198,8 @@ def compress(args):
         logger.info(f'Starting {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
         streams, infos, debug_t_list = model.compress_blocks(
             sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
-            max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points)
+            max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
+            metrics_device=getattr(args, 'metrics_device', 'host'))
         T.mark('compress_blocks', sess.device)
         if rank == 0:       # the other ranks only took part in the collectives
             if len(streams) != len(cloud.targets):
@@ -213,6 +229,9 @@ def build_parser():
                         help='Estimate the normals of each input cloud on the GPU instead of reading --input_normals (new; enables the '
                              'd2_* metrics like a normals file does).')
     parser.add_argument('--normals_k', type=int, default=16, help='Neighbours per point of --estimate_normals (3..64).')
+    parser.add_argument('--metrics_device', choices=('host', 'gpu'), default='host',
+                        help='Where the whole-cloud metrics of the final candidate selection run (new): host = scipy KD-trees, '
+                             'gpu = the HIP engine (ties to the lowest row; single process only).')
     parser.add_argument('--dec_files', nargs='*',
                         help='Decoded files. Allows compression/decompression in a single execution.')
     parser.add_argument('--checkpoint_dir', help='Directory where to save/load model checkpoints.', required=True)

@@ -1,0 +1,553 @@
+// Whole-cloud D1 / D2 distortion with Hausdorff terms (include/pcc_geo.h "cloud metrics", DESIGN.md "Cloud metrics on the GPU").
+//
+// Definition (pinned by tests/test_cloud_metrics_gpu.py against the numpy / scipy restatement in tests/_metrics_ref.py):
+//   - clouds are integer points in [0, 2^21); the nearest indexed point of a query q is the row j with the smallest
+//     (|p_j - q|^2, j) in lexicographic order: exact integer distances, ties to the lowest row (the normals kNN rule at k = 1);
+//   - with A = original, B = decoded, to_b[i] = nearest B row of A point i, to_a[j] = nearest A row of B point j, the tally is
+//     float64[9] = (N_B, D1_AB, D1_BA, D2_AB, D2_BA, H1_AB, H1_BA, H2_AB, H2_BA) as utils/pc_metric.pair_tally writes the first five:
+//     D1 sums exact in 128-bit integers (converted once, correctly rounded), per-point D2 terms ((g.x*n.x + g.y*n.y) + g.z*n.z)^2
+//     in float64 without contraction (the same bits as numpy), the H slots the maxima of the per-point D1 / D2 terms;
+//   - the normal of decoded point j on the A->B side is pc_metric.transfer_normals: the mean of a_normals[i] over to_b[i] == j,
+//     summed in float64 in increasing i, or a_normals[to_a[j]] when no original point links to j.
+//
+// Index: the normals.hip grid.  63-bit Morton codes, a hipCUB radix sort of (code, row), records (x, y, z, row) in that order, and a
+// base cell level from the histogram of the highest differing Morton bit of adjacent codes: the smallest L whose occupied cells hold
+// two points or more on average.  The cells of edge 2^L are contiguous ranges of the sorted codes.
+// Query (k_query), one lane per query: the cube of cells of Chebyshev radius 0, 1, 2 around the query cell, then radius 2 at the
+// next coarser levels, until the best squared distance is STRICTLY below the squared distance to the outside of the visited box
+// (an equidistant point with a lower row could lie just outside) or the box holds the indexed cloud's bounding box.
+// Tally: a stable radix sort of (to_b[i], i) makes every decoded point's original points a segment in increasing i (k_segments,
+// k_bnormals: one sequential float64 sum per segment, numpy bincount's order); k_tally reduces each direction into per-block
+// partials, k_finish adds the partials in a fixed order.  The only atomics are the index build's integer ones (bounding box,
+// histogram); nothing synchronises with the host: the same inputs give the same bits on every call.
+#include <hipcub/hipcub.hpp>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kCoordMask = (1 << 21) - 1;
+constexpr int kLevels = 22;           // cell edge 2^L, L = 0 .. 21 (L = 21: one cell holds the whole domain)
+constexpr int kTallyBlocks = 1024;    // upper bound of the partials of one direction (fixed per n: the sum order depends on n only)
+
+struct IndexHdr {
+    int bmin[3], bmax[3];             // bounding box of the indexed cloud
+    unsigned hist[kLevels];           // adjacent sorted pairs by floor(highest differing Morton bit / 3)
+    int level;                        // base cell level of the search
+};
+
+struct Partial {                      // one workgroup's share of one direction
+    unsigned long long d1_lo, d1_hi;  // exact sum of the squared distances (128 bits)
+    unsigned long long h1;            // max squared distance
+    double d2, h2;                    // sum / max of the per-point plane terms
+};
+
+__device__ __forceinline__ unsigned long long spread3(unsigned v) {
+    unsigned long long x = v & kCoordMask;
+    x = (x | x << 32) & 0x1f00000000ffffull;
+    x = (x | x << 16) & 0x1f0000ff0000ffull;
+    x = (x | x << 8) & 0x100f00f00f00f00full;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+__device__ __forceinline__ unsigned long long morton(int x, int y, int z) {
+    return spread3((unsigned)x) << 2 | spread3((unsigned)y) << 1 | spread3((unsigned)z);
+}
+
+// coordinates outside [0, 2^21) are a precondition violation (the Python layer refuses them); masking keeps every cell
+// computation inside the domain whatever arrives
+__device__ __forceinline__ int3 load_pt(const int32_t* pts, long long i) {
+    return make_int3(pts[3 * i] & kCoordMask, pts[3 * i + 1] & kCoordMask, pts[3 * i + 2] & kCoordMask);
+}
+
+// ---- index ---------------------------------------------------------------------------------------------------------------------
+
+struct IndexLayout {
+    size_t hdr, codes, recs, pts, codes0, rows0, rows1, sort_tmp, sort_tmp_bytes, total;
+};
+
+size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+IndexLayout index_layout(long long n) {
+    IndexLayout l;
+    const size_t N = (size_t)n;
+    size_t o = 0;
+    l.hdr = o; o += al256(sizeof(IndexHdr));
+    l.codes = o; o += al256(N * 8);
+    l.recs = o; o += al256(N * 16);
+    l.pts = o; o += al256(N * 12);
+    l.codes0 = o; o += al256(N * 8);
+    l.rows0 = o; o += al256(N * 4);
+    l.rows1 = o; o += al256(N * 4);
+    size_t tmp = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(n > 0 ? n : 1), 0, 63, (hipStream_t)0);
+    l.sort_tmp_bytes = tmp;
+    l.sort_tmp = o; o += al256(tmp + 256);
+    l.total = o;
+    return l;
+}
+
+struct IndexView {                    // device pointers of a built index
+    const IndexHdr* hdr;
+    const unsigned long long* codes;
+    const int4* recs;
+    const int32_t* pts;
+    long long n;
+};
+
+IndexView index_view(const void* index, long long n) {
+    const IndexLayout l = index_layout(n);
+    const unsigned char* b = (const unsigned char*)index;
+    return IndexView{(const IndexHdr*)(b + l.hdr), (const unsigned long long*)(b + l.codes), (const int4*)(b + l.recs),
+                     (const int32_t*)(b + l.pts), n};
+}
+
+__global__ void k_init(IndexHdr* H) {
+    for (int a = 0; a < 3; ++a) { H->bmin[a] = kCoordMask; H->bmax[a] = 0; }
+    for (int l = 0; l < kLevels; ++l) H->hist[l] = 0;
+    H->level = 0;
+}
+
+// grid-stride, one set of atomics per workgroup (normals.hip k_prepare); also keeps a masked row-order copy of the points
+__global__ void __launch_bounds__(256) k_prepare(const int32_t* __restrict__ pts, long long n, unsigned long long* __restrict__ codes,
+                                                 unsigned* __restrict__ rows, int32_t* __restrict__ copy, IndexHdr* H) {
+    __shared__ int slo[4][3], shi[4][3];
+    int lo[3] = {kCoordMask, kCoordMask, kCoordMask}, hi[3] = {0, 0, 0};
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int3 p = load_pt(pts, i);
+        codes[i] = morton(p.x, p.y, p.z);
+        rows[i] = (unsigned)i;
+        copy[3 * i] = p.x; copy[3 * i + 1] = p.y; copy[3 * i + 2] = p.z;
+        lo[0] = min(lo[0], p.x); lo[1] = min(lo[1], p.y); lo[2] = min(lo[2], p.z);
+        hi[0] = max(hi[0], p.x); hi[1] = max(hi[1], p.y); hi[2] = max(hi[2], p.z);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            lo[a] = min(lo[a], __shfl_xor(lo[a], off));
+            hi[a] = max(hi[a], __shfl_xor(hi[a], off));
+        }
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { slo[wave][a] = lo[a]; shi[wave][a] = hi[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        int l = slo[0][a], h = shi[0][a];
+        for (int w = 1; w < 4; ++w) { l = min(l, slo[w][a]); h = max(h, shi[w][a]); }
+        atomicMin(&H->bmin[a], l);
+        atomicMax(&H->bmax[a], h);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_records(const int32_t* __restrict__ copy, long long n, const unsigned long long* __restrict__ codes,
+                                                 const unsigned* __restrict__ rows, int4* __restrict__ recs, IndexHdr* H) {
+    __shared__ unsigned h[kLevels];
+    if (threadIdx.x < kLevels) h[threadIdx.x] = 0;
+    __syncthreads();
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) {
+        const unsigned r = rows[t];
+        recs[t] = make_int4(copy[3 * (long long)r], copy[3 * (long long)r + 1], copy[3 * (long long)r + 2], (int)r);
+        if (t > 0) {
+            const unsigned long long d = codes[t] ^ codes[t - 1];
+            if (d) atomicAdd(&h[(63 - __clzll((long long)d)) / 3], 1u);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < kLevels && h[threadIdx.x]) atomicAdd(&H->hist[threadIdx.x], h[threadIdx.x]);
+}
+
+// base level: the smallest L whose occupied cells hold two points or more on average (L = 21 always qualifies)
+__global__ void k_params(long long n, IndexHdr* H) {
+    unsigned long long occ = 1;                 // occupied cells of edge 1: one more than the adjacent pairs that differ
+    for (int l = 0; l < kLevels; ++l) occ += H->hist[l];
+    int level = kLevels - 1;
+    for (int l = 0; l < kLevels; ++l) {
+        if ((unsigned long long)n >= 2ull * occ) { level = l; break; }
+        occ -= H->hist[l];                      // pairs that differ at level l but not above: merged one level up
+    }
+    H->level = level;
+}
+
+// ---- query ---------------------------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ long long lower_bound(const unsigned long long* __restrict__ codes, long long n, unsigned long long key) {
+    long long lo = 0, hi = n;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (codes[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One lane per query.  RECS: the queries are another index's records (Morton order: a wave's lanes are neighbours in space, and
+// the result goes to the record's row); otherwise row-order points.  Writes nn[row] and sqd[row] (either may be NULL).
+template <bool RECS>
+__global__ void __launch_bounds__(256) k_query(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
+                                               const int4* __restrict__ recs, long long n, const int4* __restrict__ qrecs,
+                                               const int32_t* __restrict__ qpts, long long nq, int32_t* __restrict__ nn,
+                                               long long* __restrict__ sqd) {
+    const int base = H->level;
+    int bmin[3], bmax[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { bmin[a] = H->bmin[a]; bmax[a] = H->bmax[a]; }
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += (long long)gridDim.x * blockDim.x) {
+        int qc[3];
+        long long row;
+        if (RECS) {
+            const int4 q = qrecs[t];
+            qc[0] = q.x; qc[1] = q.y; qc[2] = q.z;
+            row = q.w;
+        } else {
+            const int3 q = load_pt(qpts, t);
+            qc[0] = q.x; qc[1] = q.y; qc[2] = q.z;
+            row = t;
+        }
+        unsigned long long best_d = ~0ull;
+        unsigned best_r = ~0u;
+        int level = base, rad = 0;
+        bool have_prev = false;
+        int plo[3] = {0, 0, 0}, phi[3] = {0, 0, 0};
+        for (;;) {
+            const int e = 1 << level;
+            int c[3], clo[3], chi[3], blo[3], bhi[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                c[ax] = qc[ax] >> level;
+                clo[ax] = max(c[ax] - rad, bmin[ax] >> level);
+                chi[ax] = min(c[ax] + rad, bmax[ax] >> level);
+                blo[ax] = (c[ax] - rad) * e;
+                bhi[ax] = (c[ax] + rad + 1) * e - 1;
+            }
+            for (int cx = clo[0]; cx <= chi[0]; ++cx)
+                for (int cy = clo[1]; cy <= chi[1]; ++cy)
+                    for (int cz = clo[2]; cz <= chi[2]; ++cz) {
+                        if (have_prev && cx * e >= plo[0] && (cx + 1) * e - 1 <= phi[0] && cy * e >= plo[1] && (cy + 1) * e - 1 <= phi[1] &&
+                            cz * e >= plo[2] && (cz + 1) * e - 1 <= phi[2])
+                            continue;                                        // visited at the previous stage
+                        const unsigned long long key0 = morton(cx, cy, cz) << (3 * level);
+                        for (long long pos = lower_bound(codes, n, key0); pos < n; ++pos) {
+                            const int4 r = recs[pos];
+                            if ((r.x >> level) != cx || (r.y >> level) != cy || (r.z >> level) != cz) break;
+                            if (have_prev && r.x >= plo[0] && r.x <= phi[0] && r.y >= plo[1] && r.y <= phi[1] && r.z >= plo[2] && r.z <= phi[2])
+                                continue;
+                            const long long dx = r.x - qc[0], dy = r.y - qc[1], dz = r.z - qc[2];
+                            const unsigned long long d = (unsigned long long)(dx * dx + dy * dy + dz * dz);
+                            if (d < best_d || (d == best_d && (unsigned)r.w < best_r)) { best_d = d; best_r = (unsigned)r.w; }
+                        }
+                    }
+            // nearest possible unvisited point: just outside a face of the box; faces beyond the cloud's box hide nothing
+            long long gap = -1;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                if (blo[ax] > bmin[ax]) { const long long g = qc[ax] - blo[ax] + 1; gap = gap < 0 || g < gap ? g : gap; }
+                if (bhi[ax] < bmax[ax]) { const long long g = bhi[ax] + 1 - qc[ax]; gap = gap < 0 || g < gap ? g : gap; }
+            }
+            if (gap < 0 || best_d < (unsigned long long)(gap * gap)) break;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) { plo[ax] = blo[ax]; phi[ax] = bhi[ax]; }
+            have_prev = true;
+            if (rad < 2) ++rad; else ++level;               // level 21 at radius 2 holds the whole domain: the loop always ends
+        }
+        if (nn) nn[row] = (int32_t)best_r;
+        if (sqd) sqd[row] = (long long)best_d;
+    }
+}
+
+// ---- tally ---------------------------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) k_link_keys(const int32_t* __restrict__ to_b, long long na, unsigned* __restrict__ keys,
+                                                   unsigned* __restrict__ vals) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < na) { keys[i] = (unsigned)to_b[i]; vals[i] = (unsigned)i; }
+}
+
+// segment [lo[j], hi[j]) of the sorted links holds the original points whose nearest decoded point is j (both zero: none)
+__global__ void __launch_bounds__(256) k_segments(const unsigned* __restrict__ keys, long long na, unsigned* __restrict__ lo,
+                                                  unsigned* __restrict__ hi) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= na) return;
+    const unsigned k = keys[t];
+    if (t == 0 || keys[t - 1] != k) lo[k] = (unsigned)t;
+    if (t == na - 1 || keys[t + 1] != k) hi[k] = (unsigned)(t + 1);
+}
+
+// pc_metric.transfer_normals: one sequential float64 sum per segment (increasing i, as bincount), divided by the count
+__global__ void __launch_bounds__(256) k_bnormals(const unsigned* __restrict__ lo, const unsigned* __restrict__ hi,
+                                                  const unsigned* __restrict__ vals, const double* __restrict__ an,
+                                                  const int32_t* __restrict__ to_a, long long nb, double* __restrict__ bn) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nb) return;
+    const unsigned s = lo[j], e = hi[j];
+    double acc[3] = {0.0, 0.0, 0.0}, votes = 1.0;
+    if (e > s) {
+        for (unsigned t = s; t < e; ++t) {
+            const long long i = vals[t];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += an[3 * i + c];
+        }
+        votes = (double)(e - s);
+    } else {
+        const long long i = to_a[j];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += an[3 * i + c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) bn[3 * j + c] = acc[c] / votes;
+}
+
+// ((gx*nx + gy*ny) + gz*nz)^2 rounded after every operation, numpy's order
+__device__ __forceinline__ double plane_term(double gx, double gy, double gz, const double* __restrict__ nrm) {
+#pragma clang fp contract(off)
+    const double p = (gx * nrm[0] + gy * nrm[1]) + gz * nrm[2];
+    return p * p;
+}
+
+// One direction: src point s links to dst row link[s]; nrm (NULL: no D2) is indexed by that row.  Grid-stride with a grid fixed by
+// n: every per-thread sum visits the same points in the same order on every call.
+__global__ void __launch_bounds__(256) k_tally(const int32_t* __restrict__ src, long long ns, const int32_t* __restrict__ dst,
+                                               const int32_t* __restrict__ link, const long long* __restrict__ sqd,
+                                               const double* __restrict__ nrm, Partial* __restrict__ out) {
+    __shared__ unsigned __int128 s_d1[256];
+    __shared__ unsigned long long s_h1[256];
+    __shared__ double s_d2[256], s_h2[256];
+    unsigned __int128 d1 = 0;
+    unsigned long long h1 = 0;
+    double d2 = 0.0, h2 = 0.0;
+    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < ns; s += (long long)gridDim.x * blockDim.x) {
+        const unsigned long long d = (unsigned long long)sqd[s];
+        d1 += d;
+        h1 = d > h1 ? d : h1;
+        if (nrm) {
+            const long long j = link[s];
+            const double v = plane_term((double)(src[3 * s] - dst[3 * j]), (double)(src[3 * s + 1] - dst[3 * j + 1]),
+                                        (double)(src[3 * s + 2] - dst[3 * j + 2]), nrm + 3 * j);
+            d2 += v;
+            h2 = v > h2 ? v : h2;
+        }
+    }
+    const int t = threadIdx.x;
+    s_d1[t] = d1; s_h1[t] = h1; s_d2[t] = d2; s_h2[t] = h2;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (t < w) {
+            s_d1[t] += s_d1[t + w];
+            s_h1[t] = s_h1[t + w] > s_h1[t] ? s_h1[t + w] : s_h1[t];
+            s_d2[t] += s_d2[t + w];
+            s_h2[t] = s_h2[t + w] > s_h2[t] ? s_h2[t + w] : s_h2[t];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        Partial p;
+        p.d1_lo = (unsigned long long)s_d1[0];
+        p.d1_hi = (unsigned long long)(s_d1[0] >> 64);
+        p.h1 = s_h1[0];
+        p.d2 = s_d2[0];
+        p.h2 = s_h2[0];
+        out[blockIdx.x] = p;
+    }
+}
+
+// correctly rounded double of a 128-bit unsigned integer
+__device__ __forceinline__ double u128_to_double(unsigned __int128 v) {
+    const unsigned long long hi = (unsigned long long)(v >> 64), lo = (unsigned long long)v;
+    if (!hi) return (double)lo;
+    const int s = 64 - __clzll((long long)hi);                  // 1 .. 64: bits of hi
+    const unsigned __int128 top = v >> s;                       // the highest 64 bits
+    const unsigned long long sticky = (v & (((unsigned __int128)1 << s) - 1)) != 0;
+    return ldexp((double)((unsigned long long)top | sticky), s);
+}
+
+// one workgroup: the partials of A->B (ga of them) and B->A (gb), each direction summed in a fixed order
+__global__ void __launch_bounds__(256) k_finish(const Partial* __restrict__ pab, int ga, const Partial* __restrict__ pba, int gb,
+                                                long long nb, double* __restrict__ tally) {
+    __shared__ unsigned __int128 s_d1[2][256];
+    __shared__ unsigned long long s_h1[2][256];
+    __shared__ double s_d2[2][256], s_h2[2][256];
+    const int t = threadIdx.x;
+    for (int side = 0; side < 2; ++side) {
+        const Partial* p = side ? pba : pab;
+        const int g = side ? gb : ga;
+        unsigned __int128 d1 = 0;
+        unsigned long long h1 = 0;
+        double d2 = 0.0, h2 = 0.0;
+        for (int b = t; b < g; b += 256) {
+            d1 += (unsigned __int128)p[b].d1_hi << 64 | p[b].d1_lo;
+            h1 = p[b].h1 > h1 ? p[b].h1 : h1;
+            d2 += p[b].d2;
+            h2 = p[b].h2 > h2 ? p[b].h2 : h2;
+        }
+        s_d1[side][t] = d1; s_h1[side][t] = h1; s_d2[side][t] = d2; s_h2[side][t] = h2;
+    }
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int side = 0; side < 2; ++side) {
+                s_d1[side][t] += s_d1[side][t + w];
+                s_h1[side][t] = s_h1[side][t + w] > s_h1[side][t] ? s_h1[side][t + w] : s_h1[side][t];
+                s_d2[side][t] += s_d2[side][t + w];
+                s_h2[side][t] = s_h2[side][t + w] > s_h2[side][t] ? s_h2[side][t + w] : s_h2[side][t];
+            }
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        tally[0] = (double)nb;
+        tally[1] = u128_to_double(s_d1[0][0]);
+        tally[2] = u128_to_double(s_d1[1][0]);
+        tally[3] = s_d2[0][0];
+        tally[4] = s_d2[1][0];
+        tally[5] = (double)s_h1[0][0];
+        tally[6] = (double)s_h1[1][0];
+        tally[7] = s_h2[0][0];
+        tally[8] = s_h2[1][0];
+    }
+}
+
+int tally_blocks(long long n) {
+    const long long b = (n + 255) / 256;
+    return (int)(b < kTallyBlocks ? b : kTallyBlocks);
+}
+
+int key_bits(long long nb) {                    // bits of the largest decoded row, nb - 1 (at least 1)
+    int bits = 1;
+    while (bits < 31 && ((long long)1 << bits) < nb) ++bits;
+    return bits;
+}
+
+struct DistLayout {
+    size_t nn_ab, d_ab, nn_ba, d_ba, keys0, vals0, keys1, vals1, seg_lo, seg_hi, bn, pab, pba, sort_tmp, sort_tmp_bytes, total;
+};
+
+DistLayout dist_layout(long long na, long long nb) {
+    DistLayout l;
+    const size_t A = (size_t)na, B = (size_t)nb;
+    size_t o = 0;
+    l.nn_ab = o; o += al256(A * 4);
+    l.d_ab = o; o += al256(A * 8);
+    l.nn_ba = o; o += al256(B * 4);
+    l.d_ba = o; o += al256(B * 8);
+    l.keys0 = o; o += al256(A * 4);
+    l.vals0 = o; o += al256(A * 4);
+    l.keys1 = o; o += al256(A * 4);
+    l.vals1 = o; o += al256(A * 4);
+    l.seg_lo = o; o += al256(B * 4);
+    l.seg_hi = o; o += al256(B * 4);
+    l.bn = o; o += al256(B * 24);
+    l.pab = o; o += al256(kTallyBlocks * sizeof(Partial));
+    l.pba = o; o += al256(kTallyBlocks * sizeof(Partial));
+    size_t tmp = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
+                                             (unsigned*)nullptr, (int)(na > 0 ? na : 1), 0, key_bits(nb), (hipStream_t)0);
+    l.sort_tmp_bytes = tmp;
+    l.sort_tmp = o; o += al256(tmp + 256);
+    l.total = o;
+    return l;
+}
+
+bool valid_n(int64_t n) { return n > 0 && n < ((int64_t)1 << 31); }
+
+}  // namespace
+
+PCC_API size_t pcc_cloud_index_bytes(int64_t npts) {
+    if (!valid_n(npts)) return 0;
+    return index_layout(npts).total;
+}
+
+PCC_API int pcc_cloud_index_build(pcc_ctx* ctx, const int32_t* pts, int64_t npts, void* index, void* stream) {
+    PCC_REQUIRE(ctx && pts && index, "pcc_cloud_index_build: NULL argument");
+    PCC_REQUIRE(valid_n(npts), "pcc_cloud_index_build: npts = %lld outside [1, 2^31)", (long long)npts);
+    PCC_CHECK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const long long n = npts;
+    const IndexLayout l = index_layout(n);
+    unsigned char* w = (unsigned char*)index;
+    IndexHdr* H = (IndexHdr*)(w + l.hdr);
+    unsigned long long *codes0 = (unsigned long long*)(w + l.codes0), *codes = (unsigned long long*)(w + l.codes);
+    unsigned *rows0 = (unsigned*)(w + l.rows0), *rows1 = (unsigned*)(w + l.rows1);
+    int32_t* copy = (int32_t*)(w + l.pts);
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    const unsigned cus = (unsigned)(ctx->num_cu > 0 ? ctx->num_cu : 256);
+    hipLaunchKernelGGL(k_init, dim3(1), dim3(1), 0, st, H);
+    hipLaunchKernelGGL(k_prepare, dim3(blocks < cus ? blocks : cus), dim3(256), 0, st, pts, n, codes0, rows0, copy, H);
+    size_t tmp = l.sort_tmp_bytes;
+    PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w + l.sort_tmp), tmp, (const unsigned long long*)codes0, codes,
+                                                     (const unsigned*)rows0, rows1, (int)n, 0, 63, st));
+    hipLaunchKernelGGL(k_records, dim3(blocks), dim3(256), 0, st, (const int32_t*)copy, n, (const unsigned long long*)codes,
+                       (const unsigned*)rows1, (int4*)(w + l.recs), H);
+    hipLaunchKernelGGL(k_params, dim3(1), dim3(1), 0, st, n, H);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+PCC_API int pcc_cloud_nearest(pcc_ctx* ctx, const void* index, int64_t npts, const int32_t* queries, int64_t nq, int32_t* nn,
+                              int64_t* sqdist, void* stream) {
+    PCC_REQUIRE(ctx && index && queries, "pcc_cloud_nearest: NULL argument");
+    PCC_REQUIRE(valid_n(npts), "pcc_cloud_nearest: npts = %lld outside [1, 2^31)", (long long)npts);
+    PCC_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31), "pcc_cloud_nearest: nq = %lld outside [0, 2^31)", (long long)nq);
+    if (nq == 0) return PCC_OK;
+    PCC_CHECK_HIP(hipSetDevice(ctx->device));
+    const IndexView v = index_view(index, npts);
+    hipLaunchKernelGGL(k_query<false>, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v.hdr, v.codes, v.recs,
+                       v.n, (const int4*)nullptr, queries, (long long)nq, nn, (long long*)sqdist);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+PCC_API size_t pcc_cloud_distortion_workspace_bytes(int64_t na, int64_t nb) {
+    if (!valid_n(na) || !valid_n(nb)) return 0;
+    return dist_layout(na, nb).total;
+}
+
+PCC_API int pcc_cloud_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const void* index_b, int64_t nb, const double* a_normals,
+                                 double* tally, int32_t* to_b, int32_t* to_a, void* workspace, void* stream) {
+    PCC_REQUIRE(ctx && index_a && index_b && tally && workspace, "pcc_cloud_distortion: NULL argument");
+    PCC_REQUIRE(valid_n(na) && valid_n(nb), "pcc_cloud_distortion: na = %lld, nb = %lld outside [1, 2^31)", (long long)na, (long long)nb);
+    PCC_CHECK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const IndexView A = index_view(index_a, na), B = index_view(index_b, nb);
+    const DistLayout l = dist_layout(na, nb);
+    unsigned char* w = (unsigned char*)workspace;
+    int32_t* nn_ab = to_b ? to_b : (int32_t*)(w + l.nn_ab);
+    int32_t* nn_ba = to_a ? to_a : (int32_t*)(w + l.nn_ba);
+    long long *d_ab = (long long*)(w + l.d_ab), *d_ba = (long long*)(w + l.d_ba);
+    Partial *pab = (Partial*)(w + l.pab), *pba = (Partial*)(w + l.pba);
+    const unsigned ga = (unsigned)((na + 255) / 256), gb = (unsigned)((nb + 255) / 256);
+    // queries in the other index's Morton order
+    hipLaunchKernelGGL(k_query<true>, dim3(ga), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, (const int32_t*)nullptr, A.n,
+                       nn_ab, d_ab);
+    hipLaunchKernelGGL(k_query<true>, dim3(gb), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, B.recs, (const int32_t*)nullptr, B.n,
+                       nn_ba, d_ba);
+    const double* bn = nullptr;
+    if (a_normals) {
+        unsigned *keys0 = (unsigned*)(w + l.keys0), *vals0 = (unsigned*)(w + l.vals0);
+        unsigned *keys1 = (unsigned*)(w + l.keys1), *vals1 = (unsigned*)(w + l.vals1);
+        unsigned *seg_lo = (unsigned*)(w + l.seg_lo), *seg_hi = (unsigned*)(w + l.seg_hi);
+        hipLaunchKernelGGL(k_link_keys, dim3(ga), dim3(256), 0, st, (const int32_t*)nn_ab, (long long)na, keys0, vals0);
+        size_t tmp = l.sort_tmp_bytes;                     // LSD radix sort: stable, so every segment stays in increasing i
+        PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w + l.sort_tmp), tmp, (const unsigned*)keys0, keys1, (const unsigned*)vals0,
+                                                         vals1, (int)na, 0, key_bits(nb), st));
+        PCC_CHECK_HIP(hipMemsetAsync(seg_lo, 0, (size_t)nb * 4, st));
+        PCC_CHECK_HIP(hipMemsetAsync(seg_hi, 0, (size_t)nb * 4, st));
+        hipLaunchKernelGGL(k_segments, dim3(ga), dim3(256), 0, st, (const unsigned*)keys1, (long long)na, seg_lo, seg_hi);
+        hipLaunchKernelGGL(k_bnormals, dim3(gb), dim3(256), 0, st, (const unsigned*)seg_lo, (const unsigned*)seg_hi, (const unsigned*)vals1,
+                           a_normals, (const int32_t*)nn_ba, (long long)nb, (double*)(w + l.bn));
+        bn = (const double*)(w + l.bn);
+    }
+    const int ta = tally_blocks(na), tb = tally_blocks(nb);
+    hipLaunchKernelGGL(k_tally, dim3(ta), dim3(256), 0, st, A.pts, (long long)na, B.pts, (const int32_t*)nn_ab, (const long long*)d_ab, bn, pab);
+    hipLaunchKernelGGL(k_tally, dim3(tb), dim3(256), 0, st, B.pts, (long long)nb, A.pts, (const int32_t*)nn_ba, (const long long*)d_ba,
+                       a_normals, pba);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, (const Partial*)pab, ta, (const Partial*)pba, tb, (long long)nb, tally);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}

@@ -8,7 +8,10 @@ utils/pc_metric.compute_metrics, the module the encoder itself uses for its `.en
 ev_experiment.py:158-162) carries over.
 
     python -m pcc_geo_cnn_v2_amd.ev_report --input_pc a.ply --decoded_pc a.ply.bin.ply --enc_pc a.ply.bin \\
-        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] --output report_d1.json
+        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] [--metrics_device host|gpu] [--hausdorff] --output report_d1.json
+
+`--metrics_device gpu` computes the metrics with the GPU engine (include/pcc_geo.h "cloud metrics": neighbour ties to the lowest
+row); `--hausdorff` adds pc_error's Hausdorff terms (utils/pc_metric.hausdorff_table).  Without them the report is unchanged.
 """
 import argparse
 import json
@@ -18,12 +21,13 @@ import os
 import numpy as np
 
 from .utils import pc_io
-from .utils.pc_metric import compute_metrics
+from .utils.pc_metric import cloud_tally_host, cloud_tallies_gpu, compute_metrics, hausdorff_table, metrics_table
 
 logger = logging.getLogger(__name__)
 
 
-def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, estimate_normals=False, normals_k=16):
+def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, estimate_normals=False, normals_k=16,
+                 metrics_device='host', hausdorff=False):
     if input_norm and estimate_normals:
         raise AssertionError('--estimate_normals and --input_norm are mutually exclusive')
     p1 = pc_io.load_pc(input_pc)
@@ -34,10 +38,22 @@ def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, esti
         n1 = ops.estimate_normals(ops.get_context(), p1, k=normals_k)
     if n1 is not None:
         assert len(n1) == len(p1), 'normals file must have one normal per input point'
-    m = compute_metrics(np.asarray(p1, np.float64)[:, :3], np.asarray(p2, np.float64)[:, :3], resolution - 1, p1_n=n1)
+    a, b = np.asarray(p1, np.float64)[:, :3], np.asarray(p2, np.float64)[:, :3]
+    if metrics_device == 'gpu':
+        from . import ops
+        assert len(b), 'compute_metrics: empty decoded cloud'
+        tally = cloud_tallies_gpu(ops.get_context(), a, [b], n1)[0]
+        m = metrics_table(len(a), tally[:5], resolution - 1, ('d1', 'd2') if n1 is not None else ('d1',))
+    elif metrics_device == 'host':
+        m = compute_metrics(a, b, resolution - 1, p1_n=n1)
+        tally = cloud_tally_host(a, b, n1) if hausdorff else None
+    else:
+        raise AssertionError(f'metrics_device must be host or gpu, got {metrics_device!r}')
     size = os.stat(enc_pc).st_size
     data = {'pos_total_size_in_bytes': size, 'pos_bits_per_input_point': size * 8 / len(p1), 'input_point_count': len(p1)}
     data.update({k: float(v) for k, v in m.items() if k in ('d1_mse', 'd1_psnr', 'd2_mse', 'd2_psnr')})
+    if hausdorff:
+        data.update({k: float(v) for k, v in hausdorff_table(tally, resolution - 1, n1 is not None).items()})
     return data
 
 
@@ -53,12 +69,17 @@ def main():
     p.add_argument('--estimate_normals', default=False, action='store_true',
                    help='Estimate the input normals on the GPU (enables D2 without --input_norm; new)')
     p.add_argument('--normals_k', type=int, default=16, help='Neighbours per point of --estimate_normals (3..64)')
+    p.add_argument('--metrics_device', choices=('host', 'gpu'), default='host',
+                   help='Where the metrics run: host = scipy KD-trees, gpu = the HIP engine (ties to the lowest row; new)')
+    p.add_argument('--hausdorff', default=False, action='store_true',
+                   help="Add pc_error's Hausdorff terms: d1_hausdorff[_AB|_BA|_psnr] (+ d2_* with normals; new)")
     p.add_argument('--resolution', type=int, required=True, help='Voxel grid resolution of the input (peak = resolution - 1)')
     p.add_argument('--output', required=True, help='Report JSON path')
     args = p.parse_args()
     if args.input_norm and args.estimate_normals:
         p.error('--estimate_normals and --input_norm are mutually exclusive')
-    data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm, args.estimate_normals, args.normals_k)
+    data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm, args.estimate_normals, args.normals_k,
+                        args.metrics_device, args.hausdorff)
     with open(args.output, 'w') as f:
         json.dump(data, f, sort_keys=True, indent=4)
     enc_metric = args.enc_pc + '.enc.metric.json'

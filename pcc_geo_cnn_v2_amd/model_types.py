@@ -30,7 +30,7 @@ from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
 from .model_opt import d1_tallies_gpu, d12_tallies_gpu, d2_on_gpu, decide_from_tallies, gpu_search_supported, metric_names
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
-from .utils.pc_metric import cloud_metrics_batch, finish_metrics
+from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu, finish_metrics
 
 logger = logging.getLogger(__name__)
 
@@ -70,12 +70,18 @@ def rank_candidates(names, cand_metrics, opt_groups=('d1', 'd2')):
     return picks
 
 
+METRICS_DEVICES = ('host', 'gpu')      # where the encoder's whole-cloud metrics run (compress_octree --metrics_device)
+
+
 def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, resolution, with_normals,
-                               opt_groups=('d1', 'd2'), tree=None):
+                               opt_groups=('d1', 'd2'), tree=None, metrics_device='host', ctx=None):
     """Per optimisation group, which candidate reconstruction of the whole cloud to keep (the reference's function of the same
     name, model_types.py:128-176; results pinned by tests/golden/select_best.npz).  x_hat_list[m] = the decoded blocks of
     candidate m (block-local coordinates).  Returns one dict per non-empty group: 'idx', 'metrics', 'x_hat_list',
-    'blocks_depart' (blocks in cloud coordinates), 'blocks_full' (one array)."""
+    'blocks_depart' (blocks in cloud coordinates), 'blocks_full' (one array).  metrics_device='gpu': the whole-cloud metrics come
+    from pc_metric.cloud_metrics_batch_gpu on context `ctx` (neighbour ties to the lowest row) instead of the KD-trees."""
+    if metrics_device not in METRICS_DEVICES:
+        raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
     assert len(opt_metrics) == len(x_hat_list), f'lengths of opt_metrics {len(opt_metrics)} and x_hat_list' + \
                                                 f' {len(x_hat_list)} should be equal'
     grouped = [m for m, n in enumerate(opt_metrics) if any(n.startswith(g) for g in opt_groups)]
@@ -83,8 +89,13 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
     clouds = {m: np.vstack(placed[m]) for m in grouped}
     original = points[:, :3]
     # `tree`: the KD-tree over the original points when the caller built it meanwhile (compress_blocks: beside the block loop)
-    scored = cloud_metrics_batch(original, [clouds[m] for m in grouped], resolution - 1, get_normals_if(points, with_normals),
-                                 tree if tree is not None else cKDTree(original))
+    if metrics_device == 'gpu':
+        from . import ops
+        scored = cloud_metrics_batch_gpu(ctx if ctx is not None else ops.get_context(), original, [clouds[m] for m in grouped],
+                                         resolution - 1, get_normals_if(points, with_normals))
+    else:
+        scored = cloud_metrics_batch(original, [clouds[m] for m in grouped], resolution - 1, get_normals_if(points, with_normals),
+                                     tree if tree is not None else cKDTree(original))
     cand_metrics = [None] * len(opt_metrics)
     for m, met in zip(grouped, scored):
         cand_metrics[m] = met
@@ -553,17 +564,23 @@ class CompressionModel:
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
-                        need_points=True):
+                        need_points=True, metrics_device='host'):
         """Uses the compression model to compress a point cloud (model_types.py:184-218).  Under torch.distributed (one
         process per GPU) the block list is sharded (sharding.py): rank 0 returns the complete result, the other ranks
         return (None, metadata without point lists, local debug list).  `need_points=False` skips the gather of the
-        decoded candidate point lists to rank 0 (they are only needed for --dec_files / --debug)."""
+        decoded candidate point lists to rank 0 (they are only needed for --dec_files / --debug).  metrics_device='gpu'
+        (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree."""
         from . import sharding
         rank, world = sharding.world_info()
+        if metrics_device not in METRICS_DEVICES:
+            raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
+        if metrics_device == 'gpu' and world > 1:
+            raise AssertionError('metrics_device gpu is single-process only: the sharded metric path runs on the host')
         # The KD-tree over the ORIGINAL cloud (the whole-cloud metrics of every candidate query it: pc_metric.py:80) does not depend on the
         # encode: it is built on a helper thread while the GPU codes the blocks (0.11 s of a 614 k-point cloud's 0.30 s; scipy builds
-        # without the GIL).  Same constructor call as before: the same tree, the same neighbour picks.
-        self._tree_future = self._helper_thread('tree').submit(cKDTree, points[:, :3]) if len(points) else None
+        # without the GIL).  Same constructor call as before: the same tree, the same neighbour picks.  The GPU metrics need no tree.
+        host_metrics = metrics_device == 'host'
+        self._tree_future = self._helper_thread('tree').submit(cKDTree, points[:, :3]) if len(points) and host_metrics else None
         if world == 1:
             try:
                 strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
@@ -574,7 +591,8 @@ class CompressionModel:
             # block -> opt metric to opt metric -> block
             threshold_list = list(zip(*threshold_list))
             x_hat_list = list(zip(*x_hat_list))
-            metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree)
+            metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
+                                                  metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess))
             data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
             return data_list, metadata, debug_t_list
         return self._compress_blocks_sharded(sess, blocks, binstr, points, resolution, level, with_normals, opt_metrics,

@@ -629,32 +629,32 @@ def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, cl
 NORMALS_COORD_LIMIT = 1 << 21        # include/pcc_geo.h "point normals": coordinates are integers in [0, 2^21)
 
 
-def _voxel_points(points):
-    """The input contract of estimate_normals, checked before anything reaches the GPU: an (N,3) cloud of integer coordinates in
+def _voxel_points(points, what='estimate_normals'):
+    """The input contract of estimate_normals and the cloud metrics (`what` names the caller in the messages), checked before anything reaches the GPU: an (N,3) cloud of integer coordinates in
     [0, 2^21), 1 <= N < 2^31.  Returns an int32 array (numpy input) or an int32 contiguous device tensor (torch input)."""
     if isinstance(points, torch.Tensor):
         if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
-            raise L.PccError(f'estimate_normals: points must be (N, 3) with N >= 1, got {tuple(points.shape)}')
+            raise L.PccError(f'{what}: points must be (N, 3) with N >= 1, got {tuple(points.shape)}')
         if points.is_floating_point():
             if not bool(torch.isfinite(points).all()) or not bool((points == torch.round(points)).all()):
-                raise L.PccError('estimate_normals: coordinates must be integers (voxelised cloud); got non-integer values')
+                raise L.PccError(f'{what}: coordinates must be integers (voxelised cloud); got non-integer values')
         elif points.dtype == torch.bool or points.is_complex():
-            raise L.PccError(f'estimate_normals: unsupported dtype {points.dtype}')
+            raise L.PccError(f'{what}: unsupported dtype {points.dtype}')
         if bool((points < 0).any()) or bool((points >= NORMALS_COORD_LIMIT).any()):
-            raise L.PccError(f'estimate_normals: coordinates must lie in [0, {NORMALS_COORD_LIMIT})')
+            raise L.PccError(f'{what}: coordinates must lie in [0, {NORMALS_COORD_LIMIT})')
         return points.to(torch.int32).contiguous()
     a = np.asarray(points)
     if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] == 0:
-        raise L.PccError(f'estimate_normals: points must be (N, 3) with N >= 1, got {a.shape}')
+        raise L.PccError(f'{what}: points must be (N, 3) with N >= 1, got {a.shape}')
     if a.shape[0] >= 1 << 31:
-        raise L.PccError('estimate_normals: at most 2^31 - 1 points per call')
+        raise L.PccError(f'{what}: at most 2^31 - 1 points per call')
     if a.dtype.kind == 'f':
         if not np.isfinite(a).all() or not np.array_equal(a, np.round(a)):
-            raise L.PccError('estimate_normals: coordinates must be integers (voxelised cloud); got non-integer values')
+            raise L.PccError(f'{what}: coordinates must be integers (voxelised cloud); got non-integer values')
     elif a.dtype.kind not in 'iu':
-        raise L.PccError(f'estimate_normals: unsupported dtype {a.dtype}')
+        raise L.PccError(f'{what}: unsupported dtype {a.dtype}')
     if (a < 0).any() or (a >= NORMALS_COORD_LIMIT).any():
-        raise L.PccError(f'estimate_normals: coordinates must lie in [0, {NORMALS_COORD_LIMIT})')
+        raise L.PccError(f'{what}: coordinates must lie in [0, {NORMALS_COORD_LIMIT})')
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
@@ -685,6 +685,97 @@ def estimate_normals(ctx, points, k=16, viewpoint=None, return_knn=False):
     if return_knn:
         return out, knn[:, :min(k, n)].cpu().numpy()
     return out
+
+
+CLOUD_TALLY_SLOTS = 9      # include/pcc_geo.h "cloud metrics": N_B, D1_AB, D1_BA, D2_AB, D2_BA, H1_AB, H1_BA, H2_AB, H2_BA
+
+
+def _device_points(ctx, points, what):
+    pts = _voxel_points(points, what)
+    return pts.to(ctx.device) if isinstance(pts, torch.Tensor) else torch.from_numpy(pts).to(ctx.device)
+
+
+class CloudIndex:
+    """Nearest-neighbour index over a voxelised cloud on the GPU (include/pcc_geo.h "cloud metrics"): Morton-sorted cells, exact
+    integer distances, ties to the lowest row.  points: (N,3) numpy array or device tensor of integer coordinates in [0, 2^21),
+    1 <= N < 2^31.  Built once, reusable by any number of cloud_nearest / cloud_distortion calls on the same context."""
+
+    def __init__(self, ctx, points):
+        pts = _device_points(ctx, points, 'CloudIndex')
+        self.n = int(pts.shape[0])
+        self.device = ctx.device
+        self.buffer = torch.empty((L.lib().pcc_cloud_index_bytes(self.n),), dtype=torch.uint8, device=ctx.device)
+        L.check(L.lib().pcc_cloud_index_build(ctx.handle, _ptr(pts), self.n, _ptr(self.buffer), ctx.stream), 'pcc_cloud_index_build')
+
+    def __len__(self):
+        return self.n
+
+
+def cloud_nearest(ctx, index, queries):
+    """For every query point, the row of its nearest point in `index` (ties: the lowest row) and the exact squared distance:
+    (int32[nq], int64[nq]) numpy arrays.  queries: (nq,3) integer coordinates in [0, 2^21); nq = 0 gives empty arrays."""
+    if len(queries) == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int64)
+    q = _device_points(ctx, queries, 'cloud_nearest')
+    nq = int(q.shape[0])
+    nn = torch.empty((nq,), dtype=torch.int32, device=ctx.device)
+    sq = torch.empty((nq,), dtype=torch.int64, device=ctx.device)
+    L.check(L.lib().pcc_cloud_nearest(ctx.handle, _ptr(index.buffer), index.n, _ptr(q), nq, _ptr(nn), _ptr(sq), ctx.stream),
+            'pcc_cloud_nearest')
+    return nn.cpu().numpy(), sq.cpu().numpy()
+
+
+def _normals64(a_normals, n):
+    """Host-side check of the normals of cloud_distortion; returns them as float64 (numpy) or as a float64 tensor."""
+    if a_normals is None:
+        return None
+    if isinstance(a_normals, torch.Tensor):
+        if not a_normals.is_floating_point():
+            raise L.PccError(f'cloud_distortion: normals must be floating point, got {a_normals.dtype}')
+        nrm = a_normals.to(torch.float64)
+    else:
+        nrm = np.asarray(a_normals)
+        if nrm.dtype.kind != 'f':
+            raise L.PccError(f'cloud_distortion: normals must be floating point, got {nrm.dtype}')
+        nrm = np.ascontiguousarray(nrm, np.float64)
+    if tuple(nrm.shape) != (n, 3):
+        raise L.PccError(f'cloud_distortion: normals must be ({n}, 3), got {tuple(nrm.shape)}')
+    return nrm
+
+
+def cloud_distortion_launch(ctx, index_a, b, a_normals=None, links=False):
+    """cloud_distortion without the host copy: returns the float64[9] device tally (and the int32 to_b, to_a device tensors with
+    links=True), queued on the context's stream.  b: (N_B,3) decoded points, N_B >= 1; a_normals: (N_A,3) or None."""
+    b = _voxel_points(b, 'cloud_distortion')
+    nrm = _normals64(a_normals, index_a.n)
+    dev = ctx.device
+    if nrm is not None:
+        nrm = (nrm.to(dev) if isinstance(nrm, torch.Tensor) else torch.from_numpy(nrm).to(dev)).contiguous()
+    index_b = CloudIndex(ctx, b)
+    tally = torch.empty((CLOUD_TALLY_SLOTS,), dtype=torch.float64, device=dev)
+    to_b = torch.empty((index_a.n,), dtype=torch.int32, device=dev) if links else None
+    to_a = torch.empty((index_b.n,), dtype=torch.int32, device=dev) if links else None
+    ws = torch.empty((L.lib().pcc_cloud_distortion_workspace_bytes(index_a.n, index_b.n),), dtype=torch.uint8, device=dev)
+    L.check(L.lib().pcc_cloud_distortion(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(index_b.buffer), index_b.n, _ptr(nrm),
+                                         _ptr(tally), _ptr(to_b), _ptr(to_a), _ptr(ws), ctx.stream), 'pcc_cloud_distortion')
+    return (tally, to_b, to_a) if links else tally
+
+
+def cloud_distortion(ctx, a, b, a_normals=None, index_a=None, return_links=False):
+    """Distortion tally of decoded cloud b against original cloud a on the GPU (include/pcc_geo.h "cloud metrics"): float64[9] =
+    N_B, D1_AB, D1_BA, D2_AB, D2_BA, H1_AB, H1_BA, H2_AB, H2_BA (utils/pc_metric.pair_tally's five slots plus the Hausdorff maxima).
+    a, b: (N,3) integer coordinates in [0, 2^21), N >= 1; a_normals: (N_A,3) normals of a (None: the D2 / H2 slots are 0);
+    index_a: a CloudIndex of a to reuse (a is then not read).  return_links=True also returns to_b (int32[N_A]) and to_a
+    (int32[N_B]), the nearest rows across (ties: the lowest row).  Deterministic: the same inputs give the same bits."""
+    if index_a is None:                     # every input is checked before the first GPU call
+        a = _voxel_points(a, 'cloud_distortion')
+        b = _voxel_points(b, 'cloud_distortion')
+        _normals64(a_normals, len(a))
+        index_a = CloudIndex(ctx, a)
+    out = cloud_distortion_launch(ctx, index_a, b, a_normals, links=return_links)
+    if return_links:
+        return tuple(t.cpu().numpy() for t in out)
+    return out.cpu().numpy()
 
 
 # ---------------------------------------------------------------------------------------------

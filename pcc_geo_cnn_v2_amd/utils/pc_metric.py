@@ -23,6 +23,9 @@ avail_opt_metrics = [f'{g}_{stem}' for g in GROUPS for stem in _OPT_STEMS]      
 # slots of a tally vector (float64[5]); additive over disjoint parts of B (B->A terms) and of A (A->B terms)
 N_B, D1_AB, D1_BA, D2_AB, D2_BA = range(5)
 _TALLY_SLOTS = {'d1': (D1_AB, D1_BA), 'd2': (D2_AB, D2_BA)}
+# the Hausdorff slots of a 9-slot tally (float64[9] = the five above + these): per-direction maxima of the per-point D1 / D2 terms
+H1_AB, H1_BA, H2_AB, H2_BA = range(5, 9)
+_HAUSDORFF_SLOTS = {'d1': (H1_AB, H1_BA), 'd2': (H2_AB, H2_BA)}
 
 
 def validate_opt_metrics(opt_metrics, with_normals=False):
@@ -172,3 +175,65 @@ def compute_metrics(p1, p2, r, p1_n=None, t1=None):
     """The reference's entry point (pc_metric.py:76): metrics of decoded cloud p2 against original p1, peak value r."""
     assert len(p2), 'compute_metrics: empty decoded cloud'
     return cloud_metrics_batch(p1, [p2], r, p1_n, t1)[0]
+
+
+# ---- Hausdorff terms and the GPU engine (include/pcc_geo.h "cloud metrics") ------------------------------------------------------
+def hausdorff_table(tally, peak, with_normals=False):
+    """pc_error's --hausdorff keys from 9-slot tallies: per group, '{g}_hausdorff_AB' / '_BA' (largest per-point squared error in
+    each direction), '{g}_hausdorff' (the larger of the two) and '{g}_hausdorff_psnr' = 10 log10(3 peak^2 / {g}_hausdorff).  d2
+    keys only with_normals.  Works on float64[9] (-> scalars) and float64[T, 9] (-> arrays)."""
+    tally = np.asarray(tally, np.float64)
+    out = {}
+    for g in (GROUPS if with_normals else GROUPS[:1]):
+        h_ab, h_ba = (tally[..., k] for k in _HAUSDORFF_SLOTS[g])
+        out[f'{g}_hausdorff_AB'], out[f'{g}_hausdorff_BA'] = h_ab, h_ba
+        out[f'{g}_hausdorff'] = np.maximum(h_ab, h_ba)
+        out[f'{g}_hausdorff_psnr'] = psnr(out[f'{g}_hausdorff'], 3 * peak * peak)
+    return out
+
+
+def cloud_tally_host(p1, p2, p1_n=None, t1=None):
+    """Host restatement of the 9-slot tally with the KD-tree links of cloud_metrics_batch: pair_tally's five slots plus the
+    Hausdorff maxima (np.max over the per-point terms pair_tally sums).  p2 must not be empty."""
+    p2 = np.asarray(p2).reshape(-1, 3)
+    assert len(p2), 'cloud_tally_host: empty decoded cloud'
+    tree_a = t1 if t1 is not None else cKDTree(p1, balanced_tree=False)
+    to_b, to_a = nearest(cKDTree(p2, balanced_tree=False), p1), nearest(tree_a, p2)
+    tally = np.zeros(9, np.float64)
+    tally[:5] = pair_tally(p1, p2, to_b, to_a, p1_n)
+    gap_ab, gap_ba = point_gap(p1, p2, to_b), point_gap(p2, p1, to_a)
+    tally[H1_AB], tally[H1_BA] = squared_norms(gap_ab).max(), squared_norms(gap_ba).max()
+    if p1_n is not None:
+        b_normals = transfer_normals(p1_n, to_a, to_b)
+        tally[H2_AB] = (((gap_ab * b_normals[to_b]).sum(axis=1)) ** 2).max()
+        tally[H2_BA] = (((gap_ba * p1_n[to_a]).sum(axis=1)) ** 2).max()
+    return tally
+
+
+def cloud_tallies_gpu(ctx, p1, p2_list, p1_n=None, index_a=None):
+    """9-slot tallies of every candidate decoded cloud against p1 on the GPU (ops.cloud_distortion): one float64[9] per candidate,
+    None for an empty one.  The original cloud's index is built once (or `index_a` is reused) and every candidate is queued
+    before the one host copy.  Neighbour ties go to the lowest row (include/pcc_geo.h "cloud metrics"): D1 and the D1 Hausdorff
+    terms equal the host path's whenever its float64 sums are exact; D2 may differ where cKDTree picks another equidistant point."""
+    import torch
+    from .. import ops
+    clouds = [np.asarray(p2).reshape(-1, 3) for p2 in p2_list]
+    live = [m for m, p2 in enumerate(clouds) if len(p2)]
+    out = [None] * len(clouds)
+    if not live:
+        return out
+    if index_a is None:
+        index_a = ops.CloudIndex(ctx, np.asarray(p1)[:, :3])
+    dev = [ops.cloud_distortion_launch(ctx, index_a, clouds[m], p1_n) for m in live]
+    host = torch.stack(dev).cpu().numpy()
+    for m, t in zip(live, host):
+        out[m] = t
+    return out
+
+
+def cloud_metrics_batch_gpu(ctx, p1, p2_list, r, p1_n=None, index_a=None):
+    """cloud_metrics_batch's single-process result computed on the GPU: one reference-style dictionary per candidate decoded cloud
+    (None for an empty one), D1 and, with normals p1_n, D2.  Points are integer coordinates in [0, 2^21)."""
+    n_a = index_a.n if index_a is not None else len(p1)
+    groups = GROUPS if p1_n is not None else GROUPS[:1]
+    return [None if t is None else metrics_table(n_a, t[:5], r, groups) for t in cloud_tallies_gpu(ctx, p1, p2_list, p1_n, index_a)]

@@ -1,0 +1,185 @@
+"""GPU: whole-cloud D1 / D2 distortion and Hausdorff terms (include/pcc_geo.h "cloud metrics") against the numpy / scipy
+restatement in tests/_metrics_ref.py -- exact neighbour rows and squared distances, D1 sums and Hausdorff slots bit for bit, D2 to
+1e-12 -- against the host pc_metric path where no tie rule is involved, and through compress_octree / ev_report end to end."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import _metrics_ref as R
+from pcc_geo_cnn_v2_amd import ev_report, model_opt, ops
+from pcc_geo_cnn_v2_amd.estimate_normals import normals_frame
+from pcc_geo_cnn_v2_amd.utils import pc_io, pc_metric
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PAIRS = R.cloud_pairs()
+D1_SLOTS = [0, 1, 2, 5, 6]
+
+
+def _rel(x, y):
+    return np.abs(x - y) / np.maximum(np.abs(y), 1e-300)
+
+
+@pytest.mark.parametrize('name', sorted(PAIRS))
+def test_nearest_rows_and_distances_match_the_restatement(ctx, name):
+    a, b = PAIRS[name]
+    for src, dst in ((a, b), (b, a)):
+        index = ops.CloudIndex(ctx, dst)
+        nn, sq = ops.cloud_nearest(ctx, index, src)
+        ref_nn, ref_sq = R.nearest_ref(dst, src)
+        assert nn.dtype == np.int32 and sq.dtype == np.int64
+        assert np.array_equal(sq, ref_sq), (name, np.nonzero(sq != ref_sq)[0][:5])
+        bad = np.nonzero(nn != ref_nn)[0]
+        assert len(bad) == 0, (name, len(bad), bad[:3], nn[bad[:3]], ref_nn[bad[:3]])
+
+
+@pytest.mark.parametrize('name', sorted(PAIRS))
+def test_tally_matches_the_restatement_and_the_host_d1(ctx, name):
+    a, b = PAIRS[name]
+    nrm = R.unit_normals(len(a), 3)
+    got, to_b, to_a = ops.cloud_distortion(ctx, a, b, a_normals=nrm, return_links=True)
+    ref, ref_b, ref_a = R.tally_ref(a, b, nrm)
+    assert np.array_equal(to_b, ref_b) and np.array_equal(to_a, ref_a)
+    assert got.dtype == np.float64 and got.shape == (9,)
+    assert np.array_equal(got[D1_SLOTS], ref[D1_SLOTS]), (name, got, ref)              # D1 sums and H1 maxima: bit for bit
+    assert np.array_equal(got[[7, 8]], ref[[7, 8]]), (name, got, ref)                   # H2: per-point terms are numpy's bits
+    assert np.all(_rel(got[[3, 4]], ref[[3, 4]]) <= 1e-12), (name, got, ref)
+    # D1 does not depend on the tie rule: the host KD-tree path gives the same numbers
+    host = pc_metric.compute_metrics(a.astype(np.float64), b.astype(np.float64), 1023)
+    gpu = pc_metric.cloud_metrics_batch_gpu(ctx, a, [b], 1023)[0]
+    assert set(gpu) == set(host)
+    for k in host:
+        assert np.array_equal(np.float64(gpu[k]), np.float64(host[k])), (name, k, gpu[k], host[k])
+    # the host restatement of the Hausdorff slots agrees on D1 (the tie-free part)
+    assert np.array_equal(pc_metric.cloud_tally_host(a.astype(np.float64), b.astype(np.float64))[[5, 6]], got[[5, 6]])
+
+
+def test_tally_without_normals_and_with_a_reused_index(ctx):
+    a, b = PAIRS['uniform']
+    index = ops.CloudIndex(ctx, a)
+    t = ops.cloud_distortion(ctx, None, b, index_a=index)
+    ref, _, _ = R.tally_ref(a, b)
+    assert np.array_equal(t, ref)
+    assert np.array_equal(ops.cloud_distortion(ctx, torch.from_numpy(a).to(ctx.device), b), ref)     # device tensor input
+
+
+@pytest.mark.parametrize('name', ['shell_perturbed', 'lattice_sublattice', 'duplicates_in_b'])
+def test_two_calls_give_identical_bits(ctx, name):
+    a, b = PAIRS[name]
+    nrm = R.unit_normals(len(a), 4)
+    t1 = ops.cloud_distortion(ctx, a, b, nrm)
+    t2 = ops.cloud_distortion(ctx, a, b, nrm)
+    assert t1.tobytes() == t2.tobytes()
+    idx = ops.CloudIndex(ctx, b)
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(ops.cloud_nearest(ctx, idx, a), ops.cloud_nearest(ctx, idx, a)))
+
+
+def test_empty_candidates_give_none_and_launch_nothing(ctx, monkeypatch):
+    a, b = PAIRS['uniform']
+    calls = []
+    real = ops.cloud_distortion_launch
+    monkeypatch.setattr(ops, 'cloud_distortion_launch', lambda *x, **k: calls.append(1) or real(*x, **k))
+    assert pc_metric.cloud_metrics_batch_gpu(ctx, a, [np.zeros((0, 3))], 1023) == [None]
+    assert calls == []
+    built = []
+    monkeypatch.setattr(ops, 'CloudIndex', lambda *x, **k: built.append(1))
+    assert pc_metric.cloud_metrics_batch_gpu(ctx, a, [np.zeros((0, 3)), []], 1023) == [None, None]
+    assert built == []
+    monkeypatch.undo()
+    out = pc_metric.cloud_metrics_batch_gpu(ctx, a, [np.zeros((0, 3)), b, np.zeros((0, 3)), b[:100]], 1023)
+    assert out[0] is None and out[2] is None
+    host = pc_metric.cloud_metrics_batch(a.astype(np.float64), [np.zeros((0, 3)), b, np.zeros((0, 3)), b[:100]], 1023)
+    assert out[1] == host[1] and out[3] == host[3]
+
+
+def test_d2_matches_the_host_and_the_reference_on_the_tie_free_fixture(ctx):
+    """tests/golden/model_opt_d2_tiefree.npz: sparse blocks whose level sets never meet equidistant neighbours, so the tie rule
+    cannot matter.  Every level set's D1 / D2 metrics equal the host compute_metrics (1e-12) and the reference-produced values."""
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'model_opt_d2_tiefree.npz'))
+    thresholds = np.linspace(0, 1.0, 256)
+    checked = 0
+    for i in range(int(g['n_cases'][0])):
+        blk, xh = g[f's{i}_block'], g[f's{i}_x_hat']
+        keys, want = [str(k) for k in g[f's{i}_keys']], g[f's{i}_vals']
+        sets = model_opt.level_sets(xh, thresholds)
+        assert len(sets) == len(want)
+        a, n = blk[:, :3], blk[:, 3:]
+        index = ops.CloudIndex(ctx, a)
+        got = pc_metric.cloud_metrics_batch_gpu(ctx, a, [pts for _, pts in sets], 63, n, index_a=index)
+        # the float32 block: the reference (and the host path on float32 input) rounds its arithmetic to float32
+        ref_tol = 1e-12 if blk.dtype == np.float64 else 1e-6
+        for (t, pts), m in zip(sets, got):
+            host = pc_metric.compute_metrics(a.astype(np.float64), pts.astype(np.float64), 63, p1_n=n.astype(np.float64))
+            for k in keys:
+                assert _rel(m[k], host[k]) <= 1e-12, (i, t, k, m[k], host[k])
+                assert _rel(m[k], want[t, keys.index(k)]) <= ref_tol, (i, t, k, m[k], want[t, keys.index(k)])
+            for k in host:
+                if k.startswith('d1_'):
+                    assert np.float64(m[k]) == np.float64(host[k]) or (np.isnan(m[k]) and np.isnan(host[k])), (i, t, k)
+            checked += 1
+    assert checked >= 200
+
+
+def _cloud(res, seed):                                   # tests/test_cli_gpu.py::_cloud
+    g = np.stack(np.meshgrid(*[np.arange(res)] * 3, indexing='ij'), -1).reshape(-1, 3)
+    d = np.linalg.norm(g - res / 2 + 0.3, axis=1)
+    return g[np.abs(d - res * 0.37) < 0.7].astype(np.float32)
+
+
+def test_compress_octree_metrics_device_gpu_writes_the_host_stream_and_d1(tmp_path):
+    res, level = 128, 2
+    src = str(tmp_path / 'in.ply')
+    pc_io.write_df(src, pc_io.pa_to_df(_cloud(res, 0)))
+    ck = str(tmp_path / 'ckpt')
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    run = lambda *a: subprocess.run([sys.executable, '-m'] + list(a), cwd=ROOT, env=env, check=True, capture_output=True, text=True)
+    run('pcc_geo_cnn_v2_amd.init_checkpoint', '--model_config', 'c3p', '--checkpoint_dir', ck)
+    outs = {}
+    for dev in ('host', 'gpu'):
+        out, dec = str(tmp_path / dev / 'in.ply.bin'), str(tmp_path / dev / 'dec.ply')
+        run('pcc_geo_cnn_v2_amd.compress_octree', '--input_files', src, '--output_files', out, '--dec_files', dec, '--checkpoint_dir', ck,
+            '--model_config', 'c3p', '--resolution', str(res), '--octree_level', str(level), '--opt_metrics', 'd1_mse', '--batch_size', '5',
+            *(['--metrics_device', 'gpu'] if dev == 'gpu' else []))
+        outs[dev] = (open(out, 'rb').read(), json.load(open(out + '.enc.metric.json')), out, dec)
+    (hb, hm, hout, hdec), (gb, gm, gout, gdec) = outs['host'], outs['gpu']
+    assert hb == gb
+    assert 'metrics_device' not in hm and gm.pop('metrics_device') == 'gpu'
+    assert gm == hm                                       # d1 metrics only: the same numbers, and no other key
+    assert any(k.startswith('d1_') for k in hm)
+
+    # ev_report: the GPU engine gives the host's D1 keys; --hausdorff matches the host restatement
+    host = ev_report.build_report(src, hdec, hout, res, hausdorff=True)
+    gpu = ev_report.build_report(src, gdec, gout, res, metrics_device='gpu', hausdorff=True)
+    assert set(host) == set(gpu) and {'d1_hausdorff', 'd1_hausdorff_AB', 'd1_hausdorff_BA', 'd1_hausdorff_psnr'} <= set(gpu)
+    assert host == gpu
+    plain = ev_report.build_report(src, hdec, hout, res)
+    assert {k: host[k] for k in plain} == plain
+    cmd = [sys.executable, '-m', 'pcc_geo_cnn_v2_amd.ev_report', '--input_pc', src, '--decoded_pc', gdec, '--enc_pc', gout,
+           '--resolution', str(res), '--metrics_device', 'gpu', '--hausdorff', '--output', str(tmp_path / 'r.json')]
+    subprocess.run(cmd, cwd=ROOT, env=env, check=True, capture_output=True)     # includes the encoder/decoder D1 consistency assert
+    assert json.load(open(tmp_path / 'r.json')) == gpu
+
+
+def test_ev_report_gpu_d2_hausdorff_matches_the_restatement(tmp_path):
+    a, b = PAIRS['duplicates_in_b']
+    nrm = R.unit_normals(len(a), 5)
+    pc_io.write_pc(str(tmp_path / 'a.ply'), a.astype(np.float32))
+    pc_io.write_pc(str(tmp_path / 'b.ply'), b.astype(np.float32))
+    n_path = str(tmp_path / 'a_n.ply')
+    pc_io.write_df(n_path, normals_frame(a, nrm))
+    open(tmp_path / 'a.bin', 'wb').write(b'\x00' * 100)
+    n_read = pc_io.load_normals(n_path)
+    r = ev_report.build_report(str(tmp_path / 'a.ply'), str(tmp_path / 'b.ply'), str(tmp_path / 'a.bin'), 64, input_norm=n_path,
+                               metrics_device='gpu', hausdorff=True)
+    ref, _, _ = R.tally_ref(a, b, n_read)
+    want = pc_metric.hausdorff_table(ref, 63, with_normals=True)
+    assert {k: r[k] for k in want} == {k: float(v) for k, v in want.items()}
+    host = ev_report.build_report(str(tmp_path / 'a.ply'), str(tmp_path / 'b.ply'), str(tmp_path / 'a.bin'), 64, input_norm=n_path,
+                                  hausdorff=True)
+    assert all(r[k] == host[k] for k in ('d1_mse', 'd1_psnr', 'd1_hausdorff', 'd1_hausdorff_AB', 'd1_hausdorff_BA'))
+    assert _rel(r['d2_mse'], max(ref[3] / len(a), ref[4] / len(b))) <= 1e-12
