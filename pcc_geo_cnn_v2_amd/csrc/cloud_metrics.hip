@@ -10,31 +10,19 @@
 //   - the normal of decoded point j on the A->B side is pc_metric.transfer_normals: the mean of a_normals[i] over to_b[i] == j,
 //     summed in float64 in increasing i, or a_normals[to_a[j]] when no original point links to j.
 //
-// Index: the normals.hip grid.  63-bit Morton codes, a hipCUB radix sort of (code, row), records (x, y, z, row) in that order, and a
-// base cell level from the histogram of the highest differing Morton bit of adjacent codes: the smallest L whose occupied cells hold
-// two points or more on average.  The cells of edge 2^L are contiguous ranges of the sorted codes.
-// Query (k_query), one lane per query: the cube of cells of Chebyshev radius 0, 1, 2 around the query cell, then radius 2 at the
-// next coarser levels, until the best squared distance is STRICTLY below the squared distance to the outside of the visited box
-// (an equidistant point with a lower row could lie just outside) or the box holds the indexed cloud's bounding box.
+// Index: the cell index of cell_index.h, base level for two points per occupied cell.
+// Query (k_query), one lane per query: the index search from Chebyshev radius 0, keeping the best (squared distance, row) pair.
 // Tally: a stable radix sort of (to_b[i], i) makes every decoded point's original points a segment in increasing i (k_segments,
 // k_bnormals: one sequential float64 sum per segment, numpy bincount's order); k_tally reduces each direction into per-block
 // partials, k_finish adds the partials in a fixed order.  The only atomics are the index build's integer ones (bounding box,
-// histogram); nothing synchronises with the host: the same inputs give the same bits on every call.
+// coordinate sums, histogram); nothing synchronises with the host: the same inputs give the same bits on every call.
 #include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "cell_index.h"
 
 namespace {
 
-constexpr int kCoordMask = (1 << 21) - 1;
-constexpr int kLevels = 22;           // cell edge 2^L, L = 0 .. 21 (L = 21: one cell holds the whole domain)
 constexpr int kTallyBlocks = 1024;    // upper bound of the partials of one direction (fixed per n: the sum order depends on n only)
-
-struct IndexHdr {
-    int bmin[3], bmax[3];             // bounding box of the indexed cloud
-    unsigned hist[kLevels];           // adjacent sorted pairs by floor(highest differing Morton bit / 3)
-    int level;                        // base cell level of the search
-};
 
 struct Partial {                      // one workgroup's share of one direction
     unsigned long long d1_lo, d1_hi;  // exact sum of the squared distances (128 bits)
@@ -42,150 +30,16 @@ struct Partial {                      // one workgroup's share of one direction
     double d2, h2;                    // sum / max of the per-point plane terms
 };
 
-__device__ __forceinline__ unsigned long long spread3(unsigned v) {
-    unsigned long long x = v & kCoordMask;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-__device__ __forceinline__ unsigned long long morton(int x, int y, int z) {
-    return spread3((unsigned)x) << 2 | spread3((unsigned)y) << 1 | spread3((unsigned)z);
-}
-
-// coordinates outside [0, 2^21) are a precondition violation (the Python layer refuses them); masking keeps every cell
-// computation inside the domain whatever arrives
-__device__ __forceinline__ int3 load_pt(const int32_t* pts, long long i) {
-    return make_int3(pts[3 * i] & kCoordMask, pts[3 * i + 1] & kCoordMask, pts[3 * i + 2] & kCoordMask);
-}
-
-// ---- index ---------------------------------------------------------------------------------------------------------------------
-
-struct IndexLayout {
-    size_t hdr, codes, recs, pts, codes0, rows0, rows1, sort_tmp, sort_tmp_bytes, total;
-};
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-IndexLayout index_layout(long long n) {
-    IndexLayout l;
-    const size_t N = (size_t)n;
-    size_t o = 0;
-    l.hdr = o; o += al256(sizeof(IndexHdr));
-    l.codes = o; o += al256(N * 8);
-    l.recs = o; o += al256(N * 16);
-    l.pts = o; o += al256(N * 12);
-    l.codes0 = o; o += al256(N * 8);
-    l.rows0 = o; o += al256(N * 4);
-    l.rows1 = o; o += al256(N * 4);
-    size_t tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(n > 0 ? n : 1), 0, 63, (hipStream_t)0);
-    l.sort_tmp_bytes = tmp;
-    l.sort_tmp = o; o += al256(tmp + 256);
-    l.total = o;
-    return l;
-}
-
-struct IndexView {                    // device pointers of a built index
-    const IndexHdr* hdr;
-    const unsigned long long* codes;
-    const int4* recs;
-    const int32_t* pts;
-    long long n;
-};
-
-IndexView index_view(const void* index, long long n) {
-    const IndexLayout l = index_layout(n);
-    const unsigned char* b = (const unsigned char*)index;
-    return IndexView{(const IndexHdr*)(b + l.hdr), (const unsigned long long*)(b + l.codes), (const int4*)(b + l.recs),
-                     (const int32_t*)(b + l.pts), n};
-}
-
-__global__ void k_init(IndexHdr* H) {
-    for (int a = 0; a < 3; ++a) { H->bmin[a] = kCoordMask; H->bmax[a] = 0; }
-    for (int l = 0; l < kLevels; ++l) H->hist[l] = 0;
-    H->level = 0;
-}
-
-// grid-stride, one set of atomics per workgroup (normals.hip k_prepare); also keeps a masked row-order copy of the points
-__global__ void __launch_bounds__(256) k_prepare(const int32_t* __restrict__ pts, long long n, unsigned long long* __restrict__ codes,
-                                                 unsigned* __restrict__ rows, int32_t* __restrict__ copy, IndexHdr* H) {
-    __shared__ int slo[4][3], shi[4][3];
-    int lo[3] = {kCoordMask, kCoordMask, kCoordMask}, hi[3] = {0, 0, 0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const int3 p = load_pt(pts, i);
-        codes[i] = morton(p.x, p.y, p.z);
-        rows[i] = (unsigned)i;
-        copy[3 * i] = p.x; copy[3 * i + 1] = p.y; copy[3 * i + 2] = p.z;
-        lo[0] = min(lo[0], p.x); lo[1] = min(lo[1], p.y); lo[2] = min(lo[2], p.z);
-        hi[0] = max(hi[0], p.x); hi[1] = max(hi[1], p.y); hi[2] = max(hi[2], p.z);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            lo[a] = min(lo[a], __shfl_xor(lo[a], off));
-            hi[a] = max(hi[a], __shfl_xor(hi[a], off));
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { slo[wave][a] = lo[a]; shi[wave][a] = hi[a]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        int l = slo[0][a], h = shi[0][a];
-        for (int w = 1; w < 4; ++w) { l = min(l, slo[w][a]); h = max(h, shi[w][a]); }
-        atomicMin(&H->bmin[a], l);
-        atomicMax(&H->bmax[a], h);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_records(const int32_t* __restrict__ copy, long long n, const unsigned long long* __restrict__ codes,
-                                                 const unsigned* __restrict__ rows, int4* __restrict__ recs, IndexHdr* H) {
-    __shared__ unsigned h[kLevels];
-    if (threadIdx.x < kLevels) h[threadIdx.x] = 0;
-    __syncthreads();
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < n) {
-        const unsigned r = rows[t];
-        recs[t] = make_int4(copy[3 * (long long)r], copy[3 * (long long)r + 1], copy[3 * (long long)r + 2], (int)r);
-        if (t > 0) {
-            const unsigned long long d = codes[t] ^ codes[t - 1];
-            if (d) atomicAdd(&h[(63 - __clzll((long long)d)) / 3], 1u);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < kLevels && h[threadIdx.x]) atomicAdd(&H->hist[threadIdx.x], h[threadIdx.x]);
-}
-
-// base level: the smallest L whose occupied cells hold two points or more on average (L = 21 always qualifies)
-__global__ void k_params(long long n, IndexHdr* H) {
-    unsigned long long occ = 1;                 // occupied cells of edge 1: one more than the adjacent pairs that differ
-    for (int l = 0; l < kLevels; ++l) occ += H->hist[l];
-    int level = kLevels - 1;
-    for (int l = 0; l < kLevels; ++l) {
-        if ((unsigned long long)n >= 2ull * occ) { level = l; break; }
-        occ -= H->hist[l];                      // pairs that differ at level l but not above: merged one level up
-    }
-    H->level = level;
-}
-
 // ---- query ---------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ long long lower_bound(const unsigned long long* __restrict__ codes, long long n, unsigned long long key) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (codes[mid] < key) lo = mid + 1; else hi = mid;
+struct Nearest {                      // the lowest (squared distance, row) so far
+    unsigned long long d2 = ~0ull;
+    unsigned row = ~0u;
+    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
+        if (d < d2 || (d == d2 && r < row)) { d2 = d; row = r; }
     }
-    return lo;
-}
+    __device__ __forceinline__ unsigned long long bound() const { return d2; }
+};
 
 // One lane per query.  RECS: the queries are another index's records (Morton order: a wave's lanes are neighbours in space, and
 // the result goes to the record's row); otherwise row-order points.  Writes nn[row] and sqd[row] (either may be NULL).
@@ -194,10 +48,7 @@ __global__ void __launch_bounds__(256) k_query(const IndexHdr* __restrict__ H, c
                                                const int4* __restrict__ recs, long long n, const int4* __restrict__ qrecs,
                                                const int32_t* __restrict__ qpts, long long nq, int32_t* __restrict__ nn,
                                                long long* __restrict__ sqd) {
-    const int base = H->level;
-    int bmin[3], bmax[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { bmin[a] = H->bmin[a]; bmax[a] = H->bmax[a]; }
+    const Cells g = cells(H, codes, recs, n);
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += (long long)gridDim.x * blockDim.x) {
         int qc[3];
         long long row;
@@ -210,54 +61,9 @@ __global__ void __launch_bounds__(256) k_query(const IndexHdr* __restrict__ H, c
             qc[0] = q.x; qc[1] = q.y; qc[2] = q.z;
             row = t;
         }
-        unsigned long long best_d = ~0ull;
-        unsigned best_r = ~0u;
-        int level = base, rad = 0;
-        bool have_prev = false;
-        int plo[3] = {0, 0, 0}, phi[3] = {0, 0, 0};
-        for (;;) {
-            const int e = 1 << level;
-            int c[3], clo[3], chi[3], blo[3], bhi[3];
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                c[ax] = qc[ax] >> level;
-                clo[ax] = max(c[ax] - rad, bmin[ax] >> level);
-                chi[ax] = min(c[ax] + rad, bmax[ax] >> level);
-                blo[ax] = (c[ax] - rad) * e;
-                bhi[ax] = (c[ax] + rad + 1) * e - 1;
-            }
-            for (int cx = clo[0]; cx <= chi[0]; ++cx)
-                for (int cy = clo[1]; cy <= chi[1]; ++cy)
-                    for (int cz = clo[2]; cz <= chi[2]; ++cz) {
-                        if (have_prev && cx * e >= plo[0] && (cx + 1) * e - 1 <= phi[0] && cy * e >= plo[1] && (cy + 1) * e - 1 <= phi[1] &&
-                            cz * e >= plo[2] && (cz + 1) * e - 1 <= phi[2])
-                            continue;                                        // visited at the previous stage
-                        const unsigned long long key0 = morton(cx, cy, cz) << (3 * level);
-                        for (long long pos = lower_bound(codes, n, key0); pos < n; ++pos) {
-                            const int4 r = recs[pos];
-                            if ((r.x >> level) != cx || (r.y >> level) != cy || (r.z >> level) != cz) break;
-                            if (have_prev && r.x >= plo[0] && r.x <= phi[0] && r.y >= plo[1] && r.y <= phi[1] && r.z >= plo[2] && r.z <= phi[2])
-                                continue;
-                            const long long dx = r.x - qc[0], dy = r.y - qc[1], dz = r.z - qc[2];
-                            const unsigned long long d = (unsigned long long)(dx * dx + dy * dy + dz * dz);
-                            if (d < best_d || (d == best_d && (unsigned)r.w < best_r)) { best_d = d; best_r = (unsigned)r.w; }
-                        }
-                    }
-            // nearest possible unvisited point: just outside a face of the box; faces beyond the cloud's box hide nothing
-            long long gap = -1;
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) {
-                if (blo[ax] > bmin[ax]) { const long long g = qc[ax] - blo[ax] + 1; gap = gap < 0 || g < gap ? g : gap; }
-                if (bhi[ax] < bmax[ax]) { const long long g = bhi[ax] + 1 - qc[ax]; gap = gap < 0 || g < gap ? g : gap; }
-            }
-            if (gap < 0 || best_d < (unsigned long long)(gap * gap)) break;
-#pragma unroll
-            for (int ax = 0; ax < 3; ++ax) { plo[ax] = blo[ax]; phi[ax] = bhi[ax]; }
-            have_prev = true;
-            if (rad < 2) ++rad; else ++level;               // level 21 at radius 2 holds the whole domain: the loop always ends
-        }
-        if (nn) nn[row] = (int32_t)best_r;
-        if (sqd) sqd[row] = (long long)best_d;
+        const Nearest best = search(g, qc, 0, Nearest());
+        if (nn) nn[row] = (int32_t)best.row;
+        if (sqd) sqd[row] = (long long)best.d2;
     }
 }
 
@@ -467,26 +273,7 @@ PCC_API int pcc_cloud_index_build(pcc_ctx* ctx, const int32_t* pts, int64_t npts
     PCC_REQUIRE(ctx && pts && index, "pcc_cloud_index_build: NULL argument");
     PCC_REQUIRE(valid_n(npts), "pcc_cloud_index_build: npts = %lld outside [1, 2^31)", (long long)npts);
     PCC_CHECK_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const long long n = npts;
-    const IndexLayout l = index_layout(n);
-    unsigned char* w = (unsigned char*)index;
-    IndexHdr* H = (IndexHdr*)(w + l.hdr);
-    unsigned long long *codes0 = (unsigned long long*)(w + l.codes0), *codes = (unsigned long long*)(w + l.codes);
-    unsigned *rows0 = (unsigned*)(w + l.rows0), *rows1 = (unsigned*)(w + l.rows1);
-    int32_t* copy = (int32_t*)(w + l.pts);
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    const unsigned cus = (unsigned)(ctx->num_cu > 0 ? ctx->num_cu : 256);
-    hipLaunchKernelGGL(k_init, dim3(1), dim3(1), 0, st, H);
-    hipLaunchKernelGGL(k_prepare, dim3(blocks < cus ? blocks : cus), dim3(256), 0, st, pts, n, codes0, rows0, copy, H);
-    size_t tmp = l.sort_tmp_bytes;
-    PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w + l.sort_tmp), tmp, (const unsigned long long*)codes0, codes,
-                                                     (const unsigned*)rows0, rows1, (int)n, 0, 63, st));
-    hipLaunchKernelGGL(k_records, dim3(blocks), dim3(256), 0, st, (const int32_t*)copy, n, (const unsigned long long*)codes,
-                       (const unsigned*)rows1, (int4*)(w + l.recs), H);
-    hipLaunchKernelGGL(k_params, dim3(1), dim3(1), 0, st, n, H);
-    PCC_CHECK_HIP(hipGetLastError());
-    return PCC_OK;
+    return index_build(ctx, pts, npts, index, 4, (hipStream_t)stream);
 }
 
 PCC_API int pcc_cloud_nearest(pcc_ctx* ctx, const void* index, int64_t npts, const int32_t* queries, int64_t nq, int32_t* nn,

@@ -671,9 +671,8 @@ def estimate_normals(ctx, points, k=16, viewpoint=None, return_knn=False):
         vp = np.asarray(viewpoint, np.float64).reshape(-1)
         if vp.shape != (3,) or not np.isfinite(vp).all():
             raise L.PccError(f'estimate_normals: viewpoint must be 3 finite numbers, got {viewpoint!r}')
-    pts = _voxel_points(points)
+    pts_d = _device_points(ctx, points, 'estimate_normals')
     dev = ctx.device
-    pts_d = pts.to(dev) if isinstance(pts, torch.Tensor) else torch.from_numpy(pts).to(dev)
     n = pts_d.shape[0]
     vp_d = None if vp is None else torch.from_numpy(vp).to(dev)
     normals = torch.empty((n, 3), dtype=torch.float32, device=dev)
