@@ -383,6 +383,27 @@ size_t pcc_cloud_distortion_workspace_bytes(int64_t na, int64_t nb);
 int pcc_cloud_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const void* index_b, int64_t nb, const double* a_normals,
                          double* tally, int32_t* to_b, int32_t* to_a, void* workspace, void* stream);
 
+/* ---- cloud colours (new: the colour step of the reference's evaluation, src/map_color.py, and pc_error's colour terms) ---------
+ * Colour transfer and colour distortion across two voxelised clouds on the indices of "cloud metrics" (same point contract).
+ * Colours: (n,3) uint8 R, G, B in row order, device memory.  Definition:
+ *   - the indexed points of a query q in order: rows j sorted by (|p_j - q|^2, j), exact integers, lexicographic;
+ *   - pcc_cloud_map_colors writes, for each query row i, out_colours[i] = colours of the rank-th point of that order and, when
+ *     rows is non-NULL, rows[i] = its row (int32).  rank 1 is pcc_cloud_nearest's row; rank 2 is src/map_color.py (the second of a
+ *     k = 2 KD-tree query); rank 2 needs npts >= 2.  The queries are given as their own index (pcc_cloud_index_build over the nq
+ *     query points): they are answered in its Morton order;
+ *   - colour distortion of A (original) and B (decoded): for each point q of A, over ALL points of B at the smallest squared
+ *     distance, m = (exact integer colour sums) / count and d = c_q - m in float64; then eY = (0.2126 dR + 0.7152 dG) + 0.0722 dB,
+ *     eU = (-0.1146 dR - 0.3854 dG) + 0.5 dB, eV = (0.5 dR - 0.4542 dG) - 0.0458 dB (BT.709), every operation rounded (no
+ *     contraction).  tally (device) = float64[6]: the sums of eY^2, eU^2, eV^2 over A (A->B), then the same over B against A
+ *     (B->A), summed in a fixed order that depends on the sizes only: the same inputs give the same bits on every call.  Averaging
+ *     over the equidistant set makes the tally independent of the row order of either cloud.  workspace:
+ *     pcc_cloud_color_workspace_bytes(na, nb) bytes (0 for a size outside [1, 2^31)).  No host synchronisation.          */
+int pcc_cloud_map_colors(pcc_ctx* ctx, const void* index, int64_t npts, const uint8_t* colours, const void* query_index, int64_t nq,
+                         int32_t rank, uint8_t* out_colours, int32_t* rows, void* stream);
+size_t pcc_cloud_color_workspace_bytes(int64_t na, int64_t nb);
+int pcc_cloud_color_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const uint8_t* a_colours, const void* index_b, int64_t nb,
+                               const uint8_t* b_colours, double* tally, void* workspace, void* stream);
+
 /* ---- focal loss (src/utils/focal_loss.py:5-12) ------------------------------------------
  * Deterministic two-stage reduction (wavefront DPP/shuffle tree, fixed block order); result is a
  * single float32 written to out[0] (device).  `scratch` must hold pcc_focal_scratch_floats().   */

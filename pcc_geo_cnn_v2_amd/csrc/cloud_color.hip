@@ -1,0 +1,221 @@
+// Colour transfer and colour distortion across two voxelised clouds (include/pcc_geo.h "cloud colours").
+//
+// Definition (pinned by tests/test_color_gpu.py against the numpy / scipy restatement in tests/_color_ref.py):
+//   - the indexed points of a query q in order: the rows j sorted by (|p_j - q|^2, j), exact integers, lexicographic;
+//   - map: the colour (and row) of the rank-th point of that order, rank 1 or 2 (rank 1 is pcc_cloud_nearest's row; rank 2 is the
+//     reference's map_color.py, which takes the second of a k = 2 KD-tree query);
+//   - distortion: over ALL indexed points at the smallest squared distance, the exact integer sums S of R, G, B and their count;
+//     m = S / count and d = c_q - m in float64, then the BT.709 terms eY = (0.2126 dR + 0.7152 dG) + 0.0722 dB,
+//     eU = (-0.1146 dR - 0.3854 dG) + 0.5 dB, eV = (0.5 dR - 0.4542 dG) - 0.0458 dB, every operation rounded (no contraction);
+//     tally float64[6] = the sums of eY^2, eU^2, eV^2 for A -> B (each A point against B), then for B -> A.
+//
+// Search: the cell index of cell_index.h (built by pcc_cloud_index_build), one lane per query, queries in the query cloud's
+// Morton order (its index records), as k_query<true> of cloud_metrics.hip.  Tally: the per-point terms are written by row and
+// summed by k_ctally / k_cfinish in an order fixed by the sizes; nothing synchronises with the host.
+#include "cell_index.h"
+
+namespace {
+
+constexpr int kColorBlocks = 1024;    // upper bound of the partials of one direction (fixed per n: the sum order depends on n only)
+
+// ---- map -----------------------------------------------------------------------------------------------------------------------
+
+// the two lowest (squared distance, row) pairs so far; bound: the RANK-th best, ~0 until RANK points have been seen
+template <int RANK>
+struct TwoBest {
+    unsigned long long d0 = ~0ull, d1 = ~0ull;
+    unsigned r0 = ~0u, r1 = ~0u;
+    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
+        if (d < d1 || (d == d1 && r < r1)) {
+            if (d < d0 || (d == d0 && r < r0)) { d1 = d0; r1 = r0; d0 = d; r0 = r; }
+            else { d1 = d; r1 = r; }
+        }
+    }
+    __device__ __forceinline__ unsigned long long bound() const { return RANK == 1 ? d0 : d1; }
+};
+
+// One lane per query record (Morton order); writes out[3 * row ..] and rows[row] (may be NULL) for the record's row.
+template <int RANK>
+__global__ void __launch_bounds__(256) k_map(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
+                                             const int4* __restrict__ recs, long long n, const uint8_t* __restrict__ colours,
+                                             const int4* __restrict__ qrecs, long long nq, uint8_t* __restrict__ out,
+                                             int32_t* __restrict__ rows) {
+    const Cells g = cells(H, codes, recs, n);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += (long long)gridDim.x * blockDim.x) {
+        const int4 q = qrecs[t];
+        const int qc[3] = {q.x, q.y, q.z};
+        const TwoBest<RANK> best = search(g, qc, 0, TwoBest<RANK>());
+        const long long r = RANK == 1 ? best.r0 : best.r1;    // n >= RANK: the search has seen at least RANK points
+        const long long row = q.w;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[3 * row + c] = colours[3 * r + c];
+        if (rows) rows[row] = (int32_t)r;
+    }
+}
+
+// ---- distortion ----------------------------------------------------------------------------------------------------------------
+
+// every point at the smallest squared distance so far: their count and exact colour sums
+struct TieSet {
+    const uint8_t* colours;
+    unsigned long long d2 = ~0ull;
+    unsigned long long count = 0, s[3] = {0, 0, 0};
+    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
+        if (d > d2) return;
+        if (d < d2) { d2 = d; count = 0; s[0] = s[1] = s[2] = 0; }
+        ++count;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += colours[3 * (long long)r + c];
+    }
+    __device__ __forceinline__ unsigned long long bound() const { return d2; }
+};
+
+// One lane per query record of the source cloud against the destination index: terms[3 * row ..] = (eY^2, eU^2, eV^2).
+__global__ void __launch_bounds__(256) k_cterms(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
+                                                const int4* __restrict__ recs, long long n, const uint8_t* __restrict__ colours,
+                                                const int4* __restrict__ qrecs, const uint8_t* __restrict__ qcolours, long long nq,
+                                                double* __restrict__ terms) {
+#pragma clang fp contract(off)
+    const Cells g = cells(H, codes, recs, n);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += (long long)gridDim.x * blockDim.x) {
+        const int4 q = qrecs[t];
+        const int qc[3] = {q.x, q.y, q.z};
+        TieSet init;
+        init.colours = colours;
+        const TieSet ties = search(g, qc, 0, init);
+        const long long row = q.w;
+        const double cnt = (double)ties.count;                  // exact: count < 2^31, sums < 2^39
+        const double dR = (double)qcolours[3 * row] - (double)ties.s[0] / cnt;
+        const double dG = (double)qcolours[3 * row + 1] - (double)ties.s[1] / cnt;
+        const double dB = (double)qcolours[3 * row + 2] - (double)ties.s[2] / cnt;
+        const double eY = (0.2126 * dR + 0.7152 * dG) + 0.0722 * dB;
+        const double eU = (-0.1146 * dR - 0.3854 * dG) + 0.5 * dB;
+        const double eV = (0.5 * dR - 0.4542 * dG) - 0.0458 * dB;
+        terms[3 * row] = eY * eY;
+        terms[3 * row + 1] = eU * eU;
+        terms[3 * row + 2] = eV * eV;
+    }
+}
+
+// Grid-stride over the rows with a grid fixed by n, then a fixed tree in the workgroup: partial[3 * block ..].
+__global__ void __launch_bounds__(256) k_ctally(const double* __restrict__ terms, long long n, double* __restrict__ partial) {
+    __shared__ double s[3][256];
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += terms[3 * i + c];
+    }
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s[c][t] = acc[c];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s[c][t] += s[c][t + w];
+        }
+        __syncthreads();
+    }
+    if (t < 3) partial[3 * blockIdx.x + t] = s[t][0];
+}
+
+// one workgroup: the partials of A -> B (ga of them) and B -> A (gb), each direction summed in a fixed order
+__global__ void __launch_bounds__(256) k_cfinish(const double* __restrict__ pab, int ga, const double* __restrict__ pba, int gb,
+                                                 double* __restrict__ tally) {
+    __shared__ double s[6][256];
+    const int t = threadIdx.x;
+    for (int side = 0; side < 2; ++side) {
+        const double* p = side ? pba : pab;
+        const int g = side ? gb : ga;
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int b = t; b < g; b += 256) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += p[3 * b + c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[3 * side + c][t] = acc[c];
+    }
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s[k][t] += s[k][t + w];
+        }
+        __syncthreads();
+    }
+    if (t < 6) tally[t] = s[t][0];
+}
+
+int color_blocks(long long n) {
+    const long long b = (n + 255) / 256;
+    return (int)(b < kColorBlocks ? b : kColorBlocks);
+}
+
+struct ColorLayout {
+    size_t terms_a, terms_b, pab, pba, total;
+};
+
+ColorLayout color_layout(long long na, long long nb) {
+    ColorLayout l;
+    size_t o = 0;
+    l.terms_a = o; o += al256((size_t)na * 24);
+    l.terms_b = o; o += al256((size_t)nb * 24);
+    l.pab = o; o += al256(kColorBlocks * 24);
+    l.pba = o; o += al256(kColorBlocks * 24);
+    l.total = o;
+    return l;
+}
+
+bool valid_n(int64_t n) { return n > 0 && n < ((int64_t)1 << 31); }
+
+}  // namespace
+
+PCC_API int pcc_cloud_map_colors(pcc_ctx* ctx, const void* index, int64_t npts, const uint8_t* colours, const void* query_index, int64_t nq,
+                                 int32_t rank, uint8_t* out_colours, int32_t* rows, void* stream) {
+    PCC_REQUIRE(ctx && index && colours && query_index && out_colours, "pcc_cloud_map_colors: NULL argument");
+    PCC_REQUIRE(valid_n(npts) && valid_n(nq), "pcc_cloud_map_colors: npts = %lld, nq = %lld outside [1, 2^31)", (long long)npts,
+                (long long)nq);
+    PCC_REQUIRE(rank == 1 || rank == 2, "pcc_cloud_map_colors: rank = %d, must be 1 or 2", (int)rank);
+    PCC_REQUIRE(npts >= rank, "pcc_cloud_map_colors: rank %d needs at least %d indexed points, got %lld", (int)rank, (int)rank,
+                (long long)npts);
+    PCC_CHECK_HIP(hipSetDevice(ctx->device));
+    const IndexView v = index_view(index, npts), q = index_view(query_index, nq);
+    const dim3 grid((unsigned)((nq + 255) / 256));
+    if (rank == 1)
+        hipLaunchKernelGGL(k_map<1>, grid, dim3(256), 0, (hipStream_t)stream, v.hdr, v.codes, v.recs, v.n, colours, q.recs, q.n,
+                           out_colours, rows);
+    else
+        hipLaunchKernelGGL(k_map<2>, grid, dim3(256), 0, (hipStream_t)stream, v.hdr, v.codes, v.recs, v.n, colours, q.recs, q.n,
+                           out_colours, rows);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+PCC_API size_t pcc_cloud_color_workspace_bytes(int64_t na, int64_t nb) {
+    if (!valid_n(na) || !valid_n(nb)) return 0;
+    return color_layout(na, nb).total;
+}
+
+PCC_API int pcc_cloud_color_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const uint8_t* a_colours, const void* index_b,
+                                       int64_t nb, const uint8_t* b_colours, double* tally, void* workspace, void* stream) {
+    PCC_REQUIRE(ctx && index_a && a_colours && index_b && b_colours && tally && workspace, "pcc_cloud_color_distortion: NULL argument");
+    PCC_REQUIRE(valid_n(na) && valid_n(nb), "pcc_cloud_color_distortion: na = %lld, nb = %lld outside [1, 2^31)", (long long)na,
+                (long long)nb);
+    PCC_CHECK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const IndexView A = index_view(index_a, na), B = index_view(index_b, nb);
+    const ColorLayout l = color_layout(na, nb);
+    unsigned char* w = (unsigned char*)workspace;
+    double *terms_a = (double*)(w + l.terms_a), *terms_b = (double*)(w + l.terms_b);
+    double *pab = (double*)(w + l.pab), *pba = (double*)(w + l.pba);
+    hipLaunchKernelGGL(k_cterms, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, b_colours, A.recs,
+                       a_colours, A.n, terms_a);
+    hipLaunchKernelGGL(k_cterms, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, a_colours, B.recs,
+                       b_colours, B.n, terms_b);
+    const int ta = color_blocks(na), tb = color_blocks(nb);
+    hipLaunchKernelGGL(k_ctally, dim3(ta), dim3(256), 0, st, (const double*)terms_a, (long long)na, pab);
+    hipLaunchKernelGGL(k_ctally, dim3(tb), dim3(256), 0, st, (const double*)terms_b, (long long)nb, pba);
+    hipLaunchKernelGGL(k_cfinish, dim3(1), dim3(256), 0, st, (const double*)pab, ta, (const double*)pba, tb, tally);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}

@@ -8,10 +8,12 @@ utils/pc_metric.compute_metrics, the module the encoder itself uses for its `.en
 ev_experiment.py:158-162) carries over.
 
     python -m pcc_geo_cnn_v2_amd.ev_report --input_pc a.ply --decoded_pc a.ply.bin.ply --enc_pc a.ply.bin \\
-        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] [--metrics_device host|gpu] [--hausdorff] --output report_d1.json
+        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] [--metrics_device host|gpu] [--hausdorff] [--color] --output report_d1.json
 
 `--metrics_device gpu` computes the metrics with the GPU engine (include/pcc_geo.h "cloud metrics": neighbour ties to the lowest
-row); `--hausdorff` adds pc_error's Hausdorff terms (utils/pc_metric.hausdorff_table).  Without them the report is unchanged.
+row); `--hausdorff` adds pc_error's Hausdorff terms (utils/pc_metric.hausdorff_table); `--color` adds pc_error's colour keys
+y/u/v_mse and y/u/v_psnr (utils/pc_metric.color_table; both clouds must carry colours: recolour a decoded cloud with map_color).
+Without them the report is unchanged.
 """
 import argparse
 import json
@@ -21,17 +23,20 @@ import os
 import numpy as np
 
 from .utils import pc_io
-from .utils.pc_metric import cloud_tally_host, cloud_tallies_gpu, compute_metrics, hausdorff_table, metrics_table
+from .utils.pc_metric import (cloud_tally_host, cloud_tallies_gpu, color_table, color_tally_host, compute_metrics, hausdorff_table,
+                              metrics_table)
 
 logger = logging.getLogger(__name__)
 
 
 def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, estimate_normals=False, normals_k=16,
-                 metrics_device='host', hausdorff=False):
+                 metrics_device='host', hausdorff=False, color=False):
     if input_norm and estimate_normals:
         raise AssertionError('--estimate_normals and --input_norm are mutually exclusive')
     p1 = pc_io.load_pc(input_pc)
     p2 = pc_io.load_pc(decoded_pc)
+    if color:
+        c1, c2 = load_report_colors(input_pc, decoded_pc)
     n1 = pc_io.load_normals(input_norm) if input_norm else None
     if estimate_normals:
         from . import ops
@@ -42,11 +47,15 @@ def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, esti
     if metrics_device == 'gpu':
         from . import ops
         assert len(b), 'compute_metrics: empty decoded cloud'
-        tally = cloud_tallies_gpu(ops.get_context(), a, [b], n1)[0]
+        ctx = ops.get_context()
+        index_a = ops.CloudIndex(ctx, a)
+        tally = cloud_tallies_gpu(ctx, a, [b], n1, index_a=index_a)[0]
         m = metrics_table(len(a), tally[:5], resolution - 1, ('d1', 'd2') if n1 is not None else ('d1',))
+        color_tally = ops.cloud_color_distortion(ctx, index_a, c1, b, c2) if color else None
     elif metrics_device == 'host':
         m = compute_metrics(a, b, resolution - 1, p1_n=n1)
         tally = cloud_tally_host(a, b, n1) if hausdorff else None
+        color_tally = color_tally_host(a, c1, b, c2) if color else None
     else:
         raise AssertionError(f'metrics_device must be host or gpu, got {metrics_device!r}')
     size = os.stat(enc_pc).st_size
@@ -54,7 +63,21 @@ def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, esti
     data.update({k: float(v) for k, v in m.items() if k in ('d1_mse', 'd1_psnr', 'd2_mse', 'd2_psnr')})
     if hausdorff:
         data.update({k: float(v) for k, v in hausdorff_table(tally, resolution - 1, n1 is not None).items()})
+    if color:
+        data.update({k: float(v) for k, v in color_table(color_tally, len(a), len(b)).items()})
     return data
+
+
+def load_report_colors(input_pc, decoded_pc):
+    """The colours of --color: both clouds must carry them.  A decoded cloud straight from the codec has none; map_color gives it
+    the original's."""
+    c1 = pc_io.load_colors(input_pc)
+    try:
+        c2 = pc_io.load_colors(decoded_pc)
+    except ValueError as e:
+        raise ValueError(f'--color: {e}; recolour the decoded cloud first: python -m pcc_geo_cnn_v2_amd.map_color {input_pc} '
+                         f'{decoded_pc} <output.ply>') from None
+    return c1, c2
 
 
 def main():
@@ -73,13 +96,15 @@ def main():
                    help='Where the metrics run: host = scipy KD-trees, gpu = the HIP engine (ties to the lowest row; new)')
     p.add_argument('--hausdorff', default=False, action='store_true',
                    help="Add pc_error's Hausdorff terms: d1_hausdorff[_AB|_BA|_psnr] (+ d2_* with normals; new)")
+    p.add_argument('--color', default=False, action='store_true',
+                   help="Add pc_error's colour keys y/u/v_mse and y/u/v_psnr (both clouds need red green blue; see map_color; new)")
     p.add_argument('--resolution', type=int, required=True, help='Voxel grid resolution of the input (peak = resolution - 1)')
     p.add_argument('--output', required=True, help='Report JSON path')
     args = p.parse_args()
     if args.input_norm and args.estimate_normals:
         p.error('--estimate_normals and --input_norm are mutually exclusive')
     data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm, args.estimate_normals, args.normals_k,
-                        args.metrics_device, args.hausdorff)
+                        args.metrics_device, args.hausdorff, args.color)
     with open(args.output, 'w') as f:
         json.dump(data, f, sort_keys=True, indent=4)
     enc_metric = args.enc_pc + '.enc.metric.json'

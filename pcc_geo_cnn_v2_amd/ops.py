@@ -777,6 +777,94 @@ def cloud_distortion(ctx, a, b, a_normals=None, index_a=None, return_links=False
     return out.cpu().numpy()
 
 
+COLOR_TALLY_SLOTS = 6      # include/pcc_geo.h "cloud colours": Y, U, V sums of A->B, then of B->A
+
+
+def _colors_u8(colors, n, what):
+    """Host-side check of an (n,3) colour array (numpy or tensor, integer values in 0..255); returns it as uint8 of the same kind."""
+    if isinstance(colors, torch.Tensor):
+        if colors.is_floating_point() or colors.is_complex() or colors.dtype == torch.bool:
+            raise L.PccError(f'{what}: colours must be integers in 0..255, got {colors.dtype}')
+        if tuple(colors.shape) != (n, 3):
+            raise L.PccError(f'{what}: colours must be ({n}, 3), got {tuple(colors.shape)}')
+        if colors.dtype != torch.uint8 and n and (bool((colors < 0).any()) or bool((colors > 255).any())):
+            raise L.PccError(f'{what}: colours must be integers in 0..255')
+        return colors.to(torch.uint8).contiguous()
+    c = np.asarray(colors)
+    if c.dtype.kind not in 'iu':
+        raise L.PccError(f'{what}: colours must be integers in 0..255, got {c.dtype}')
+    if c.shape != (n, 3):
+        raise L.PccError(f'{what}: colours must be ({n}, 3), got {c.shape}')
+    if c.dtype != np.uint8 and c.size and (c.min() < 0 or c.max() > 255):
+        raise L.PccError(f'{what}: colours must be integers in 0..255')
+    return np.ascontiguousarray(c, np.uint8)
+
+
+def _device_u8(ctx, colors):
+    return (colors.to(ctx.device) if isinstance(colors, torch.Tensor) else torch.from_numpy(colors).to(ctx.device)).contiguous()
+
+
+def _index_or_points(index, what):
+    """A CloudIndex, or points checked by _voxel_points (the index is then built by the caller after every check)."""
+    if isinstance(index, CloudIndex):
+        return index, index.n
+    pts = _voxel_points(index, what)
+    return pts, int(pts.shape[0])
+
+
+def map_colors(ctx, index_a, a_colors, queries, rank=2, return_rows=False):
+    """Colour of every query point taken from the original cloud (include/pcc_geo.h "cloud colours"): for each query, the colour of
+    its rank-th nearest point of the original cloud, points ordered by (squared distance, row).  rank=2 (the default) is the
+    reference's map_color.py (the second of a k = 2 KD-tree query), rank=1 the nearest point (cloud_nearest's row).
+    index_a: a CloudIndex of the original cloud or its (N,3) points; a_colors: (N,3) integer colours in 0..255; queries: (nq,3)
+    integer coordinates in [0, 2^21).  Returns (nq,3) uint8 numpy colours (and the int32 rows with return_rows=True); nq = 0 gives
+    empty arrays.  Every input is checked before the first GPU call."""
+    if rank not in (1, 2):
+        raise L.PccError(f'map_colors: rank = {rank!r}, must be 1 or 2')
+    index_a, n = _index_or_points(index_a, 'map_colors')
+    if rank > n:
+        raise L.PccError(f'map_colors: rank {rank} needs at least {rank} original points, got {n}')
+    colors = _colors_u8(a_colors, n, 'map_colors')
+    if len(queries) == 0:
+        out = np.zeros((0, 3), np.uint8)
+        return (out, np.zeros(0, np.int32)) if return_rows else out
+    q = _voxel_points(queries, 'map_colors')
+    if not isinstance(index_a, CloudIndex):
+        index_a = CloudIndex(ctx, index_a)
+    index_q = CloudIndex(ctx, q)
+    nq = index_q.n
+    colors_d = _device_u8(ctx, colors)          # held in a local: a temporary's block could be handed out again before the launch
+    out = torch.empty((nq, 3), dtype=torch.uint8, device=ctx.device)
+    rows = torch.empty((nq,), dtype=torch.int32, device=ctx.device) if return_rows else None
+    L.check(L.lib().pcc_cloud_map_colors(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(colors_d), _ptr(index_q.buffer), nq, rank, _ptr(out),
+                                         _ptr(rows), ctx.stream), 'pcc_cloud_map_colors')
+    if return_rows:
+        return out.cpu().numpy(), rows.cpu().numpy()
+    return out.cpu().numpy()
+
+
+def cloud_color_distortion(ctx, index_a, a_colors, b_points, b_colors):
+    """Colour distortion tally of a decoded coloured cloud B against the original A on the GPU (include/pcc_geo.h "cloud colours"):
+    float64[6] = the sums of the squared BT.709 Y, U, V errors over A (against the mean colour of each point's equidistant nearest
+    points of B), then over B against A.  index_a: a CloudIndex of A or its (N_A,3) points; colours (N,3) integers in 0..255;
+    b_points (N_B,3), N_B >= 1.  utils/pc_metric.color_table turns it into mse / psnr.  Every input is checked before the first GPU
+    call; the same inputs give the same bits."""
+    index_a, n = _index_or_points(index_a, 'cloud_color_distortion')
+    colors_a = _colors_u8(a_colors, n, 'cloud_color_distortion')
+    b = _voxel_points(b_points, 'cloud_color_distortion')
+    colors_b = _colors_u8(b_colors, int(b.shape[0]), 'cloud_color_distortion')
+    if not isinstance(index_a, CloudIndex):
+        index_a = CloudIndex(ctx, index_a)
+    index_b = CloudIndex(ctx, b)
+    dev = ctx.device
+    ca_d, cb_d = _device_u8(ctx, colors_a), _device_u8(ctx, colors_b)     # both alive until the launch (see map_colors)
+    tally = torch.empty((COLOR_TALLY_SLOTS,), dtype=torch.float64, device=dev)
+    ws = torch.empty((L.lib().pcc_cloud_color_workspace_bytes(index_a.n, index_b.n),), dtype=torch.uint8, device=dev)
+    L.check(L.lib().pcc_cloud_color_distortion(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(ca_d), _ptr(index_b.buffer), index_b.n,
+                                               _ptr(cb_d), _ptr(tally), _ptr(ws), ctx.stream), 'pcc_cloud_color_distortion')
+    return tally.cpu().numpy()
+
+
 # ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------

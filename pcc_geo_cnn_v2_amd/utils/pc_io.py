@@ -99,6 +99,22 @@ def load_normals(path):
     return read_ply(path)[['nx', 'ny', 'nz']].values
 
 
+COLOR_COLUMNS = ('red', 'green', 'blue')
+
+
+def load_colors(path):
+    """(n,3) uint8 colours of a PLY file (its `red green blue` vertex properties).  A file without them, or with values that are
+    not integers in 0..255, raises ValueError naming the file."""
+    df = read_ply(path)
+    missing = [c for c in COLOR_COLUMNS if c not in df.columns]
+    if missing:
+        raise ValueError(f'{path}: no colour (the vertex properties {", ".join(missing)} are missing)')
+    c = df[list(COLOR_COLUMNS)].values
+    if c.dtype.kind not in 'iuf' or not np.isfinite(c).all() or (c < 0).any() or (c > 255).any() or not np.array_equal(c, np.round(c)):
+        raise ValueError(f'{path}: colours must be integers in 0..255')
+    return np.ascontiguousarray(c, dtype=np.uint8)
+
+
 def write_pc(path, pc):
     write_df(path, pa_to_df(pc))
 

@@ -237,3 +237,69 @@ def cloud_metrics_batch_gpu(ctx, p1, p2_list, r, p1_n=None, index_a=None):
     n_a = index_a.n if index_a is not None else len(p1)
     groups = GROUPS if p1_n is not None else GROUPS[:1]
     return [None if t is None else metrics_table(n_a, t[:5], r, groups) for t in cloud_tallies_gpu(ctx, p1, p2_list, p1_n, index_a)]
+
+
+# ---- colour distortion (include/pcc_geo.h "cloud colours") -------------------------------------------------------------------
+COLOR_KEYS = ('y', 'u', 'v')
+# BT.709 RGB -> YUV rows; each term is evaluated as ((w0 dR + w1 dG) + w2 dB), every operation rounded
+BT709 = ((0.2126, 0.7152, 0.0722), (-0.1146, -0.3854, 0.5), (0.5, -0.4542, -0.0458))
+
+
+def color_table(tally, n_a, n_b):
+    """pc_error's colour keys from 6-slot colour tallies (ops.cloud_color_distortion / color_tally_host): per channel c of y, u, v,
+    '{c}_mse' = max(A->B sum / n_a, B->A sum / n_b) and '{c}_psnr' = psnr(mse, 255^2).  Works on float64[6] (-> scalars) and
+    float64[T, 6] (-> arrays)."""
+    tally = np.asarray(tally, np.float64)
+    out = {}
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for c, k in enumerate(COLOR_KEYS):
+            out[f'{k}_mse'] = np.maximum(tally[..., c] / n_a, tally[..., 3 + c] / n_b)
+        for k in COLOR_KEYS:
+            out[f'{k}_psnr'] = psnr(out[f'{k}_mse'], 255 ** 2)
+    return out
+
+
+def yuv_terms(c_q, mean):
+    """(n,3) float64 squared BT.709 errors of colours c_q against mean colours, in the operation order of the GPU engine."""
+    d = np.asarray(c_q, np.float64) - mean
+    out = np.empty_like(d)
+    for k, (w0, w1, w2) in enumerate(BT709):
+        e = (w0 * d[:, 0] + w1 * d[:, 1]) + w2 * d[:, 2]
+        out[:, k] = e * e
+    return out
+
+
+def tie_mean_colors(points, colors, queries, k=16):
+    """(nq,3) float64 mean colour of ALL points at the smallest squared distance from each query (exact integer sums over the
+    equidistant set, divided once).  Coordinates are integers: distances are recomputed exactly from the candidates of a k-nearest
+    query, and a query whose candidates all lie at that distance takes the equidistant set from an exact ball query."""
+    p, q = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(queries, np.float64).reshape(-1, 3)
+    col = np.asarray(colors, np.int64)
+    k = min(k, len(p))
+    tree = cKDTree(p, balanced_tree=False)
+    _, cand = tree.query(q, k=k, workers=-1 if max(len(p), len(q)) > 200000 else 1)
+    cand = cand.reshape(len(q), k)
+    d2 = ((p[cand] - q[:, None, :]) ** 2).sum(-1)                     # exact: integer coordinates below 2^21
+    best = d2.min(1)
+    tie = d2 == best[:, None]
+    sums = (col[cand] * tie[..., None]).sum(1)
+    count = tie.sum(1)
+    incomplete = np.nonzero(tie.all(1) & (k < len(p)))[0]
+    if len(incomplete):
+        balls = tree.query_ball_point(q[incomplete], np.sqrt(best[incomplete]) * (1 + 1e-12) + 1e-9)
+        for i, nb in zip(incomplete, balls):
+            nb = np.asarray(nb, np.int64)
+            nb = nb[((p[nb] - q[i]) ** 2).sum(-1) == best[i]]
+            sums[i], count[i] = col[nb].sum(0), len(nb)
+    return sums.astype(np.float64) / count[:, None].astype(np.float64)
+
+
+def color_tally_host(p1, c1, p2, c2):
+    """Host restatement of the colour tally of ops.cloud_color_distortion (scipy KD-trees): float64[6] = the sums of eY^2, eU^2,
+    eV^2 of every original point against the mean colour of its equidistant nearest decoded points, then the same for the decoded
+    points against the original.  p1, p2: integer coordinates; c1, c2: (n,3) colours in 0..255; neither cloud may be empty."""
+    assert len(p1) and len(p2), 'color_tally_host: empty cloud'
+    tally = np.zeros(6, np.float64)
+    tally[:3] = yuv_terms(c1, tie_mean_colors(p2, c2, p1)).sum(0)
+    tally[3:] = yuv_terms(c2, tie_mean_colors(p1, c1, p2)).sum(0)
+    return tally
