@@ -404,6 +404,30 @@ size_t pcc_cloud_color_workspace_bytes(int64_t na, int64_t nb);
 int pcc_cloud_color_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const uint8_t* a_colours, const void* index_b, int64_t nb,
                                const uint8_t* b_colours, double* tally, void* workspace, void* stream);
 
+/* ---- mesh sampling (new: the reference's dataset step src/ds_mesh_to_pc.py, pyntcloud's mesh_random sampler + voxelisation) -----
+ * A triangle mesh to a voxelised point cloud, reproducible from a seed.  Inputs (device): verts (nverts,3) float64, tris (ntris,3)
+ * int32; n samples; seed; grid size vg.  Definition (restated in numpy by utils/mesh_sampling.py, which returns the same bits):
+ *   1. area_i = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz), c = (v2 - v1) x (v3 - v1) (cx = e1y e2z - e1z e2y, ...), float64, every
+ *      operation rounded, no contraction;
+ *   2. w_i = floor(ldexp(area_i / A_max, 32)) (uint64), C = their inclusive prefix sums, W = C[ntris-1] < 2^63 (exact: any scan
+ *      order gives the same C).  A triangle below 2^-32 of the largest one is never picked;
+ *   3. sample s takes the outputs r0..r3 of Philox4x64-10 with counter (s,0,0,0) and key (seed,0) -- row s of numpy's
+ *      Philox(key=seed, counter=2**256-1).random_raw(4n).reshape(n,4);
+ *   4. triangle = the smallest i with C[i] > umul64hi(r0, W); u = (r1>>11) 2^-53, v = (1-u) ((r2>>11) 2^-53);
+ *      p = ((v1 u) + (v2 v)) + ((1-(u+v)) v3) in float64, rounded to float32: the raw samples, written to samples (n,3) when it
+ *      is non-NULL;
+ *   5. float32, every operation correctly rounded: mn = the min over all 3n coordinates, mx = max - mn,
+ *      q = rint(((p - mn) / mx) * (vg-1)); mx == 0 gives q = 0;
+ *   6. the first sample of every distinct voxel, in sample order: points (capacity n rows) receives M rows of float32 integers
+ *      in [0, vg) (a zero is +0) and *npoints_dev (int64, device) = M.
+ * Limits: 1 <= ntris, n < 2^31; 1 <= vg <= 2^21.  The caller checks on the host (the kernels cannot): finite vertices within
+ * +-2^100, indices in [0, nverts), a total area above 0.  workspace: pcc_mesh_sample_workspace_bytes(ntris, n) bytes (0 for a size
+ * outside the limits), queried while ctx's device is the current one (hipCUB sizes its temporary storage for the current
+ * device).  One stream, no host synchronisation; the same inputs give the same bits on every call.                            */
+size_t pcc_mesh_sample_workspace_bytes(int64_t ntris, int64_t n);
+int pcc_mesh_to_points(pcc_ctx* ctx, const double* verts, int64_t nverts, const int32_t* tris, int64_t ntris, int64_t n, uint64_t seed,
+                       int32_t vg, float* samples, float* points, int64_t* npoints_dev, void* workspace, void* stream);
+
 /* ---- focal loss (src/utils/focal_loss.py:5-12) ------------------------------------------
  * Deterministic two-stage reduction (wavefront DPP/shuffle tree, fixed block order); result is a
  * single float32 written to out[0] (device).  `scratch` must hold pcc_focal_scratch_floats().   */

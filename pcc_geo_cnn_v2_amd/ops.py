@@ -865,6 +865,30 @@ def cloud_color_distortion(ctx, index_a, a_colors, b_points, b_colors):
     return tally.cpu().numpy()
 
 
+def mesh_to_points(ctx, vertices, faces, n_samples=500000, vg_size=64, seed=0, return_samples=False):
+    """A triangle mesh to a voxelised point cloud on the GPU (include/pcc_geo.h "mesh sampling"): the reference's ds_mesh_to_pc
+    (area-weighted sampling with pyntcloud's barycentrics, one scalar min / max over all axes, rint onto a vg_size^3 grid, the first
+    sample of every voxel), reproducible from `seed` (0 <= seed < 2^64).  vertices (V,3) float64, faces (F,3) integer indices.
+    Returns (M,3) float32 voxels in sample order (and the (n,3) float32 raw samples with return_samples=True): the same bits as
+    utils/mesh_sampling.mesh_to_points.  Every input is checked on the host before the first GPU call (ValueError)."""
+    from .utils import mesh_sampling
+    v, f = mesh_sampling.check_mesh(vertices, faces, n_samples, vg_size, seed)
+    n, vg = int(n_samples), int(vg_size)
+    dev = ctx.device
+    v_d, f_d = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+    samples = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_samples else None
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):            # hipCUB sizes its temporary storage for the current device
+        ws_bytes = L.lib().pcc_mesh_sample_workspace_bytes(f.shape[0], n)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    L.check(L.lib().pcc_mesh_to_points(ctx.handle, _ptr(v_d), v.shape[0], _ptr(f_d), f.shape[0], n, C.c_uint64(int(seed)), vg,
+                                       _ptr(samples), _ptr(points), _ptr(count), _ptr(ws), ctx.stream), 'pcc_mesh_to_points')
+    m = int(count.item())
+    out = points[:m].cpu().numpy()
+    return (out, samples.cpu().numpy()) if return_samples else out
+
+
 # ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------
