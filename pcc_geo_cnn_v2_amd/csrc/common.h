@@ -90,8 +90,6 @@ __host__ __device__ inline int pcc_same_pad_low(int n, int k, int s) {
 // entry points implemented per translation unit
 int pcc_conv3d_generic(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w,
                        const float* bias, const float* residual, float* out, hipStream_t st);
-int pcc_conv3d_mfma(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed,
-                    const float* bias, const float* residual, float* out, hipStream_t st);
 // The fixed-threshold extraction folded into the last layer (16 -> 1 transposed conv, conv_cout1_mfma_kernel): the kernel also
 // writes bit (z,y,x) of block n = (clip ? clamp01(x_hat) : x_hat) > thr[n] into `mask` (one bit per voxel, row-major, 32-bit
 // words little-endian).  *fused tells the caller whether the layer took that path (else: pcc_threshold_compact on x_hat).
@@ -99,7 +97,18 @@ struct pcc_thr_fuse { const float* thr; int clip; uint32_t* mask; };
 struct pcc_conv_ext;
 int pcc_conv3d_mfma_thr(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias,
                         const float* residual, float* out, const pcc_thr_fuse* fuse, bool* fused, pcc_conv_ext* ext, hipStream_t st);
-bool pcc_conv_wants_amax(const pcc_ctx* ctx, const pcc_conv_desc* d);
+// The kernel family that computes a layer (conv_mfma.hip, pcc_conv_route): one value per name pcc_conv_kernel_family prints
+enum pcc_conv_family {
+    PCC_FAM_GENERIC, PCC_FAM_F16, PCC_FAM_FWD, PCC_FAM_FWD_F16, PCC_FAM_SPLIT16, PCC_FAM_SPLIT32, PCC_FAM_WINO, PCC_FAM_WINO_BF16,
+    PCC_FAM_WINO_F16S, PCC_FAM_TR2, PCC_FAM_TR2M_F16, PCC_FAM_TR2M_F16S, PCC_FAM_TR2_SPLIT, PCC_FAM_TR2M_BF16, PCC_FAM_TR2M,
+    PCC_FAM_CIN1, PCC_FAM_COUT1M, PCC_FAM_COUT1, PCC_FAM_COUNT
+};
+pcc_conv_family pcc_conv_route(const pcc_conv_desc* d, uint32_t numerics);
+// the two fp16-pair families scale each block by the max |x| of their input: the layer that produces it records it
+inline bool pcc_conv_wants_amax(const pcc_ctx* ctx, const pcc_conv_desc* d) {
+    const pcc_conv_family f = pcc_conv_route(d, ctx->numerics);
+    return f == PCC_FAM_WINO_F16S || f == PCC_FAM_TR2M_F16S;
+}
 int pcc_conv3d_ext(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w, const float* w_packed, const float* bias,
                    const float* residual, float* out, pcc_conv_ext* ext, void* stream);
 // points from the bit mask (elementwise.hip): scratch = [B * D plane counts][B * D*H*W / 32 mask words]
@@ -120,7 +129,6 @@ int pcc_conv_wino(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const f
                   const float* bias, const float* residual, float* out, hipStream_t st);
 // z-marching k3 stride-2 transposed conv for 32 -> 16 / 64 -> 32 (conv_tr2m.hip); weights in conv_tr2g_kernel's packed order
 bool pcc_tr2m_eligible(const pcc_conv_desc* d);
-bool pcc_tr2m_preferred(const pcc_ctx* ctx, const pcc_conv_desc* d);
 int pcc_conv_tr2m(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_tr2g, const float* bias, float* out,
                   hipStream_t st);
 // the same march with split-bf16 operands for 32 -> 16 (conv_tr2m_bf16.hip)
@@ -133,7 +141,6 @@ int pcc_conv_tr2m_bf16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
 constexpr int PCC_TR2M_F16S_TAIL = 64;      // floats behind the fragments, [0] = the weight scale
 size_t pcc_tr2m_f16s_packed_floats(int Cin, int Cout);
 void pcc_tr2m_f16s_pack(int Cin, int Cout, const float* w_tr2g, float* out);
-bool pcc_tr2m_f16s_covers(const pcc_conv_desc* d);
 int pcc_conv_tr2m_f16s(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_f16s, const float* bias, float* out,
                        pcc_conv_ext* ext, hipStream_t st);
 // the march in the fp16 mode (conv_tr2m_f16.hip, round 5): fp32 input, fp16 MFMA, fp16 output (PCC_CONV_F16 | PCC_CONV_OUT16), 32 -> 16 and 64 -> 32
@@ -149,7 +156,6 @@ int pcc_conv_f16(pcc_ctx* ctx, const pcc_conv_desc* d, const void* in, const voi
 constexpr int PCC_WINO_U_FLOATS = 48 * 64 * 4;   // per (cin group, cout group): [z tap][point][lane][cin quad member]
 // split-bf16 Winograd path (conv_wino_bf16.hip): the same U as three bf16 pieces, two MFMA operands of 16 B per (row, lane)
 constexpr int PCC_WINO_UB_FLOATS = 48 * 2 * 64 * 4;
-bool pcc_wino_bf16_covers(const pcc_conv_desc* d);      // (given pcc_wino_eligible)
 void pcc_wino_bf16_pack(int ngroups, const float* u_f32, float* out);
 int pcc_conv_wino_bf16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* ub_packed, const float* bias,
                        const float* residual, float* out, hipStream_t st);
@@ -164,13 +170,13 @@ int pcc_conv_wino_f16s(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
 size_t pcc_split_packed_floats(int C);
 void pcc_split_pack(int C, const float* wlog, float* out);
 bool pcc_split_covers(const pcc_conv_desc* d);
-bool pcc_split_preferred(const pcc_ctx* ctx, const pcc_conv_desc* d);
 // Conv3DTranspose k3 stride 2, 64 -> 32 / 64 -> 64, split operands (conv_split.hip); weights = pcc_tr2m_bf16_pack(tr2g-order image)
 bool pcc_tr2_split_covers(const pcc_conv_desc* d);
 int pcc_conv_tr2_split(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_split, const float* bias, float* out,
                        pcc_conv_ext* ext, hipStream_t st);
-int pcc_conv_split(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_split, const float* bias, const float* residual,
-                   float* out, hipStream_t st);
+// mfma32: the 32x32x16 formulation (W % 32 == 0 or W == 16), else 16x16x32 -- chosen by pcc_conv_route
+int pcc_conv_split(pcc_ctx* ctx, const pcc_conv_desc* d, bool mfma32, const float* in, const float* w_split, const float* bias,
+                   const float* residual, float* out, hipStream_t st);
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize, which is set per DEVICE:
 // remember the (function, device) pairs this thread has configured.
 #include <utility>

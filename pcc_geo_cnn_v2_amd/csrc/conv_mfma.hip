@@ -1724,48 +1724,55 @@ PCC_API int pcc_conv_mfma_supported(const pcc_conv_desc* d) {
     return make_plan(d).kind != K_NONE ? 1 : 0;
 }
 
-#define NGROUPS(c) ((c) / 16)
-// stride-2 transposed k3 layers that carry a split-bf16 image behind their two fp32 images: 32 -> 16 (conv_tr2m_bf16.hip), 64 -> 32 and
-// 64 -> 64 (conv_tr2_split_kernel, conv_split.hip)
-static bool tr2_has_f16s_image(int Cin, int Cout) { return (Cin == 32 && Cout == 16) || (Cin == 64 && Cout == 32); }
-static bool tr2_has_split_image(int Cin, int Cout) { return (Cin == 32 && Cout == 16) || (Cin == 64 && (Cout == 32 || Cout == 64)); }
-
-// two-piece fp16 image of U behind everything else of a k3 stride-1 layer (conv_wino_f16s.hip): the 16- and 32-channel layers carry one
-static size_t wino_f16s_floats(int C) { return (size_t)NGROUPS(C) * NGROUPS(C) * PCC_WINO_UH_FLOATS + PCC_WINO_UH_TAIL; }
-static size_t wino_f16s_offset(int C) {
-    return (size_t)27 * C * C + (size_t)NGROUPS(C) * NGROUPS(C) * (PCC_WINO_U_FLOATS + PCC_WINO_UB_FLOATS) + pcc_f16_packed_bytes(C) / 4 +
-           (C >= 32 ? pcc_split_packed_floats(C) : 0);
-}
-
-PCC_API size_t pcc_conv_packed_floats(const pcc_conv_desc* d) {
-    if (!d) return 0;
-    const Plan p = make_plan(d);
-    const size_t k3 = (size_t)d->k * d->k * d->k;
-    switch (p.kind) {
-        case K_FWD:
-            // 16->16 / 32->32 k3 stride-1 layers also carry the Winograd-transformed weights (conv_wino.hip)
-            if (pcc_wino_channels(d->Cin, d->Cout) && d->k == 3 && d->stride == 1)
-                return k3 * d->Cin * d->Cout + (size_t)NGROUPS(d->Cin) * NGROUPS(d->Cout) * PCC_WINO_U_FLOATS +
-                       pcc_f16_packed_bytes(d->Cin) / 4 +     // + the fp16 fragments of conv_f16.hip
-                       (size_t)NGROUPS(d->Cin) * NGROUPS(d->Cout) * PCC_WINO_UB_FLOATS +    // + the split-bf16 image of U (conv_wino_bf16.hip)
-                       (d->Cin >= 32 ? pcc_split_packed_floats(d->Cin) : 0) +              // + the split image of the direct kernel (conv_split.hip)
-                       wino_f16s_floats(d->Cin);                                            // + the two-piece fp16 image of U (conv_wino_f16s.hip)
-            return k3 * d->Cin * d->Cout;
-        case K_TR2:     // k3: second copy in the order of conv_tr2g_kernel; 32 -> 16: + its split-bf16 image (conv_tr2m_bf16.hip)
-            return k3 * d->Cin * d->Cout * (d->k == 3 ? 2 : 1) + (d->k == 3 && tr2_has_split_image(d->Cin, d->Cout) ? pcc_tr2m_bf16_packed_floats(d->Cin, d->Cout) : 0) +
-                   (d->k == 3 && tr2_has_f16s_image(d->Cin, d->Cout) ? pcc_tr2m_f16s_packed_floats(d->Cin, d->Cout) : 0);      // 32 -> 16: + its two-piece fp16 image (conv_tr2m_f16s.hip)
-        case K_CIN1: return (size_t)d->k * d->k * ((d->k + 3) / 4) * 4 * d->Cout;
-        case K_COUT1: return k3 * d->Cin;
-        case K_COUT1M: return 2 * 64 * 4;
-        default: return 0;
+// The packed image of a layer: the Keras-order taps at 0, then the images of the kernels that can compute the layer, each at its
+// offset in floats (0: the layer carries no such image).  A function of the layer's kind and (Cin, Cout, k, stride) only, never of
+// its grid: pcc_weights_pack lays a network's blob out once.
+struct Packed {
+    size_t wino_u = 0;      // Winograd-transformed weights U (conv_wino.hip): 16 / 32 / 64-channel k3 stride-1 layers
+    size_t f16 = 0;         // fp16 fragments (conv_f16.hip)
+    size_t wino_ub = 0;     // U as three bf16 pieces (conv_wino_bf16.hip)
+    size_t split = 0;       // split-bf16 taps of the direct kernel (conv_split.hip), 32 / 64 channels
+    size_t wino_uh = 0;     // U as two fp16 pieces (conv_wino_f16s.hip)
+    size_t tr2g = 0;        // k3 stride-2 transposed layers: the taps in the order of conv_tr2g_kernel and the z marches
+    size_t tr2_split = 0;   // its split-bf16 image (conv_tr2m_bf16.hip, conv_tr2_split_kernel): 32 -> 16, 64 -> 32, 64 -> 64
+    size_t tr2_f16s = 0;    // its two-piece fp16 image (conv_tr2m_f16s.hip): 32 -> 16, 64 -> 32
+    size_t total = 0;
+};
+static Packed packed_layout(const pcc_conv_desc* d, Kind kind) {
+    Packed L;
+    const int ci = d->Cin, co = d->Cout, k = d->k;
+    const size_t groups = (size_t)(ci / 16) * (co / 16);
+    size_t end = (size_t)k * k * k * ci * co;
+    auto put = [&end](size_t& at, size_t floats) { at = end; end += floats; };
+    if (kind == K_FWD && pcc_wino_channels(ci, co) && k == 3 && d->stride == 1) {
+        put(L.wino_u, groups * PCC_WINO_U_FLOATS);
+        put(L.f16, pcc_f16_packed_bytes(ci) / 4);
+        put(L.wino_ub, groups * PCC_WINO_UB_FLOATS);
+        if (ci >= 32) put(L.split, pcc_split_packed_floats(ci));
+        put(L.wino_uh, groups * PCC_WINO_UH_FLOATS + PCC_WINO_UH_TAIL);
+    } else if (kind == K_TR2 && k == 3) {
+        put(L.tr2g, (size_t)27 * ci * co);
+        if ((ci == 32 && co == 16) || (ci == 64 && (co == 32 || co == 64))) put(L.tr2_split, pcc_tr2m_bf16_packed_floats(ci, co));
+        if ((ci == 32 && co == 16) || (ci == 64 && co == 32)) put(L.tr2_f16s, pcc_tr2m_f16s_packed_floats(ci, co));
+    } else if (kind == K_CIN1) {
+        end = (size_t)k * k * ((k + 3) / 4) * 4 * co;
+    } else if (kind == K_COUT1M) {
+        end = 2 * 64 * 4;
+    } else if (kind == K_NONE) {
+        end = 0;
     }
+    L.total = end;
+    return L;
 }
+
+PCC_API size_t pcc_conv_packed_floats(const pcc_conv_desc* d) { return d ? packed_layout(d, make_plan(d).kind).total : 0; }
 
 // Keras layouts: forward (k,k,k,Cin,Cout); transposed (k,k,k,Cout,Cin).
 PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float* pk) {
     PCC_REQUIRE(d && w && pk, "pcc_conv_pack_weights: NULL argument");
     const Plan p = make_plan(d);
     PCC_REQUIRE(p.kind != K_NONE, "pcc_conv_pack_weights: shape not covered by the MFMA path");
+    const Packed L = packed_layout(d, p.kind);
     const int k = d->k, Cin = d->Cin, Cout = d->Cout;
     const int NG = Cin / 16, NCT = Cout / 16;
     // logical forward-style weight W(tap, ci, co) for the gather formulation
@@ -1785,11 +1792,11 @@ PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float*
                             pk[((((size_t)g * k * k * k + tap) * NCT + ct) * 64 + lane) * 4 + j] =
                                 Wf(kz, ky, kx, g * 16 + 4 * (lane >> 4) + j, ct * 16 + (lane & 15));
             }
-        if (pcc_wino_channels(Cin, Cout) && k == 3 && d->stride == 1) {
+        if (L.wino_u) {
             // [cin group][cout group] U[dz][py][px][lane][kk] = (G (x) G) g_dz  for cin = 16 cig + 4*(lane>>4) + kk,
             // cout = 16 cog + (lane & 15); double precision
             static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-            float* u = pk + (size_t)27 * Cin * Cout;
+            float* u = pk + L.wino_u;
             for (int cig = 0; cig < NG; ++cig) for (int cog = 0; cog < NCT; ++cog)
                 for (int kz = 0; kz < 3; ++kz) for (int py = 0; py < 4; ++py) for (int px = 0; px < 4; ++px)
                     for (int lane = 0; lane < 64; ++lane)
@@ -1799,20 +1806,17 @@ PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float*
                                 s += G[py][ky] * G[px][kx] * (double)Wf(kz, ky, kx, 16 * cig + 4 * (lane >> 4) + kk, 16 * cog + (lane & 15));
                             u[(((size_t)(cig * NCT + cog) * 48 + (kz * 4 + py) * 4 + px) * 64 + lane) * 4 + kk] = (float)s;
                         }
-            {      // fp16 fragment image of conv_f16.hip behind the Winograd block
-                float* wlog = (float*)malloc((size_t)27 * Cin * Cout * sizeof(float));
-                PCC_REQUIRE(wlog != nullptr, "pcc_conv_pack_weights: out of memory");
-                for (int kz = 0; kz < 3; ++kz) for (int ky = 0; ky < 3; ++ky) for (int kx = 0; kx < 3; ++kx)
-                    for (int ci = 0; ci < Cin; ++ci) for (int co = 0; co < Cout; ++co)
-                        wlog[((((size_t)kz * 3 + ky) * 3 + kx) * Cin + ci) * Cout + co] = Wf(kz, ky, kx, ci, co);
-                pcc_f16_pack(Cin, wlog, (unsigned short*)(u + (size_t)NG * NCT * PCC_WINO_U_FLOATS));
-                // split-bf16 image of U behind the fp16 block, the direct kernel's split taps behind that
-                float* ub = u + (size_t)NG * NCT * PCC_WINO_U_FLOATS + pcc_f16_packed_bytes(Cin) / 4;
-                pcc_wino_bf16_pack(NG, u, ub);
-                if (Cin >= 32) pcc_split_pack(Cin, wlog, ub + (size_t)NG * NCT * PCC_WINO_UB_FLOATS);
-                if (wino_f16s_floats(Cin)) pcc_wino_f16s_pack(NG, u, pk + wino_f16s_offset(Cin));
-                free(wlog);
-            }
+            // the images built from U and from the logical taps
+            float* wlog = (float*)malloc((size_t)27 * Cin * Cout * sizeof(float));
+            PCC_REQUIRE(wlog != nullptr, "pcc_conv_pack_weights: out of memory");
+            for (int kz = 0; kz < 3; ++kz) for (int ky = 0; ky < 3; ++ky) for (int kx = 0; kx < 3; ++kx)
+                for (int ci = 0; ci < Cin; ++ci) for (int co = 0; co < Cout; ++co)
+                    wlog[((((size_t)kz * 3 + ky) * 3 + kx) * Cin + ci) * Cout + co] = Wf(kz, ky, kx, ci, co);
+            pcc_f16_pack(Cin, wlog, (unsigned short*)(pk + L.f16));
+            pcc_wino_bf16_pack(NG, u, pk + L.wino_ub);
+            if (L.split) pcc_split_pack(Cin, wlog, pk + L.split);
+            pcc_wino_f16s_pack(NG, u, pk + L.wino_uh);
+            free(wlog);
         }
     } else if (p.kind == K_TR2) {
         // consumption order of conv_tr2_kernel: [parity class (pz,py,px)][taps of the class (kz,ky,kx)][g][ct][lane][j]
@@ -1827,9 +1831,9 @@ PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float*
                                 for (int j = 0; j < 4; ++j)
                                     pk[(((seq * NCT) + ct) * 64 + lane) * 4 + j] =
                                         Wf(kz, ky, kx, g * 16 + 4 * (lane >> 4) + j, ct * 16 + (lane & 15));
-        if (k == 3) {
+        if (L.tr2g) {
             // conv_tr2g_kernel: [g][parity class][taps of the class][ct][lane][j]
-            float* pg = pk + (size_t)27 * Cin * Cout;
+            float* pg = pk + L.tr2g;
             for (int g = 0; g < NG; ++g) {
                 size_t sq = 0;
                 for (int pz = 0; pz < 2; ++pz) for (int py = 0; py < 2; ++py) for (int px = 0; px < 2; ++px)
@@ -1840,8 +1844,8 @@ PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float*
                                     pg[((((size_t)g * 27 + sq) * NCT + ct) * 64 + lane) * 4 + j] =
                                         Wf(kz, ky, kx, g * 16 + 4 * (lane >> 4) + j, ct * 16 + (lane & 15));
             }
-            if (tr2_has_split_image(Cin, Cout)) pcc_tr2m_bf16_pack(Cin, Cout, pg, pg + (size_t)27 * Cin * Cout);
-            if (tr2_has_f16s_image(Cin, Cout)) pcc_tr2m_f16s_pack(Cin, Cout, pg, pg + (size_t)27 * Cin * Cout + pcc_tr2m_bf16_packed_floats(Cin, Cout));
+            if (L.tr2_split) pcc_tr2m_bf16_pack(Cin, Cout, pg, pk + L.tr2_split);
+            if (L.tr2_f16s) pcc_tr2m_f16s_pack(Cin, Cout, pg, pk + L.tr2_f16s);
         }
     } else if (p.kind == K_CIN1) {
         // [kz][ky][kxg][ct][lane] : kx = kxg*4 + (lane>>4) (zero beyond k), cout = ct*16 + (lane&15)
@@ -1869,90 +1873,76 @@ PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float*
     return PCC_OK;
 }
 
-int pcc_conv3d_mfma(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias,
-                    const float* residual, float* out, hipStream_t st) {
-    return pcc_conv3d_mfma_thr(ctx, d, in, w_packed, bias, residual, out, nullptr, nullptr, nullptr, st);
-}
-
-// The dispatch rules of the k3 stride-1 layers with Cin = Cout in {16, 32, 64} (shape + context state only), in the order
-// pcc_conv3d_mfma_thr applies them: 0 = a direct kernel, 1 = the direct split-bf16 kernel (conv_split.hip), 2 = Winograd exact fp32,
-// 3 = Winograd split-bf16 (16 channels), 4 = Winograd two-piece fp16 (16 / 32 channels, conv_wino_f16s.hip)
-static bool f16s64_preferred(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    return !(d->flags & (PCC_CONV_F16 | PCC_CONV_OUT16 | PCC_CONV_CLIP01)) && !ctx->num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_F16S | PCC_NUM_NO_WINOGRAD | PCC_NUM_NO_WINOGRAD64) &&
-           pcc_wino_eligible(d) && pcc_wino_f16s_covers(d);
-}
-static int k3s1_route(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    const int ci = d->Cin;
-    if (d->impl == PCC_IMPL_SPLIT) return 1;
-    // 64 channels on grids of 16-multiples: the two-piece fp16 Winograd kernel as two launches of two cin groups (conv_wino_f16s.hip)
-    // ahead of the direct bf16 kernel; PCC_NO_F16S=1 / PCC_NO_WINOGRAD64=1: the direct kernel (A/B)
-    if (d->impl == PCC_IMPL_AUTO && ci == 64 && f16s64_preferred(ctx, d)) return 4;
-    if (d->impl == PCC_IMPL_AUTO && ci >= 32 && !(d->flags & (PCC_CONV_F16 | PCC_CONV_OUT16)) && !ctx->num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_DIRECT) &&
-        pcc_split_covers(d) && pcc_split_preferred(ctx, d))
-        return 1;
-    const bool no_wino = ctx->num(PCC_NUM_NO_WINOGRAD), no_wino32 = ctx->num(PCC_NUM_NO_WINOGRAD32), wino64 = !ctx->num(PCC_NUM_NO_WINOGRAD64);
-    const bool want = d->impl == PCC_IMPL_WINOGRAD || (d->impl == PCC_IMPL_AUTO && !(d->flags & PCC_CONV_F16) && !no_wino && !(ci == 32 && (no_wino32 || d->D < 16)) && !(ci == 64 && !wino64));
-    if (!(want && pcc_wino_eligible(d))) return 0;
-    if (!ctx->num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_F16S) && pcc_wino_f16s_covers(d) && (ci == 16 || !(d->flags & PCC_CONV_CLIP01)) && !(ci == 64 && (d->flags & PCC_CONV_F16))) return 4;
-    if (!ctx->num(PCC_NUM_NO_SPLIT) && pcc_wino_bf16_covers(d)) return 3;
-    return 2;
-}
-
-// The dispatch rules of the k3 stride-2 transposed layers (shape + context state only), in the order pcc_conv3d_mfma_thr applies them:
-// 0 = tiled exact-fp32 kernels, 1 = z march in the fp16 MODE (conv_tr2m_f16.hip), 2 = z march with two fp16 pieces (conv_tr2m_f16s.hip:
-// 32 -> 16, 64 -> 32 on grids of 16-multiples), 3 = parity-class tiles with three bf16 pieces (conv_tr2_split_kernel), 4 = z march with
-// three bf16 pieces (32 -> 16), 5 = z march exact fp32
-static int tr2_route(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    if (d->k != 3) return 0;
-    const bool autoi = d->impl == PCC_IMPL_AUTO;
-    if (autoi && !ctx->num(PCC_NUM_NO_TR2M) && pcc_tr2m_f16_covers(d)) return 1;
-    const bool plain = !(d->flags & (PCC_CONV_F16 | PCC_CONV_OUT16));
-    if (autoi && plain && !ctx->num(PCC_NUM_NO_TR2M | PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2 | PCC_NUM_NO_F16S) && pcc_tr2m_f16s_covers(d)) return 2;
-    if (autoi && plain && pcc_tr2_split_covers(d) && !ctx->num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2)) return 3;
-    if (!ctx->num(PCC_NUM_NO_TR2M) && (ctx->num(PCC_NUM_TR2M) ? pcc_tr2m_eligible(d) : pcc_tr2m_preferred(ctx, d))) {
-        if (plain && !ctx->num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2 | PCC_NUM_NO_F16S) && pcc_tr2m_f16s_covers(d)) return 2;      // (PCC_IMPL_MFMA callers)
-        return pcc_tr2m_bf16_covers(d) && !ctx->num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2) ? 4 : 5;
-    }
-    return 0;
-}
-
-// Does the kernel picked for this layer take the fp16-split path (it then wants the per-block max of its input)?
-bool pcc_conv_wants_amax(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    if (d->flags & (PCC_CONV_IN16 | PCC_CONV_OUT16)) return false;
+// The kernel family that computes a layer: a function of the layer (shape, flags, impl) and the context's numerics word only, never
+// of the batch -- encoder and decoder run with different batch sizes, and the family is part of the stream's identity (DESIGN.md
+// section 5).  Everything that depends on the choice reads it here: the dispatch below, pcc_conv_kernel_family, the block-maximum rows
+// of pcc_network_forward (pcc_conv_wants_amax) and the generic / MFMA decision of pcc_conv3d.
+pcc_conv_family pcc_conv_route(const pcc_conv_desc* d, uint32_t numerics) {
+    auto num = [numerics](uint32_t bits) { return (numerics & bits) != 0; };
     const Plan p = make_plan(d);
-    if (p.kind == K_TR2) return tr2_route(ctx, d) == 2;
-    if (p.kind != K_FWD || !(pcc_wino_channels(d->Cin, d->Cout) && d->k == 3 && (p.flip ? 1 : d->stride) == 1)) return false;
-    return k3s1_route(ctx, d) == 4;
+    const int ci = d->Cin, fl = d->flags, impl = d->impl;
+    const bool autoi = impl == PCC_IMPL_AUTO;
+    if (p.kind == K_NONE || !(autoi || impl == PCC_IMPL_MFMA || impl == PCC_IMPL_WINOGRAD || impl == PCC_IMPL_SPLIT)) return PCC_FAM_GENERIC;
+    if ((fl & (PCC_CONV_IN16 | PCC_CONV_RES16)) && p.kind != K_COUT1M) return PCC_FAM_F16;
+    if (p.kind == K_CIN1) return PCC_FAM_CIN1;
+    if (p.kind == K_COUT1M) return PCC_FAM_COUT1M;
+    if (p.kind == K_COUT1) return PCC_FAM_COUT1;
+    const bool plain = !(fl & (PCC_CONV_F16 | PCC_CONV_OUT16));
+    if (p.kind == K_TR2) {
+        // k3 stride 2: fp16-mode march | two-piece fp16 march (32 -> 16, 64 -> 32 on grids of 16-multiples) | parity-class tiles, bf16 x 3
+        // (64 -> 32 / 64 -> 64) | bf16 x 3 march (32 -> 16) | exact-fp32 march | the tiled exact-fp32 kernels (also every k5 layer)
+        if (d->k != 3) return PCC_FAM_TR2;
+        if (autoi && !num(PCC_NUM_NO_TR2M) && pcc_tr2m_f16_covers(d)) return PCC_FAM_TR2M_F16;
+        const bool f16s = plain && !num(PCC_NUM_NO_TR2M | PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2 | PCC_NUM_NO_F16S) && pcc_tr2m_eligible(d);
+        if (autoi && f16s) return PCC_FAM_TR2M_F16S;
+        if (autoi && plain && pcc_tr2_split_covers(d) && !num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2)) return PCC_FAM_TR2_SPLIT;
+        // The march (PCC_IMPL_MFMA callers, PCC_TR2M=1: wherever eligible): 32 -> 16 always; 64 -> 32 from 32 input planes up (16^3 x 32
+        // blocks gives 4-plane slabs: the 9-tap halo plane and the 108 KB weight prologue per workgroup make the tiled conv_tr2g_kernel
+        // faster there: 127 vs 135 us).  The two sum in different orders (DESIGN_HISTORY.md section 4).
+        if (num(PCC_NUM_NO_TR2M) || !pcc_tr2m_eligible(d) || !(num(PCC_NUM_TR2M) || ci == 32 || d->D >= 32)) return PCC_FAM_TR2;
+        if (f16s) return PCC_FAM_TR2M_F16S;
+        return pcc_tr2m_bf16_covers(d) && !num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_TR2) ? PCC_FAM_TR2M_BF16 : PCC_FAM_TR2M;
+    }
+    const pcc_conv_family fwd = (fl & PCC_CONV_F16) ? PCC_FAM_FWD_F16 : PCC_FAM_FWD;
+    if (!(pcc_wino_channels(ci, d->Cout) && d->k == 3 && d->stride == 1)) return fwd;
+    // k3 stride 1, Cin = Cout in {16, 32, 64}.  The direct split-bf16 kernel (conv_split.hip) in its 16x16x32 or 32x32x16 MFMA
+    // formulation, measured at batch 32 (tools/bench_one.py): 64 -> 64 @16^3 128 us (16x16x32, tile 2 x 4 x 16) / 134 - 148 (32x32x16);
+    // 32 -> 32 @16^3 41 / 38.5 us, @32^3 332 / 373 us.  The 32x32 tiles need W % 32 == 0 or W == 16.  PCC_SPLIT_MFMA=16 | 32 overrides (A/B).
+    const bool mfma32 = !num(PCC_NUM_SPLIT_MFMA16) && (num(PCC_NUM_SPLIT_MFMA32) || ci == 32) && (d->W % 32 == 0 || d->W == 16);
+    const pcc_conv_family split = mfma32 ? PCC_FAM_SPLIT32 : PCC_FAM_SPLIT16;
+    if (impl == PCC_IMPL_SPLIT) return split;
+    // 64 channels on grids of 16-multiples: the two-piece fp16 Winograd kernel as two launches of two cin groups (conv_wino_f16s.hip)
+    // ahead of the direct split kernel; PCC_NO_F16S=1 / PCC_NO_WINOGRAD64=1: the direct kernel (A/B)
+    if (autoi && ci == 64 && !(fl & (PCC_CONV_F16 | PCC_CONV_OUT16 | PCC_CONV_CLIP01)) &&
+        !num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_F16S | PCC_NUM_NO_WINOGRAD | PCC_NUM_NO_WINOGRAD64) && pcc_wino_eligible(d))
+        return PCC_FAM_WINO_F16S;
+    // The direct split kernel where it beats the fp32-MFMA Winograd kernel: 64 channels (128 us against 138 - 146 @16^3 x 32); 32 channels
+    // on the small grids only (38.5 against 45 us @16^3; at 32^3 the Winograd kernel's 241 us stand against 332: every tile of the
+    // direct kernel pays its staging, split and epilogue un-overlapped, DESIGN_HISTORY.md 3.0d).  PCC_NO_SPLIT_DIRECT=1: off (A/B)
+    if (autoi && plain && !num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_SPLIT_DIRECT) && pcc_split_covers(d) &&
+        (ci == 64 || (ci == 32 && d->D <= 16 && (d->W % 32 == 0 || d->W == 16))))
+        return split;
+    const bool want = impl == PCC_IMPL_WINOGRAD || (autoi && !(fl & PCC_CONV_F16) && !num(PCC_NUM_NO_WINOGRAD) &&
+                                                    !(ci == 32 && (num(PCC_NUM_NO_WINOGRAD32) || d->D < 16)) && !(ci == 64 && num(PCC_NUM_NO_WINOGRAD64)));
+    if (!(want && pcc_wino_eligible(d))) return fwd;
+    // two fp16 pieces under a per-block power-of-two pre-scale (conv_wino_f16s.hip); PCC_NO_F16S=1: three bf16 pieces (16 channels) /
+    // exact fp32; PCC_NO_SPLIT=1: exact-fp32 MFMA everywhere (A/B)
+    if (!num(PCC_NUM_NO_SPLIT | PCC_NUM_NO_F16S) && (ci == 16 || !(fl & PCC_CONV_CLIP01)) && !(ci == 64 && (fl & PCC_CONV_F16))) return PCC_FAM_WINO_F16S;
+    if (!num(PCC_NUM_NO_SPLIT) && ci == 16) return PCC_FAM_WINO_BF16;
+    return PCC_FAM_WINO;
 }
 
-// The kernel family pcc_conv3d takes for a layer on this context (same tests, same order as the dispatch below): what bench.py prints
-// beside every layer's time, and what a maintainer asks when two builds disagree in the last bits.
+// What bench.py prints beside every layer's time, and what a maintainer asks when two builds disagree in the last bits.
 PCC_API int pcc_conv_kernel_family(pcc_ctx* ctx, const pcc_conv_desc* d, char* buf, int32_t cap) {
     PCC_REQUIRE(ctx && d && buf && cap > 0, "pcc_conv_kernel_family: NULL argument");
-    const char* name = "generic (reference-order fp32 FMA chain)";
-    const Plan p = make_plan(d);
-    const int ci = d->Cin, co = d->Cout, k = d->k;
-    if (d->impl == PCC_IMPL_GENERIC || p.kind == K_NONE) {
-    } else if ((d->flags & (PCC_CONV_IN16 | PCC_CONV_RES16)) && p.kind != K_COUT1M) name = "conv_f16 (fp16 storage, f16 MFMA)";
-    else if (p.kind == K_FWD) {
-        name = (d->flags & PCC_CONV_F16) ? "conv_fwd (f16 MFMA)" : "conv_fwd (exact fp32 MFMA)";
-        if (pcc_wino_channels(ci, co) && k == 3 && (p.flip ? 1 : d->stride) == 1) {
-            switch (k3s1_route(ctx, d)) {
-                case 1: name = (ctx->num(PCC_NUM_SPLIT_MFMA32) || (!ctx->num(PCC_NUM_SPLIT_MFMA16) && ci == 32)) && d->W != 8 ? "conv_k3s1_split32 (direct, bf16 x 3, 32x32x16 MFMA)" : "conv_k3s1_split (direct, bf16 x 3, 16x16x32 MFMA)"; break;
-                case 2: name = "conv16_wino (Winograd, exact fp32 MFMA)"; break;
-                case 3: name = "conv16_wino_bf16 (Winograd, bf16 x 3)"; break;
-                case 4: name = "conv16_wino_f16s (Winograd, fp16 x 2 under a per-block pre-scale)"; break;
-                default: break;
-            }
-        }
-    } else if (p.kind == K_TR2) {
-        static const char* const tn[6] = {"conv_tr2 (exact fp32 MFMA)", "conv_tr2m_f16 (z march, f16 MFMA)", "conv_tr2m_f16s (z march, fp16 x 2 under a per-block pre-scale)",
-                                          "conv_tr2_split (parity classes, bf16 x 3)", "conv_tr2m_bf16 (z march, bf16 x 3)", "conv_tr2m (z march, exact fp32 MFMA)"};
-        name = tn[tr2_route(ctx, d)];
-    } else if (p.kind == K_CIN1) name = "conv_cin1 (exact fp32 MFMA)";
-    else if (p.kind == K_COUT1M) name = "conv_cout1_mfma (exact fp32 MFMA)";
-    else if (p.kind == K_COUT1) name = "conv_cout1 (fp32 VALU)";
-    snprintf(buf, (size_t)cap, "%s", name);
+    static const char* const names[PCC_FAM_COUNT] = {
+        "generic (reference-order fp32 FMA chain)", "conv_f16 (fp16 storage, f16 MFMA)", "conv_fwd (exact fp32 MFMA)", "conv_fwd (f16 MFMA)",
+        "conv_k3s1_split (direct, bf16 x 3, 16x16x32 MFMA)", "conv_k3s1_split32 (direct, bf16 x 3, 32x32x16 MFMA)",
+        "conv16_wino (Winograd, exact fp32 MFMA)", "conv16_wino_bf16 (Winograd, bf16 x 3)", "conv16_wino_f16s (Winograd, fp16 x 2 under a per-block pre-scale)",
+        "conv_tr2 (exact fp32 MFMA)", "conv_tr2m_f16 (z march, f16 MFMA)", "conv_tr2m_f16s (z march, fp16 x 2 under a per-block pre-scale)",
+        "conv_tr2_split (parity classes, bf16 x 3)", "conv_tr2m_bf16 (z march, bf16 x 3)", "conv_tr2m (z march, exact fp32 MFMA)",
+        "conv_cin1 (exact fp32 MFMA)", "conv_cout1_mfma (exact fp32 MFMA)", "conv_cout1 (fp32 VALU)"};
+    snprintf(buf, (size_t)cap, "%s", names[pcc_conv_route(d, ctx->numerics)]);
     return PCC_OK;
 }
 
@@ -1961,7 +1951,9 @@ int pcc_conv3d_mfma_thr(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, c
     if (fused) *fused = false;
     if (ext) ext->out_recorded = false;
     const Plan p = make_plan(d);
-    PCC_REQUIRE(p.kind != K_NONE, "pcc_conv3d_mfma: shape not covered");
+    const pcc_conv_family fam = pcc_conv_route(d, ctx->numerics);
+    PCC_REQUIRE(fam != PCC_FAM_GENERIC, "pcc_conv3d_mfma: shape not covered");
+    const Packed L = packed_layout(d, p.kind);
     ConvArgs a;
     a.in = in; a.w = w_packed; a.bias = bias; a.res = residual; a.out = out;
     a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
@@ -1971,57 +1963,42 @@ int pcc_conv3d_mfma_thr(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, c
     a.oco = d->out_coffset;
     a.ntz = a.nty = a.ntx = 0;
     const int ci = d->Cin, co = d->Cout, k = d->k, s = d->stride;
-
-#define PCC_CASE_FWD(CI, CO, K, S) if (ci == CI && co == CO && k == K && fs == S) return launch_fwd<CI, CO, K, S>(p.tx, a, st, ctx->num_cu, ctx->numerics);
-#define PCC_CASE_TR2(CI, CO, K) if (ci == CI && co == CO && k == K) return launch_tr2<CI, CO, K>(p.tx, a, st, ctx->num_cu, ctx->numerics);
     PCC_REQUIRE(!(d->flags & PCC_CONV_OUT16) || p.kind == K_FWD || p.kind == K_TR2 || p.kind == K_CIN1,
                 "pcc_conv3d: PCC_CONV_OUT16 needs a layer with Cout a multiple of 16");
-    if ((d->flags & (PCC_CONV_IN16 | PCC_CONV_RES16)) && p.kind != K_COUT1M) {
-        // fp16-storage layer (conv_f16.hip): fp16 input (and residual), fp16 or fp32 output
-        PCC_REQUIRE(p.kind == K_FWD && (d->flags & PCC_CONV_IN16) && pcc_f16_eligible(d),
-                    "pcc_conv3d: PCC_CONV_IN16 covers k3 stride-1 layers with Cin = Cout in {16, 32, 64} (H, W multiples of 16) and the 16 -> 1 transposed layer");
-        const float* f16w = w_packed + (size_t)27 * ci * co + (size_t)(ci / 16) * (co / 16) * PCC_WINO_U_FLOATS;
-        return pcc_conv_f16(ctx, d, in, f16w, bias, residual, out, !(d->flags & PCC_CONV_OUT16), st);
-    }
-    if (p.kind == K_FWD) {
-        PCC_REQUIRE(!(d->flags & PCC_CONV_OUT16) || d->impl != PCC_IMPL_WINOGRAD, "pcc_conv3d: PCC_CONV_OUT16 is not implemented by the Winograd kernel (fp32)");
-        const int fs = p.flip ? 1 : s;
-        if (pcc_wino_channels(ci, co) && k == 3 && fs == 1) {
-            // 32- / 64-channel layers: direct convolution on the bf16 MFMA pipe with split operands (conv_split.hip) where it beats the
-            // fp32-MFMA Winograd kernel.  PCC_NO_SPLIT=1 (all split paths) / PCC_NO_SPLIT_DIRECT=1 (this one) for A/B runs
-            const float* w_split = w_packed + (size_t)27 * ci * co + (size_t)(ci / 16) * (co / 16) * (PCC_WINO_U_FLOATS + PCC_WINO_UB_FLOATS) + pcc_f16_packed_bytes(ci) / 4;
-            const int route = k3s1_route(ctx, d);
-            if (route == 1) {
-                PCC_REQUIRE(ci >= 32 && pcc_split_covers(d) && !(d->flags & (PCC_CONV_F16 | PCC_CONV_OUT16)), "pcc_conv3d: PCC_IMPL_SPLIT covers fp32 k3 stride-1 layers with Cin = Cout in {32, 64}, W % 16 == 0");
-                return pcc_conv_split(ctx, d, in, w_split, bias, residual, out, st);
-            }
-            const float* u32 = w_packed + (size_t)27 * ci * co;
-            // two fp16 pieces under a per-block power-of-two pre-scale (conv_wino_f16s.hip, round 6: 16- and 32-channel layers);
-            // PCC_NO_F16S=1: three bf16 pieces (16 channels) / exact fp32; PCC_NO_SPLIT=1: exact-fp32 MFMA everywhere (A/B)
-            if (route == 4) return pcc_conv_wino_f16s(ctx, d, in, w_packed + wino_f16s_offset(ci), bias, residual, out, ext, st);
-            if (route == 3) return pcc_conv_wino_bf16(ctx, d, in, u32 + (size_t)(ci / 16) * (co / 16) * PCC_WINO_U_FLOATS + pcc_f16_packed_bytes(ci) / 4, bias, residual, out, st);
-            if (route == 2) return pcc_conv_wino(ctx, d, in, u32, bias, residual, out, st);
-            PCC_REQUIRE(d->impl != PCC_IMPL_WINOGRAD, "pcc_conv3d: PCC_IMPL_WINOGRAD needs W and H multiples of 16");
-        } else {
-            PCC_REQUIRE(d->impl != PCC_IMPL_WINOGRAD, "pcc_conv3d: PCC_IMPL_WINOGRAD covers Cin = Cout in {16,32,64} k3 stride-1 layers only");
-        }
-        PCC_CASE_FWD(16, 16, 3, 1) PCC_CASE_FWD(32, 32, 3, 1) PCC_CASE_FWD(64, 64, 3, 1)
-        PCC_CASE_FWD(16, 32, 3, 2) PCC_CASE_FWD(32, 64, 3, 2) PCC_CASE_FWD(64, 64, 3, 2)
-        PCC_CASE_FWD(32, 32, 3, 2) PCC_CASE_FWD(32, 32, 5, 2)
-    } else if (p.kind == K_TR2) {
-        // tr2_route: fp16-mode march | two-piece fp16 march (32 -> 16, 64 -> 32; PCC_NO_F16S=1 off) | parity-class tiles, bf16 x 3 (64 -> 32 / 64 -> 64;
-        // PCC_NO_SPLIT=1 / PCC_NO_SPLIT_TR2=1 off) | bf16 x 3 march (32 -> 16) | exact-fp32 march (PCC_NO_TR2M=1: the tiled kernels below)
-        switch (tr2_route(ctx, d)) {
-            case 1: return pcc_conv_tr2m_f16(ctx, d, in, w_packed + (size_t)27 * ci * co, bias, out, st);
-            case 2: return pcc_conv_tr2m_f16s(ctx, d, in, w_packed + (size_t)2 * 27 * ci * co + pcc_tr2m_bf16_packed_floats(ci, co), bias, out, ext, st);
-            case 3: return pcc_conv_tr2_split(ctx, d, in, w_packed + (size_t)2 * 27 * ci * co, bias, out, ext, st);
-            case 4: return pcc_conv_tr2m_bf16(ctx, d, in, w_packed + (size_t)2 * 27 * ci * co, bias, out, ext, st);
-            case 5: return pcc_conv_tr2m(ctx, d, in, w_packed + (size_t)27 * ci * co, bias, out, st);
-            default: break;
-        }
-        PCC_CASE_TR2(64, 64, 3) PCC_CASE_TR2(64, 32, 3) PCC_CASE_TR2(32, 16, 3) PCC_CASE_TR2(32, 32, 3)
-        PCC_CASE_TR2(32, 32, 5)
-    } else if (p.kind == K_CIN1) {
+    PCC_REQUIRE(!(d->flags & PCC_CONV_OUT16) || d->impl != PCC_IMPL_WINOGRAD, "pcc_conv3d: PCC_CONV_OUT16 is not implemented by the Winograd kernel (fp32)");
+
+#define PCC_CASE_FWD(CI, CO, K, S) if (ci == CI && co == CO && k == K && s == S) return launch_fwd<CI, CO, K, S>(p.tx, a, st, ctx->num_cu, ctx->numerics);
+#define PCC_CASE_TR2(CI, CO, K) if (ci == CI && co == CO && k == K) return launch_tr2<CI, CO, K>(p.tx, a, st, ctx->num_cu, ctx->numerics);
+    switch (fam) {
+        case PCC_FAM_F16:      // fp16 input (and residual), fp16 or fp32 output
+            PCC_REQUIRE(p.kind == K_FWD && (d->flags & PCC_CONV_IN16) && pcc_f16_eligible(d),
+                        "pcc_conv3d: PCC_CONV_IN16 covers k3 stride-1 layers with Cin = Cout in {16, 32, 64} (H, W multiples of 16) and the 16 -> 1 transposed layer");
+            return pcc_conv_f16(ctx, d, in, w_packed + L.f16, bias, residual, out, !(d->flags & PCC_CONV_OUT16), st);
+        case PCC_FAM_SPLIT16:
+        case PCC_FAM_SPLIT32:
+            PCC_REQUIRE(ci >= 32 && pcc_split_covers(d) && !(d->flags & (PCC_CONV_F16 | PCC_CONV_OUT16)), "pcc_conv3d: PCC_IMPL_SPLIT covers fp32 k3 stride-1 layers with Cin = Cout in {32, 64}, W % 16 == 0");
+            return pcc_conv_split(ctx, d, fam == PCC_FAM_SPLIT32, in, w_packed + L.split, bias, residual, out, st);
+        case PCC_FAM_WINO_F16S: return pcc_conv_wino_f16s(ctx, d, in, w_packed + L.wino_uh, bias, residual, out, ext, st);
+        case PCC_FAM_WINO_BF16: return pcc_conv_wino_bf16(ctx, d, in, w_packed + L.wino_ub, bias, residual, out, st);
+        case PCC_FAM_WINO: return pcc_conv_wino(ctx, d, in, w_packed + L.wino_u, bias, residual, out, st);
+        case PCC_FAM_FWD:
+        case PCC_FAM_FWD_F16:
+            PCC_REQUIRE(d->impl != PCC_IMPL_WINOGRAD, "%s", L.wino_u ? "pcc_conv3d: PCC_IMPL_WINOGRAD needs W and H multiples of 16"
+                                                                     : "pcc_conv3d: PCC_IMPL_WINOGRAD covers Cin = Cout in {16,32,64} k3 stride-1 layers only");
+            PCC_CASE_FWD(16, 16, 3, 1) PCC_CASE_FWD(32, 32, 3, 1) PCC_CASE_FWD(64, 64, 3, 1)
+            PCC_CASE_FWD(16, 32, 3, 2) PCC_CASE_FWD(32, 64, 3, 2) PCC_CASE_FWD(64, 64, 3, 2)
+            PCC_CASE_FWD(32, 32, 3, 2) PCC_CASE_FWD(32, 32, 5, 2)
+            break;
+        case PCC_FAM_TR2M_F16: return pcc_conv_tr2m_f16(ctx, d, in, w_packed + L.tr2g, bias, out, st);
+        case PCC_FAM_TR2M_F16S: return pcc_conv_tr2m_f16s(ctx, d, in, w_packed + L.tr2_f16s, bias, out, ext, st);
+        case PCC_FAM_TR2_SPLIT: return pcc_conv_tr2_split(ctx, d, in, w_packed + L.tr2_split, bias, out, ext, st);
+        case PCC_FAM_TR2M_BF16: return pcc_conv_tr2m_bf16(ctx, d, in, w_packed + L.tr2_split, bias, out, ext, st);
+        case PCC_FAM_TR2M: return pcc_conv_tr2m(ctx, d, in, w_packed + L.tr2g, bias, out, st);
+        case PCC_FAM_TR2:
+            PCC_CASE_TR2(64, 64, 3) PCC_CASE_TR2(64, 32, 3) PCC_CASE_TR2(32, 16, 3) PCC_CASE_TR2(32, 32, 3)
+            PCC_CASE_TR2(32, 32, 5)
+            break;
+        case PCC_FAM_CIN1:
 #define PCC_CIN1(CO, K, TZ, TY, R)                                                                      \
     if (co == CO && k == K) {                                                                           \
         using C = Cin1Cfg<CO, K, TZ, TY, R>;                                                            \
@@ -2029,46 +2006,50 @@ int pcc_conv3d_mfma_thr(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, c
         a.ntz = cdiv(a.OD, TZ); a.nty = cdiv(a.OH, TY); a.ntx = cdiv(a.OW, 16);                         \
         return launch(conv_cin1_kernel<CO, K, TZ, TY, R>, C::NT, C::LDS_BYTES, a.N * a.ntz * a.nty * a.ntx, a, st); \
     }
-        PCC_CIN1(16, 3, 2, 8, 4) PCC_CIN1(32, 3, 2, 8, 4) PCC_CIN1(16, 9, 2, 8, 4) PCC_CIN1(32, 9, 2, 8, 4)
+            PCC_CIN1(16, 3, 2, 8, 4) PCC_CIN1(32, 3, 2, 8, 4) PCC_CIN1(16, 9, 2, 8, 4) PCC_CIN1(32, 9, 2, 8, 4)
 #undef PCC_CIN1
-    } else if (p.kind == K_COUT1M) {
-        // 32 x 32 columns (one 16-wave workgroup per CU) when H, W allow it and the grid, z-split into slabs of >= 16 planes, still
-        // gives every CU a workgroup; else 16 x 16 columns, whole z range.  PCC_COUT1_T16=1 forces the latter (A/B runs).
-        const bool t16 = ctx->num(PCC_NUM_COUT1_T16);
-        typedef void (*kern_t)(ConvArgs);
-        const bool in16 = (d->flags & PCC_CONV_IN16) != 0;
-        // the occupancy bits ride along when the caller asked for them and whole T-voxel rows map to whole mask pieces
-        const bool thr = fuse != nullptr && a.ocs == 1 && a.oco == 0 && a.W % 16 == 0 && ((size_t)a.H * a.W) % 32 == 0;
-        if (thr) { a.thr = fuse->thr; a.mask = (unsigned short*)fuse->mask; a.thr_clip = fuse->clip; }
-        if (fused) *fused = thr;
-        if (!t16 && a.H % 32 == 0 && a.W % 32 == 0) {
-            const int base = a.N * (a.H / 32) * (a.W / 32);
-            int zsp = 1;
-            while (base * zsp < ctx->num_cu && a.D / (zsp * 2) >= 16) zsp *= 2;
-            if (base * zsp >= ctx->num_cu) {
-                using C = Cout1M<32>;
-                a.ntz = zsp; a.nty = a.H / 32; a.ntx = a.W / 32;
-                static const kern_t k32[4] = {conv_cout1_mfma_kernel<false, 32, false>, conv_cout1_mfma_kernel<true, 32, false>,
-                                              conv_cout1_mfma_kernel<false, 32, true>, conv_cout1_mfma_kernel<true, 32, true>};
-                const kern_t kern = k32[(in16 ? 1 : 0) + (thr ? 2 : 0)];
-                { const int rc = pcc_enable_big_lds((const void*)kern, C::LDS_BYTES); if (rc != PCC_OK) return rc; }
-                return launch(kern, C::NT, C::LDS_BYTES, base * zsp, a, st);
+            break;
+        case PCC_FAM_COUT1M: {
+            // 32 x 32 columns (one 16-wave workgroup per CU) when H, W allow it and the grid, z-split into slabs of >= 16 planes, still
+            // gives every CU a workgroup; else 16 x 16 columns, whole z range.  PCC_COUT1_T16=1 forces the latter (A/B runs).
+            const bool t16 = ctx->num(PCC_NUM_COUT1_T16);
+            typedef void (*kern_t)(ConvArgs);
+            const bool in16 = (d->flags & PCC_CONV_IN16) != 0;
+            // the occupancy bits ride along when the caller asked for them and whole T-voxel rows map to whole mask pieces
+            const bool thr = fuse != nullptr && a.ocs == 1 && a.oco == 0 && a.W % 16 == 0 && ((size_t)a.H * a.W) % 32 == 0;
+            if (thr) { a.thr = fuse->thr; a.mask = (unsigned short*)fuse->mask; a.thr_clip = fuse->clip; }
+            if (fused) *fused = thr;
+            if (!t16 && a.H % 32 == 0 && a.W % 32 == 0) {
+                const int base = a.N * (a.H / 32) * (a.W / 32);
+                int zsp = 1;
+                while (base * zsp < ctx->num_cu && a.D / (zsp * 2) >= 16) zsp *= 2;
+                if (base * zsp >= ctx->num_cu) {
+                    using C = Cout1M<32>;
+                    a.ntz = zsp; a.nty = a.H / 32; a.ntx = a.W / 32;
+                    static const kern_t k32[4] = {conv_cout1_mfma_kernel<false, 32, false>, conv_cout1_mfma_kernel<true, 32, false>,
+                                                  conv_cout1_mfma_kernel<false, 32, true>, conv_cout1_mfma_kernel<true, 32, true>};
+                    const kern_t kern = k32[(in16 ? 1 : 0) + (thr ? 2 : 0)];
+                    { const int rc = pcc_enable_big_lds((const void*)kern, C::LDS_BYTES); if (rc != PCC_OK) return rc; }
+                    return launch(kern, C::NT, C::LDS_BYTES, base * zsp, a, st);
+                }
             }
+            using C = Cout1M<16>;
+            a.ntz = 1; a.nty = cdiv(a.H, C::TYX); a.ntx = cdiv(a.W, C::TYX);
+            static const kern_t k16[4] = {conv_cout1_mfma_kernel<false, 16, false>, conv_cout1_mfma_kernel<true, 16, false>,
+                                          conv_cout1_mfma_kernel<false, 16, true>, conv_cout1_mfma_kernel<true, 16, true>};
+            return launch(k16[(in16 ? 1 : 0) + (thr ? 2 : 0)], C::NT, C::LDS_BYTES, a.N * a.nty * a.ntx, a, st);
         }
-        using C = Cout1M<16>;
-        a.ntz = 1; a.nty = cdiv(a.H, C::TYX); a.ntx = cdiv(a.W, C::TYX);
-        static const kern_t k16[4] = {conv_cout1_mfma_kernel<false, 16, false>, conv_cout1_mfma_kernel<true, 16, false>,
-                                      conv_cout1_mfma_kernel<false, 16, true>, conv_cout1_mfma_kernel<true, 16, true>};
-        return launch(k16[(in16 ? 1 : 0) + (thr ? 2 : 0)], C::NT, C::LDS_BYTES, a.N * a.nty * a.ntx, a, st);
-    } else if (p.kind == K_COUT1) {
+        case PCC_FAM_COUT1:
 #define PCC_COUT1(CI, K, S, TZ, TY, TXT)                                                                \
     if (ci == CI && k == K && s == S) {                                                                 \
         using C = Cout1Cfg<CI, K, S, TZ, TY, TXT>;                                                      \
         a.ntz = cdiv(a.D, TZ); a.nty = cdiv(a.H, TY); a.ntx = cdiv(a.W, TXT);                           \
         return launch(conv_cout1_kernel<CI, K, S, TZ, TY, TXT>, C::NT, C::LDS_BYTES, a.N * a.ntz * a.nty * a.ntx, a, st); \
     }
-        PCC_COUT1(16, 3, 1, 4, 8, 8) PCC_COUT1(32, 3, 1, 4, 8, 8) PCC_COUT1(32, 9, 2, 2, 8, 8)
+            PCC_COUT1(16, 3, 1, 4, 8, 8) PCC_COUT1(32, 3, 1, 4, 8, 8) PCC_COUT1(32, 9, 2, 2, 8, 8)
 #undef PCC_COUT1
+            break;
+        default: break;
     }
     pcc_set_error("pcc_conv3d_mfma: no instantiation for Cin=%d Cout=%d k=%d s=%d transposed=%d", ci, co, k, s, d->transposed);
     return PCC_ERR_ARG;

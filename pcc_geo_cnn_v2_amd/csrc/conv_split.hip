@@ -795,32 +795,14 @@ bool pcc_split_covers(const pcc_conv_desc* d) {
     return (double)d->D * d->H * d->W * d->Cin * 4.0 < 2147483648.0;        // one image per buffer descriptor
 }
 
-// AUTO takes this path for the 64-channel layers (tile = 2 x 4 x 16 voxels, two workgroups per CU).
-// Measured (batch 32, tools/bench_one.py): 64 -> 64 @16^3 128 us against 138 - 146 us for conv16_wino_cin_kernel<4> and 234 us for the
-// exact-fp32 direct kernel; 32 -> 32 @32^3 333 us against 241 us (Winograd) and 468 us (fp32 direct): with R x CTW = 4 x 1 MFMA
-// groups per operand fetch the 32-channel launch is bound by its operand traffic (5 GB of weight fragments from L2, 15 GB of input
-// fragments from LDS per launch -- MFMA busy 0.29 - 0.46), so the Winograd kernel keeps those layers (DESIGN_HISTORY.md 3.0d).
-// The choice depends on the layer shape ONLY, never on the batch: encoder and decoder run with different batch sizes and must produce
-// the same bits (tests/test_codec_gpu.py::test_blocks_128_cubed_roundtrip_and_layer_parity caught a batch-dependent rule).
-bool pcc_split_preferred(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    (void)ctx;
-    // 64 channels: 128 us against 138 - 146 (Winograd fp32) @16^3 x 32.  32 channels: only on the small grids (38.5 against 45 us @16^3;
-    // at 32^3 the Winograd kernel's 241 us stand against 332: every tile of this kernel pays its staging, split and epilogue
-    // un-overlapped -- at bf16 MFMA rates they are as long as the 27 taps themselves, see DESIGN_HISTORY.md 3.0d)
-    return d->Cin == 64 || (d->Cin == 32 && d->D <= 16 && (d->W % 32 == 0 || d->W == 16));
-}
-
-int pcc_conv_split(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_split, const float* bias, const float* residual,
-                   float* out, hipStream_t st) {
+int pcc_conv_split(pcc_ctx* ctx, const pcc_conv_desc* d, bool mfma32, const float* in, const float* w_split, const float* bias,
+                   const float* residual, float* out, hipStream_t st) {
     PCC_REQUIRE(pcc_split_covers(d), "pcc_conv_split: shape not covered");
     SplitArgs a;
     a.in = in; a.w = w_split; a.bias = bias; a.res = residual; a.out = out;
     a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
     a.flags = d->flags; a.ocs = d->out_cstride ? d->out_cstride : d->Cout; a.oco = d->out_coffset;
-    // Which formulation: measured at batch 32 (tools/bench_one.py) -- 64 -> 64 @16^3: 128 us (16x16x32, tile 2 x 4 x 16) / 134 - 148 (32x32x16);
-    // 32 -> 32 @16^3: 41 / 38.5 us; 32 -> 32 @32^3: 332 / 373 us.  A function of the layer shape only.  PCC_SPLIT_MFMA=16 | 32 overrides (A/B).
-    const int force = ctx->num(PCC_NUM_SPLIT_MFMA16) ? 16 : ctx->num(PCC_NUM_SPLIT_MFMA32) ? 32 : 0;
-    const bool use32 = force ? force == 32 : d->Cin == 32;
+    PCC_REQUIRE(!mfma32 || d->W % 32 == 0 || d->W == 16, "pcc_conv_split: the 32x32x16 formulation needs W % 32 == 0 or W == 16");
     if (d->W == 8) {
         // 64 -> 64 on the 8^3 grids (analysis block 3, first / last hyper layers): one z plane x 8 lines x 8 voxels per workgroup =
         // 8 planes x 32 blocks = 256 workgroups of 4 waves (2 rows x 2 cout tiles each); the fp32 kernel took 36.7 us per launch
@@ -832,7 +814,7 @@ int pcc_conv_split(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const 
         PCC_CHECK_HIP(hipGetLastError());
         return PCC_OK;
     }
-    if (use32 && (d->W % 32 == 0 || d->W == 16)) {
+    if (mfma32) {
         a.w = w_split + split16_floats(d->Cin);
 #define PCC_SPLIT32_LAUNCH(CH, TZ, TY, TXW, R)                                                                     \
     {                                                                                                              \

@@ -426,12 +426,9 @@ void pcc_tr2m_f16s_pack(int Cin, int Cout, const float* w_tr2g, float* out) {
     out[(size_t)NCT * NGi * (WG_BYTES / 4)] = su;
 }
 
-// 32 -> 16 and 64 -> 32 on grids of 16-multiples (the layers conv_tr2m.hip marches); shape-only rule
-bool pcc_tr2m_f16s_covers(const pcc_conv_desc* d) { return pcc_tr2m_eligible(d); }
-
 int pcc_conv_tr2m_f16s(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_f16s, const float* bias, float* out,
                        pcc_conv_ext* ext, hipStream_t st) {
-    PCC_REQUIRE(pcc_tr2m_f16s_covers(d), "pcc_conv_tr2m_f16s: shape not covered");
+    PCC_REQUIRE(pcc_tr2m_eligible(d), "pcc_conv_tr2m_f16s: shape not covered");
     const int NGi = d->Cin / 16;
     Tr2mArgs a;
     a.in = in; a.w = w_f16s; a.bias = bias; a.out = out;

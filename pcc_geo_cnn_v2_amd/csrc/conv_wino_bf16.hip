@@ -504,8 +504,6 @@ void pcc_wino_bf16_pack(int ngroups, const float* u_f32, float* out) {
             }
 }
 
-bool pcc_wino_bf16_covers(const pcc_conv_desc* d) { return d->Cin == 16 && d->Cout == 16; }
-
 int pcc_conv_wino_bf16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* ub_packed, const float* bias,
                        const float* residual, float* out, hipStream_t st) {
     PCC_REQUIRE(pcc_wino_eligible(d) && d->Cin == 16, "pcc_conv_wino_bf16: shape not covered");

@@ -154,16 +154,12 @@ int pcc_conv3d_ext(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const 
                 "pcc_conv3d: an fp16-input layer takes its residual in fp16 (PCC_CONV_RES16)");
     PCC_CHECK_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const bool fast_ok = w_packed != nullptr && pcc_conv_mfma_supported(d) == 1;
-    if (d->flags & (PCC_CONV_IN16 | PCC_CONV_OUT16)) {
-        PCC_REQUIRE(fast_ok && d->impl == PCC_IMPL_AUTO, "pcc_conv3d: fp16 storage needs the packed weights and PCC_IMPL_AUTO");
-        return pcc_conv3d_mfma_thr(ctx, d, in, w_packed, bias, residual, out, nullptr, nullptr, ext, st);
-    }
-    if (d->impl == PCC_IMPL_MFMA || d->impl == PCC_IMPL_WINOGRAD || d->impl == PCC_IMPL_SPLIT) {
-        PCC_REQUIRE(fast_ok, "pcc_conv3d: PCC_IMPL_MFMA/WINOGRAD/SPLIT requested but shape not covered or w_packed NULL");
-        return pcc_conv3d_mfma_thr(ctx, d, in, w_packed, bias, residual, out, nullptr, nullptr, ext, st);
-    }
-    if (d->impl == PCC_IMPL_AUTO && fast_ok) return pcc_conv3d_mfma_thr(ctx, d, in, w_packed, bias, residual, out, nullptr, nullptr, ext, st);
+    const bool mfma = w_packed != nullptr && pcc_conv_route(d, ctx->numerics) != PCC_FAM_GENERIC;
+    if (d->flags & (PCC_CONV_IN16 | PCC_CONV_OUT16))
+        PCC_REQUIRE(mfma && d->impl == PCC_IMPL_AUTO, "pcc_conv3d: fp16 storage needs the packed weights and PCC_IMPL_AUTO");
+    if (d->impl == PCC_IMPL_MFMA || d->impl == PCC_IMPL_WINOGRAD || d->impl == PCC_IMPL_SPLIT)
+        PCC_REQUIRE(mfma, "pcc_conv3d: PCC_IMPL_MFMA/WINOGRAD/SPLIT requested but shape not covered or w_packed NULL");
+    if (mfma) return pcc_conv3d_mfma_thr(ctx, d, in, w_packed, bias, residual, out, nullptr, nullptr, ext, st);
     PCC_REQUIRE(w != nullptr, "pcc_conv3d: generic path needs the Keras-layout weights `w`");
     return pcc_conv3d_generic(ctx, d, in, w, bias, residual, out, st);
 }

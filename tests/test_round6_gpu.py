@@ -34,16 +34,55 @@ def _ctx():
     return ops.get_context(torch.device('cuda', 0))
 
 
+# One layer per kernel family the route can return (csrc/conv_mfma.hip, pcc_conv_route): expected name prefix, (N, D, H, W, Cin, Cout,
+# k, stride, transposed), flags on top of BIAS | RELU, impl, numerics switches
+_F16, _IN16, _OUT16 = 16, 32, 64
+FAMILY_CASES = [
+    ('generic (', (1, 16, 16, 16, 16, 16, 3, 1, 0), 0, 'GENERIC', {}),
+    ('generic (', (1, 7, 9, 6, 3, 5, 3, 1, 0), 0, 'AUTO', {}),
+    ('conv_f16 (', (2, 16, 16, 16, 16, 16, 3, 1, 0), _F16 | _IN16, 'AUTO', {}),
+    ('conv_fwd (exact fp32', (1, 16, 16, 16, 16, 32, 3, 2, 0), 0, 'AUTO', {}),
+    ('conv_fwd (f16', (1, 16, 16, 16, 16, 32, 3, 2, 0), _F16, 'AUTO', {}),
+    ('conv_fwd (exact fp32', (1, 32, 32, 32, 16, 16, 3, 1, 0), 0, 'MFMA', {}),
+    ('conv_k3s1_split (', (4, 8, 8, 8, 64, 64, 3, 1, 1), 0, 'AUTO', {}),
+    ('conv_k3s1_split32', (4, 16, 16, 16, 32, 32, 3, 1, 1), 0, 'AUTO', {}),
+    ('conv_k3s1_split32', (1, 16, 16, 32, 64, 64, 3, 1, 0), 0, 'SPLIT', {'split_mfma32': True}),
+    ('conv_k3s1_split (', (1, 16, 16, 16, 32, 32, 3, 1, 0), 0, 'SPLIT', {'split_mfma16': True}),
+    # the 32x32x16 formulation needs W % 32 == 0 or W == 16: at W = 48 the 16x16x32 kernel runs, and is named
+    ('conv_k3s1_split (', (1, 8, 16, 48, 32, 32, 3, 1, 1), 0, 'SPLIT', {}),
+    ('conv_k3s1_split (', (1, 8, 16, 48, 64, 64, 3, 1, 0), 0, 'SPLIT', {'split_mfma32': True}),
+    ('conv16_wino (', (1, 64, 64, 64, 16, 16, 3, 1, 1), 0, 'AUTO', {'no_split': True}),
+    ('conv16_wino (', (1, 32, 32, 32, 32, 32, 3, 1, 1), 0, 'WINOGRAD', {'no_f16s': True}),
+    ('conv16_wino_bf16', (1, 64, 64, 64, 16, 16, 3, 1, 1), 0, 'AUTO', {'no_f16s': True}),
+    ('conv16_wino_f16s', (1, 64, 64, 64, 16, 16, 3, 1, 1), 0, 'AUTO', {}),
+    ('conv16_wino_f16s', (1, 16, 16, 16, 64, 64, 3, 1, 0), 0, 'WINOGRAD', {}),
+    ('conv_tr2 (', (1, 32, 32, 32, 32, 16, 3, 2, 1), 0, 'AUTO', {'no_tr2m': True}),
+    ('conv_tr2 (', (1, 8, 8, 8, 32, 32, 5, 2, 1), 0, 'AUTO', {}),
+    ('conv_tr2m_f16 (', (1, 32, 32, 32, 32, 16, 3, 2, 1), _F16 | _OUT16, 'AUTO', {}),
+    ('conv_tr2m_f16s', (1, 32, 32, 32, 32, 16, 3, 2, 1), 0, 'AUTO', {}),
+    ('conv_tr2m_f16s', (1, 32, 32, 32, 64, 32, 3, 2, 1), 0, 'MFMA', {}),
+    ('conv_tr2_split', (1, 8, 8, 8, 64, 64, 3, 2, 1), 0, 'AUTO', {}),
+    ('conv_tr2_split', (1, 16, 16, 16, 64, 32, 3, 2, 1), 0, 'AUTO', {'no_f16s': True}),
+    ('conv_tr2m_bf16', (1, 32, 32, 32, 32, 16, 3, 2, 1), 0, 'AUTO', {'no_f16s': True}),
+    ('conv_tr2m (', (1, 32, 32, 32, 32, 16, 3, 2, 1), 0, 'AUTO', {'no_split': True}),
+    ('conv_cin1', (1, 32, 32, 32, 1, 16, 9, 2, 0), 0, 'AUTO', {}),
+    ('conv_cout1_mfma', (1, 16, 16, 16, 16, 1, 3, 1, 1), 0, 'AUTO', {}),
+    ('conv_cout1 (', (1, 16, 16, 16, 32, 1, 3, 1, 1), 0, 'AUTO', {}),
+]
+
+
 def test_kernel_family_names_the_round6_kernels_and_follows_the_numerics_switches():
     """pcc_conv_kernel_family (include/pcc_geo.h): the c3p layers that VERDICT r05 item 1 asked to move take the two-piece fp16 kernels by
     default, PCC_NO_F16S=1 (numerics switch no_f16s) gives round 5's kernels, PCC_NO_SPLIT=1 the exact-fp32 ones -- a function of the layer
-    shape and the context only, never of the batch (encoder and decoder chunks must take the same kernel)."""
+    shape and the context only, never of the batch (encoder and decoder chunks must take the same kernel).  Every family the route can
+    return is named for a layer that reaches it (FAMILY_CASES), and the name is the kernel the launcher runs."""
     import ctypes
     from pcc_geo_cnn_v2_amd import _lib as L
     ctx = _ctx()
 
-    def fam(N, D, cin, cout, stride=1, tr=1):
-        d = L.ConvDesc(N=N, D=D, H=D, W=D, Cin=cin, Cout=cout, k=3, stride=stride, transposed=tr, flags=L.PCC_CONV_BIAS | L.PCC_CONV_RELU)
+    def fam(N, D, cin, cout, stride=1, tr=1, H=None, W=None, k=3, flags=0, impl=L.PCC_IMPL_AUTO):
+        d = L.ConvDesc(N=N, D=D, H=H or D, W=W or D, Cin=cin, Cout=cout, k=k, stride=stride, transposed=tr,
+                       flags=L.PCC_CONV_BIAS | L.PCC_CONV_RELU | flags, impl=impl)
         buf = ctypes.create_string_buffer(96)
         L.check(L.lib().pcc_conv_kernel_family(ctx.handle, ctypes.byref(d), buf, 96), 'pcc_conv_kernel_family')
         return buf.value.decode()
@@ -55,6 +94,13 @@ def test_kernel_family_names_the_round6_kernels_and_follows_the_numerics_switche
         assert fam(32, 32, 32, 16, 2).startswith('conv_tr2m_bf16')
     with ctx.numerics_override(no_split=True):
         assert fam(32, 64, 16, 16).startswith('conv16_wino (') and fam(32, 32, 32, 16, 2).startswith('conv_tr2m (')
+    names = set()
+    for want, (N, D, H, W, cin, cout, k, stride, tr), flags, impl, switches in FAMILY_CASES:
+        with ctx.numerics_override(**switches):
+            got = fam(N, D, cin, cout, stride, tr, H, W, k, flags, getattr(L, 'PCC_IMPL_' + impl))
+        assert got.startswith(want), (want, got, (N, D, H, W, cin, cout, k, stride, tr), flags, impl, switches)
+        names.add(got)
+    assert len(names) == 18, sorted(names)       # every family, each under its own name
 
 
 @pytest.mark.parametrize('C,D,N', [(16, 32, 3), (32, 32, 2), (64, 16, 3)])
