@@ -428,6 +428,28 @@ size_t pcc_mesh_sample_workspace_bytes(int64_t ntris, int64_t n);
 int pcc_mesh_to_points(pcc_ctx* ctx, const double* verts, int64_t nverts, const int32_t* tris, int64_t ntris, int64_t n, uint64_t seed,
                        int32_t vg, float* samples, float* points, int64_t* npoints_dev, void* workspace, void* stream);
 
+/* ---- point rendering (new: the rendering step of the reference's evaluation, utils/o3d.py pc_to_img without Open3D) ---------
+ * A z-buffered square splat of a point cloud through a pinhole camera.  Inputs: points (n,3) float64 and colours (n,3) uint8
+ * (device; colours NULL: every point grey 128); extrinsic E (4x4, row-major, world -> camera) and intrinsic K (3x3, row-major,
+ * [[fx, k01, cx], [0, fy, cy], [0, 0, 1]]) as host arrays; image W x H; integer point size s; background RGB.  Definition
+ * (restated in numpy by utils/render.py, which returns the same bytes), float64, every operation rounded, none contracted:
+ *   1. xc = ((e00 x + e01 y) + e02 z) + e03, yc and zc the same with rows 1 and 2 of E;
+ *   2. kept only if zc > 0; u = ((fx xc + k01 yc) + cx zc) / zc, v = (fy yc + cy zc) / zc; kept only if |u|, |v| < 2^30
+ *      (finite);
+ *   3. h = s/2 - 1 (exact), i0 = floor(u - h), j0 = floor(v - h): the point covers the pixels i0 <= i < i0+s, j0 <= j < j0+s
+ *      inside the image (s = 1: floor(u + 0.5), pixel centres at integer u);
+ *   4. key = bits(float32(zc)) << 32 | row; every pixel takes the smallest key (the nearest point; a depth tie to the lower row);
+ *   5. image (H,W,3) uint8: image[j,i] = colours[row], or the background where no point landed; rows (H,W) int32 (nullable): that
+ *      row, or -1.
+ * Limits: 0 <= n < 2^31; 1 <= W, H <= 16384; 1 <= s <= 64; finite camera values, K rows 1-2 and E's bottom row [0,0,0,1] as
+ * above (checked here as well; the Python layer checks them before any GPU call).  workspace: pcc_render_workspace_bytes(W, H)
+ * bytes (0 for a size outside the limits).  One stream, no host synchronisation; the same inputs give the same bits on every
+ * call, whatever the launch order.                                                                                            */
+size_t pcc_render_workspace_bytes(int32_t width, int32_t height);
+int pcc_render_points(pcc_ctx* ctx, const double* points, int64_t n, const uint8_t* colours, const double extrinsic[16],
+                      const double intrinsic[9], int32_t width, int32_t height, int32_t point_size, const uint8_t background[3],
+                      uint8_t* image, int32_t* rows, void* workspace, void* stream);
+
 /* ---- focal loss (src/utils/focal_loss.py:5-12) ------------------------------------------
  * Deterministic two-stage reduction (wavefront DPP/shuffle tree, fixed block order); result is a
  * single float32 written to out[0] (device).  `scratch` must hold pcc_focal_scratch_floats().   */

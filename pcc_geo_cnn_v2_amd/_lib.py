@@ -30,7 +30,7 @@ EXPORTS = [
     'pcc_profile_select', 'pcc_profile_read', 'pcc_normals_workspace_bytes', 'pcc_estimate_normals',
     'pcc_cloud_index_bytes', 'pcc_cloud_index_build', 'pcc_cloud_nearest', 'pcc_cloud_distortion_workspace_bytes', 'pcc_cloud_distortion',
     'pcc_cloud_map_colors', 'pcc_cloud_color_workspace_bytes', 'pcc_cloud_color_distortion',
-    'pcc_mesh_sample_workspace_bytes', 'pcc_mesh_to_points',
+    'pcc_mesh_sample_workspace_bytes', 'pcc_mesh_to_points', 'pcc_render_workspace_bytes', 'pcc_render_points',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -135,6 +135,10 @@ def lib():
     L.pcc_mesh_sample_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.pcc_mesh_sample_workspace_bytes.restype = sz
     L.pcc_mesh_to_points.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_uint64, i32, vp, vp, vp, vp, vp]
+    L.pcc_render_workspace_bytes.argtypes = [i32, i32]
+    L.pcc_render_workspace_bytes.restype = sz
+    L.pcc_render_points.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32, i32,
+                                    C.POINTER(C.c_uint8), vp, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

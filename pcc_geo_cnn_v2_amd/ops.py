@@ -889,6 +889,49 @@ def mesh_to_points(ctx, vertices, faces, n_samples=500000, vg_size=64, seed=0, r
     return (out, samples.cpu().numpy()) if return_samples else out
 
 
+def render_points(ctx, points, camera, colors=None, point_size=1, background=(255, 255, 255), return_rows=False):
+    """A z-buffered square splat of a point cloud through a pinhole camera on the GPU (include/pcc_geo.h "point rendering").
+    points: (n,3) float32, float64 or integer coordinates (any values: points behind the camera or off-screen are dropped);
+    camera: a utils.render.Camera; colors: (n,3) integers in 0..255, or None for flat grey (128); point_size: integer side of each
+    point's square in [1, 64]; background: RGB.  Returns the (H,W,3) uint8 numpy image (and the (H,W) int32 row of every pixel,
+    -1 for the background, with return_rows=True): the same bytes as utils.render.render_host.  Every limit is checked on the
+    host before any GPU call (ValueError); n = 0 gives the background without a launch."""
+    from .utils import render
+    p, c, s, bg = render.check_render_args(points, colors, camera, point_size, background)
+    W, H = camera.width, camera.height
+    n = int(p.shape[0])
+    if n == 0:
+        img = np.broadcast_to(bg, (H, W, 3)).copy()
+        return (img, np.full((H, W), -1, np.int32)) if return_rows else img
+    dev = ctx.device
+    p_d = torch.from_numpy(p).to(dev)
+    c_d = None if c is None else torch.from_numpy(c).to(dev)
+    img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    rows = torch.empty((H, W), dtype=torch.int32, device=dev) if return_rows else None
+    ws = torch.empty((L.lib().pcc_render_workspace_bytes(W, H),), dtype=torch.uint8, device=dev)
+    E = (C.c_double * 16)(*camera.extrinsic.ravel().tolist())
+    K = (C.c_double * 9)(*camera.intrinsic.ravel().tolist())
+    bgc = (C.c_uint8 * 3)(*bg.tolist())
+    L.check(L.lib().pcc_render_points(ctx.handle, _ptr(p_d), n, _ptr(c_d), E, K, W, H, s, bgc, _ptr(img), _ptr(rows), _ptr(ws),
+                                      ctx.stream), 'pcc_render_points')
+    if return_rows:
+        return img.cpu().numpy(), rows.cpu().numpy()
+    return img.cpu().numpy()
+
+
+def error_map(ctx, index_a, b_points):
+    """The squared D1 residual of every decoded point: for each row of b_points, the exact squared distance to its nearest point of
+    the original cloud (int64 numpy array; cloud_nearest's distance, so the reference's compute_d1_res_ba whatever the tie rule).
+    index_a: a CloudIndex of the original or its (N,3) points; b_points: (nb,3) integer coordinates in [0, 2^21)."""
+    index_a, _ = _index_or_points(index_a, 'error_map')
+    if len(b_points) == 0:
+        return np.zeros(0, np.int64)
+    _voxel_points(b_points, 'error_map')
+    if not isinstance(index_a, CloudIndex):
+        index_a = CloudIndex(ctx, index_a)
+    return cloud_nearest(ctx, index_a, b_points)[1]
+
+
 # ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------
