@@ -457,6 +457,35 @@ int pcc_focal_loss(pcc_ctx* ctx, const float* y_true, const float* y_pred, size_
                    float alpha, float* out, float* scratch, void* stream);
 size_t pcc_focal_scratch_floats(void);
 
+/* ---- training: gradients of the conv layers and of the focal loss ------------------------------
+ * Input gradient of a layer: pcc_conv3d on its DUAL descriptor (forward <-> transposed, Cin <-> Cout, same k and stride, the
+ * layer's output grid) with the SAME Keras kernel array and no bias / ReLU / ADD: a Conv3DTranspose is the adjoint of the SAME Conv3D
+ * on its larger grid.
+ * pcc_conv3d_wgrad: dw (device, the layer's Keras layout) and db (device, Cout floats; may be NULL) of the layer `d` (flags ignored)
+ * from its input `in` and output gradient `dout` (the gradient of the conv output, after the ReLU mask).  Exact-fp32 MFMA over fixed
+ * voxel slices into `workspace` (>= pcc_conv_wgrad_workspace_bytes(d) bytes, 16-byte aligned), then a fixed-order sum of the
+ * slices: bitwise identical run to run, no float atomics.                                                                    */
+size_t pcc_conv_wgrad_workspace_bytes(const pcc_conv_desc* d);
+/* The reduction depth of pcc_conv3d_wgrad on `d`: the number of voxel slices S, and the longest FMA chain of one slice
+ * (voxels of its tiles, zero-padded tiles included) -- each dW element's error is below (slice_terms + S) 2^-24 sum|terms|. */
+int pcc_conv_wgrad_slices(const pcc_conv_desc* d, int32_t* slices, int64_t* slice_terms);
+int pcc_conv3d_wgrad(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* dout, float* dw, float* db,
+                     void* workspace, size_t ws_bytes, void* stream);
+/* grad[i] = 0 where !(act[i] > 0), in place */
+int pcc_relu_backward(pcc_ctx* ctx, float* grad, const float* act, size_t n, void* stream);
+/* grad = scale[0] * d pcc_focal_loss / d y_pred (tf.clip_by_value gradient: zero strictly outside [1e-3, 0.999]).  scale: device
+ * float (NULL: 1), so that the upstream gradient never travels to the host. */
+int pcc_focal_loss_grad(pcc_ctx* ctx, const float* y_true, const float* y_pred, size_t n, float gamma, float alpha,
+                        const float* scale, float* grad, void* stream);
+/* Packed weight images rebuilt on the device from a device Keras kernel.  pcc_conv_repack_map (host) writes
+ * pcc_conv_packed_floats(d) int32: the Keras index each packed float copies, -1 for a packed zero, -2 for the segments that are not
+ * reorders of the taps (Winograd U, bf16 / fp16 pieces).  pcc_conv_repack_weights_device gathers with that map (uploaded by the
+ * caller): bit-identical to pcc_conv_pack_weights on the gathered segments, NaN on the others -- a context that computes with the
+ * image must have the split, fp16-piece and Winograd families off (pcc_ctx_set_numerics: NO_SPLIT | NO_F16S | NO_WINOGRAD).   */
+int pcc_conv_repack_map(const pcc_conv_desc* d, int32_t* map);
+int pcc_conv_repack_weights_device(pcc_ctx* ctx, const pcc_conv_desc* d, const int32_t* map, const float* w, float* pk,
+                                   void* stream);
+
 /* ---- range coder (HOST) ----------------------------------------------------------------
  * Replaces tfc's C++ ops range_coding_ops.unbounded_index_range_encode/decode
  * (src/utils/patch_gaussian_conditional.py:27-31; src/model_types.py:291-292,382-387,404-407),

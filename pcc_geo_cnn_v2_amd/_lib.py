@@ -31,6 +31,8 @@ EXPORTS = [
     'pcc_cloud_index_bytes', 'pcc_cloud_index_build', 'pcc_cloud_nearest', 'pcc_cloud_distortion_workspace_bytes', 'pcc_cloud_distortion',
     'pcc_cloud_map_colors', 'pcc_cloud_color_workspace_bytes', 'pcc_cloud_color_distortion',
     'pcc_mesh_sample_workspace_bytes', 'pcc_mesh_to_points', 'pcc_render_workspace_bytes', 'pcc_render_points',
+    'pcc_conv_wgrad_workspace_bytes', 'pcc_conv_wgrad_slices', 'pcc_conv3d_wgrad', 'pcc_relu_backward', 'pcc_focal_loss_grad', 'pcc_conv_repack_map',
+    'pcc_conv_repack_weights_device',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -139,6 +141,14 @@ def lib():
     L.pcc_render_workspace_bytes.restype = sz
     L.pcc_render_points.argtypes = [vp, vp, C.c_int64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32, i32,
                                     C.POINTER(C.c_uint8), vp, vp, vp, vp]
+    L.pcc_conv_wgrad_workspace_bytes.argtypes = [C.POINTER(ConvDesc)]
+    L.pcc_conv_wgrad_workspace_bytes.restype = sz
+    L.pcc_conv_wgrad_slices.argtypes = [C.POINTER(ConvDesc), C.POINTER(i32), C.POINTER(C.c_int64)]
+    L.pcc_conv3d_wgrad.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, sz, vp]
+    L.pcc_relu_backward.argtypes = [vp, vp, vp, sz, vp]
+    L.pcc_focal_loss_grad.argtypes = [vp, vp, vp, sz, C.c_float, C.c_float, vp, vp, vp]
+    L.pcc_conv_repack_map.argtypes = [C.POINTER(ConvDesc), vp]
+    L.pcc_conv_repack_weights_device.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

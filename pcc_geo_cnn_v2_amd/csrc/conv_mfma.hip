@@ -2055,4 +2055,33 @@ int pcc_conv3d_mfma_thr(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, c
     return PCC_ERR_ARG;
 }
 
+// Gather map of the packed image for pcc_conv_repack_weights_device (train.hip): the segments that are pure reorders of the Keras taps
+// -- the base image of every kind (conv_fwd, conv_tr2, conv_cin1, conv_cout1_mfma, conv_cout1) and the tr2g image of the k3 stride-2
+// transposed layers -- found by packing an iota kernel (indices + 1 as floats: exact below 2^24; 0 = a zero the packer wrote).
+// Every other segment (Winograd U and the bf16 / fp16 piece images) is marked -2: the training context turns those families off.
+PCC_API int pcc_conv_repack_map(const pcc_conv_desc* d, int32_t* map) {
+    PCC_REQUIRE(d && map, "pcc_conv_repack_map: NULL argument");
+    const Plan p = make_plan(d);
+    PCC_REQUIRE(p.kind != K_NONE, "pcc_conv_repack_map: shape not covered by the MFMA path");
+    const Packed L = packed_layout(d, p.kind);
+    const size_t taps = (size_t)d->k * d->k * d->k * d->Cin * d->Cout;
+    PCC_REQUIRE(taps < (size_t(1) << 24), "pcc_conv_repack_map: kernel too large for an fp32 iota");
+    size_t base_end = L.total;
+    for (size_t off : {L.wino_u, L.f16, L.wino_ub, L.split, L.wino_uh, L.tr2g, L.tr2_split, L.tr2_f16s})
+        if (off && off < base_end) base_end = off;
+    float* iota = (float*)malloc(taps * sizeof(float));
+    float* pk = (float*)malloc(L.total * sizeof(float));
+    if (!iota || !pk) { free(iota); free(pk); PCC_REQUIRE(false, "pcc_conv_repack_map: out of memory"); }
+    for (size_t i = 0; i < taps; ++i) iota[i] = (float)(i + 1);
+    const int rc = pcc_conv_pack_weights(d, iota, pk);
+    if (rc == PCC_OK)
+        for (size_t i = 0; i < L.total; ++i) {
+            const bool gathered = i < base_end || (L.tr2g && i >= L.tr2g && i < L.tr2g + (size_t)27 * d->Cin * d->Cout);
+            map[i] = gathered ? (int32_t)pk[i] - 1 : -2;
+        }
+    free(iota);
+    free(pk);
+    return rc;
+}
+
 #endif  // PCC_PART == 0

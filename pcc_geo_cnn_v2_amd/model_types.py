@@ -857,9 +857,11 @@ class CompressionModelV1(CompressionModel):
         self.entropy_bottleneck = None
         super().__init__(*args, **kwargs)
 
-    def train(self, x, gamma, alpha, lmbda):
-        raise NotImplementedError('training is out of scope of the MI355X hot path (SURVEY.md §2); '
-                                  'the focal-loss reduction is available as utils.focal_loss.focal_loss')
+    def train(self, x, gamma, alpha, lmbda, **trainer_args):
+        """The training model (src/model_types.py:250-277 / :327-369) as a train.Trainer: `x` is unused (the trainer
+        voxelises its own batches from `train_blocks` / `val_blocks`); see train.Trainer for the other arguments."""
+        from .train import Trainer
+        return Trainer(self, gamma=gamma, alpha=alpha, lmbda=lmbda, **trainer_args)
 
     def _transforms(self):
         t = []
@@ -976,9 +978,11 @@ class CompressionModelV2(CompressionModel):
         self.entropy_bottleneck = self.conditional_bottleneck = None
         super().__init__(*args, **kwargs)
 
-    def train(self, x, gamma, alpha, lmbda):
-        raise NotImplementedError('training is out of scope of the MI355X hot path (SURVEY.md §2); '
-                                  'the focal-loss reduction is available as utils.focal_loss.focal_loss')
+    def train(self, x, gamma, alpha, lmbda, **trainer_args):
+        """The training model (src/model_types.py:250-277 / :327-369) as a train.Trainer: `x` is unused (the trainer
+        voxelises its own batches from `train_blocks` / `val_blocks`); see train.Trainer for the other arguments."""
+        from .train import Trainer
+        return Trainer(self, gamma=gamma, alpha=alpha, lmbda=lmbda, **trainer_args)
 
     def _transforms(self):
         t = []

@@ -578,6 +578,67 @@ def focal_loss(ctx, y_true, y_pred, gamma=2.0, alpha=0.9):
     return out[0]
 
 
+def focal_loss_grad(ctx, y_true, y_pred, scale=None, gamma=2.0, alpha=0.9):
+    """scale * d focal_loss / d y_pred (pcc_focal_loss_grad); scale: a one-element float32 device tensor (None: 1)."""
+    assert y_true.numel() == y_pred.numel() and y_true.is_contiguous() and y_pred.is_contiguous()
+    assert scale is None or (scale.dtype == torch.float32 and scale.numel() == 1 and scale.device == y_pred.device)
+    grad = torch.empty_like(y_pred)
+    L.check(L.lib().pcc_focal_loss_grad(ctx.handle, _ptr(y_true), _ptr(y_pred), y_pred.numel(), gamma, alpha,
+                                        _ptr(None if scale is None else scale.contiguous()), _ptr(grad), ctx.stream),
+            'pcc_focal_loss_grad')
+    return grad
+
+
+def relu_backward(ctx, grad, act):
+    """grad *= (act > 0), in place (pcc_relu_backward)."""
+    assert grad.is_contiguous() and act.is_contiguous() and grad.numel() == act.numel() and grad.dtype == act.dtype == torch.float32
+    L.check(L.lib().pcc_relu_backward(ctx.handle, _ptr(grad), _ptr(act), grad.numel(), ctx.stream), 'pcc_relu_backward')
+    return grad
+
+
+def dual_desc(d):
+    """The descriptor whose pcc_conv3d is the input gradient of layer `d` (include/pcc_geo.h, training): forward <-> transposed,
+    Cin <-> Cout, on the layer's output grid, no bias / ReLU / residual."""
+    od, oh, ow = C.c_int32(), C.c_int32(), C.c_int32()
+    L.check(L.lib().pcc_conv_out_dims(C.byref(d), C.byref(od), C.byref(oh), C.byref(ow)), 'pcc_conv_out_dims')
+    return L.ConvDesc(d.N, od.value, oh.value, ow.value, d.Cout, d.Cin, d.k, d.stride, 1 - d.transposed, 0, L.PCC_IMPL_AUTO, 0, 0)
+
+
+def conv_repack_map(d):
+    """int32 gather map of the packed image of `d` (pcc_conv_repack_map), or None when the MFMA path does not cover `d`."""
+    if L.lib().pcc_conv_mfma_supported(C.byref(d)) != 1:
+        return None
+    m = np.empty(L.lib().pcc_conv_packed_floats(C.byref(d)), np.int32)
+    L.check(L.lib().pcc_conv_repack_map(C.byref(d), m.ctypes.data_as(C.c_void_p)), 'pcc_conv_repack_map')
+    return m
+
+
+def conv_repack_device(ctx, d, map_dev, w, pk):
+    """pk <- the packed image of the device Keras kernel w (pcc_conv_repack_weights_device, gather segments only)."""
+    assert map_dev.dtype == torch.int32 and w.dtype == pk.dtype == torch.float32 and w.is_contiguous() and pk.is_contiguous()
+    L.check(L.lib().pcc_conv_repack_weights_device(ctx.handle, C.byref(d), _ptr(map_dev), _ptr(w), _ptr(pk), ctx.stream),
+            'pcc_conv_repack_weights_device')
+    return pk
+
+
+def conv_wgrad_slices(d):
+    """(S, longest slice chain) of pcc_conv3d_wgrad on descriptor d (pcc_conv_wgrad_slices)."""
+    s, n = C.c_int32(), C.c_int64()
+    L.check(L.lib().pcc_conv_wgrad_slices(C.byref(d), C.byref(s), C.byref(n)), 'pcc_conv_wgrad_slices')
+    return int(s.value), int(n.value)
+
+
+def conv3d_wgrad(ctx, d, x, dout, dw, db=None, workspace=None):
+    """dw (Keras layout) and db of layer `d` from its input x and the gradient dout of its conv output (pcc_conv3d_wgrad)."""
+    assert x.is_contiguous() and dout.is_contiguous() and dw.is_contiguous()
+    nbytes = L.lib().pcc_conv_wgrad_workspace_bytes(C.byref(d))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty((int(nbytes),), dtype=torch.uint8, device=x.device)
+    L.check(L.lib().pcc_conv3d_wgrad(ctx.handle, C.byref(d), _ptr(x), _ptr(dout), _ptr(dw), _ptr(db), _ptr(workspace),
+                                     workspace.numel(), ctx.stream), 'pcc_conv3d_wgrad')
+    return dw, db
+
+
 def d1_threshold_stats(ctx, x_hat, thr, pts, block_of, clip=True):
     """Exact D1 sums for every threshold of every block (see include/pcc_geo.h).  x_hat (B,D,H,W) float32,
     thr (T<=256,) float32, pts (n,3) int32 grouped by block, block_of (n,) int32 -- all on the device.
