@@ -22,28 +22,13 @@
 // sums in a context-owned scratch tensor, the launch of input half 1 adds them (fp32) before bias / ReLU / residual; both cout
 // halves are workgroups of the same launch.  Deterministic: fixed k order, no atomics.
 #include <cstdlib>
-#include <type_traits>
 
 #include "common.h"
+#include "kernel_common.h"
 
 namespace pccf16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-constexpr unsigned kOOB = 0x80000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
+using namespace pcck;
 
 // timing probes (tools/build_variant.sh, tools/r06_f16_probe.sh): 1 no MFMAs, 2 no plane loads, 4 no residual loads / stores, 8 no vmcnt wait / barrier
 // (2 | 4 leaves nothing observable: the compiler removes the kernel).  C = 16 @128^3 x 8 alone, round 6, us avg | min of 51 launches, with / without
@@ -121,12 +106,12 @@ __global__ void __launch_bounds__(256, 2) conv_f16_kernel(F16Args a, int nwg) {
     const unsigned char* in_n = (const unsigned char*)a.in + (size_t)n * a.D * PLB;
 
     // ---- A fragments of this wave's cout group: resident for the life of the workgroup
-    h16x8 A[K::NA];
+    f16x8 A[K::NA];
     {
         const __amdgpu_buffer_rsrc_t rw = make_rsrc((const unsigned char*)a.w + (size_t)(cog * K::NCT + ct) * K::NA * 1024, (unsigned)K::NA * 1024u);
 #pragma unroll
         for (int i = 0; i < K::NA; ++i)
-            A[i] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(i * 1024 + lane * 16), 0, 0));
+            A[i] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(i * 1024 + lane * 16), 0, 0));
     }
 
     // ---- staging: global -> LDS directly; the plane image in LDS is the 18 x 18 haloed tile in memory order
@@ -211,9 +196,9 @@ __global__ void __launch_bounds__(256, 2) conv_f16_kernel(F16Args a, int nwg) {
         const unsigned char* pl = smem + slotC + brow0;
 #pragma unroll
         for (int yi = 0; yi < K::R + 2; ++yi) {
-            h16x8 B[K::NF];
+            f16x8 B[K::NF];
 #pragma unroll
-            for (int f = 0; f < K::NF; ++f) B[f] = *reinterpret_cast<const h16x8*>(pl + yi * 18 * K::VB + bfo[f]);
+            for (int f = 0; f < K::NF; ++f) B[f] = *reinterpret_cast<const f16x8*>(pl + yi * 18 * K::VB + bfo[f]);
 #pragma unroll
             for (int f = 0; f < K::NF; ++f)
 #pragma unroll
@@ -239,7 +224,7 @@ __global__ void __launch_bounds__(256, 2) conv_f16_kernel(F16Args a, int nwg) {
                 const unsigned vox = (unsigned)(oy * a.W + ox);
                 f32x4 o = acc[PH][i];
                 if (SUB) {
-                    const h16x4 ph = __builtin_bit_cast(h16x4, preq[PH][i]);      // zeros when there is no previous half
+                    const f16x4 ph = __builtin_bit_cast(f16x4, preq[PH][i]);      // zeros when there is no previous half
 #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] += (float)ph[c];
                 }
@@ -247,7 +232,7 @@ __global__ void __launch_bounds__(256, 2) conv_f16_kernel(F16Args a, int nwg) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) o[c] = fmaxf(o[c], relu_lo);
                 if (has_res) {
-                    const h16x4 rh = __builtin_bit_cast(h16x4, resq[PH][i]);
+                    const f16x4 rh = __builtin_bit_cast(f16x4, resq[PH][i]);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] += (float)rh[c];
                 }
@@ -258,7 +243,7 @@ __global__ void __launch_bounds__(256, 2) conv_f16_kernel(F16Args a, int nwg) {
                 if (OUT32 && !raw) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rout, (int)(ok ? (vox * GS + cofs) * 4u : kOOB), 0, 0);
                 } else {
-                    h16x4 oh;
+                    f16x4 oh;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) oh[c] = (_Float16)o[c];      // round to nearest even
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, oh), rout, (int)(ok ? (vox * GS + cofs) * 2u : kOOB), 0, 0);

@@ -19,10 +19,9 @@
 //   conv_cin1_kernel: Conv3D with Cin = 1 (first layer): k-slots of the MFMA are kernel taps along x.
 //   conv_cout1_kernel: Conv3DTranspose with Cout = 1 (last layer): VALU dot products from an LDS tile.
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
 #include "common.h"
+#include "kernel_common.h"
 
 // Compiled several times with -DPCC_PART=k (see Makefile): part 0 holds the dispatcher, the weight packer and the
 // first/last-layer kernels; parts 1.. hold the explicit instantiations of launch_fwd<> / launch_tr2<> so that the
@@ -33,10 +32,7 @@
 
 namespace pccmfma {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using namespace pcck;
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -44,25 +40,14 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 // PCC_CONV_F16 (BASELINE.json configs[4]): the same fragments -- a lane's float4 holds k-slots 4*(lane>>4)..+3 of a
 // 16-channel group, exactly the k layout of v_mfma_f32_16x16x16_f16 -- are rounded to fp16 (v_cvt_pk_f16_f32, RTN) and
 // contracted by ONE matrix instruction instead of four; accumulation, bias, activations in HBM and LDS stay fp32.
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 mfma16h(const f32x4& a, const f32x4& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_convertvector(a, h16x4), __builtin_convertvector(b, h16x4), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_convertvector(a, f16x4), __builtin_convertvector(b, f16x4), c, 0, 0, 0);
 }
 
-// Raw buffer resources: the hardware range check returns 0 for offsets >= num_records, which implements the
-// SAME zero padding (and the tile overhang) without a single branch; the descriptor is wave-uniform (SGPRs).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-constexpr unsigned kOOB = 0x80000000u;                 // >= any per-image byte size the planner admits
 // sched_barrier mask: VALU, SALU, DS and transcendental ops may cross; vector-memory ops and MFMAs may not ->
 // a prefetch load stays in front of the MFMAs of the tap it was written in (two taps before its use).
+// (The stricter PCC_PIN_MEM_MFMA is in kernel_common.h.)
 #define PCC_PIN_VMEM() __builtin_amdgcn_sched_barrier(0x786)
-// stricter: only VALU / SALU / transcendental ops may cross (memory ops and MFMAs keep their written order)
-#define PCC_PIN_MEM_MFMA() __builtin_amdgcn_sched_barrier(0x406)
 
 struct ConvArgs {
     const float* in;
@@ -92,21 +77,13 @@ __device__ __forceinline__ f32x4 store_out(const ConvArgs& a, f32x4 v, size_t vo
         v.z = fminf(fmaxf(v.z, 0.f), 1.f); v.w = fminf(fmaxf(v.w, 0.f), 1.f);
     }
     if (a.flags & PCC_CONV_OUT16) {      // fp16 hand-over to conv_f16.hip (fp16 mode): 8 bytes per lane
-        h16x4 h;
+        f16x4 h;
         h[0] = (_Float16)v.x; h[1] = (_Float16)v.y; h[2] = (_Float16)v.z; h[3] = (_Float16)v.w;
-        *reinterpret_cast<h16x4*>(reinterpret_cast<_Float16*>(a.out) + vox * a.ocs + a.oco + c0) = h;
+        *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(a.out) + vox * a.ocs + a.oco + c0) = h;
     } else {
         *reinterpret_cast<f32x4*>(a.out + vox * a.ocs + a.oco + c0) = v;
     }
     return v;
-}
-
-// XCD-aware tile index: consecutive tile ids go to the same XCD (blocks are dispatched round-robin over
-// the 8 XCDs), so that neighbouring tiles share their halos in one L2.  Bijective for any grid size.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 
 // =====================================================================================================
@@ -294,9 +271,9 @@ conv_fwd_kernel(ConvArgs a) {
                         o.z = fminf(fmaxf(o.z, 0.f), 1.f); o.w = fminf(fmaxf(o.w, 0.f), 1.f);
                     }
                     if (a.flags & PCC_CONV_OUT16) {      // (wave-uniform) fp16 hand-over, as store_out
-                        h16x4 h;
+                        f16x4 h;
                         h[0] = (_Float16)o.x; h[1] = (_Float16)o.y; h[2] = (_Float16)o.z; h[3] = (_Float16)o.w;
-                        *reinterpret_cast<h16x4*>(reinterpret_cast<_Float16*>(a.out) + vox * a.ocs + a.oco + c0) = h;
+                        *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(a.out) + vox * a.ocs + a.oco + c0) = h;
                     } else {
                         *reinterpret_cast<f32x4*>(a.out + vox * a.ocs + a.oco + c0) = o;
                     }
@@ -806,9 +783,6 @@ __host__ __device__ constexpr Tr2gTap tr2g_tap(int want) {
     return Tr2gTap{0, 0, 0, 0, false, false};
 }
 
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
 // EPI: the epilogue is compiled for the layer's flags (the per-store flag tests of a generic epilogue cost this kernel more
 // scalar registers and branches than it has to spare): 0 = bias / ReLU, fp32 store (every stride-2 transposed layer of the c*
 // graphs); 1 = bias / ReLU, fp16 store (PCC_CONV_OUT16, the fp16 mode); 2 = any flags (residual, clip), tested at run time.
@@ -1005,7 +979,7 @@ conv_tr2g_kernel(ConvArgs a, int ntiles) {
                             }
                             const unsigned boff = ooff[i] + coff + (unsigned)((ct0 + ct) * 16) * esz;
                             if (EPI == TR2G_EPI_F16 || (EPI == TR2G_EPI_ANY && any_out16)) {
-                                h16x4 oh;
+                                f16x4 oh;
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) oh[c] = (_Float16)o[c];
                                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, oh), rout, (int)boff, 0, 0);
@@ -1332,7 +1306,7 @@ __global__ void __launch_bounds__((Cout1M<T>::NT)) conv_cout1_mfma_kernel(ConvAr
     const unsigned char* inb = (const unsigned char*)a.in + (size_t)n * a.D * plane_bytes;
     const __amdgpu_buffer_rsrc_t rin = make_rsrc(inb, (unsigned)a.D * plane_bytes);
     // fp16 input arrives as 4 halfs in the low half of the float4 slot (bit pattern), converted weights beside it
-    const h16x4 wA0h = __builtin_convertvector(wA0, h16x4), wA1h = __builtin_convertvector(wA1, h16x4);
+    const f16x4 wA0h = __builtin_convertvector(wA0, f16x4), wA1h = __builtin_convertvector(wA1, f16x4);
     auto load_in = [&](unsigned voff_, unsigned soff) -> f32x4 {
         if constexpr (IN16) {
             const u32x2 r = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rin, (int)voff_, (int)soff, 0));
@@ -1391,7 +1365,7 @@ __global__ void __launch_bounds__((Cout1M<T>::NT)) conv_cout1_mfma_kernel(ConvAr
 #pragma unroll
             for (int k = K0; k < K1; ++k) {
                 const u32x4 cb = __builtin_bit_cast(u32x4, x[k]);
-                const h16x4 bh = __builtin_bit_cast(h16x4, (u32x2){cb[0], cb[1]});
+                const f16x4 bh = __builtin_bit_cast(f16x4, (u32x2){cb[0], cb[1]});
                 d0[k] = __builtin_amdgcn_mfma_f32_16x16x16f16(wA0h, bh, zero4, 0, 0, 0);
                 d1[k] = __builtin_amdgcn_mfma_f32_16x16x16f16(wA1h, bh, zero4, 0, 0, 0);
             }

@@ -23,68 +23,19 @@
 // on distinct bank quads, like the 24-dword stride of the fp32 kernel.  Weights stream from L2 through a register ring two taps
 // ahead; the next group's staging loads and the residual rows ride in the tap sections.
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
-#include <utility>
 
 #include "common.h"
+#include "kernel_common.h"
 
 namespace pccsplit {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using namespace pcck;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-__device__ __forceinline__ u32x4 buf_load4u(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-constexpr unsigned kOOB = 0x80000000u;
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// only VALU / SALU may cross: memory operations and MFMAs keep their written order (as PCC_PIN_MEM_MFMA in conv_mfma.hip)
-#define PCC_SPLIT_PIN() __builtin_amdgcn_sched_barrier(0x406)
 // timing probes (tools/build_variant.sh): 1 no weight loads in the tap loop, 2 no LDS operand reads in the tap loop, 4 no staging loads,
 // 8 (16x16x32 kernel only) MFMAs of tap 0 only.  64 -> 64 @8^3 x 32 alone, round 6: 23.8 us; 1: 19.0; 2: 22.5; 4: 22.5; 7: 17.5; 8: 8.5; 15: 7.9
 #ifndef PCC_SPLIT_PROBE
 #define PCC_SPLIT_PROBE 0
 #endif
-
-// Two staging items (2 x 4 input channels of a voxel each): fp32 -> B1 = [dh | dm], B2 = [dl | dh] each.  ONE asm block, because
-// v_dot2c_f32_bf16 is a DOT instruction: a different VALU op that reads its result needs 3 wait states behind it
-// (GCNHazardRecognizer: DotWriteDifferentVALURead) and the hazard recogniser cannot see into inline asm.  Inside the block every
-// reader sits >= 3 instructions behind its writer; K0 / K1 = the bf16 pairs {-1, 0} / {0, -1}: x -= lo(h) / hi(h), exactly.
-__device__ __forceinline__ void split_items2(u32x4& p_b1, u32x4& p_b2, u32x4& q_b1, u32x4& q_b2, const f32x4& pv, const f32x4& qv) {
-    float a = pv[0], b = pv[1], c = pv[2], d = pv[3], e = qv[0], f = qv[1], g = qv[2], h = qv[3];
-    unsigned ph01, ph23, pm01, pm23, pl01, pl23, pg01, pg23, qh01, qh23, qm01, qm23, ql01, ql23, qg01, qg23;
-    asm volatile(
-        "v_cvt_pk_bf16_f32 %8, %0, %1\n\tv_cvt_pk_bf16_f32 %9, %2, %3\n\tv_cvt_pk_bf16_f32 %16, %4, %5\n\tv_cvt_pk_bf16_f32 %17, %6, %7\n\t"
-        "v_cvt_pk_bf16_f32 %14, %0, %1\n\tv_cvt_pk_bf16_f32 %15, %2, %3\n\tv_cvt_pk_bf16_f32 %22, %4, %5\n\tv_cvt_pk_bf16_f32 %23, %6, %7\n\t"
-        "v_dot2c_f32_bf16 %0, %24, %8\n\tv_dot2c_f32_bf16 %1, %25, %8\n\tv_dot2c_f32_bf16 %2, %24, %9\n\tv_dot2c_f32_bf16 %3, %25, %9\n\t"
-        "v_dot2c_f32_bf16 %4, %24, %16\n\tv_dot2c_f32_bf16 %5, %25, %16\n\tv_dot2c_f32_bf16 %6, %24, %17\n\tv_dot2c_f32_bf16 %7, %25, %17\n\t"
-        "v_cvt_pk_bf16_f32 %10, %0, %1\n\tv_cvt_pk_bf16_f32 %11, %2, %3\n\tv_cvt_pk_bf16_f32 %18, %4, %5\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %19, %6, %7\n\t"
-        "v_dot2c_f32_bf16 %0, %24, %10\n\tv_dot2c_f32_bf16 %1, %25, %10\n\tv_dot2c_f32_bf16 %2, %24, %11\n\tv_dot2c_f32_bf16 %3, %25, %11\n\t"
-        "v_dot2c_f32_bf16 %4, %24, %18\n\tv_dot2c_f32_bf16 %5, %25, %18\n\tv_dot2c_f32_bf16 %6, %24, %19\n\tv_dot2c_f32_bf16 %7, %25, %19\n\t"
-        "v_cvt_pk_bf16_f32 %12, %0, %1\n\tv_cvt_pk_bf16_f32 %13, %2, %3\n\tv_cvt_pk_bf16_f32 %20, %4, %5\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %21, %6, %7\n\ts_nop 2"
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h),
-          "=&v"(ph01), "=&v"(ph23), "=&v"(pm01), "=&v"(pm23), "=&v"(pl01), "=&v"(pl23), "=&v"(pg01), "=&v"(pg23),
-          "=&v"(qh01), "=&v"(qh23), "=&v"(qm01), "=&v"(qm23), "=&v"(ql01), "=&v"(ql23), "=&v"(qg01), "=&v"(qg23)
-        : "s"(0x0000bf80u), "s"(0xbf800000u));
-    p_b1 = (u32x4){ph01, ph23, pm01, pm23}; p_b2 = (u32x4){pl01, pl23, pg01, pg23};
-    q_b1 = (u32x4){qh01, qh23, qm01, qm23}; q_b2 = (u32x4){ql01, ql23, qg01, qg23};
-}
-
 
 struct SplitArgs {
     const float* in;
@@ -253,7 +204,7 @@ conv_k3s1_split_kernel(SplitArgs a) {
             }
             // the prefetches of the NEXT tap are issued before this tap's MFMAs, not sunk behind them (the scheduler otherwise moves
             // them to the end of the region, i.e. right in front of their first use: every tap then waits for its LDS reads)
-            PCC_SPLIT_PIN();
+            PCC_PIN_MEM_MFMA();
             // three MFMAs per (row, cout tile); term outermost: consecutive MFMAs go to different accumulators
 #pragma unroll
             for (int tm = 0; tm < 3; ++tm)
@@ -263,7 +214,7 @@ conv_k3s1_split_kernel(SplitArgs a) {
                     for (int ct = 0; ct < CTW; ++ct)
                         if (!(PCC_SPLIT_PROBE & 8) || ts == 0)
                         acc[i][ct] = mfma_bf16(tm == 2 ? wf2[ts % RING][ct] : wf1[ts % RING][ct], tm == 1 ? b2[ts & 1][i] : b1[ts & 1][i], acc[i][ct]);
-            PCC_SPLIT_PIN();
+            PCC_PIN_MEM_MFMA();
         }
         if (!last) {
             __syncthreads();   // every wave finished reading group g
@@ -433,7 +384,7 @@ __global__ void __launch_bounds__((Split32Cfg<CH, TZ, TY, TXW, R>::NT), 1) conv_
                         if (!(PCC_SPLIT_PROBE & 2)) b[(ts + 1) & 1][i][p] = *reinterpret_cast<const u32x4*>(lbase + toff + i * ROW_OFF + p * 8);
                 if (ts < 2 * C::ITEMS && !(PCC_SPLIT_PROBE & 4)) stg[ts] = buf_load4(rin, soff[ts >> 1], gnext + (unsigned)((ts & 1) * 16));
             }
-            PCC_SPLIT_PIN();         // (prefetches first, see the 16x16x32 kernel)
+            PCC_PIN_MEM_MFMA();         // (prefetches first, see the 16x16x32 kernel)
             // six product terms; the term outermost so that consecutive MFMAs go to different accumulators
 #pragma unroll
             for (int tm = 0; tm < 6; ++tm) {
@@ -443,7 +394,7 @@ __global__ void __launch_bounds__((Split32Cfg<CH, TZ, TY, TXW, R>::NT), 1) conv_
 #pragma unroll
                     for (int h = 0; h < NH; ++h) acc[i][h] = mfma32_bf16(wf[ts % RING][h][PA[tm]], b[ts & 1][i][PB[tm]], acc[i][h]);
             }
-            PCC_SPLIT_PIN();
+            PCC_PIN_MEM_MFMA();
         }
         if (!last) {
             __syncthreads();
@@ -504,8 +455,6 @@ __host__ __device__ constexpr Tr2Tap tr2_tap(int want) {
     }
     return Tr2Tap{0, 0, 0, 0, false};
 }
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 template <int CIN, int COUT, int TZ, int TY, int R, int CTW, int TXW>
 struct Tr2SplitCfg {
@@ -652,7 +601,7 @@ conv_tr2_split_kernel(SplitArgs a) {
                 }
                 if constexpr (!LAST && ts < C::ITEMS) stg[ts] = buf_load4(rin, soff[ts], gnext);
             }
-            PCC_SPLIT_PIN();
+            PCC_PIN_MEM_MFMA();
 #pragma unroll
             for (int tm = 0; tm < 3; ++tm)
 #pragma unroll
@@ -660,7 +609,7 @@ conv_tr2_split_kernel(SplitArgs a) {
 #pragma unroll
                     for (int ct = 0; ct < CTW; ++ct)
                         acc[cls][i][ct] = mfma_bf16(tm == 2 ? wf2[WS][ct] : wf1[WS][ct], tm == 1 ? b2[ts & 1][i] : b1[ts & 1][i], acc[cls][i][ct]);
-            PCC_SPLIT_PIN();
+            PCC_PIN_MEM_MFMA();
             if constexpr (LAST && T.last) {      // the class is complete: ReLU and stores (the bias is in the accumulators)
                 constexpr int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;
                 const unsigned coff = (unsigned)(((pz * OH + py) * OW + px) * a.ocs) * 4u;
@@ -697,19 +646,6 @@ using namespace pccsplit;
 // ---- host: split image of the logical forward weights.  wlog: [kz][ky][kx][ci][co] (already flipped for transposed layers);
 //      out: [cin group][tap][cout tile][operand][lane][8 bf16]; operand 0 = [Wh c0..c3 | Wm], 1 = [Wl | Wh]; cin = 16 g + 4 (lane >> 4) + c,
 //      cout = 16 ct + (lane & 15)
-static inline unsigned short bf16_rn(float v) {
-    unsigned b;
-    memcpy(&b, &v, 4);
-    if ((b & 0x7f800000u) == 0x7f800000u) return (unsigned short)(b >> 16);
-    b += 0x7fffu + ((b >> 16) & 1u);
-    return (unsigned short)(b >> 16);
-}
-static inline float bf16_f(unsigned short h) {
-    const unsigned b = (unsigned)h << 16;
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
-}
 // two images: the 16x16x32 kernel's ([g][tap][ct][2 operands][lane][8 bf16]) and, behind it, the 32x32x16 kernel's
 // ([g][tap][cout half][piece h, m, l][lane][8 bf16]: lane (n, o) = output channel 32 half + n, input channels 16 g + 8 o .. + 7)
 static size_t split16_floats(int C) { return (size_t)(C / 16) * 27 * (C / 16) * 2 * 64 * 4; }
@@ -725,10 +661,7 @@ void pcc_split_pack(int C, const float* wlog, float* out) {
                     unsigned short h[4], m[4], l[4];
                     for (int c = 0; c < 4; ++c) {
                         const float x = wlog[((size_t)tap * C + g * 16 + 4 * (lane >> 4) + c) * C + ct * 16 + (lane & 15)];
-                        h[c] = bf16_rn(x);
-                        const float r1 = x - bf16_f(h[c]);
-                        m[c] = bf16_rn(r1);
-                        l[c] = bf16_rn(r1 - bf16_f(m[c]));
+                        bf16_split3(x, h[c], m[c], l[c]);
                     }
                     unsigned short* a1 = o + (((((size_t)g * 27 + tap) * NG + ct) * 2 + 0) * 64 + lane) * 8;
                     unsigned short* a2 = o + (((((size_t)g * 27 + tap) * NG + ct) * 2 + 1) * 64 + lane) * 8;
@@ -741,10 +674,8 @@ void pcc_split_pack(int C, const float* wlog, float* out) {
                 for (int lane = 0; lane < 64; ++lane)
                     for (int c = 0; c < 8; ++c) {
                         const float x = wlog[((size_t)tap * C + g * 16 + 8 * (lane >> 5) + c) * C + half * 32 + (lane & 31)];
-                        const unsigned short hh = bf16_rn(x);
-                        const float r1 = x - bf16_f(hh);
-                        const unsigned short mm = bf16_rn(r1);
-                        const unsigned short ll = bf16_rn(r1 - bf16_f(mm));
+                        unsigned short hh, mm, ll;
+                        bf16_split3(x, hh, mm, ll);
                         const size_t base = ((((size_t)g * 27 + tap) * (C / 32) + half) * 3) * 64;
                         o3[((base + 0 * 64 + lane) * 8) + c] = hh;
                         o3[((base + 1 * 64 + lane) * 8) + c] = mm;

@@ -19,39 +19,14 @@
 //   * everything that selects code is a compile-time constant (plane parity, first micro-step): no branches in the stream.
 // Fixed summation order per output (cin group -> tap -> k-slice, one fp32 chain): bit-deterministic, batch invariant.
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
-#include "common.h"
+#include "tr2m_common.h"
 
 namespace pcctr2m {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace pcck;
+using namespace pcctr2;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, f32x4 v, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, 0);
-}
-constexpr unsigned kOOB = 0x80000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-__device__ __forceinline__ f32x4 acc_read(const f32x4& a) {
-    f32x4 d;
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
-                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "a"(a[0]), "a"(a[1]), "a"(a[2]), "a"(a[3]));
-    return d;
-}
-
-constexpr int NT = 256;
-constexpr int LXY = 17;                                 // tile edge incl. the low-side halo (taps reach b - 1 only)
-constexpr int TILE_SLOTS = LXY * LXY * 4;               // 16-byte slots of one (plane, cin group) tile: 1156
 constexpr int ITEMS = 5;                                // 1 KB chunks per wave (4 x 5 = 20 >= 1156 / 64)
 constexpr int TILE_BYTES = 4 * ITEMS * 1024;            // 20480
 constexpr int W_BASE = 2 * TILE_BYTES;                  // ring of two tiles, then the weights
@@ -67,29 +42,6 @@ struct Tr2mArgs {
     int flags, ocs, oco;
 };
 
-// tap t = 0..26 of a micro-step, kz-major; within a kz the (ky, kx) order keeps equal input offsets together and lets the
-// first four taps open the four parity classes
-struct Tap { int kz, ky, kx, cls, dyi, dxi, sq; bool opens; };
-__host__ __device__ constexpr int tr2g_seq(int kz, int ky, int kx) {      // position in the packed (class-major) weight order
-    int seq = 0;
-    for (int cls = 0; cls < 8; ++cls) {
-        const int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;
-        for (int z = pz; z < 3; z += 2)
-            for (int y = py; y < 3; y += 2)
-                for (int x = px; x < 3; x += 2, ++seq)
-                    if (z == kz && y == ky && x == kx) return seq;
-    }
-    return -1;
-}
-__host__ __device__ constexpr Tap tap_of(int t) {
-    constexpr int KY[9] = {0, 0, 1, 1, 0, 1, 2, 2, 2}, KX[9] = {0, 1, 0, 1, 2, 2, 0, 1, 2};
-    const int kz = t / 9, r = t % 9, ky = KY[r], kx = KX[r];
-    return Tap{kz, ky, kx, (ky & 1) * 2 + (kx & 1), ky == 2 ? 1 : 0, kx == 2 ? 1 : 0, tr2g_seq(kz, ky, kx), r < 4};
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
 template <int NG, bool RELU>
 __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -98,13 +50,8 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
     auto ldsr = [&](unsigned off) -> f32x4 { return *reinterpret_cast<const f32x4*>(smem + off); };
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int ct = wg % a.nct; wg /= a.nct;          // cout tile: neighbours in the grid share their input tiles in L2
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
     const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 16;
     const size_t HW = (size_t)a.H * a.W;
@@ -283,26 +230,11 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
 
 using namespace pcctr2m;
 
-// Eligible: k3 stride-2 transposed, (Cin, Cout) in {(32, 16), (64, 32)}, H and W multiples of 16, bias / ReLU epilogue only
-// (no layer of the c* graphs adds a residual to, or clips, a stride-2 transposed conv), fp32.
+// Eligible: the z-march shapes (tr2m_common.h) with a bias / ReLU epilogue only (no layer of the c* graphs adds a residual to, or
+// clips, a stride-2 transposed conv), fp32.
 bool pcc_tr2m_eligible(const pcc_conv_desc* d) {
-    if (!d->transposed || d->k != 3 || d->stride != 2) return false;
-    if (!((d->Cin == 32 && d->Cout == 16) || (d->Cin == 64 && d->Cout == 32))) return false;
-    if (d->H % 16 || d->W % 16) return false;
     if (d->flags & (PCC_CONV_ADD | PCC_CONV_CLIP01 | PCC_CONV_F16 | PCC_CONV_OUT16 | PCC_CONV_IN16 | PCC_CONV_RES16)) return false;
-    const int ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    if (ocs % 4 || d->out_coffset % 4) return false;
-    if ((double)d->H * d->W * d->Cin * 4.0 >= 2147483648.0) return false;                 // one input plane per descriptor
-    if (2.0 * (2.0 * d->H) * (2.0 * d->W) * ocs * 4.0 >= 2147483648.0) return false;      // two output planes per descriptor
-    return true;
-}
-
-// z split: every CU gets a workgroup; every split pays one extra (halo) input plane of 9 taps
-static int tr2m_zsplit(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    const int base = d->N * (d->H / 16) * (d->W / 16) * (d->Cout / 16);
-    int zs = 1;
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= 4) zs *= 2;
-    return zs;
+    return tr2m_shape_ok(d, 4);
 }
 
 int pcc_conv_tr2m(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_tr2g, const float* bias, float* out,

@@ -15,69 +15,14 @@
 // (64 -> 32: 216 KB) does not fit and keeps the fp32 kernel / conv_tr2g_kernel.  Everything else -- parity decomposition, three
 // accumulator sets, epilogue under the first taps of the next plane, compile-time plane parity -- is conv_tr2m_kernel's.
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
-#include <utility>
 
-#include "common.h"
+#include "tr2m_common.h"
 
 namespace pcctr2mb {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+using namespace pcck;
+using namespace pcctr2;
 
-// Two B-operand vectors (4 input channels of a voxel each): fp32 -> B1 = [dh | dm], B2 = [dl | dh] each.  ONE asm block, because
-// v_dot2c_f32_bf16 is a DOT instruction: a different VALU op that reads its result needs 3 wait states behind it
-// (GCNHazardRecognizer: DotWriteDifferentVALURead) and the hazard recogniser cannot see into inline asm.  Inside the block every
-// reader sits >= 3 instructions behind its writer; K0 / K1 = the bf16 pairs {-1, 0} / {0, -1}: x -= lo(h) / hi(h), exactly.
-__device__ __forceinline__ void split_vec2(u32x4& p_b1, u32x4& p_b2, u32x4& q_b1, u32x4& q_b2, const f32x4& pv, const f32x4& qv) {
-    float a = pv[0], b = pv[1], c = pv[2], d = pv[3], e = qv[0], f = qv[1], g = qv[2], h = qv[3];
-    unsigned ph01, ph23, pm01, pm23, pl01, pl23, pg01, pg23, qh01, qh23, qm01, qm23, ql01, ql23, qg01, qg23;
-    asm volatile(
-        "v_cvt_pk_bf16_f32 %8, %0, %1\n\tv_cvt_pk_bf16_f32 %9, %2, %3\n\tv_cvt_pk_bf16_f32 %16, %4, %5\n\tv_cvt_pk_bf16_f32 %17, %6, %7\n\t"
-        "v_cvt_pk_bf16_f32 %14, %0, %1\n\tv_cvt_pk_bf16_f32 %15, %2, %3\n\tv_cvt_pk_bf16_f32 %22, %4, %5\n\tv_cvt_pk_bf16_f32 %23, %6, %7\n\t"
-        "v_dot2c_f32_bf16 %0, %24, %8\n\tv_dot2c_f32_bf16 %1, %25, %8\n\tv_dot2c_f32_bf16 %2, %24, %9\n\tv_dot2c_f32_bf16 %3, %25, %9\n\t"
-        "v_dot2c_f32_bf16 %4, %24, %16\n\tv_dot2c_f32_bf16 %5, %25, %16\n\tv_dot2c_f32_bf16 %6, %24, %17\n\tv_dot2c_f32_bf16 %7, %25, %17\n\t"
-        "v_cvt_pk_bf16_f32 %10, %0, %1\n\tv_cvt_pk_bf16_f32 %11, %2, %3\n\tv_cvt_pk_bf16_f32 %18, %4, %5\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %19, %6, %7\n\t"
-        "v_dot2c_f32_bf16 %0, %24, %10\n\tv_dot2c_f32_bf16 %1, %25, %10\n\tv_dot2c_f32_bf16 %2, %24, %11\n\tv_dot2c_f32_bf16 %3, %25, %11\n\t"
-        "v_dot2c_f32_bf16 %4, %24, %18\n\tv_dot2c_f32_bf16 %5, %25, %18\n\tv_dot2c_f32_bf16 %6, %24, %19\n\tv_dot2c_f32_bf16 %7, %25, %19\n\t"
-        "v_cvt_pk_bf16_f32 %12, %0, %1\n\tv_cvt_pk_bf16_f32 %13, %2, %3\n\tv_cvt_pk_bf16_f32 %20, %4, %5\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %21, %6, %7\n\ts_nop 2"
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h),
-          "=&v"(ph01), "=&v"(ph23), "=&v"(pm01), "=&v"(pm23), "=&v"(pl01), "=&v"(pl23), "=&v"(pg01), "=&v"(pg23),
-          "=&v"(qh01), "=&v"(qh23), "=&v"(qm01), "=&v"(qm23), "=&v"(ql01), "=&v"(ql23), "=&v"(qg01), "=&v"(qg23)
-        : "s"(0x0000bf80u), "s"(0xbf800000u));
-    p_b1 = (u32x4){ph01, ph23, pm01, pm23}; p_b2 = (u32x4){pl01, pl23, pg01, pg23};
-    q_b1 = (u32x4){qh01, qh23, qm01, qm23}; q_b2 = (u32x4){ql01, ql23, qg01, qg23};
-}
-
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, f32x4 v, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, 0);
-}
-constexpr unsigned kOOB = 0x80000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-__device__ __forceinline__ f32x4 acc_read(const f32x4& a) {
-    f32x4 d;
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
-                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "a"(a[0]), "a"(a[1]), "a"(a[2]), "a"(a[3]));
-    return d;
-}
-
-constexpr int NT = 256;
-constexpr int LXY = 17;                                 // tile edge incl. the low-side halo (taps reach b - 1 only)
-constexpr int TILE_SLOTS = LXY * LXY * 4;               // 16-byte slots of one (plane, cin group) tile: 1156
 constexpr int ITEMS = 5;                                // (voxel, channel quad) items per thread: 5 x 256 = 1280 >= 1156
 constexpr int VSB = 160;                                // bytes per voxel of the operand-form tile: B1 x 4 quads, B2 x 4 quads, 32 pad (10 bank quads:
                                                         // the 8 voxels x 2 quads of a ds_read_b128 lane group fall on 16 different ones)
@@ -96,29 +41,6 @@ struct Tr2mArgs {
     unsigned* amax_out = nullptr;      // per-block max |out| for the fp16-split layer behind this one (common.h, pcc_conv_ext)
 };
 
-// tap t = 0..26 of a micro-step, kz-major; within a kz the (ky, kx) order keeps equal input offsets together and lets the
-// first four taps open the four parity classes
-struct Tap { int kz, ky, kx, cls, dyi, dxi, sq; bool opens; };
-__host__ __device__ constexpr int tr2g_seq(int kz, int ky, int kx) {      // position in the packed (class-major) weight order
-    int seq = 0;
-    for (int cls = 0; cls < 8; ++cls) {
-        const int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;
-        for (int z = pz; z < 3; z += 2)
-            for (int y = py; y < 3; y += 2)
-                for (int x = px; x < 3; x += 2, ++seq)
-                    if (z == kz && y == ky && x == kx) return seq;
-    }
-    return -1;
-}
-__host__ __device__ constexpr Tap tap_of(int t) {
-    constexpr int KY[9] = {0, 0, 1, 1, 0, 1, 2, 2, 2}, KX[9] = {0, 1, 0, 1, 2, 2, 0, 1, 2};
-    const int kz = t / 9, r = t % 9, ky = KY[r], kx = KX[r];
-    return Tap{kz, ky, kx, (ky & 1) * 2 + (kx & 1), ky == 2 ? 1 : 0, kx == 2 ? 1 : 0, tr2g_seq(kz, ky, kx), r < 4};
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
 template <int NG, bool RELU>
 __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int nwg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -127,13 +49,8 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
     auto ldsu = [&](unsigned off) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + off); };
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int ct = wg % a.nct; wg /= a.nct;          // cout tile: neighbours in the grid share their input tiles in L2
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
     const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 16;
     const size_t HW = (size_t)a.H * a.W;
@@ -175,7 +92,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
     auto commit2 = [&](auto j_tag) __attribute__((always_inline)) {
         constexpr int j = decltype(j_tag)::value, j1 = j + 1 < ITEMS ? j + 1 : j;
         u32x4 p1, p2, q1, q2;
-        split_vec2(p1, p2, q1, q2, stg[j], stg[j1]);
+        split_items2(p1, p2, q1, q2, stg[j], stg[j1]);
         *reinterpret_cast<u32x4*>(smem + cw + (unsigned)(j * 64 * VSB)) = p1;
         *reinterpret_cast<u32x4*>(smem + cw + (unsigned)(j * 64 * VSB + 64)) = p2;
         if constexpr (j1 != j) {
@@ -352,19 +269,6 @@ using namespace pcctr2mb;
 
 // ---- host: split image of the class-major weights.  w_tr2g: [cin group][27][cout tile][64 lanes][4 floats] (conv_tr2g order, fp32)
 //      -> out: [cin group][27][cout tile][operand][64 lanes][8 bf16]; operand 0 = [Wh | Wm], 1 = [Wl | Wh]
-static inline unsigned short bf16_rn_(float v) {
-    unsigned b;
-    memcpy(&b, &v, 4);
-    if ((b & 0x7f800000u) == 0x7f800000u) return (unsigned short)(b >> 16);
-    b += 0x7fffu + ((b >> 16) & 1u);
-    return (unsigned short)(b >> 16);
-}
-static inline float bf16_f_(unsigned short h) {
-    const unsigned b = (unsigned)h << 16;
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
-}
 size_t pcc_tr2m_bf16_packed_floats(int Cin, int Cout) { return (size_t)(Cin / 16) * 27 * (Cout / 16) * 2 * 64 * 4; }
 void pcc_tr2m_bf16_pack(int Cin, int Cout, const float* w_tr2g, float* out) {
     unsigned short* o = reinterpret_cast<unsigned short*>(out);
@@ -374,10 +278,7 @@ void pcc_tr2m_bf16_pack(int Cin, int Cout, const float* w_tr2g, float* out) {
             unsigned short h[4], m[4], l[4];
             for (int c = 0; c < 4; ++c) {
                 const float x = w_tr2g[(f * 64 + lane) * 4 + c];
-                h[c] = bf16_rn_(x);
-                const float r1 = x - bf16_f_(h[c]);
-                m[c] = bf16_rn_(r1);
-                l[c] = bf16_rn_(r1 - bf16_f_(m[c]));
+                bf16_split3(x, h[c], m[c], l[c]);
             }
             unsigned short* a1 = o + ((f * 2 + 0) * 64 + lane) * 8;
             unsigned short* a2 = o + ((f * 2 + 1) * 64 + lane) * 8;
@@ -399,11 +300,9 @@ int pcc_conv_tr2m_bf16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
     a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
     a.oco = d->out_coffset;
     if (ext && ext->out_amax) { a.amax_out = ext->out_amax; ext->out_recorded = true; }
-    const int base = d->N * (d->H / 16) * (d->W / 16) * (d->Cout / 16);
-    int zs = 1;
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= 4) zs *= 2;
+    const int zs = tr2m_zsplit(ctx, d);
     a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = base * zs;
+    const int nwg = d->N * a.nty * a.ntx * a.nct * zs;
     const int lds = W_BASE + 2 * 27 * 2048;
     typedef void (*kern_t)(Tr2mArgs, int);
     const kern_t kern = (d->flags & PCC_CONV_RELU) ? (kern_t)conv_tr2m_bf16_kernel<2, true> : (kern_t)conv_tr2m_bf16_kernel<2, false>;

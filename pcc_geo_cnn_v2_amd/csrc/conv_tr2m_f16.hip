@@ -20,48 +20,20 @@
 // bit-deterministic, independent of batch and z split; NOT the order of conv_tr2g_kernel<F16>, so the dispatch is a function of the layer
 // shape only (encoder and decoder must produce the same bits).
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
-#include <utility>
 
-#include "common.h"
+#include "tr2m_common.h"
 
 namespace pcctr2mh {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
+using namespace pcck;
+using namespace pcctr2;
 
-__device__ __forceinline__ f32x4 mfma_f16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-}
 // 8 fp32 -> 8 fp16, round to nearest even
 __device__ __forceinline__ u32x4 to_h8(const f32x4& lo, const f32x4& hi) {
     const f32x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(u32x4, __builtin_convertvector(v, h16x8));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-constexpr unsigned kOOB = 0x80000000u;
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-__device__ __forceinline__ f32x4 acc_read(const f32x4& a) {
-    f32x4 d;
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
-                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "a"(a[0]), "a"(a[1]), "a"(a[2]), "a"(a[3]));
-    return d;
+    return __builtin_bit_cast(u32x4, __builtin_convertvector(v, f16x8));
 }
 
-constexpr int NT = 256;
-constexpr int LXY = 17;                                 // tile edge incl. the low-side halo (taps reach b - 1 only)
-constexpr int TILE_SLOTS = LXY * LXY * 4;               // (voxel, 8-channel quad) items of one (plane, 32-channel cin group) tile: 1156
 constexpr int ITEMS = 5;                                // items per thread: 5 x 256 = 1280 >= 1156
 constexpr int VSB = 96;                                 // bytes per voxel of the fp16 tile: 4 quads x 16 B + 32 pad
 constexpr int TILE_BYTES = ITEMS * 64 * VSB;            // 30720: 320 voxel slots (289 used; the items past the tile write zeros into the rest)
@@ -78,27 +50,6 @@ struct Args {
     int flags, ocs, oco;
 };
 
-struct Tap { int kz, ky, kx, cls, dyi, dxi, sq; bool opens; };
-__host__ __device__ constexpr int tr2g_seq(int kz, int ky, int kx) {      // position in the packed (class-major) weight order
-    int seq = 0;
-    for (int cls = 0; cls < 8; ++cls) {
-        const int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;
-        for (int z = pz; z < 3; z += 2)
-            for (int y = py; y < 3; y += 2)
-                for (int x = px; x < 3; x += 2, ++seq)
-                    if (z == kz && y == ky && x == kx) return seq;
-    }
-    return -1;
-}
-__host__ __device__ constexpr Tap tap_of(int t) {
-    constexpr int KY[9] = {0, 0, 1, 1, 0, 1, 2, 2, 2}, KX[9] = {0, 1, 0, 1, 2, 2, 0, 1, 2};
-    const int kz = t / 9, r = t % 9, ky = KY[r], kx = KX[r];
-    return Tap{kz, ky, kx, (ky & 1) * 2 + (kx & 1), ky == 2 ? 1 : 0, kx == 2 ? 1 : 0, tr2g_seq(kz, ky, kx), r < 4};
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
 // NG = 32-channel cin groups (1: 32 -> 16, 2: 64 -> 32)
 template <int NG, bool RELU>
 __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
@@ -107,13 +58,8 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
     const int v = lane & 15, cq = lane >> 4;
     auto ldsu = [&](unsigned off) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + off); };
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int ct = wg % a.nct; wg /= a.nct;          // cout tile: neighbours in the grid share their input tiles in L2
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
     const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 32;
     const size_t HW = (size_t)a.H * a.W;
@@ -214,7 +160,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
         constexpr int pz = e < 16 ? 1 : 0, cls = (e >> 2) & 3, i = e & 3, py = cls >> 1, px = cls & 1;
         f32x4 o = acc_read(pz ? O[cls][i] : E[PH ^ 1][cls][i]);
         if (RELU) o = __builtin_elementwise_maximum(o, zero4);
-        keep = __builtin_bit_cast(u32x2, __builtin_convertvector(o, h16x4));
+        keep = __builtin_bit_cast(u32x2, __builtin_convertvector(o, f16x4));
         const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.ocs * 2);
         __builtin_amdgcn_raw_buffer_store_b64(keep, rout, (int)ob, (int)soff, 0);
     };
@@ -305,16 +251,9 @@ using namespace pcctr2mh;
 
 // fp16 mode with fp16 hand-over only; shape-only rule (both layers always take it when eligible: no batch / grid dependence)
 bool pcc_tr2m_f16_covers(const pcc_conv_desc* d) {
-    if (!d->transposed || d->k != 3 || d->stride != 2) return false;
-    if (!((d->Cin == 32 && d->Cout == 16) || (d->Cin == 64 && d->Cout == 32))) return false;
-    if (d->H % 16 || d->W % 16) return false;
     if ((d->flags & (PCC_CONV_F16 | PCC_CONV_OUT16)) != (PCC_CONV_F16 | PCC_CONV_OUT16)) return false;
     if (d->flags & (PCC_CONV_ADD | PCC_CONV_CLIP01 | PCC_CONV_IN16 | PCC_CONV_RES16)) return false;
-    const int ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    if (ocs % 4 || d->out_coffset % 4) return false;
-    if ((double)d->H * d->W * d->Cin * 4.0 >= 2147483648.0) return false;                 // one input plane per descriptor
-    if (2.0 * (2.0 * d->H) * (2.0 * d->W) * ocs * 2.0 >= 2147483648.0) return false;      // two output planes per descriptor
-    return true;
+    return tr2m_shape_ok(d, 2);
 }
 
 int pcc_conv_tr2m_f16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_tr2g, const float* bias, void* out,
@@ -327,11 +266,9 @@ int pcc_conv_tr2m_f16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, con
     a.flags = d->flags;
     a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
     a.oco = d->out_coffset;
-    const int base = d->N * a.nty * a.ntx * a.nct;
-    int zs = 1;
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= 4) zs *= 2;
+    const int zs = tr2m_zsplit(ctx, d);
     a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = base * zs;
+    const int nwg = d->N * a.nty * a.ntx * a.nct * zs;
     const int NG = d->Cin / 32;
     const int lds = W_BASE + NG * 27 * 1024;
     typedef void (*kern_t)(Args, int);

@@ -15,24 +15,14 @@
 // loop they are the ONLY LDS operations, two taps ahead, so "at most 4 younger reads outstanding" is the wait in front of every tap.
 // Everything else -- /root/reference/src/model_transforms.py:78 inside :126-137, parity decomposition, three accumulator sets, epilogue
 // under the first taps of the next plane, compile-time plane parity, the recorded maximum of the output -- is conv_tr2m_bf16.hip's.
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <type_traits>
-#include <utility>
 
-#include "common.h"
+#include "tr2m_common.h"
 
 namespace pcctr2mh {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 mfma_f16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
+using namespace pcck;
+using namespace pcctr2;
 
 // One B-operand vector (4 input channels of a voxel): fp32 -> [dh c0..c3 | dl c0..c3] under the block's scale.  l = fp16(s x - h) comes out of
 // v_fma_mix{lo,hi}_f16 (h x -1.0 + s x, the fp16 operand widened exactly, one rounding: the bits of cvt(s x - h), conv_wino_f16s.hip).
@@ -56,12 +46,6 @@ __device__ __forceinline__ u32x4 lds_read2_dup(unsigned addr) {      // {8 bytes
 }
 template <int N>
 __device__ __forceinline__ void lgkm_wait_w(u32x4& a, u32x4& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N)); }
-__device__ __forceinline__ f32x4 mul4s(const f32x4& a, const f32x2& s) {
-    f32x2 lo, hi;
-    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(s));
-    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(hi) : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(s));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
 // the block's pre-scale from its recorded max |x| (conv_wino_f16s.hip, f16s_scale_bits): here |operand| = |x| <= max, no transform in front
 // of the split, so s max lands in [2^14, 2^15)
 __device__ __forceinline__ unsigned tr2m_scale_bits(unsigned m, int lsu) {
@@ -72,30 +56,6 @@ __device__ __forceinline__ unsigned tr2m_scale_bits(unsigned m, int lsu) {
     return (unsigned)se << 23;
 }
 
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, f32x4 v, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, 0);
-}
-constexpr unsigned kOOB = 0x80000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-__device__ __forceinline__ f32x4 acc_read(const f32x4& a) {
-    f32x4 d;
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
-                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "a"(a[0]), "a"(a[1]), "a"(a[2]), "a"(a[3]));
-    return d;
-}
-
-constexpr int NT = 256;
-constexpr int LXY = 17;                                 // tile edge incl. the low-side halo (taps reach b - 1 only)
-constexpr int TILE_SLOTS = LXY * LXY * 4;               // 16-byte slots of one (plane, cin group) tile: 1156
 constexpr int ITEMS = 5;                                // (voxel, channel quad) items per thread: 5 x 256 = 1280 >= 1156
 constexpr int VSB = 96;                                 // bytes per voxel of the operand-form tile: [dh | dl] x 4 quads + 32 pad (6 bank quads: brute-forced over the
                                                         // ds_read_b128 lane groups and the 8-lane groups of the staging ds_write_b128: no conflicts)
@@ -118,29 +78,6 @@ struct Tr2mArgs {
     unsigned* amax_out = nullptr;      // per-block max |out| for the fp16-split layer behind this one (common.h, pcc_conv_ext)
 };
 
-// tap t = 0..26 of a micro-step, kz-major; within a kz the (ky, kx) order keeps equal input offsets together and lets the
-// first four taps open the four parity classes
-struct Tap { int kz, ky, kx, cls, dyi, dxi, sq; bool opens; };
-__host__ __device__ constexpr int tr2g_seq(int kz, int ky, int kx) {      // position in the packed (class-major) weight order
-    int seq = 0;
-    for (int cls = 0; cls < 8; ++cls) {
-        const int pz = cls >> 2, py = (cls >> 1) & 1, px = cls & 1;
-        for (int z = pz; z < 3; z += 2)
-            for (int y = py; y < 3; y += 2)
-                for (int x = px; x < 3; x += 2, ++seq)
-                    if (z == kz && y == ky && x == kx) return seq;
-    }
-    return -1;
-}
-__host__ __device__ constexpr Tap tap_of(int t) {
-    constexpr int KY[9] = {0, 0, 1, 1, 0, 1, 2, 2, 2}, KX[9] = {0, 1, 0, 1, 2, 2, 0, 1, 2};
-    const int kz = t / 9, r = t % 9, ky = KY[r], kx = KX[r];
-    return Tap{kz, ky, kx, (ky & 1) * 2 + (kx & 1), ky == 2 ? 1 : 0, kx == 2 ? 1 : 0, tr2g_seq(kz, ky, kx), r < 4};
-}
-
-template <int... I, class F>
-__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
 template <int NG, bool RELU>
 __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16s_kernel(Tr2mArgs a, int nwg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -149,13 +86,8 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16s_kernel(Tr2mArgs a, int n
     auto ldsu = [&](unsigned off) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + off); };
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int ct = wg % a.nct; wg /= a.nct;          // cout tile: neighbours in the grid share their input tiles in L2
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
     const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 16;
     const size_t HW = (size_t)a.H * a.W;
@@ -381,35 +313,12 @@ using namespace pcctr2mh;
 // ---- host: two-piece fp16 image of the class-major weights.  w_tr2g: [cin group][27][cout tile][64 lanes][4 floats] (conv_tr2g order, fp32)
 //      -> out: [cin group][27][cout tile][operand][64 lanes][8 fp16]; operand 0 = [Wh | Wh], 1 = [Wl | Wl], all scaled by su (max |W| su in
 //      [2^13, 2^14)); behind the fragments PCC_TR2M_F16S_TAIL floats, [0] = su
-static inline unsigned short f16_bits_(float v) {
-    const _Float16 h = (_Float16)v;
-    unsigned short b;
-    memcpy(&b, &h, 2);
-    return b;
-}
-static inline float f16_value_(unsigned short b) {
-    _Float16 h;
-    memcpy(&h, &b, 2);
-    return (float)h;
-}
 size_t pcc_tr2m_f16s_packed_floats(int Cin, int Cout) { return (size_t)(Cout / 16) * (Cin / 16) * (WG_BYTES / 4) + PCC_TR2M_F16S_TAIL; }
 // w_tr2g: [cin group][27][cout tile][64 lanes][4 floats] -> out: [cout tile][cin group][lane][27][4 h | 4 l] (+ 8 B pad per lane), tail[0] = su
 void pcc_tr2m_f16s_pack(int Cin, int Cout, const float* w_tr2g, float* out) {
     const int NGi = Cin / 16, NCT = Cout / 16;
     const size_t nfrag = (size_t)NGi * 27 * NCT;
-    float wmax = 0.f;
-    for (size_t i = 0; i < nfrag * 256; ++i) {
-        const float v = fabsf(w_tr2g[i]);
-        if (v > wmax && v <= 3.0e38f) wmax = v;
-    }
-    int e = 0;
-    float su = 1.f;
-    if (wmax > 0.f) {
-        frexpf(wmax, &e);
-        int se = 14 - e;
-        se = se < -100 ? -100 : se > 100 ? 100 : se;
-        su = ldexpf(1.f, se);
-    }
+    const float su = f16s_weight_scale(w_tr2g, nfrag * 256);
     memset(out, 0, pcc_tr2m_f16s_packed_floats(Cin, Cout) * sizeof(float));
     unsigned short* o = reinterpret_cast<unsigned short*>(out);
     for (int g = 0; g < NGi; ++g)
@@ -419,8 +328,8 @@ void pcc_tr2m_f16s_pack(int Cin, int Cout, const float* w_tr2g, float* out) {
                     unsigned short* d = o + ((size_t)(ct * NGi + g) * WG_BYTES + (size_t)lane * WL_LANE + (size_t)sq * 16) / 2;
                     for (int c = 0; c < 4; ++c) {
                         const float x = w_tr2g[((((size_t)g * 27 + sq) * NCT + ct) * 64 + lane) * 4 + c] * su;          // exact
-                        d[c] = f16_bits_(x);
-                        d[4 + c] = f16_bits_(x - f16_value_(d[c]));                                                    // the difference is exact
+                        d[c] = f16_bits(x);
+                        d[4 + c] = f16_bits(x - f16_value(d[c]));                                                    // the difference is exact
                     }
                 }
     out[(size_t)NCT * NGi * (WG_BYTES / 4)] = su;
@@ -447,11 +356,9 @@ int pcc_conv_tr2m_f16s(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
         { const int rc = pcc_block_amax(ctx, in, d->N, (size_t)d->D * d->H * d->W * d->Cin, am, st); if (rc != PCC_OK) return rc; }
         a.amax_in = am;
     }
-    const int base = d->N * (d->H / 16) * (d->W / 16) * (d->Cout / 16);
-    int zs = 1;
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= 4) zs *= 2;
+    const int zs = tr2m_zsplit(ctx, d);
     a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = base * zs;
+    const int nwg = d->N * a.nty * a.ntx * a.nct * zs;
     const int lds = W_BASE + ((NGi * WG_BYTES + 1023) / 1024) * 1024;
     typedef void (*kern_t)(Tr2mArgs, int);
     static const kern_t kerns[4] = {conv_tr2m_f16s_kernel<2, false>, conv_tr2m_f16s_kernel<2, true>, conv_tr2m_f16s_kernel<4, false>, conv_tr2m_f16s_kernel<4, true>};

@@ -33,7 +33,6 @@ namespace pccwino {
 
 // PRE: this launch handles a later cin group of a multi-group layer launched group by group (clip layers; PCC_WINO_PER_GROUP):
 // the partial sums of the earlier groups are read back from `out` (same lane, same address as its own earlier store).
-enum { M_ALL = 0, M_S0 = 1, M_S1 = 2, M_S1O = 3, M_FIN = 4 };
 
 template <bool RELU, bool CLIP, bool PRE>
 __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg) {
@@ -152,12 +151,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg)
     unsigned long long out_pl = (unsigned long long)out_n + (unsigned long long)(long long)(zb - 2 + s0) * HWO;
     in_pl += (unsigned long long)s0 * HWI;                                                                          // plane s0 + 2
     // one input plane: s = step index (input plane z = zb-1+s), PH = s mod 3
-    // MODE: which of the 12 MFMA rows (dz = 2, 1, 0 x 4 point rows) a step runs.
-    //   M_ALL  every interior step
-    //   M_S0   step 0 (plane zb - 1 of a slab inside the volume): only its dz = 0 rows feed an output plane of this slab
-    //   M_S1   step 1 behind M_S0: its dz = 2 rows would finish output plane zb - 1, which belongs to the slab below
-    //   M_S1O  step 1 of a slab that starts at z = 0 (step 0 skipped): as M_S1, and its dz = 1 rows OPEN their accumulators
-    //   M_FIN  last step of a slab that ends at z = D: no matrix work, only the reduction + store of output plane D - 1
+    // MODE: which of the 12 MFMA rows a step runs (wino_common.h)
     // (66 -> 65 plane-equivalents per 64-plane slab inside the volume, 66 -> 64.8 for a whole-volume slab)
     auto step = [&](auto ph_tag, int s, auto mode_tag) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_tag)::value;

@@ -28,7 +28,7 @@
 //   * the summation order per output element is the one of conv_wino.hip per plane (dz = 2, 1, 0 of consecutive input planes),
 //     with three MFMAs per row instead of four.
 #include <cstdlib>
-#include <cstring>
+
 #include "wino_common.h"
 
 // timing probes (tools/build_variant.sh): 1 no step barrier / vmcnt wait, 2 no plane loads, 4 no residual loads / stores, 8 no DOT
@@ -40,18 +40,10 @@
 
 namespace pccwino {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int UB_ROW_BYTES = 2048;                       // per (dz, point): A1 = [Uh | Um] (64 lanes x 16 B), A2 = [Ul | Uh]
 constexpr int UB_BYTES = 48 * UB_ROW_BYTES;              // 98304
 constexpr int LDS_BYTES_B = U_BASE + UB_BYTES;           // 162816 <= 160 KB
 
-__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 mfma_bf16_k16(const u32x2& a, const u32x2& b, const f32x4& c) {
     f32x4 d;
     asm volatile("v_mfma_f32_16x16x16_bf16 %0, %1, %2, %3" : "=a"(d) : "v"(a), "v"(b), "a"(c));
@@ -71,7 +63,6 @@ __device__ __forceinline__ void dot2c_sub16(float (&Y)[16], unsigned p0, unsigne
           "+v"(Y[8]), "+v"(Y[9]), "+v"(Y[10]), "+v"(Y[11]), "+v"(Y[12]), "+v"(Y[13]), "+v"(Y[14]), "+v"(Y[15])
         : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(p4), "v"(p5), "v"(p6), "v"(p7), "s"(0x0000bf80u), "s"(0xbf800000u));
 }
-__device__ __forceinline__ void acc_read1(float& d, const float& a) { asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(d) : "a"(a)); }
 
 // B^T along x on one patch row (4 voxels x 4 channels), in place
 __device__ __forceinline__ void transform_x_row(f32x4 (&P)[4]) {
@@ -98,33 +89,6 @@ __device__ __forceinline__ unsigned unpark_lds(unsigned a) {
     return v;
 }
 
-// compile-time loop: the slot index must be a constant expression (row masks, U offsets and accumulator slots follow from it)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-enum { MB_ALL = 0, MB_S0 = 1, MB_S1 = 2, MB_S1O = 3, MB_FIN = 4 };
-__host__ __device__ constexpr bool mb_row_active(int mode, int dz) {
-    return mode == MB_ALL || (mode == MB_S0 && dz == 0) || ((mode == MB_S1 || mode == MB_S1O) && dz <= 1);
-}
-__host__ __device__ constexpr int mb_next_mode(int mode) { return mode == MB_S0 ? MB_S1 : MB_ALL; }
-// first active slot q' > q of this step, or 12 + the first active slot of the next step
-__host__ __device__ constexpr int mb_next_slot(int mode, int q) {
-    for (int n = q + 1; n < 12; ++n)
-        if (mb_row_active(mode, 2 - n % 3)) return n;
-    for (int n = 0; n < 12; ++n)
-        if (mb_row_active(mb_next_mode(mode), 2 - n % 3)) return 12 + n;
-    return 12;
-}
-__host__ __device__ constexpr int mb_first_slot(int mode) {
-    for (int n = 0; n < 12; ++n)
-        if (mb_row_active(mode, 2 - n % 3)) return n;
-    return 0;
-}
 __host__ __device__ constexpr unsigned ub_row_off(int q) { return (unsigned)(q * 4 * UB_ROW_BYTES); }       // the image is stored in slot order: row (py, dz) of slot q, px = 0
 
 template <bool RELU, bool CLIP>
@@ -283,7 +247,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     for (int i = 0; i < 16; ++i) { acc[0][i] = zero4; acc[1][i] = zero4; acc[2][i] = zero4; }
     {
         // U fragments of the first active row of the first step that runs
-        const unsigned fo = first_zero ? ub_row_off(mb_first_slot(MB_S1O)) : ub_row_off(mb_first_slot(MB_S0));
+        const unsigned fo = first_zero ? ub_row_off(first_slot(M_S1O)) : ub_row_off(first_slot(M_S0));
 #pragma unroll
         for (int px = 0; px < 4; ++px) { A1[px] = ldsu(ua + fo + (unsigned)(px * UB_ROW_BYTES)); A2[px] = ldsu(ua + fo + (unsigned)(px * UB_ROW_BYTES + 1024)); }
     }
@@ -313,7 +277,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     auto step = [&](auto ph_tag, int s, auto mode_tag) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_tag)::value;
         constexpr int MODE = decltype(mode_tag)::value;
-        constexpr bool FIN = MODE == MB_FIN;
+        constexpr bool FIN = MODE == M_FIN;
         constexpr unsigned slotN = (unsigned)((PH + 1) % 3) * PLANE_BYTES;   // plane s+1 (read)
         constexpr unsigned slotW = (unsigned)((PH + 2) % 3) * PLANE_BYTES;   // plane s+2 (written)
         constexpr int AF = PH;                                               // acc slot of the plane finished by dz = 2
@@ -331,10 +295,10 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
             constexpr int q = decltype(q_tag)::value;
             constexpr int py = q / 3, dz = 2 - q % 3;
             constexpr int as = (PH + 2 - dz) % 3;
-            constexpr bool active = mb_row_active(MODE, dz);
-            constexpr int qn = mb_next_slot(MODE, q) % 12;
+            constexpr bool active = row_active(MODE, dz);
+            constexpr int qn = next_slot(MODE, q) % 12;
             const unsigned un = ua + ub_row_off(qn);
-            constexpr bool opens = dz == 0 || (MODE == MB_S1O && dz == 1);
+            constexpr bool opens = dz == 0 || (MODE == M_S1O && dz == 1);
             using RS = std::integral_constant<int, (q / 3 + 3) % 4>;        // V row in the split pipeline during this slot
             using STG = std::integral_constant<int, q % 3>;                  // its stage
             unsigned pa_s = 0, ovo_s = 0, rvo_s = 0;                         // parked addresses this slot needs (one AccVGPR read each)
@@ -438,13 +402,13 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     using P0t = std::integral_constant<int, 0>;
     using P1t = std::integral_constant<int, 1>;
     using P2t = std::integral_constant<int, 2>;
-    using MAll = std::integral_constant<int, MB_ALL>;
-    using MFin = std::integral_constant<int, MB_FIN>;
+    using MAll = std::integral_constant<int, M_ALL>;
+    using MFin = std::integral_constant<int, M_FIN>;
 
-    if (first_zero) step(P1t{}, 1, std::integral_constant<int, MB_S1O>{});
+    if (first_zero) step(P1t{}, 1, std::integral_constant<int, M_S1O>{});
     else {
-        step(P0t{}, 0, std::integral_constant<int, MB_S0>{});
-        step(P1t{}, 1, std::integral_constant<int, MB_S1>{});
+        step(P0t{}, 0, std::integral_constant<int, M_S0>{});
+        step(P1t{}, 1, std::integral_constant<int, M_S1>{});
     }
     const int nloop = nsteps - (last_zero ? 1 : 0);
     for (int s = 2; s < nloop; s += 3) {
@@ -469,19 +433,6 @@ using namespace pccwino;
 // ---- host: split-bf16 image of the Winograd-transformed weights.  Per (cin group, cout group): [slot q = 3 py + 2 - dz][px][operand][lane][8 bf16]
 //      (the order the kernel consumes it in: the first 48 KB are the rows of slots 0..5)
 //      operand 0 = [Uh c0..c3 | Um c0..c3], operand 1 = [Ul | Uh];  cin = 16 cig + 4 (lane >> 4) + c, cout = 16 cog + (lane & 15)
-static inline unsigned short bf16_rn_bits(float v) {
-    unsigned b;
-    memcpy(&b, &v, 4);
-    if ((b & 0x7f800000u) == 0x7f800000u) return (unsigned short)(b >> 16);      // inf / nan: truncate
-    b += 0x7fffu + ((b >> 16) & 1u);
-    return (unsigned short)(b >> 16);
-}
-static inline float bf16_bits_to_float(unsigned short h) {
-    const unsigned b = (unsigned)h << 16;
-    float v;
-    memcpy(&v, &b, 4);
-    return v;
-}
 // u_f32: the fp32 Winograd image of conv_wino.hip ([cin group][cout group][48][64 lanes][4]) -> out: PCC_WINO_UB_FLOATS per pair
 void pcc_wino_bf16_pack(int ngroups, const float* u_f32, float* out) {
     unsigned short* o = reinterpret_cast<unsigned short*>(out);
@@ -491,11 +442,7 @@ void pcc_wino_bf16_pack(int ngroups, const float* u_f32, float* out) {
                 unsigned short h[4], m[4], l[4];
                 for (int c = 0; c < 4; ++c) {
                     const float x = u_f32[(((size_t)pair * 48 + row) * 64 + lane) * 4 + c];
-                    h[c] = bf16_rn_bits(x);
-                    const float r1 = x - bf16_bits_to_float(h[c]);          // exact
-                    m[c] = bf16_rn_bits(r1);
-                    const float r2 = r1 - bf16_bits_to_float(m[c]);         // exact
-                    l[c] = bf16_rn_bits(r2);
+                    bf16_split3(x, h[c], m[c], l[c]);
                 }
                 const int dz = row / 16, py = (row / 4) % 4, px = row % 4, orow = (3 * py + 2 - dz) * 4 + px;
                 unsigned short* a1 = o + ((((size_t)pair * 48 + orow) * 2 + 0) * 64 + lane) * 8;

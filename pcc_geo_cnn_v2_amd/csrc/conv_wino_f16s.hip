@@ -28,9 +28,8 @@
 // Everything else follows conv_wino_bf16.hip: workgroup = 4 waves = 16 x 16 (x, y) outputs marching along z, ring of 3 input planes
 // in LDS filled by buffer_load ... lds, lane = (tile, cin quad) transforms its own 4 x 4 patch, three output planes in flight in
 // 192 AccVGPRs, A^T . A lane-local, rows py-major.
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
+
 #include "wino_common.h"
 
 // timing probes (tools/build_variant.sh): 1 no step barrier / vmcnt wait, 2 no plane loads, 4 no residual loads / stores, 8 no DOT
@@ -45,9 +44,6 @@
 
 namespace pccwino {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 // U in LDS, lane-contiguous: lane L of (cin group, cout group) owns 776 B = [slot q = 3 py + 2 - dz][px][4 h | 4 l fp16] (768 B) + 8 B
 // pad.  One ds_read2_b64 with offset0 == offset1 delivers the 8 bytes of a piece TWICE into four consecutive registers: the
 // duplicated MFMA operands [Uh | Uh] / [Ul | Ul] without a duplicated image (48.5 KB per group pair instead of 96 KB: two cin groups
@@ -57,9 +53,6 @@ constexpr int UL_LANE_BYTES = 776;
 constexpr int UG_BYTES = 64 * UL_LANE_BYTES;             // 49664 per (cin group, cout group)
 __host__ __device__ constexpr int f16s_lds_bytes(int G) { return U_BASE + ((G * UG_BYTES + 1023) / 1024) * 1024; }      // 114688 / 163840 (= 160 KB)
 
-__device__ __forceinline__ f32x4 mfma_f16(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 // low pieces of one value pair: L = {fp16_rn(a - H.lo), fp16_rn(b - H.hi)} -- subtraction and rounding FUSED in v_fma_mix{lo,hi}_f16
 // (H.lo x -1.0 + a with the fp16 operand widened exactly, one rounding to fp16; a - H.lo is exact in fp32 anyway, so these are the
 // bits of cvt(a - H.lo)): 3 VALU ops per value pair with the cvt_pk of H, against cvt_pk + two dot2c + cvt_pk.  Not DOT
@@ -99,15 +92,8 @@ template <int N>
 __device__ __forceinline__ void lgkm_wait_p(f32x4 (&P)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(P[0]), "+v"(P[1]), "+v"(P[2]), "+v"(P[3]) : "n"(N));
 }
-__device__ __forceinline__ void acc_read1h(float& d, const float& a) { asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(d) : "a"(a)); }
 
-// packed helpers with the block's scale s2 = {s, s}: a s, a s - c, c - a s (c already scaled)
-__device__ __forceinline__ f32x4 mul4s(const f32x4& a, const f32x2& s) {
-    f32x2 lo, hi;
-    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(s));
-    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(hi) : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(s));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
+// packed helpers with the block's scale s2 = {s, s} (a s: mul4s): a s - c, c - a s (c already scaled)
 __device__ __forceinline__ f32x4 fms4s(const f32x4& a, const f32x2& s, const f32x4& c) {
     f32x2 lo, hi;
     asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(s), "v"(__builtin_shufflevector(c, c, 0, 1)));
@@ -136,33 +122,6 @@ __device__ __forceinline__ void transform_x_row_s(f32x4 (&P)[4], const f32x2& s)
 __device__ __forceinline__ void amax4(float& m, const f32x4& o) {
     asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(o[0]), "v"(o[1]));
     asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(m) : "v"(o[2]), "v"(o[3]));
-}
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for_h(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for_h<I + 1, N>(f);
-    }
-}
-
-enum { MH_ALL = 0, MH_S0 = 1, MH_S1 = 2, MH_S1O = 3, MH_FIN = 4 };
-__host__ __device__ constexpr bool mh_row_active(int mode, int dz) {
-    return mode == MH_ALL || (mode == MH_S0 && dz == 0) || ((mode == MH_S1 || mode == MH_S1O) && dz <= 1);
-}
-__host__ __device__ constexpr int mh_next_mode(int mode) { return mode == MH_S0 ? MH_S1 : MH_ALL; }
-// first active slot q' > q of this step, or 12 + the first active slot of the next step
-__host__ __device__ constexpr int mh_next_slot(int mode, int q) {
-    for (int n = q + 1; n < 12; ++n)
-        if (mh_row_active(mode, 2 - n % 3)) return n;
-    for (int n = 0; n < 12; ++n)
-        if (mh_row_active(mh_next_mode(mode), 2 - n % 3)) return 12 + n;
-    return 12;
-}
-__host__ __device__ constexpr int mh_first_slot(int mode) {
-    for (int n = 0; n < 12; ++n)
-        if (mh_row_active(mode, 2 - n % 3)) return n;
-    return 0;
 }
 
 // The block's pre-scale from its recorded max |x| (fp32 bits m, finite): biased exponent of s = 127 + 12 - (e - 127), kept inside
@@ -317,8 +276,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     // a whole row at once (prologue only)
     auto split_row = [&](auto r_tag) __attribute__((always_inline)) {
         yrow(r_tag);
-        static_for_h<0, 8>([&](auto j) __attribute__((always_inline)) { cvt_task(r_tag, ST0{}, j); });
-        static_for_h<0, 8>([&](auto j) __attribute__((always_inline)) { cvt_task(r_tag, ST1{}, j); });
+        static_for<0, 8>([&](auto j) __attribute__((always_inline)) { cvt_task(r_tag, ST0{}, j); });
+        static_for<0, 8>([&](auto j) __attribute__((always_inline)) { cvt_task(r_tag, ST1{}, j); });
     };
     // U fragments of (slot q, point px) of cin group c
     auto load_u = [&](auto q_tag, auto px_tag, int c) __attribute__((always_inline)) {
@@ -332,15 +291,15 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
         P[x] = lds_read128<pa_off(dy, x) + SLOT * PLANE_BYTES>(pa0);
     };
     auto prologue = [&](auto slot_tag, auto first_slot_tag) __attribute__((always_inline)) {
-        static_for_h<0, 4>([&](auto x) __attribute__((always_inline)) {
+        static_for<0, 4>([&](auto x) __attribute__((always_inline)) {
             load_p(P0, R0{}, x, slot_tag); load_p(P1, R1{}, x, slot_tag); load_p(P2, R2{}, x, slot_tag); load_p(P3, R3{}, x, slot_tag); });
-        static_for_h<0, 4>([&](auto px) __attribute__((always_inline)) { load_u(first_slot_tag, px, 0); });
+        static_for<0, 4>([&](auto px) __attribute__((always_inline)) { load_u(first_slot_tag, px, 0); });
         lgkm_wait_p<0>(P0); lgkm_wait_p<0>(P1); lgkm_wait_p<0>(P2); lgkm_wait_p<0>(P3);
         lgkm_wait_u<0>(A1[0], A2[0], A1[1], A2[1]); lgkm_wait_u<0>(A1[2], A2[2], A1[3], A2[3]);
     };
     // tile m0 sits in ring slot (G s0) mod 3; the first step that runs is S1O (slab at z = 0) or S0
-    if (first_zero) prologue(std::integral_constant<int, G % 3>{}, std::integral_constant<int, mh_first_slot(MH_S1O)>{});
-    else prologue(std::integral_constant<int, 0>{}, std::integral_constant<int, mh_first_slot(MH_S0)>{});
+    if (first_zero) prologue(std::integral_constant<int, G % 3>{}, std::integral_constant<int, first_slot(M_S1O)>{});
+    else prologue(std::integral_constant<int, 0>{}, std::integral_constant<int, first_slot(M_S0)>{});
     transform_x_row_s(P0, s2); transform_x_row_s(P1, s2); transform_x_row_s(P2, s2); transform_x_row_s(P3, s2);
     split_row(R0{}); split_row(R1{}); split_row(R2{});
     yrow(R3{});                                  // row 3 goes through the split in slots 0..1 of the first step
@@ -368,11 +327,11 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     auto step = [&](auto ph_tag, auto c_tag, int s, auto mode_tag) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_tag)::value, C = decltype(c_tag)::value;
         constexpr int MODE = decltype(mode_tag)::value;
-        constexpr bool FIN = MODE == MH_FIN, FIRST = C == 0, LAST = C == G - 1, EXACT = MODE == MH_ALL;
+        constexpr bool FIN = MODE == M_FIN, FIRST = C == 0, LAST = C == G - 1, EXACT = MODE == M_ALL;
         constexpr int TN = (G * PH + C + 1) % 3, TW = (G * PH + C + 2) % 3;      // ring slots of tile m+1 (read) / m+2 (written)
         constexpr int AF = PH;                                               // acc slot of the plane finished by dz = 2
-        constexpr bool ZO = MODE == MH_ALL || MODE == MH_FIN;                // the finished plane zo = zb - 2 + s exists (s >= 2)
-        constexpr int NMODE = LAST ? mh_next_mode(MODE) : MODE;              // mode of the next micro-step
+        constexpr bool ZO = MODE == M_ALL || MODE == M_FIN;                // the finished plane zo = zb - 2 + s exists (s >= 2)
+        constexpr int NMODE = LAST ? next_mode(MODE) : MODE;              // mode of the next micro-step
         const bool zo_ok = s >= 2;
         const __amdgpu_buffer_rsrc_t rout = make_rsrc((const void*)(zo_ok ? out_pl : (unsigned long long)out_n), zo_ok && LAST ? HWO : 0u);
         const __amdgpu_buffer_rsrc_t rres = make_rsrc((const void*)(zo_ok ? res_pl : (unsigned long long)res_n), zo_ok && has_res && LAST ? HWR : 0u);
@@ -381,17 +340,17 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
         const bool in_ok = (unsigned)(zb - 1 + s + DS2) < (unsigned)a.D;
         const __amdgpu_buffer_rsrc_t rin = make_rsrc((const void*)(in_ok ? in_pl + (unsigned long long)DS2 * HWI + 64ull * C2 : (unsigned long long)in_n), in_ok ? HWI - 64u * C2 : 0u);
         if constexpr (LAST) { res_pl += HWR; out_pl += HWO; in_pl += HWI; }
-        static_for_h<0, 12>([&](auto q_tag) __attribute__((always_inline)) {
+        static_for<0, 12>([&](auto q_tag) __attribute__((always_inline)) {
             constexpr int q = decltype(q_tag)::value;
             constexpr int py = q / 3, dz = 2 - q % 3;
             constexpr int as = (PH + 2 - dz) % 3;
-            constexpr bool active = mh_row_active(MODE, dz);
+            constexpr bool active = row_active(MODE, dz);
             // the next active row: in this micro-step (same cin group) or the first one of the next micro-step
-            constexpr int qraw = mh_next_slot(MODE, q);
+            constexpr int qraw = next_slot(MODE, q);
             constexpr bool wraps = qraw >= 12;
-            constexpr int qn = wraps ? mh_first_slot(NMODE) : qraw;
+            constexpr int qn = wraps ? first_slot(NMODE) : qraw;
             constexpr int cn = wraps ? (C + 1) % G : C;
-            constexpr bool opens = FIRST && (dz == 0 || (MODE == MH_S1O && dz == 1));
+            constexpr bool opens = FIRST && (dz == 0 || (MODE == M_S1O && dz == 1));
             constexpr bool preads = !FIN && (q == 0 || q == 1 || q == 4 || q == 9);                 // this slot reads a patch row
             constexpr bool pprev = !FIN && (q == 1 || q == 2 || q == 5 || q == 10);                  // the previous slot did
             using RS = std::integral_constant<int, (q / 3 + 3) % 4>;        // V row in the split pipeline during this slot
@@ -399,7 +358,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
             using TNt = std::integral_constant<int, TN>;
             using QN = std::integral_constant<int, qn>;
             // ---- F(q): MFMA i, then what runs in its shadow
-            static_for_h<0, 8>([&](auto i_tag) __attribute__((always_inline)) {
+            static_for<0, 8>([&](auto i_tag) __attribute__((always_inline)) {
                 constexpr int i = decltype(i_tag)::value;
                 if constexpr (active && !(PCC_WH_PROBE & 16)) {
                     // two halves of two points each, two MFMAs per point, alternating between the points of a half (a dependent MFMA
@@ -431,14 +390,14 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
                     constexpr int r = q / 3;
 #pragma unroll
                     for (int e = 2 * i; e < 2 * i + 2; ++e)
-                        acc_read1h(Mr[e], acc[AF][r * 4 + (e >> 2)][e & 3]);
+                        acc_read1(Mr[e], acc[AF][r * 4 + (e >> 2)][e & 3]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
             // ---- K(q)
             if constexpr (!FIN) {
                 if constexpr (q % 3 == 1 && PCC_WH_MIXK && !(PCC_WH_PROBE & 32))
-                    static_for_h<0, 8>([&](auto j) __attribute__((always_inline)) { cvt_task(RS{}, ST1{}, j); });
+                    static_for<0, 8>([&](auto j) __attribute__((always_inline)) { cvt_task(RS{}, ST1{}, j); });
                 if constexpr (!(PCC_WH_PROBE & 128)) {
                     if constexpr (q == 1) { lgkm_wait_p<EXACT ? 12 : 0>(P2); transform_x_row_s(P2, s2); }
                     if constexpr (q == 2) { lgkm_wait_p<EXACT ? 12 : 0>(P0); transform_x_row_s(P0, s2); yrow(R0{}); }
@@ -506,18 +465,18 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     using P0t = std::integral_constant<int, 0>;
     using P1t = std::integral_constant<int, 1>;
     using P2t = std::integral_constant<int, 2>;
-    using MAll = std::integral_constant<int, MH_ALL>;
-    using MFin = std::integral_constant<int, MH_FIN>;
+    using MAll = std::integral_constant<int, M_ALL>;
+    using MFin = std::integral_constant<int, M_FIN>;
     // one input plane = G micro-steps
     auto plane = [&](auto ph_tag, int s, auto mode_tag) __attribute__((always_inline)) {
-        static_for_h<0, G>([&](auto c_tag) __attribute__((always_inline)) { step(ph_tag, c_tag, s, mode_tag); });
+        static_for<0, G>([&](auto c_tag) __attribute__((always_inline)) { step(ph_tag, c_tag, s, mode_tag); });
     };
     using CL = std::integral_constant<int, G - 1>;
 
-    if (first_zero) plane(P1t{}, 1, std::integral_constant<int, MH_S1O>{});
+    if (first_zero) plane(P1t{}, 1, std::integral_constant<int, M_S1O>{});
     else {
-        plane(P0t{}, 0, std::integral_constant<int, MH_S0>{});
-        plane(P1t{}, 1, std::integral_constant<int, MH_S1>{});
+        plane(P0t{}, 0, std::integral_constant<int, M_S0>{});
+        plane(P1t{}, 1, std::integral_constant<int, M_S1>{});
     }
     const int nloop = nsteps - (last_zero ? 1 : 0);
     for (int s = 2; s < nloop; s += 3) {
@@ -571,34 +530,11 @@ int pcc_block_amax(pcc_ctx* ctx, const float* x, int N, size_t per_block, unsign
 //      [cout group][cin group][lane][slot q = 3 py + 2 - dz][px][4 h | 4 l fp16] + 8 B pad per lane;
 //      cin = 16 cig + 4 (lane >> 4) + c, cout = 16 cog + (lane & 15); behind the pairs: PCC_WINO_UH_TAIL floats, [0] = su (the power of
 //      two all pieces were scaled by)
-static inline unsigned short f16_bits(float v) {
-    const _Float16 h = (_Float16)v;          // round to nearest even, denormals kept
-    unsigned short b;
-    memcpy(&b, &h, 2);
-    return b;
-}
-static inline float f16_value(unsigned short b) {
-    _Float16 h;
-    memcpy(&h, &b, 2);
-    return (float)h;
-}
 // u_f32: the fp32 Winograd image of conv_wino.hip ([cin group][cout group][48][64 lanes][4]) -> out: PCC_WINO_UH_FLOATS per pair + tail
 void pcc_wino_f16s_pack(int ngroups, const float* u_f32, float* out) {
     static_assert(PCC_WINO_UH_FLOATS * 4 == UG_BYTES, "image size");
     const size_t nu = (size_t)ngroups * ngroups * 48 * 64 * 4;
-    float umax = 0.f;
-    for (size_t i = 0; i < nu; ++i) {
-        const float v = fabsf(u_f32[i]);
-        if (v > umax && v <= 3.0e38f) umax = v;
-    }
-    int e = 0;
-    float su = 1.f;
-    if (umax > 0.f) {
-        frexpf(umax, &e);                      // umax = f 2^e, f in [0.5, 1)
-        int se = 14 - e;                       // su umax in [2^13, 2^14)
-        se = se < -100 ? -100 : se > 100 ? 100 : se;
-        su = ldexpf(1.f, se);
-    }
+    const float su = f16s_weight_scale(u_f32, nu);
     memset(out, 0, ((size_t)ngroups * ngroups * PCC_WINO_UH_FLOATS + PCC_WINO_UH_TAIL) * sizeof(float));
     unsigned short* o = reinterpret_cast<unsigned short*>(out);
     for (int cig = 0; cig < ngroups; ++cig)

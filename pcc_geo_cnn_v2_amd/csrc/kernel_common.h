@@ -1,0 +1,173 @@
+// Primitives the conv kernel families are written from (conv_mfma, conv_f16, conv_split, conv_wino*, conv_tr2m*): vector types, raw
+// buffer resources, the XCD remap, AccVGPR reads, compile-time loops, the 16x16x32 MFMA wrappers and the operand splits -- and, on the
+// host, the numerics of the packed weight images (bf16 / fp16 bits, the exact piece splits, the power-of-two scale of the two-piece
+// images).  A kernel file brings them into its own namespace with `using namespace pcck;`.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <type_traits>
+#include <utility>
+
+namespace pcck {
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// Raw buffer resources: the hardware range check returns 0 for offsets >= num_records, which implements the
+// SAME zero padding (and the tile overhang) without a single branch; the descriptor is wave-uniform (SGPRs).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ u32x4 buf_load4u(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, f32x4 v, unsigned voff, unsigned soff) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, 0);
+}
+constexpr unsigned kOOB = 0x80000000u;                 // >= any per-image byte size the planner admits
+
+// sched_barrier mask: only VALU / SALU / transcendental ops may cross (memory ops and MFMAs keep their written order)
+#define PCC_PIN_MEM_MFMA() __builtin_amdgcn_sched_barrier(0x406)
+
+// XCD-aware tile index: consecutive tile ids go to the same XCD (blocks are dispatched round-robin over
+// the 8 XCDs), so that neighbouring tiles share their halos in one L2.  Bijective for any grid size.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = bid & 7, k = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+}
+
+// AccVGPR -> VGPR at a place of OUR choosing (the register allocator otherwise splits the live range right behind the
+// defining MFMA, i.e. in the middle of an MFMA block).  Inline asm is invisible to the hazard recogniser: callers keep at least
+// one slot of 16 MFMAs between the MFMA that wrote the accumulator and this read.
+__device__ __forceinline__ f32x4 acc_read(const f32x4& a) {
+    f32x4 d;
+    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
+                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "a"(a[0]), "a"(a[1]), "a"(a[2]), "a"(a[3]));
+    return d;
+}
+__device__ __forceinline__ void acc_read1(float& d, const float& a) { asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(d) : "a"(a)); }
+
+// compile-time loops: the index reaches f as a std::integral_constant, so that it is a constant expression inside the body
+template <int... I, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
+
+__device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma_f16(const u32x4& a, const u32x4& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// Two B-operand vectors (4 input channels of a voxel each): fp32 -> B1 = [dh | dm], B2 = [dl | dh] each.  ONE asm block, because
+// v_dot2c_f32_bf16 is a DOT instruction: a different VALU op that reads its result needs 3 wait states behind it
+// (GCNHazardRecognizer: DotWriteDifferentVALURead) and the hazard recogniser cannot see into inline asm.  Inside the block every
+// reader sits >= 3 instructions behind its writer; K0 / K1 = the bf16 pairs {-1, 0} / {0, -1}: x -= lo(h) / hi(h), exactly.
+__device__ __forceinline__ void split_items2(u32x4& p_b1, u32x4& p_b2, u32x4& q_b1, u32x4& q_b2, const f32x4& pv, const f32x4& qv) {
+    float a = pv[0], b = pv[1], c = pv[2], d = pv[3], e = qv[0], f = qv[1], g = qv[2], h = qv[3];
+    unsigned ph01, ph23, pm01, pm23, pl01, pl23, pg01, pg23, qh01, qh23, qm01, qm23, ql01, ql23, qg01, qg23;
+    asm volatile(
+        "v_cvt_pk_bf16_f32 %8, %0, %1\n\tv_cvt_pk_bf16_f32 %9, %2, %3\n\tv_cvt_pk_bf16_f32 %16, %4, %5\n\tv_cvt_pk_bf16_f32 %17, %6, %7\n\t"
+        "v_cvt_pk_bf16_f32 %14, %0, %1\n\tv_cvt_pk_bf16_f32 %15, %2, %3\n\tv_cvt_pk_bf16_f32 %22, %4, %5\n\tv_cvt_pk_bf16_f32 %23, %6, %7\n\t"
+        "v_dot2c_f32_bf16 %0, %24, %8\n\tv_dot2c_f32_bf16 %1, %25, %8\n\tv_dot2c_f32_bf16 %2, %24, %9\n\tv_dot2c_f32_bf16 %3, %25, %9\n\t"
+        "v_dot2c_f32_bf16 %4, %24, %16\n\tv_dot2c_f32_bf16 %5, %25, %16\n\tv_dot2c_f32_bf16 %6, %24, %17\n\tv_dot2c_f32_bf16 %7, %25, %17\n\t"
+        "v_cvt_pk_bf16_f32 %10, %0, %1\n\tv_cvt_pk_bf16_f32 %11, %2, %3\n\tv_cvt_pk_bf16_f32 %18, %4, %5\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %19, %6, %7\n\t"
+        "v_dot2c_f32_bf16 %0, %24, %10\n\tv_dot2c_f32_bf16 %1, %25, %10\n\tv_dot2c_f32_bf16 %2, %24, %11\n\tv_dot2c_f32_bf16 %3, %25, %11\n\t"
+        "v_dot2c_f32_bf16 %4, %24, %18\n\tv_dot2c_f32_bf16 %5, %25, %18\n\tv_dot2c_f32_bf16 %6, %24, %19\n\tv_dot2c_f32_bf16 %7, %25, %19\n\t"
+        "v_cvt_pk_bf16_f32 %12, %0, %1\n\tv_cvt_pk_bf16_f32 %13, %2, %3\n\tv_cvt_pk_bf16_f32 %20, %4, %5\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %21, %6, %7\n\ts_nop 2"
+        : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h),
+          "=&v"(ph01), "=&v"(ph23), "=&v"(pm01), "=&v"(pm23), "=&v"(pl01), "=&v"(pl23), "=&v"(pg01), "=&v"(pg23),
+          "=&v"(qh01), "=&v"(qh23), "=&v"(qm01), "=&v"(qm23), "=&v"(ql01), "=&v"(ql23), "=&v"(qg01), "=&v"(qg23)
+        : "s"(0x0000bf80u), "s"(0xbf800000u));
+    p_b1 = (u32x4){ph01, ph23, pm01, pm23}; p_b2 = (u32x4){pl01, pl23, pg01, pg23};
+    q_b1 = (u32x4){qh01, qh23, qm01, qm23}; q_b2 = (u32x4){ql01, ql23, qg01, qg23};
+}
+
+// packed multiply by a scale pair s = {s, s}
+__device__ __forceinline__ f32x4 mul4s(const f32x4& a, const f32x2& s) {
+    f32x2 lo, hi;
+    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(s));
+    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(hi) : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(s));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
+}
+
+// ---- host: numerics of the packed weight images
+
+// bf16 bits of v, rounded to nearest even (inf / nan: truncated), and back
+static inline unsigned short bf16_bits(float v) {
+    unsigned b;
+    memcpy(&b, &v, 4);
+    if ((b & 0x7f800000u) == 0x7f800000u) return (unsigned short)(b >> 16);
+    b += 0x7fffu + ((b >> 16) & 1u);
+    return (unsigned short)(b >> 16);
+}
+static inline float bf16_value(unsigned short h) {
+    const unsigned b = (unsigned)h << 16;
+    float v;
+    memcpy(&v, &b, 4);
+    return v;
+}
+// x = h + m + l, three bf16 pieces: h = bf16_rn(x), m = bf16_rn(x - h), l = bf16_rn(x - h - m); both differences are exact
+static inline void bf16_split3(float x, unsigned short& h, unsigned short& m, unsigned short& l) {
+    h = bf16_bits(x);
+    const float r1 = x - bf16_value(h);
+    m = bf16_bits(r1);
+    l = bf16_bits(r1 - bf16_value(m));
+}
+
+// fp16 bits of v, rounded to nearest even (denormals kept), and back
+static inline unsigned short f16_bits(float v) {
+    const _Float16 h = (_Float16)v;
+    unsigned short b;
+    memcpy(&b, &h, 2);
+    return b;
+}
+static inline float f16_value(unsigned short b) {
+    _Float16 h;
+    memcpy(&h, &b, 2);
+    return (float)h;
+}
+
+// su, the power of two that the pieces of a two-piece fp16 image are scaled by: su max |w| in [2^13, 2^14) (non-finite values left out of
+// the max; all zero: su = 1).  The pieces of x su are h = f16_bits(x su) and f16_bits(x su - f16_value(h)); the scaling and the
+// difference are exact.
+static inline float f16s_weight_scale(const float* w, size_t n) {
+    float wmax = 0.f;
+    for (size_t i = 0; i < n; ++i) {
+        const float v = fabsf(w[i]);
+        if (v > wmax && v <= 3.0e38f) wmax = v;
+    }
+    int e = 0;
+    float su = 1.f;
+    if (wmax > 0.f) {
+        frexpf(wmax, &e);                      // wmax = f 2^e, f in [0.5, 1)
+        int se = 14 - e;
+        se = se < -100 ? -100 : se > 100 ? 100 : se;
+        su = ldexpf(1.f, se);
+    }
+    return su;
+}
+
+}  // namespace pcck

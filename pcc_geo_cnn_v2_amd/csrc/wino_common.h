@@ -1,32 +1,15 @@
-// Shared pieces of the Winograd F(2x2,3x3)+z kernels (conv_wino.hip: exact-fp32 MFMA; conv_wino_bf16.hip: split-bf16 MFMA):
-// buffer-descriptor helpers, the LDS plane geometry, the launch arguments and the fp32 input / output transforms.
+// Shared pieces of the Winograd F(2x2,3x3)+z kernels (conv_wino.hip: exact-fp32 MFMA; conv_wino_bf16.hip: split-bf16 MFMA;
+// conv_wino_f16s.hip: two-piece fp16 MFMA): the LDS plane geometry, the launch arguments, the fp32 input / output transforms and
+// the micro-step modes of the z march.
 #pragma once
 #include <cstdlib>
-#include <type_traits>
 
 #include "common.h"
+#include "kernel_common.h"
 
 namespace pccwino {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, f32x4 v, unsigned voff, unsigned soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, (int)soff, 0);
-}
-constexpr unsigned kOOB = 0x80000000u;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = bid & 7, k = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
+using namespace pcck;
 
 constexpr int NT = 256;
 constexpr int PLANE_VOX = 18 * 18;
@@ -64,7 +47,6 @@ struct WinoArgs {
 // (v_mfma_f32_16x16x4_f32 runs at the packed-FMA rate of the same SIMD): every VALU op costs ~5 cycles of MFMA time,
 // v_mov / v_accvgpr_read ~8.  Hence: packed adds everywhere (the compiler turns a-b into two scalar v_sub), no
 // register copies, no per-lane address arithmetic in the loop.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 sub4(const f32x4& a, const f32x4& b) {
     f32x2 lo, hi;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(__builtin_shufflevector(b, b, 0, 1)));
@@ -76,16 +58,6 @@ __device__ __forceinline__ f32x4 add4(const f32x4& a, const f32x4& b) {
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(lo) : "v"(__builtin_shufflevector(a, a, 0, 1)), "v"(__builtin_shufflevector(b, b, 0, 1)));
     asm("v_pk_add_f32 %0, %1, %2" : "=v"(hi) : "v"(__builtin_shufflevector(a, a, 2, 3)), "v"(__builtin_shufflevector(b, b, 2, 3)));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
-}
-
-// AccVGPR -> VGPR at a place of OUR choosing (the register allocator otherwise splits the live range right behind the
-// defining MFMA, i.e. in the middle of an MFMA block).  Inline asm is invisible to the hazard recogniser: callers keep at least
-// one slot of 16 MFMAs between the MFMA that wrote the accumulator and this read.
-__device__ __forceinline__ f32x4 acc_read(const f32x4& a) {
-    f32x4 d;
-    asm volatile("v_accvgpr_read_b32 %0, %4\n\tv_accvgpr_read_b32 %1, %5\n\tv_accvgpr_read_b32 %2, %6\n\tv_accvgpr_read_b32 %3, %7"
-                 : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]) : "a"(a[0]), "a"(a[1]), "a"(a[2]), "a"(a[3]));
-    return d;
 }
 
 // B^T along x, in place, on a 4x4 array of float4 (4 input channels each)
@@ -105,6 +77,32 @@ __device__ __forceinline__ void transform_y_row(f32x4 (&V)[16], const f32x4 (&P)
         else if (r == 2) V[8 + x] = sub4(P[8 + x], P[4 + x]);
         else V[12 + x] = sub4(P[4 + x], P[12 + x]);
     }
+}
+
+// Micro-step modes of the z march: which of the 12 MFMA rows (dz = 2, 1, 0 x 4 point rows) a step runs.
+//   M_ALL  every interior step
+//   M_S0   step 0 (plane zb - 1 of a slab inside the volume): only its dz = 0 rows feed an output plane of this slab
+//   M_S1   step 1 behind M_S0: its dz = 2 rows would finish output plane zb - 1, which belongs to the slab below
+//   M_S1O  step 1 of a slab that starts at z = 0 (step 0 skipped): as M_S1, and its dz = 1 rows OPEN their accumulators
+//   M_FIN  last step of a slab that ends at z = D: no matrix work, only the reduction + store of output plane D - 1
+enum { M_ALL = 0, M_S0 = 1, M_S1 = 2, M_S1O = 3, M_FIN = 4 };
+__host__ __device__ constexpr bool row_active(int mode, int dz) {
+    return mode == M_ALL || (mode == M_S0 && dz == 0) || ((mode == M_S1 || mode == M_S1O) && dz <= 1);
+}
+__host__ __device__ constexpr int next_mode(int mode) { return mode == M_S0 ? M_S1 : M_ALL; }
+// Slots q = 0..11 in py-major order (py = q / 3, dz = 2 - q % 3; conv_wino_bf16.hip, conv_wino_f16s.hip): the first active slot q' > q
+// of this step, or 12 + the first active slot of the next step
+__host__ __device__ constexpr int next_slot(int mode, int q) {
+    for (int n = q + 1; n < 12; ++n)
+        if (row_active(mode, 2 - n % 3)) return n;
+    for (int n = 0; n < 12; ++n)
+        if (row_active(next_mode(mode), 2 - n % 3)) return 12 + n;
+    return 12;
+}
+__host__ __device__ constexpr int first_slot(int mode) {
+    for (int n = 0; n < 12; ++n)
+        if (row_active(mode, 2 - n % 3)) return n;
+    return 0;
 }
 
 }  // namespace pccwino
