@@ -72,7 +72,7 @@ def _h(t):
 def run_transform_fp16(name, filters, params, prefix, x):
     """The fp16 mode of the BUILD (BASELINE.json configs[4]; the reference has no such mode) restated on the CPU: the same layer
     lists, every operand rounded to fp16 exactly where pcc_geo_cnn_v2_amd/csrc/network.hip + conv_f16.hip + the PCC_CONV_F16
-    kernels of conv_mfma.hip round it, products accumulated in fp32 (oneDNN: another summation order than the MFMA chains):
+    kernels of conv_fwd.hip / conv_tr2.hip round it, products accumulated in fp32 (oneDNN: another summation order than the MFMA chains):
 
       * a block (stride-2 layer with res = 'save' and 16 / 32 / 64 output channels on a grid of 16-multiples, followed by its two
         k3 stride-1 layers) keeps its two intermediate tensors in fp16: layer 0 rounds its output (after bias + ReLU), layer 1

@@ -97,7 +97,7 @@ struct pcc_thr_fuse { const float* thr; int clip; uint32_t* mask; };
 struct pcc_conv_ext;
 int pcc_conv3d_mfma_thr(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias,
                         const float* residual, float* out, const pcc_thr_fuse* fuse, bool* fused, pcc_conv_ext* ext, hipStream_t st);
-// The kernel family that computes a layer (conv_mfma.hip, pcc_conv_route): one value per name pcc_conv_kernel_family prints
+// The kernel family that computes a layer (conv_route.hip, pcc_conv_route): one value per name pcc_conv_kernel_family prints
 enum pcc_conv_family {
     PCC_FAM_GENERIC, PCC_FAM_F16, PCC_FAM_FWD, PCC_FAM_FWD_F16, PCC_FAM_SPLIT16, PCC_FAM_SPLIT32, PCC_FAM_WINO, PCC_FAM_WINO_BF16,
     PCC_FAM_WINO_F16S, PCC_FAM_TR2, PCC_FAM_TR2M_F16, PCC_FAM_TR2M_F16S, PCC_FAM_TR2_SPLIT, PCC_FAM_TR2M_BF16, PCC_FAM_TR2M,
@@ -177,6 +177,20 @@ int pcc_conv_tr2_split(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
 // mfma32: the 32x32x16 formulation (W % 32 == 0 or W == 16), else 16x16x32 -- chosen by pcc_conv_route
 int pcc_conv_split(pcc_ctx* ctx, const pcc_conv_desc* d, bool mfma32, const float* in, const float* w_split, const float* bias,
                    const float* residual, float* out, hipStream_t st);
+// direct exact-fp32 (PCC_CONV_F16: f16) MFMA kernels on rows of tx = 16 / 8 / 4 voxels along x (pcc_conv_route's plan): forward conv and
+// transposed stride 1 (conv_fwd.hip), transposed stride 2 (conv_tr2.hip); weights = the base image of pcc_conv_pack_weights
+int pcc_conv_fwd(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias, const float* residual,
+                 float* out, int tx, hipStream_t st);
+int pcc_conv_tr2(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias, const float* residual,
+                 float* out, int tx, hipStream_t st);
+// the first layer (Cin = 1) and the last ones (Cout = 1: 16 -> 1 on the matrix cores with the optional pcc_thr_fuse bits, else VALU)
+// (conv_edge.hip)
+int pcc_conv_cin1(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias, const float* residual,
+                  float* out, pcc_conv_ext* ext, hipStream_t st);
+int pcc_conv_cout1_mfma(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias,
+                        const float* residual, float* out, const pcc_thr_fuse* fuse, bool* fused, hipStream_t st);
+int pcc_conv_cout1(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w_packed, const float* bias, const float* residual,
+                   float* out, hipStream_t st);
 // Kernels that use more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize, which is set per DEVICE:
 // remember the (function, device) pairs this thread has configured.
 #include <utility>

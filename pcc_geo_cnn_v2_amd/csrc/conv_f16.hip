@@ -6,7 +6,7 @@
 // to an fp32 consumer).
 //
 // Why a kernel of its own: with fp16 matrix instructions (16x the fp32 MFMA rate) these layers are bound by HBM, and the
-// direct kernels of conv_mfma.hip (fp32 tiles in LDS, one ds_read per MFMA) become LDS/issue-bound long before that.  Here
+// direct kernels of conv_fwd.hip (fp32 tiles in LDS, one ds_read per MFMA) become LDS/issue-bound long before that.  Here
 //   * a voxel is 32 B (C = 16) / 64 B (C = 32): half the HBM and LDS traffic of the fp32 path;
 //   * GEMM view per input plane: D[cout][voxel] += W[cout][(tap, cin)] . In[(tap, cin)][voxel], A = weights (resident in
 //     registers for the life of the workgroup), B = 16 consecutive voxels of one input row.  K = 32 of one MFMA = two x-taps x

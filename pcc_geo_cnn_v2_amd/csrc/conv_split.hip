@@ -14,7 +14,7 @@
 // fp32 accumulation in a fixed order (cin group -> tap -> the three MFMAs): bit-deterministic, independent of tile position and
 // launch geometry.
 //
-// Structure = conv_fwd_kernel's k3 path (conv_mfma.hip): workgroup = 4 waves = tile of 2 x 8 x 16 output voxels; a wave owns the
+// Structure = conv_fwd_kernel's k3 path (conv_fwd.hip): workgroup = 4 waves = tile of 2 x 8 x 16 output voxels; a wave owns the
 // R = 8 rows of 16 voxels of one z plane and HALF of the cout tiles.  (First version: 4 rows x all cout tiles per wave -- every wave
 // then pulls all weights of a tap from L2, 42 B/clk/CU, and the MFMA pipe sat at 0.46 / 0.64 busy waiting for them; with 8 rows per
 // weight fragment it is 21 B/clk/CU, and the LDS serves the 2 x 8 row fragments per tap at 85 - 170 B/clk of its 256.)  Per cin
@@ -433,7 +433,7 @@ __global__ void __launch_bounds__((Split32Cfg<CH, TZ, TY, TXW, R>::NT), 1) conv_
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Conv3DTranspose k3 stride 2 (64 -> 32 @16^3 -> 32^3, 64 -> 64 @8^3 -> 16^3 of /root/reference/src/model_transforms.py:126-137) with
-// split-bf16 operands.  Parity decomposition as in conv_tr2g_kernel (conv_mfma.hip): output voxel 2 b + p takes, per dimension,
+// split-bf16 operands.  Parity decomposition as in conv_tr2g_kernel (conv_tr2.hip): output voxel 2 b + p takes, per dimension,
 // tap 1 of input b for odd p and taps 0 / 2 of inputs b / b - 1 for even p -- 8 parity classes of 8, 4, 4, 2, 4, 2, 2, 1 taps, 27 in
 // all per input voxel, i.e. the multiply count of a k3 stride-1 layer per INPUT voxel and 8 outputs for it.  Same tile loop as
 // conv_k3s1_split_kernel: per cin group the haloed input tile (halo on the low side only) is staged global -> registers -> split ->

@@ -1,4 +1,4 @@
-// Primitives the conv kernel families are written from (conv_mfma, conv_f16, conv_split, conv_wino*, conv_tr2m*): vector types, raw
+// Primitives the conv kernel families are written from (conv_direct.h, conv_f16, conv_split, conv_wino*, conv_tr2m*): vector types, raw
 // buffer resources, the XCD remap, AccVGPR reads, compile-time loops, the 16x16x32 MFMA wrappers and the operand splits -- and, on the
 // host, the numerics of the packed weight images (bf16 / fp16 bits, the exact piece splits, the power-of-two scale of the two-piece
 // images).  A kernel file brings them into its own namespace with `using namespace pcck;`.

@@ -34,7 +34,7 @@ def _ctx():
     return ops.get_context(torch.device('cuda', 0))
 
 
-# One layer per kernel family the route can return (csrc/conv_mfma.hip, pcc_conv_route): expected name prefix, (N, D, H, W, Cin, Cout,
+# One layer per kernel family the route can return (csrc/conv_route.hip, pcc_conv_route): expected name prefix, (N, D, H, W, Cin, Cout,
 # k, stride, transposed), flags on top of BIAS | RELU, impl, numerics switches
 _F16, _IN16, _OUT16 = 16, 32, 64
 FAMILY_CASES = [

@@ -1,7 +1,8 @@
 #!/bin/bash
 # A/B builds of libpcc_geo_hip.so: tools/build_variant.sh <name> <source> "<extra -D flags>" [object-to-replace]
 #   <source>: a file name under csrc/ or a path (e.g. an old revision exported with `git show`);
-#   conv_mfma.hip is built in parts: pass "-DPCC_PART=k" and conv_mfma_pk.o as the object to replace.
+#   conv_fwd.hip / conv_tr2.hip are built per instantiation group: pass "-DPCC_INST_GROUP=n" and conv_fwd_gn.o / conv_tr2_gn.o as the
+#   object to replace (the kernel under test is in that group's object; see the group lists in the source).
 # -> build_ab/lib<name>.so (select with PCC_GEO_LIB=build_ab/lib<name>.so); all other objects come from the in-tree build.
 set -e
 NAME=$1; SRC=$2; FLAGS=$3; REPL=$4
