@@ -383,6 +383,28 @@ size_t pcc_cloud_distortion_workspace_bytes(int64_t na, int64_t nb);
 int pcc_cloud_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const void* index_b, int64_t nb, const double* a_normals,
                          double* tally, int32_t* to_b, int32_t* to_a, void* workspace, void* stream);
 
+/* Tie-averaged D2 (new; DESIGN.md "Tie-averaged D2"): pcc_cloud_distortion with a rule for equidistant nearest points.
+ * tie_mode PCC_TIES_PICK is pcc_cloud_distortion itself (same kernels, same bits).  PCC_TIES_MEAN, with T_B(a) = ALL rows of B at
+ * the smallest squared distance from original point a and T_A(b) the same the other way:
+ *   - normal of decoded point b: the unweighted mean of a_normals[a] over votes(b) = {a : b in T_B(a)}, summed in float64 in
+ *     increasing a and divided by the count; with no votes, the mean of a_normals[a] over T_A(b);
+ *   - per-point terms: t(a) = mean over b in T_B(a) of e(a - b, normal of b), t(b) = mean over a in T_A(b) of e(b - a, a_normals[a]),
+ *     e(g, n) = ((g.x*n.x + g.y*n.y) + g.z*n.z)^2 in float64 without contraction; sums inside one tie set run in the index's
+ *     visiting order, so the result depends on the row order of either cloud by float64 rounding only;
+ *   - D2_* = sums of the terms (the fixed order of pcc_cloud_distortion), H2_* = their maxima; the D1 / H1 slots, to_b and to_a
+ *     (the LOWEST tied row) are pcc_cloud_distortion's.  Without a_normals the call is pcc_cloud_distortion.
+ * The (b, a) pairs of the votes are materialised: their number, the sum of |T_B(a)| over a, is data-dependent, and the caller
+ * states a capacity max_pairs in [1, 2^31) that sizes the workspace.  status (device, int64[2]) receives that number and 1 if it
+ * exceeded max_pairs: then no pair was written, the D2 / H2 slots are NaN (D1 / H1 stay valid) and a call with max_pairs >=
+ * status[0] succeeds.  Nothing is read back by the call itself: the caller reads status with the tally.  workspace:
+ * pcc_cloud_distortion_ties_workspace_bytes(na, nb, tie_mode, max_pairs) bytes (0 for a size or mode outside the contract).    */
+#define PCC_TIES_PICK 0
+#define PCC_TIES_MEAN 1
+size_t pcc_cloud_distortion_ties_workspace_bytes(int64_t na, int64_t nb, int32_t tie_mode, int64_t max_pairs);
+int pcc_cloud_distortion_ties(pcc_ctx* ctx, const void* index_a, int64_t na, const void* index_b, int64_t nb, const double* a_normals,
+                              int32_t tie_mode, int64_t max_pairs, double* tally, int64_t* status, int32_t* to_b, int32_t* to_a,
+                              void* workspace, void* stream);
+
 /* ---- cloud colours (new: the colour step of the reference's evaluation, src/map_color.py, and pc_error's colour terms) ---------
  * Colour transfer and colour distortion across two voxelised clouds on the indices of "cloud metrics" (same point contract).
  * Colours: (n,3) uint8 R, G, B in row order, device memory.  Definition:

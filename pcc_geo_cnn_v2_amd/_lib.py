@@ -29,6 +29,7 @@ EXPORTS = [
     'pcc_codec_workspace_bytes', 'pcc_codec_encode', 'pcc_codec_decode_hyper', 'pcc_codec_decode_main',
     'pcc_profile_select', 'pcc_profile_read', 'pcc_normals_workspace_bytes', 'pcc_estimate_normals',
     'pcc_cloud_index_bytes', 'pcc_cloud_index_build', 'pcc_cloud_nearest', 'pcc_cloud_distortion_workspace_bytes', 'pcc_cloud_distortion',
+    'pcc_cloud_distortion_ties_workspace_bytes', 'pcc_cloud_distortion_ties',
     'pcc_cloud_map_colors', 'pcc_cloud_color_workspace_bytes', 'pcc_cloud_color_distortion',
     'pcc_mesh_sample_workspace_bytes', 'pcc_mesh_to_points', 'pcc_render_workspace_bytes', 'pcc_render_points',
     'pcc_conv_wgrad_workspace_bytes', 'pcc_conv_wgrad_slices', 'pcc_conv3d_wgrad', 'pcc_relu_backward', 'pcc_focal_loss_grad', 'pcc_conv_repack_map',
@@ -130,6 +131,9 @@ def lib():
     L.pcc_cloud_distortion_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.pcc_cloud_distortion_workspace_bytes.restype = sz
     L.pcc_cloud_distortion.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.pcc_cloud_distortion_ties_workspace_bytes.argtypes = [C.c_int64, C.c_int64, i32, C.c_int64]
+    L.pcc_cloud_distortion_ties_workspace_bytes.restype = sz
+    L.pcc_cloud_distortion_ties.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, i32, C.c_int64, vp, vp, vp, vp, vp, vp]
     L.pcc_cloud_map_colors.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, i32, vp, vp, vp]
     L.pcc_cloud_color_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.pcc_cloud_color_workspace_bytes.restype = sz

@@ -3,7 +3,7 @@
   python -m pcc_geo_cnn_v2_amd.compress_octree --input_files a.ply --output_files a.ply.bin \\
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
-         [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu]
+         [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu] [--d2_ties pick|mean]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
@@ -114,6 +114,15 @@ def check_metrics_device(metrics_device, world):
                              'host, drop the flag or run on one GPU')
 
 
+def check_d2_ties(d2_ties, world):
+    """--d2_ties mean averages the whole-cloud D2 over all equidistant nearest points in one process; tie sets are not sharded."""
+    from .utils.pc_metric import check_ties
+    try:
+        check_ties(d2_ties, world)
+    except AssertionError as e:
+        raise AssertionError(f'--d2_ties: {e}') from None
+
+
 def _block_grid(resolution, level, data_format):
     """Octree geometry: the bounding box of the whole cloud and the dense shape of one leaf block."""
     from .utils import pc_io
@@ -140,6 +149,8 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
         record = dict({name: float(val) for name, val in info['metrics'].items()}, codec_numerics=info['numerics_tag'])
         if getattr(args, 'metrics_device', 'host') != 'host':      # host mode writes exactly the keys it always wrote
             record['metrics_device'] = args.metrics_device
+        if getattr(args, 'd2_ties', 'pick') != 'pick':
+            record['d2_ties'] = args.d2_ties
         json.dump(record, fh, sort_keys=True, indent=4)
     if decoded_path is not None:
         pc_io.write_df(decoded_path, pc_io.pa_to_df(info['blocks_full']))
@@ -164,6 +175,7 @@ def compress(args):
     clouds, with_normals = _plan(args)
     rank, world, local = _join_process_group()
     check_metrics_device(getattr(args, 'metrics_device', 'host'), world)
+    check_d2_ties(getattr(args, 'd2_ties', 'pick'), world)
     if args.debug and world > 1:
         raise AssertionError('--debug dumps every intermediate of every block: run it on one GPU')
     sess = ops.get_context(torch.device('cuda', local))        # what tf.Session is to the reference (compress_octree.py:84)
@@ -199,7 +211,7 @@ def compress(args):
         streams, infos, debug_t_list = model.compress_blocks(
             sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
             max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
-            metrics_device=getattr(args, 'metrics_device', 'host'))
+            metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'))
         T.mark('compress_blocks', sess.device)
         if rank == 0:       # the other ranks only took part in the collectives
             if len(streams) != len(cloud.targets):
@@ -232,6 +244,11 @@ def build_parser():
     parser.add_argument('--metrics_device', choices=('host', 'gpu'), default='host',
                         help='Where the whole-cloud metrics of the final candidate selection run (new): host = scipy KD-trees, '
                              'gpu = the HIP engine (ties to the lowest row; single process only).')
+    parser.add_argument('--d2_ties', choices=('pick', 'mean'), default='pick',
+                        help='Which of several equidistant nearest points the whole-cloud D2 reads (the metrics that rank the candidates '
+                             'and go to .enc.metric.json; new): pick = one of them, mean = the average over all of them (row-order '
+                             'independent, the same on host and gpu; single process only).  The per-block threshold search keeps its '
+                             'own rules either way.')
     parser.add_argument('--dec_files', nargs='*',
                         help='Decoded files. Allows compression/decompression in a single execution.')
     parser.add_argument('--checkpoint_dir', help='Directory where to save/load model checkpoints.', required=True)

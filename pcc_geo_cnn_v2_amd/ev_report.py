@@ -8,12 +8,14 @@ utils/pc_metric.compute_metrics, the module the encoder itself uses for its `.en
 ev_experiment.py:158-162) carries over.
 
     python -m pcc_geo_cnn_v2_amd.ev_report --input_pc a.ply --decoded_pc a.ply.bin.ply --enc_pc a.ply.bin \\
-        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] [--metrics_device host|gpu] [--hausdorff] [--color] --output report_d1.json
+        --resolution 1024 [--input_norm a_n.ply | --estimate_normals] [--metrics_device host|gpu] [--d2_ties pick|mean] [--hausdorff] [--color] --output report_d1.json
 
 `--metrics_device gpu` computes the metrics with the GPU engine (include/pcc_geo.h "cloud metrics": neighbour ties to the lowest
 row); `--hausdorff` adds pc_error's Hausdorff terms (utils/pc_metric.hausdorff_table); `--color` adds pc_error's colour keys
 y/u/v_mse and y/u/v_psnr (utils/pc_metric.color_table; both clouds must carry colours: recolour a decoded cloud with map_color).
-Without them the report is unchanged.
+`--d2_ties mean` evaluates D2 (and its Hausdorff terms) over ALL equidistant nearest points instead of one of them (DESIGN.md
+"Tie-averaged D2"): the same numbers on either device up to float64 rounding, whatever the row order of the files; the report then
+carries "d2_ties".  Without them the report is unchanged.
 """
 import argparse
 import json
@@ -23,14 +25,15 @@ import os
 import numpy as np
 
 from .utils import pc_io
-from .utils.pc_metric import (cloud_tally_host, cloud_tallies_gpu, color_table, color_tally_host, compute_metrics, hausdorff_table,
-                              metrics_table)
+from .utils.pc_metric import (check_ties, cloud_tally_host, cloud_tallies_gpu, color_table, color_tally_host, compute_metrics,
+                              hausdorff_table, metrics_table)
 
 logger = logging.getLogger(__name__)
 
 
 def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, estimate_normals=False, normals_k=16,
-                 metrics_device='host', hausdorff=False, color=False):
+                 metrics_device='host', hausdorff=False, color=False, d2_ties='pick'):
+    check_ties(d2_ties)
     if input_norm and estimate_normals:
         raise AssertionError('--estimate_normals and --input_norm are mutually exclusive')
     p1 = pc_io.load_pc(input_pc)
@@ -49,12 +52,17 @@ def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, esti
         assert len(b), 'compute_metrics: empty decoded cloud'
         ctx = ops.get_context()
         index_a = ops.CloudIndex(ctx, a)
-        tally = cloud_tallies_gpu(ctx, a, [b], n1, index_a=index_a)[0]
+        tally = cloud_tallies_gpu(ctx, a, [b], n1, index_a=index_a, ties=d2_ties)[0]
         m = metrics_table(len(a), tally[:5], resolution - 1, ('d1', 'd2') if n1 is not None else ('d1',))
         color_tally = ops.cloud_color_distortion(ctx, index_a, c1, b, c2) if color else None
     elif metrics_device == 'host':
-        m = compute_metrics(a, b, resolution - 1, p1_n=n1)
-        tally = cloud_tally_host(a, b, n1) if hausdorff else None
+        if d2_ties == 'pick':
+            m = compute_metrics(a, b, resolution - 1, p1_n=n1)
+            tally = cloud_tally_host(a, b, n1) if hausdorff else None
+        else:
+            assert len(b), 'compute_metrics: empty decoded cloud'
+            tally = cloud_tally_host(a, b, n1, ties=d2_ties)
+            m = metrics_table(len(a), tally[:5], resolution - 1, ('d1', 'd2') if n1 is not None else ('d1',))
         color_tally = color_tally_host(a, c1, b, c2) if color else None
     else:
         raise AssertionError(f'metrics_device must be host or gpu, got {metrics_device!r}')
@@ -65,6 +73,8 @@ def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, esti
         data.update({k: float(v) for k, v in hausdorff_table(tally, resolution - 1, n1 is not None).items()})
     if color:
         data.update({k: float(v) for k, v in color_table(color_tally, len(a), len(b)).items()})
+    if d2_ties != 'pick':      # the default writes exactly the keys it always wrote
+        data['d2_ties'] = d2_ties
     return data
 
 
@@ -94,6 +104,9 @@ def main():
     p.add_argument('--normals_k', type=int, default=16, help='Neighbours per point of --estimate_normals (3..64)')
     p.add_argument('--metrics_device', choices=('host', 'gpu'), default='host',
                    help='Where the metrics run: host = scipy KD-trees, gpu = the HIP engine (ties to the lowest row; new)')
+    p.add_argument('--d2_ties', choices=('pick', 'mean'), default='pick',
+                   help='Which of several equidistant nearest points the D2 terms read: pick = one of them (the KD-tree\'s choice on the '
+                        'host, the lowest row on the gpu), mean = the average over all of them (row-order independent; new)')
     p.add_argument('--hausdorff', default=False, action='store_true',
                    help="Add pc_error's Hausdorff terms: d1_hausdorff[_AB|_BA|_psnr] (+ d2_* with normals; new)")
     p.add_argument('--color', default=False, action='store_true',
@@ -104,7 +117,7 @@ def main():
     if args.input_norm and args.estimate_normals:
         p.error('--estimate_normals and --input_norm are mutually exclusive')
     data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm, args.estimate_normals, args.normals_k,
-                        args.metrics_device, args.hausdorff, args.color)
+                        args.metrics_device, args.hausdorff, args.color, args.d2_ties)
     with open(args.output, 'w') as f:
         json.dump(data, f, sort_keys=True, indent=4)
     enc_metric = args.enc_pc + '.enc.metric.json'

@@ -74,12 +74,13 @@ METRICS_DEVICES = ('host', 'gpu')      # where the encoder's whole-cloud metrics
 
 
 def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, resolution, with_normals,
-                               opt_groups=('d1', 'd2'), tree=None, metrics_device='host', ctx=None):
+                               opt_groups=('d1', 'd2'), tree=None, metrics_device='host', ctx=None, d2_ties='pick'):
     """Per optimisation group, which candidate reconstruction of the whole cloud to keep (the reference's function of the same
     name, model_types.py:128-176; results pinned by tests/golden/select_best.npz).  x_hat_list[m] = the decoded blocks of
     candidate m (block-local coordinates).  Returns one dict per non-empty group: 'idx', 'metrics', 'x_hat_list',
     'blocks_depart' (blocks in cloud coordinates), 'blocks_full' (one array).  metrics_device='gpu': the whole-cloud metrics come
-    from pc_metric.cloud_metrics_batch_gpu on context `ctx` (neighbour ties to the lowest row) instead of the KD-trees."""
+    from pc_metric.cloud_metrics_batch_gpu on context `ctx` (neighbour ties to the lowest row) instead of the KD-trees.
+    d2_ties='mean': either engine averages D2 over all equidistant nearest points (pc_metric.tie_mean_tally)."""
     if metrics_device not in METRICS_DEVICES:
         raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
     assert len(opt_metrics) == len(x_hat_list), f'lengths of opt_metrics {len(opt_metrics)} and x_hat_list' + \
@@ -92,10 +93,10 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
     if metrics_device == 'gpu':
         from . import ops
         scored = cloud_metrics_batch_gpu(ctx if ctx is not None else ops.get_context(), original, [clouds[m] for m in grouped],
-                                         resolution - 1, get_normals_if(points, with_normals))
+                                         resolution - 1, get_normals_if(points, with_normals), ties=d2_ties)
     else:
         scored = cloud_metrics_batch(original, [clouds[m] for m in grouped], resolution - 1, get_normals_if(points, with_normals),
-                                     tree if tree is not None else cKDTree(original))
+                                     tree if tree is not None else cKDTree(original), ties=d2_ties)
     cand_metrics = [None] * len(opt_metrics)
     for m, met in zip(grouped, scored):
         cand_metrics[m] = met
@@ -564,14 +565,17 @@ class CompressionModel:
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
-                        need_points=True, metrics_device='host'):
+                        need_points=True, metrics_device='host', d2_ties='pick'):
         """Uses the compression model to compress a point cloud (model_types.py:184-218).  Under torch.distributed (one
         process per GPU) the block list is sharded (sharding.py): rank 0 returns the complete result, the other ranks
         return (None, metadata without point lists, local debug list).  `need_points=False` skips the gather of the
         decoded candidate point lists to rank 0 (they are only needed for --dec_files / --debug).  metrics_device='gpu'
-        (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree."""
+        (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree.  d2_ties='mean' (single process
+        only): the whole-cloud D2 averages over all equidistant nearest points; the per-block threshold search is not affected."""
         from . import sharding
+        from .utils.pc_metric import check_ties
         rank, world = sharding.world_info()
+        check_ties(d2_ties, world)
         if metrics_device not in METRICS_DEVICES:
             raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
         if metrics_device == 'gpu' and world > 1:
@@ -592,7 +596,8 @@ class CompressionModel:
             threshold_list = list(zip(*threshold_list))
             x_hat_list = list(zip(*x_hat_list))
             metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
-                                                  metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess))
+                                                  metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess),
+                                                  d2_ties=d2_ties)
             data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
             return data_list, metadata, debug_t_list
         return self._compress_blocks_sharded(sess, blocks, binstr, points, resolution, level, with_normals, opt_metrics,

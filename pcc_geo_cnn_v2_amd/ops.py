@@ -803,36 +803,88 @@ def _normals64(a_normals, n):
     return nrm
 
 
-def cloud_distortion_launch(ctx, index_a, b, a_normals=None, links=False):
+TIE_MODES = {'pick': 0, 'mean': 1}      # include/pcc_geo.h PCC_TIES_*: which of several equidistant nearest points D2 reads
+_PAIR_LIMIT = (1 << 31) - 1
+
+
+def tie_pair_capacity(n_a):
+    """Default pair capacity of ties='mean' (DESIGN.md "Tie-averaged D2", workspace rule): room for four equidistant decoded points
+    per original point on average, 4 N_A + 1024, capped at the engine's limit of 2^31 - 1 pairs."""
+    return min(4 * int(n_a) + 1024, _PAIR_LIMIT)
+
+
+def _tie_mode(ties):
+    if ties not in TIE_MODES:
+        raise L.PccError(f'cloud_distortion: ties must be one of {tuple(TIE_MODES)}, got {ties!r}')
+    return TIE_MODES[ties]
+
+
+def cloud_distortion_launch(ctx, index_a, b, a_normals=None, links=False, ties='pick', max_pairs=None):
     """cloud_distortion without the host copy: returns the float64[9] device tally (and the int32 to_b, to_a device tensors with
-    links=True), queued on the context's stream.  b: (N_B,3) decoded points, N_B >= 1; a_normals: (N_A,3) or None."""
+    links=True), queued on the context's stream.  b: (N_B,3) decoded points, N_B >= 1; a_normals: (N_A,3) or None.  ties='mean'
+    (pcc_cloud_distortion_ties) appends the int64[2] device status (pairs needed, 1 = more than max_pairs: the D2 / H2 slots are
+    then NaN) to what is returned; max_pairs defaults to tie_pair_capacity(N_A)."""
+    mode = _tie_mode(ties)
     b = _voxel_points(b, 'cloud_distortion')
     nrm = _normals64(a_normals, index_a.n)
     dev = ctx.device
     if nrm is not None:
         nrm = (nrm.to(dev) if isinstance(nrm, torch.Tensor) else torch.from_numpy(nrm).to(dev)).contiguous()
+    if mode:
+        max_pairs = tie_pair_capacity(index_a.n) if max_pairs is None else int(max_pairs)
+        if not 1 <= max_pairs <= _PAIR_LIMIT:
+            raise L.PccError(f'cloud_distortion: max_pairs = {max_pairs} outside [1, 2^31)')
     index_b = CloudIndex(ctx, b)
     tally = torch.empty((CLOUD_TALLY_SLOTS,), dtype=torch.float64, device=dev)
     to_b = torch.empty((index_a.n,), dtype=torch.int32, device=dev) if links else None
     to_a = torch.empty((index_b.n,), dtype=torch.int32, device=dev) if links else None
-    ws = torch.empty((L.lib().pcc_cloud_distortion_workspace_bytes(index_a.n, index_b.n),), dtype=torch.uint8, device=dev)
-    L.check(L.lib().pcc_cloud_distortion(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(index_b.buffer), index_b.n, _ptr(nrm),
-                                         _ptr(tally), _ptr(to_b), _ptr(to_a), _ptr(ws), ctx.stream), 'pcc_cloud_distortion')
-    return (tally, to_b, to_a) if links else tally
+    if not mode:
+        ws = torch.empty((L.lib().pcc_cloud_distortion_workspace_bytes(index_a.n, index_b.n),), dtype=torch.uint8, device=dev)
+        L.check(L.lib().pcc_cloud_distortion(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(index_b.buffer), index_b.n, _ptr(nrm),
+                                             _ptr(tally), _ptr(to_b), _ptr(to_a), _ptr(ws), ctx.stream), 'pcc_cloud_distortion')
+        return (tally, to_b, to_a) if links else tally
+    status = torch.empty((2,), dtype=torch.int64, device=dev)
+    ws = torch.empty((L.lib().pcc_cloud_distortion_ties_workspace_bytes(index_a.n, index_b.n, mode, max_pairs),), dtype=torch.uint8,
+                     device=dev)
+    L.check(L.lib().pcc_cloud_distortion_ties(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(index_b.buffer), index_b.n, _ptr(nrm), mode,
+                                              max_pairs, _ptr(tally), _ptr(status), _ptr(to_b), _ptr(to_a), _ptr(ws), ctx.stream),
+            'pcc_cloud_distortion_ties')
+    return (tally, to_b, to_a, status) if links else (tally, status)
 
 
-def cloud_distortion(ctx, a, b, a_normals=None, index_a=None, return_links=False):
+class TiePairOverflow(L.PccError):
+    """ties='mean' met more equidistant pairs than the stated capacity; `.pairs` is the capacity that suffices."""
+
+    def __init__(self, pairs, max_pairs):
+        super().__init__(f'cloud_distortion: ties=\'mean\' needs {pairs} tie pairs, the workspace holds {max_pairs}; '
+                         f'pass max_pairs >= {pairs}')
+        self.pairs, self.max_pairs = int(pairs), int(max_pairs)
+
+
+def cloud_distortion(ctx, a, b, a_normals=None, index_a=None, return_links=False, ties='pick', max_pairs=None):
     """Distortion tally of decoded cloud b against original cloud a on the GPU (include/pcc_geo.h "cloud metrics"): float64[9] =
     N_B, D1_AB, D1_BA, D2_AB, D2_BA, H1_AB, H1_BA, H2_AB, H2_BA (utils/pc_metric.pair_tally's five slots plus the Hausdorff maxima).
     a, b: (N,3) integer coordinates in [0, 2^21), N >= 1; a_normals: (N_A,3) normals of a (None: the D2 / H2 slots are 0);
     index_a: a CloudIndex of a to reuse (a is then not read).  return_links=True also returns to_b (int32[N_A]) and to_a
-    (int32[N_B]), the nearest rows across (ties: the lowest row).  Deterministic: the same inputs give the same bits."""
+    (int32[N_B]), the nearest rows across (ties: the lowest row).  Deterministic: the same inputs give the same bits.
+    ties='mean': D2 / H2 average over ALL equidistant nearest points (DESIGN.md "Tie-averaged D2"), independent of either cloud's
+    row order up to float64 rounding.  Its pair workspace holds max_pairs pairs (default tie_pair_capacity(N_A)); with the default,
+    a cloud that needs more is run once more with the exact number the first run reported, an explicit max_pairs that is too small
+    raises TiePairOverflow."""
+    mode = _tie_mode(ties)
     if index_a is None:                     # every input is checked before the first GPU call
         a = _voxel_points(a, 'cloud_distortion')
         b = _voxel_points(b, 'cloud_distortion')
         _normals64(a_normals, len(a))
         index_a = CloudIndex(ctx, a)
-    out = cloud_distortion_launch(ctx, index_a, b, a_normals, links=return_links)
+    out = cloud_distortion_launch(ctx, index_a, b, a_normals, links=return_links, ties=ties, max_pairs=max_pairs)
+    if mode:
+        pairs, over = (int(v) for v in out[-1].cpu())
+        if over:
+            if max_pairs is not None or pairs > _PAIR_LIMIT:
+                raise TiePairOverflow(pairs, tie_pair_capacity(index_a.n) if max_pairs is None else max_pairs)
+            out = cloud_distortion_launch(ctx, index_a, b, a_normals, links=return_links, ties=ties, max_pairs=pairs)
+        out = out[:-1] if return_links else out[0]
     if return_links:
         return tuple(t.cpu().numpy() for t in out)
     return out.cpu().numpy()

@@ -139,13 +139,15 @@ class SingleProcess:
         return tallies
 
 
-def cloud_metrics_batch(p1, p2_locals, r, p1_n=None, t1=None, comm=None, partial=False):
+def cloud_metrics_batch(p1, p2_locals, r, p1_n=None, t1=None, comm=None, partial=False, ties='pick'):
     """D1 (and, with normals `p1_n`, D2) metrics between the original cloud p1 (replicated on every rank) and each of several
     candidate decoded clouds, candidate m = union over ranks of `p2_locals[m]`.  Returns one reference-style dictionary per
     candidate (None where the decoded cloud is empty on every rank).  Two collectives for ALL candidates (one MIN, one SUM),
     none in a single process.  Exact for D1 in any world size (squared distances between integer points are integers; A->B is
-    a MIN over ranks, B->A a SUM).  D2 across ranks: see sharding.RankGroup.claim."""
+    a MIN over ranks, B->A a SUM).  D2 across ranks: see sharding.RankGroup.claim.  ties='mean' (single process only): the D2
+    slots come from tie_mean_tally, the tie-averaged rule of DESIGN.md "Tie-averaged D2"; D1 is the same either way."""
     comm = comm or SingleProcess()
+    check_ties(ties, comm.world)
     tree_a = t1 if t1 is not None else cKDTree(p1, balanced_tree=False)
     links = []
     for p2 in p2_locals:
@@ -160,6 +162,8 @@ def cloud_metrics_batch(p1, p2_locals, r, p1_n=None, t1=None, comm=None, partial
     for m, ((p2, to_b, to_a, _), mine) in enumerate(zip(links, owned)):
         if mine is not None:
             tallies[m] = pair_tally(p1, p2, to_b, to_a, p1_n, None if mine.all() else mine)
+            if ties == 'mean' and p1_n is not None:
+                tallies[m, [D2_AB, D2_BA]] = tie_mean_tally(p1, p2, p1_n, tree_a)[[D2_AB, D2_BA]]
     if partial:     # the caller sums the per-rank tallies itself (they ride in a collective it issues anyway) and finishes with finish_metrics
         return tallies, [o is not None for o in owned]
     return finish_metrics(len(p1), comm.total(tallies), [o is not None for o in owned], r, p1_n is not None)
@@ -192,12 +196,15 @@ def hausdorff_table(tally, peak, with_normals=False):
     return out
 
 
-def cloud_tally_host(p1, p2, p1_n=None, t1=None):
+def cloud_tally_host(p1, p2, p1_n=None, t1=None, ties='pick'):
     """Host restatement of the 9-slot tally with the KD-tree links of cloud_metrics_batch: pair_tally's five slots plus the
-    Hausdorff maxima (np.max over the per-point terms pair_tally sums).  p2 must not be empty."""
+    Hausdorff maxima (np.max over the per-point terms pair_tally sums).  p2 must not be empty.  ties='mean': tie_mean_tally."""
+    check_ties(ties)
     p2 = np.asarray(p2).reshape(-1, 3)
     assert len(p2), 'cloud_tally_host: empty decoded cloud'
     tree_a = t1 if t1 is not None else cKDTree(p1, balanced_tree=False)
+    if ties == 'mean':
+        return tie_mean_tally(p1, p2, p1_n, tree_a)
     to_b, to_a = nearest(cKDTree(p2, balanced_tree=False), p1), nearest(tree_a, p2)
     tally = np.zeros(9, np.float64)
     tally[:5] = pair_tally(p1, p2, to_b, to_a, p1_n)
@@ -210,13 +217,17 @@ def cloud_tally_host(p1, p2, p1_n=None, t1=None):
     return tally
 
 
-def cloud_tallies_gpu(ctx, p1, p2_list, p1_n=None, index_a=None):
+def cloud_tallies_gpu(ctx, p1, p2_list, p1_n=None, index_a=None, ties='pick'):
     """9-slot tallies of every candidate decoded cloud against p1 on the GPU (ops.cloud_distortion): one float64[9] per candidate,
     None for an empty one.  The original cloud's index is built once (or `index_a` is reused) and every candidate is queued
     before the one host copy.  Neighbour ties go to the lowest row (include/pcc_geo.h "cloud metrics"): D1 and the D1 Hausdorff
-    terms equal the host path's whenever its float64 sums are exact; D2 may differ where cKDTree picks another equidistant point."""
+    terms equal the host path's whenever its float64 sums are exact; D2 may differ where cKDTree picks another equidistant point.
+    ties='mean': D2 averages over all equidistant points (DESIGN.md "Tie-averaged D2") and agrees with the host path's 'mean' up to
+    float64 rounding.  Every candidate runs with the default pair capacity and its status rides in the one host copy; a candidate
+    that reported more pairs than that is run once more with the exact number."""
     import torch
     from .. import ops
+    check_ties(ties)
     clouds = [np.asarray(p2).reshape(-1, 3) for p2 in p2_list]
     live = [m for m, p2 in enumerate(clouds) if len(p2)]
     out = [None] * len(clouds)
@@ -224,19 +235,107 @@ def cloud_tallies_gpu(ctx, p1, p2_list, p1_n=None, index_a=None):
         return out
     if index_a is None:
         index_a = ops.CloudIndex(ctx, np.asarray(p1)[:, :3])
-    dev = [ops.cloud_distortion_launch(ctx, index_a, clouds[m], p1_n) for m in live]
+    if ties == 'mean' and p1_n is not None:
+        runs = [ops.cloud_distortion_launch(ctx, index_a, clouds[m], p1_n, ties='mean') for m in live]
+        dev = [t for t, _ in runs]
+        for k, (pairs, over) in enumerate(torch.stack([st for _, st in runs]).cpu().tolist()):
+            if over:
+                dev[k] = torch.from_numpy(ops.cloud_distortion(ctx, None, clouds[live[k]], p1_n, index_a=index_a, ties='mean',
+                                                               max_pairs=pairs)).to(dev[k].device)
+    else:
+        dev = [ops.cloud_distortion_launch(ctx, index_a, clouds[m], p1_n) for m in live]
     host = torch.stack(dev).cpu().numpy()
     for m, t in zip(live, host):
         out[m] = t
     return out
 
 
-def cloud_metrics_batch_gpu(ctx, p1, p2_list, r, p1_n=None, index_a=None):
+def cloud_metrics_batch_gpu(ctx, p1, p2_list, r, p1_n=None, index_a=None, ties='pick'):
     """cloud_metrics_batch's single-process result computed on the GPU: one reference-style dictionary per candidate decoded cloud
-    (None for an empty one), D1 and, with normals p1_n, D2.  Points are integer coordinates in [0, 2^21)."""
+    (None for an empty one), D1 and, with normals p1_n, D2.  Points are integer coordinates in [0, 2^21).  ties: cloud_tallies_gpu."""
     n_a = index_a.n if index_a is not None else len(p1)
     groups = GROUPS if p1_n is not None else GROUPS[:1]
-    return [None if t is None else metrics_table(n_a, t[:5], r, groups) for t in cloud_tallies_gpu(ctx, p1, p2_list, p1_n, index_a)]
+    return [None if t is None else metrics_table(n_a, t[:5], r, groups) for t in cloud_tallies_gpu(ctx, p1, p2_list, p1_n, index_a, ties)]
+
+
+# ---- tie-averaged D2 (DESIGN.md "Tie-averaged D2"; include/pcc_geo.h pcc_cloud_distortion_ties) ----------------------------------
+TIES = ('pick', 'mean')     # pick: one neighbour per point (whichever the engine returns); mean: all equidistant nearest points
+
+
+def check_ties(ties, world=1):
+    """The tie rules of the D2 terms; 'mean' runs in one process (its tie sets are not sharded)."""
+    if ties not in TIES:
+        raise AssertionError(f'ties must be one of {TIES}, got {ties!r}')
+    if ties == 'mean' and world > 1:
+        raise AssertionError(f"ties 'mean' is single-process only (world size {world}): the sharded metric path picks one "
+                             'neighbour per point, drop the flag or run on one GPU')
+
+
+def tie_pairs(points, queries, tree=None, k=8):
+    """All equidistant nearest points: (q, j, best) with one entry of q (query row, non-decreasing) and j (row of `points`) per member
+    of a query's tie set -- every j at the smallest squared distance best[q] (int64[nq], exact: integer coordinates below 2^21).  The
+    KD-tree proposes k candidates per query and distances are recomputed in integers; a query whose k candidates all tie takes its
+    set from a ball query instead."""
+    p, q = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(queries, np.float64).reshape(-1, 3)
+    pi, qi = p.astype(np.int64), q.astype(np.int64)
+    k = min(k, len(p))
+    tree = tree if tree is not None else cKDTree(p, balanced_tree=False)
+    _, cand = tree.query(q, k=k, workers=-1 if max(len(p), len(q)) > 200000 else 1)
+    cand = cand.reshape(len(q), k)
+    d2 = ((pi[cand] - qi[:, None, :]) ** 2).sum(-1)
+    best = d2.min(1)
+    tie = d2 == best[:, None]
+    incomplete = np.nonzero(tie.all(1) & (k < len(p)))[0]
+    tie[incomplete] = False
+    rows, cols = np.nonzero(tie)
+    qs, js = [rows], [cand[rows, cols]]
+    if len(incomplete):
+        balls = tree.query_ball_point(q[incomplete], np.sqrt(best[incomplete].astype(np.float64)) * (1 + 1e-12) + 1e-9)
+        for i, nb in zip(incomplete, balls):
+            nb = np.sort(np.asarray(nb, np.int64))
+            nb = nb[((pi[nb] - qi[i]) ** 2).sum(-1) == best[i]]
+            qs.append(np.full(len(nb), i, np.int64))
+            js.append(nb)
+        qs, js = np.concatenate(qs), np.concatenate(js)
+        order = np.argsort(qs, kind='stable')
+        return qs[order], js[order], best
+    return qs[0], js[0], best
+
+
+def plane_terms(gap, normals):
+    """Per-point squared projection ((g.x n.x + g.y n.y) + g.z n.z)^2, every operation rounded: plane_error's terms."""
+    return ((gap * normals).sum(axis=1)) ** 2
+
+
+def tie_mean_tally(p1, p2, p1_n=None, t1=None):
+    """The 9-slot tally under ties = 'mean' on the host (the definition of DESIGN.md "Tie-averaged D2", which the GPU engine's
+    pcc_cloud_distortion_ties restates): the normal of a decoded point is the mean normal of the original points that have it in
+    their tie set (bincount: summed in increasing original row), or of its own tie set when nobody does; each point's term is the
+    mean plane term over its tie set.  With singleton tie sets every operation is pair_tally's: the same bits."""
+    a, b = np.asarray(p1, np.float64)[:, :3], np.asarray(p2, np.float64).reshape(-1, 3)
+    assert len(b), 'tie_mean_tally: empty decoded cloud'
+    qa, jb, d_ab = tie_pairs(b, a)
+    qb, ja, d_ba = tie_pairs(a, b, t1)
+    tally = np.zeros(9, np.float64)
+    tally[N_B] = len(b)
+    tally[D1_AB], tally[D1_BA] = d_ab.astype(np.float64).sum(), d_ba.astype(np.float64).sum()
+    tally[H1_AB], tally[H1_BA] = d_ab.max(), d_ba.max()
+    if p1_n is None:
+        return tally
+    n_a = np.asarray(p1_n, np.float64)
+    votes = np.bincount(jb, minlength=len(b)).astype(np.float64)
+    acc = np.stack([np.bincount(jb, weights=n_a[qa, c], minlength=len(b)) for c in range(3)], axis=1)
+    orphan = votes == 0
+    if orphan.any():
+        own = orphan[qb]
+        acc[orphan] = np.stack([np.bincount(qb[own], weights=n_a[ja[own], c], minlength=len(b)) for c in range(3)], axis=1)[orphan]
+        votes[orphan] = np.bincount(qb[own], minlength=len(b))[orphan]
+    n_b = acc / votes[:, None]
+    t_ab = np.bincount(qa, weights=plane_terms(a[qa] - b[jb], n_b[jb]), minlength=len(a)) / np.bincount(qa, minlength=len(a))
+    t_ba = np.bincount(qb, weights=plane_terms(b[qb] - a[ja], n_a[ja]), minlength=len(b)) / np.bincount(qb, minlength=len(b))
+    tally[D2_AB], tally[D2_BA] = t_ab.sum(), t_ba.sum()
+    tally[H2_AB], tally[H2_BA] = t_ab.max(), t_ba.max()
+    return tally
 
 
 # ---- colour distortion (include/pcc_geo.h "cloud colours") -------------------------------------------------------------------
