@@ -337,6 +337,30 @@ int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t
                             int64_t npts, const float* normals, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum,
                             uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream);
 
+/* The same search under the tie-averaged D2 definition (DESIGN.md "Tie-averaged D2", applied per block and threshold with A = the
+ * block's rows and B = B_t): T_B(a) = ALL voxels of B_t at the smallest squared distance from row a, T_A(v) = ALL rows at the
+ * smallest squared distance from voxel v (rows that share a voxel are separate members).  A voxel b takes the unweighted float64 mean
+ * of normals[a] over {a : b in T_B(a)}, summed in increasing row;  d2_ab[b][t] = sum_a mean_{v in T_B(a)} e(a - v, n_B(v)),
+ * d2_ba[b][t] = sum_{v in B_t} mean_{a in T_A(v)} e(v - a, normals[a]),  e(g, n) = ((g.x n.x + g.y n.y) + g.z n.z)^2 in float64
+ * without contraction.  Nothing depends on which of several equidistant points is met first, so a host restatement gives the same
+ * sums up to float64 rounding.  The D1 outputs (s_ab, hsum, hcnt, tcount) are those of pcc_d1_threshold_stats.  Differences to
+ * pcc_d12_threshold_stats:
+ *   normals     : (npts,3) float64 (device)
+ *   max_pairs   : capacity of the pair list of ONE chunk of thresholds, in [1, 2^31): the number of (row, tied voxel) pairs is data
+ *                 dependent.  pcc_d12_search_ties_chunk(B,D,H,W) thresholds are processed at a time.
+ *   status      : int64[2] (device), written by the call: [0] = the largest pair count of a chunk (the capacity that suffices),
+ *                 [1] = 1 when a chunk needed more than max_pairs.  Then no pair was written past the capacity, EVERY d2_ab / d2_ba
+ *                 entry is NaN and the D1 outputs are valid: call again with max_pairs >= status[0].  Never a silent truncation.
+ *   workspace2  : pcc_d12_search_ties_workspace_bytes(B,D,H,W,npts,max_pairs) bytes (0 = bad arguments), beside `workspace`
+ * No floating-point atomics, every sum in a fixed order: two calls give the same bits.                                      */
+int32_t pcc_d12_search_ties_chunk(int32_t B, int32_t D, int32_t H, int32_t W);
+size_t pcc_d12_search_ties_workspace_bytes(int32_t B, int32_t D, int32_t H, int32_t W, int64_t npts, int64_t max_pairs);
+int pcc_d12_threshold_stats_ties(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const float* thr,
+                                 int32_t nthr, int32_t clip, const int32_t* pts, const int32_t* block_of, const int32_t* block_start,
+                                 int64_t npts, const double* normals, int64_t max_pairs, int64_t* status, void* workspace,
+                                 void* workspace2, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab,
+                                 double* d2_ba, void* stream);
+
 /* ---- point normals (new: the reference reads them from a `--input_normals` file, src/compress_octree.py:142-144) ----------------
  * The normals the D2 metrics need (pcc_d12_threshold_stats, utils/pc_metric.py) estimated from the cloud itself.  Definition:
  *   - pts: (npts,3) int32, every coordinate in [0, 2^21) (the codec's voxelised clouds; other values give unspecified normals,

@@ -23,6 +23,7 @@ EXPORTS = [
     'pcc_symbols_tiles', 'pcc_symbols_pack', 'pcc_symbols_unpack',
     'pcc_range_encode_batch', 'pcc_range_decode_batch', 'pcc_range_encode_batch_n', 'pcc_range_decode_batch_n', 'pcc_pmf_to_quantized_cdf',
     'pcc_d1_search_workspace_bytes', 'pcc_d1_threshold_stats', 'pcc_d12_search_workspace_bytes', 'pcc_d12_threshold_stats', 'pcc_octree_bucket',
+    'pcc_d12_search_ties_chunk', 'pcc_d12_search_ties_workspace_bytes', 'pcc_d12_threshold_stats_ties',
     'pcc_network_num_layers', 'pcc_network_layer', 'pcc_weights_blob_floats', 'pcc_weights_pack', 'pcc_weights_upload',
     'pcc_network_workspace_bytes', 'pcc_network_out_dims', 'pcc_network_forward', 'pcc_network_forward_analysis',
     'pcc_network_forward_synthesis', 'pcc_network_forward_hyper_a', 'pcc_network_forward_hyper_s',
@@ -121,6 +122,12 @@ def lib():
     L.pcc_d12_search_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_int64]
     L.pcc_d12_search_workspace_bytes.restype = sz
     L.pcc_d12_threshold_stats.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pcc_d12_search_ties_chunk.argtypes = [i32, i32, i32, i32]
+    L.pcc_d12_search_ties_chunk.restype = i32
+    L.pcc_d12_search_ties_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_int64, C.c_int64]
+    L.pcc_d12_search_ties_workspace_bytes.restype = sz
+    L.pcc_d12_threshold_stats_ties.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, vp, vp, vp, vp,
+                                               vp, vp, vp, vp]
     L.pcc_normals_workspace_bytes.argtypes = [C.c_int64, i32]
     L.pcc_normals_workspace_bytes.restype = sz
     L.pcc_estimate_normals.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp]

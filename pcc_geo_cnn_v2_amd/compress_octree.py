@@ -3,7 +3,7 @@
   python -m pcc_geo_cnn_v2_amd.compress_octree --input_files a.ply --output_files a.ply.bin \\
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
-         [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu] [--d2_ties pick|mean]
+         [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu] [--d2_ties pick|mean] [--search_ties pick|mean]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
@@ -67,6 +67,7 @@ def _plan(args):
         metrics.append(name)
     args.opt_metrics = metrics
     validate_opt_metrics(metrics, with_normals=with_normals)
+    check_search_ties(getattr(args, 'search_ties', 'pick'), metrics, with_normals, getattr(args, 'fixed_threshold', False))
     per_cloud = len(metrics) if len(metrics) > 1 else 1
     n_in = len(args.input_files)
     if len(args.output_files) != per_cloud * n_in:
@@ -123,6 +124,17 @@ def check_d2_ties(d2_ties, world):
         raise AssertionError(f'--d2_ties: {e}') from None
 
 
+def check_search_ties(search_ties, opt_metrics, with_normals, fixed_threshold=False):
+    """--search_ties mean changes the d2_* statistics of the per-block threshold search: refused where it could not do anything."""
+    from .model_opt import check_search_ties as check
+    try:
+        check(search_ties, opt_metrics, with_normals)
+        if search_ties == 'mean' and fixed_threshold:
+            raise AssertionError('--fixed_threshold runs no threshold search, drop one of the two flags')
+    except AssertionError as e:
+        raise AssertionError(f'--search_ties: {e}') from None
+
+
 def _block_grid(resolution, level, data_format):
     """Octree geometry: the bounding box of the whole cloud and the dense shape of one leaf block."""
     from .utils import pc_io
@@ -151,6 +163,8 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
             record['metrics_device'] = args.metrics_device
         if getattr(args, 'd2_ties', 'pick') != 'pick':
             record['d2_ties'] = args.d2_ties
+        if getattr(args, 'search_ties', 'pick') != 'pick':
+            record['search_ties'] = args.search_ties
         json.dump(record, fh, sort_keys=True, indent=4)
     if decoded_path is not None:
         pc_io.write_df(decoded_path, pc_io.pa_to_df(info['blocks_full']))
@@ -198,6 +212,7 @@ def compress(args):
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
     model.d2_search = getattr(args, 'd2_search', None)      # per model, not a module global
+    model.search_ties = getattr(args, 'search_ties', 'pick')
     model.compress(np.concatenate(((1,), block_shape)))
     model.restore(args.checkpoint_dir)      # asserts 'Checkpoint ... was not found' like compress_octree.py:91
     T.mark('checkpoint_restore')
@@ -248,7 +263,14 @@ def build_parser():
                         help='Which of several equidistant nearest points the whole-cloud D2 reads (the metrics that rank the candidates '
                              'and go to .enc.metric.json; new): pick = one of them, mean = the average over all of them (row-order '
                              'independent, the same on host and gpu; single process only).  The per-block threshold search keeps its '
-                             'own rules either way.')
+                             'own rules either way (its flag: --search_ties).')
+    parser.add_argument('--search_ties', choices=('pick', 'mean'), default='pick',
+                        help='Which of several equidistant nearest points the d2_* statistics of the per-block threshold search read '
+                             '(new): pick = one of them (each engine its own, see --d2_search), mean = the average over all of them: '
+                             'row-order independent, the same sums on the GPU (the default engine for mean) and with --d2_search kdtree '
+                             '(or PCC_D2_HOST=1: the slow host restatement, for checking; PCC_D2_GPU has no effect under mean), and the function '
+                             '--d2_ties mean reports.  Needs a d2 metric '
+                             'in --opt_metrics and normals.')
     parser.add_argument('--dec_files', nargs='*',
                         help='Decoded files. Allows compression/decompression in a single execution.')
     parser.add_argument('--checkpoint_dir', help='Directory where to save/load model checkpoints.', required=True)

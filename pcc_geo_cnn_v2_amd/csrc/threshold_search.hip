@@ -659,3 +659,365 @@ PCC_API int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B,
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
 }
+
+
+// =====================================================================================================================
+// Tie-averaged D2 statistics (pcc_d12_threshold_stats_ties): DESIGN.md 4.8.1 ("Tie-averaged D2") applied per (block, threshold) with
+// A = the block's rows and B = B_t.  Every equidistant nearest point counts: a decoded voxel takes the mean normal of ALL rows that
+// have it in their tie set, a row's term is the mean plane error over its tie set, a voxel's term the mean over ALL rows at its
+// smallest distance.  Nothing depends on which of several equidistant points an engine meets first, so the sums equal the host
+// restatement (model_opt.host_threshold_stats(ties='mean')) up to float64 rounding.  pcc_d12_threshold_stats and its kernels above
+// are untouched; the D1 outputs come from the same pcc_d1_threshold_stats call.
+//   B -> A (once per block): d^2(v) is the EDT of A the D1 call left in its workspace.  Every voxel of level >= 1 walks the block's
+//        rows (staged through LDS, increasing row) and averages e over the rows at exactly that distance; k_d2_ba's per-threshold
+//        sum over the level sets follows.
+//   A -> B (per chunk of thresholds): z/y pass -> in-plane squared distance g[x'][y][z]; the x pass at a row gives d^2_t(a); the tie
+//        set is then enumerated exactly: every plane x' with (x_a - x')^2 + g[x'][y_a][z_a] == d^2 holds the lattice points of the
+//        circle of the remaining radius^2 around (y_a, z_a), of which those of level > t belong.  Count, exclusive scan, emit
+//        (block, t, voxel) -> pair at offsets that increase with (t, row), stable radix sort by key: every group lists its rows in
+//        increasing order; the head of a group sums their normals in that order and writes e of every member; each row averages e
+//        over its own pairs; k_d2_ab's fixed-order sum per (block, t) follows.
+// The pair count of a chunk is only known on the device: k_tie_total compares it with the caller's capacity, past it no pair is
+// written, the chunk's later kernels return early, and k_tie_finish turns every D2 slot into NaN.  status = (largest pair count of a
+// chunk, overflowed).  No float atomics, every sum in a fixed order, vector stores only.
+namespace {
+
+struct TieCtl {                       // written by k_tie_total, once per chunk
+    unsigned long long pairs;         // pairs of this chunk
+    int overflow;                     // pairs > capacity: nothing below k_tie_total touches the pair arrays in this chunk
+};
+
+// ((gx*nx + gy*ny) + gz*nz)^2, every operation rounded: pc_metric.plane_terms
+__device__ __forceinline__ double tie_plane_term(int gx, int gy, int gz, double nx, double ny, double nz) {
+#pragma clang fp contract(off)
+    const double p = ((double)gx * nx + (double)gy * ny) + (double)gz * nz;
+    return p * p;
+}
+
+// B -> A: ebar[b][v] = mean of e(v - a, n[a]) over ALL rows a of block b with |v - a|^2 == edt_a[v], for the voxels of level >= 1
+// (0 elsewhere).  thread <-> voxel; the rows pass through LDS in tiles of 256, in increasing row.
+__global__ void __launch_bounds__(256) k_tie_ba(const unsigned char* __restrict__ lev, const unsigned short* __restrict__ edt_a,
+                                                const int* __restrict__ pts, const double* __restrict__ normals,
+                                                const int* __restrict__ block_start, size_t nvox, int H, int W, double* __restrict__ ebar) {
+    __shared__ int sp[256][3];
+    __shared__ double sn[256][3];
+    const int b = blockIdx.y;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < nvox && lev[(size_t)b * nvox + i] != 0;
+    const int any = __syncthreads_or(live ? 1 : 0);
+    if (!any) {
+        if (i < nvox) ebar[(size_t)b * nvox + i] = 0.0;
+        return;
+    }
+    const int z = (int)(i % W), y = (int)((i / W) % H), x = (int)(i / ((size_t)H * W));
+    const int want = live ? (int)edt_a[(size_t)b * nvox + i] : -1;
+    double acc = 0.0, cnt = 0.0;
+    const int lo = block_start[b], hi = block_start[b + 1];
+    for (int r0 = lo; r0 < hi; r0 += 256) {
+        const int r = r0 + (int)threadIdx.x;
+        if (r < hi) {
+            sp[threadIdx.x][0] = pts[(size_t)r * 3]; sp[threadIdx.x][1] = pts[(size_t)r * 3 + 1]; sp[threadIdx.x][2] = pts[(size_t)r * 3 + 2];
+            sn[threadIdx.x][0] = normals[(size_t)r * 3]; sn[threadIdx.x][1] = normals[(size_t)r * 3 + 1]; sn[threadIdx.x][2] = normals[(size_t)r * 3 + 2];
+        }
+        __syncthreads();
+        const int n = hi - r0 < 256 ? hi - r0 : 256;
+        if (live) {
+            for (int k = 0; k < n; ++k) {
+                const int gx = x - sp[k][0], gy = y - sp[k][1], gz = z - sp[k][2];
+                if (gx * gx + gy * gy + gz * gz == want) { acc += tie_plane_term(gx, gy, gz, sn[k][0], sn[k][1], sn[k][2]); cnt += 1.0; }
+            }
+        }
+        __syncthreads();
+    }
+    if (i < nvox) ebar[(size_t)b * nvox + i] = cnt > 0.0 ? acc / cnt : 0.0;
+}
+
+__device__ __forceinline__ int tie_isqrt(int v) {
+    int s = (int)sqrtf((float)v);
+    while (s * s > v) --s;
+    while ((s + 1) * (s + 1) <= v) ++s;
+    return s;
+}
+
+// x pass at one row: d^2 = min_x' (xa - x')^2 + g[x'][ya][za]  (k_edt_points' loop; c = g at (x' = 0, ya, za) of the row's (block, slot))
+__device__ __forceinline__ unsigned tie_x_pass(const unsigned short* __restrict__ c, size_t hw, int xa, int D) {
+    unsigned best = c[(size_t)xa * hw];
+    for (int d = 1; d < D; ++d) {
+        const unsigned dd = (unsigned)(d * d);
+        if (dd >= best) break;
+        if (xa - d >= 0) { const unsigned v = c[(size_t)(xa - d) * hw]; if (v != kInf && v + dd < best) best = v + dd; }
+        if (xa + d < D) { const unsigned v = c[(size_t)(xa + d) * hw]; if (v != kInf && v + dd < best) best = v + dd; }
+    }
+    return best;
+}
+
+// Every voxel of level > t at squared distance exactly d2 from (xa, ya, za), given that d2 is the smallest such distance: f(row-major
+// voxel index), in a fixed order (x' ascending, then |dy| ascending, -dy before +dy, -dz before +dz).  l = the block's levels.
+template <typename F>
+__device__ __forceinline__ void tie_for_each(const unsigned short* __restrict__ c, const unsigned char* __restrict__ l, int t, int D, int H,
+                                             int W, int xa, int ya, int za, unsigned d2, F f) {
+    const size_t hw = (size_t)H * W;
+    const int reach = tie_isqrt((int)d2);
+    const int x_lo = xa - reach > 0 ? xa - reach : 0, x_hi = xa + reach < D - 1 ? xa + reach : D - 1;
+    for (int xs = x_lo; xs <= x_hi; ++xs) {
+        const int dx = xa - xs, r = (int)d2 - dx * dx;
+        if (r < 0 || (int)c[(size_t)xs * hw] != r) continue;       // (kInf = 65535 > any r <= 3 * 127^2: an empty plane never matches)
+        for (int dy = 0; dy * dy <= r; ++dy) {
+            const int rem = r - dy * dy, dz = tie_isqrt(rem);
+            if (dz * dz != rem) continue;
+            for (int sy = (dy ? -1 : 1); sy <= 1; sy += 2) {
+                const int y = ya + sy * dy;
+                if (y < 0 || y >= H) continue;
+                for (int sz = (dz ? -1 : 1); sz <= 1; sz += 2) {
+                    const int z = za + sz * dz;
+                    if (z < 0 || z >= W) continue;
+                    const size_t v = ((size_t)xs * H + y) * W + z;
+                    if ((int)l[v] > t) f((unsigned)v);
+                }
+            }
+        }
+    }
+}
+
+// pass 1: |T_B(a)| and d^2_t(a) of every (slot, row); 0 pairs where t >= tcount[block]
+__global__ void __launch_bounds__(256) k_tie_count(const unsigned short* __restrict__ g, const unsigned char* __restrict__ lev,
+                                                   const int* __restrict__ tcount, int tmax, int t0, const int* __restrict__ pts,
+                                                   const int* __restrict__ block_of, long long npts, int D, int H, int W,
+                                                   unsigned long long* __restrict__ cnt, unsigned* __restrict__ dist) {
+    const int tl = blockIdx.y, t = t0 + tl;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    const int b = block_of[i];
+    unsigned long long n = 0;
+    unsigned d2 = 0;
+    const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
+    const bool inside = xa >= 0 && xa < D && ya >= 0 && ya < H && za >= 0 && za < W;      // (k_occupancy's rule: a row outside the grid takes no part)
+    if (inside && t < tcount[b]) {
+        const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
+        const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
+        d2 = tie_x_pass(c, hw, xa, D);
+        tie_for_each(c, lev + (size_t)b * nvox, t, D, H, W, xa, ya, za, d2, [&](unsigned) { ++n; });
+    }
+    cnt[(size_t)tl * npts + i] = n;
+    dist[(size_t)tl * npts + i] = d2;
+}
+
+__global__ void k_tie_total(const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off, size_t n,
+                            unsigned long long cap, TieCtl* __restrict__ ctl, long long* __restrict__ status) {
+    const unsigned long long pairs = off[n - 1] + cnt[n - 1];
+    ctl->pairs = pairs;
+    ctl->overflow = pairs > cap;
+    if ((long long)pairs > status[0]) status[0] = (long long)pairs;
+    if (pairs > cap) status[1] = 1;
+}
+
+// pass 2: the pairs of (slot, row) at [off, off + cnt): key (block, slot, voxel), value = the pair's own position; prow = its row
+__global__ void __launch_bounds__(256) k_tie_emit(const unsigned short* __restrict__ g, const unsigned char* __restrict__ lev,
+                                                  const int* __restrict__ tcount, int tmax, int t0, const int* __restrict__ pts,
+                                                  const int* __restrict__ block_of, long long npts, int D, int H, int W,
+                                                  const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off,
+                                                  const unsigned* __restrict__ dist, const TieCtl* __restrict__ ctl, unsigned long long cap,
+                                                  unsigned long long* __restrict__ keys, unsigned* __restrict__ vals, unsigned* __restrict__ prow) {
+    if (ctl->overflow) return;
+    const int tl = blockIdx.y, t = t0 + tl;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    const size_t slot = (size_t)tl * npts + i;
+    const unsigned long long n = cnt[slot];
+    if (n == 0) return;
+    const int b = block_of[i];
+    const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
+    const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
+    const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
+    unsigned long long p = off[slot];
+    const unsigned long long end = p + n;
+    const unsigned long long head = ((unsigned long long)b << 32) | ((unsigned long long)tl << 24);      // voxel < 2^21 (128^3), slot < 256
+    tie_for_each(c, lev + (size_t)b * nvox, t, D, H, W, xa, ya, za, dist[slot], [&](unsigned v) {
+        if (p < end && p < cap) { keys[p] = head | v; vals[p] = (unsigned)p; prow[p] = (unsigned)i; }
+        ++p;
+    });
+}
+
+// the tail of the capacity sorts behind every pair (block 0xFFFF does not exist: B <= 65535)
+__global__ void __launch_bounds__(256) k_tie_pad(const TieCtl* __restrict__ ctl, unsigned long long cap, unsigned long long* __restrict__ keys,
+                                                 unsigned* __restrict__ vals) {
+    if (ctl->overflow) return;
+    for (unsigned long long p = ctl->pairs + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; p < cap;
+         p += (unsigned long long)gridDim.x * blockDim.x) {
+        keys[p] = ~0ull;
+        vals[p] = (unsigned)p;
+    }
+}
+
+// sorted groups (block, slot, voxel): the head sums the normals of the group's rows in increasing row (the stable sort kept the
+// emit order) and writes e(a - voxel, mean normal) of every member at the pair's own position
+__global__ void __launch_bounds__(256) k_tie_groups(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                    const unsigned* __restrict__ prow, const TieCtl* __restrict__ ctl, unsigned long long cap,
+                                                    const int* __restrict__ pts, const double* __restrict__ normals, int H, int W,
+                                                    double* __restrict__ perr) {
+    if (ctl->overflow) return;
+    const unsigned long long n = ctl->pairs < cap ? ctl->pairs : cap;
+    const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const unsigned long long key = keys[j];
+    if (j > 0 && keys[j - 1] == key) return;            // not a group head
+    double sx = 0.0, sy = 0.0, sz = 0.0, votes = 0.0;
+    unsigned long long end = j;
+    for (; end < n && keys[end] == key; ++end) {
+        const size_t r = prow[vals[end]];
+        sx += normals[r * 3]; sy += normals[r * 3 + 1]; sz += normals[r * 3 + 2]; votes += 1.0;
+    }
+    sx /= votes; sy /= votes; sz /= votes;
+    const unsigned arg = (unsigned)(key & 0xFFFFFFu);
+    const int zs = (int)(arg % (unsigned)W), ys = (int)((arg / (unsigned)W) % (unsigned)H), xs = (int)(arg / (unsigned)(W * H));
+    for (unsigned long long m = j; m < end; ++m) {
+        const unsigned p = vals[m];
+        const size_t r = prow[p];
+        perr[p] = tie_plane_term(pts[r * 3] - xs, pts[r * 3 + 1] - ys, pts[r * 3 + 2] - zs, sx, sy, sz);
+    }
+}
+
+// err[slot][row] = mean of perr over the row's own pairs (emit order)
+__global__ void __launch_bounds__(256) k_tie_row_mean(const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off,
+                                                      const double* __restrict__ perr, const TieCtl* __restrict__ ctl, size_t n,
+                                                      double* __restrict__ err) {
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    double v = 0.0;
+    if (!ctl->overflow && cnt[s]) {
+        const unsigned long long o = off[s], c = cnt[s];
+        double acc = 0.0;
+        for (unsigned long long k = 0; k < c; ++k) acc += perr[o + k];
+        v = acc / (double)c;
+    }
+    err[s] = v;
+}
+
+// a chunk met more pairs than the capacity: every D2 slot becomes NaN (the D1 outputs stay valid)
+__global__ void __launch_bounds__(256) k_tie_finish(const long long* __restrict__ status, int n, double* __restrict__ d2_ab, double* __restrict__ d2_ba) {
+    if (!status[1]) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { d2_ab[i] = __longlong_as_double(0x7FF8000000000000ll); d2_ba[i] = __longlong_as_double(0x7FF8000000000000ll); }
+}
+
+struct TieLayout {
+    size_t g0, g1, ebar, cnt, off, dist, err, ctl, keys0, keys1, vals0, vals1, prow, perr, scan_tmp, scan_tmp_bytes, sort_tmp, sort_tmp_bytes, total;
+    int TC;
+};
+int tie_chunk(int32_t B, size_t nvox) {
+    const int tc = chunk_thresholds(B, nvox);
+    return tc > 64 ? 64 : tc;
+}
+TieLayout tie_layout(int32_t B, size_t nvox, int64_t npts, int64_t max_pairs) {
+    TieLayout l;
+    l.TC = tie_chunk(B, nvox);
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t slots = (size_t)l.TC * (size_t)npts, cap = (size_t)max_pairs;
+    size_t o = 0;
+    l.g0 = o; o += al((size_t)B * l.TC * nvox * 2);
+    l.g1 = o; o += al((size_t)B * l.TC * nvox * 2);
+    l.ebar = o; o += al((size_t)B * nvox * 8);
+    l.cnt = o; o += al(slots * 8);
+    l.off = o; o += al(slots * 8);
+    l.dist = o; o += al(slots * 4);
+    l.err = o; o += al(slots * 8);
+    l.ctl = o; o += al(sizeof(TieCtl));
+    l.keys0 = o; o += al(cap * 8);
+    l.keys1 = o; o += al(cap * 8);
+    l.vals0 = o; o += al(cap * 4);
+    l.vals1 = o; o += al(cap * 4);
+    l.prow = o; o += al(cap * 4);
+    l.perr = o; o += al(cap * 8);
+    size_t tmp = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                           (int)(slots ? slots : 1), (hipStream_t)0);
+    l.scan_tmp_bytes = tmp;
+    l.scan_tmp = o; o += al(tmp + 256);
+    tmp = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(cap ? cap : 1), 0, 48, (hipStream_t)0);
+    l.sort_tmp_bytes = tmp;
+    l.sort_tmp = o; o += al(tmp + 256);
+    l.total = o + 4096;
+    return l;
+}
+
+}  // namespace
+
+PCC_API int32_t pcc_d12_search_ties_chunk(int32_t B, int32_t D, int32_t H, int32_t W) {
+    return tie_chunk(B, (size_t)D * H * W);
+}
+
+PCC_API size_t pcc_d12_search_ties_workspace_bytes(int32_t B, int32_t D, int32_t H, int32_t W, int64_t npts, int64_t max_pairs) {
+    if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || npts <= 0 || max_pairs < 1 || max_pairs > 0x7FFFFFFFll) return 0;
+    return tie_layout(B, (size_t)D * H * W, npts, max_pairs).total;
+}
+
+// As pcc_d12_threshold_stats with float64 normals and the tie-averaged D2 definition (include/pcc_geo.h).  workspace:
+// pcc_d1_search_workspace_bytes; workspace2: pcc_d12_search_ties_workspace_bytes(..., max_pairs); status: int64[2] (device).
+PCC_API int pcc_d12_threshold_stats_ties(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const float* thr,
+                                         int32_t nthr, int32_t clip, const int32_t* pts, const int32_t* block_of,
+                                         const int32_t* block_start, int64_t npts, const double* normals, int64_t max_pairs,
+                                         int64_t* status, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt,
+                                         int32_t* tcount, double* d2_ab, double* d2_ba, void* stream) {
+    PCC_REQUIRE(normals && block_start && workspace2 && d2_ab && d2_ba && pts && status && npts > 0, "pcc_d12_threshold_stats_ties: NULL argument");
+    PCC_REQUIRE((size_t)npts * 64 < ((size_t)1 << 31), "pcc_d12_threshold_stats_ties: too many points for one call");
+    PCC_REQUIRE(max_pairs >= 1 && max_pairs <= 0x7FFFFFFFll, "pcc_d12_threshold_stats_ties: max_pairs outside [1, 2^31)");
+    { const int rc = pcc_d1_threshold_stats(ctx, x_hat, B, D, H, W, thr, nthr, clip, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
+      if (rc != PCC_OK) return rc; }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nvox = (size_t)D * H * W;
+    const TieLayout l = tie_layout(B, nvox, npts, max_pairs);
+    unsigned char* w2 = (unsigned char*)workspace2;
+    unsigned short *g0 = (unsigned short*)(w2 + l.g0), *g1 = (unsigned short*)(w2 + l.g1);
+    double *ebar = (double*)(w2 + l.ebar), *err = (double*)(w2 + l.err), *perr = (double*)(w2 + l.perr);
+    unsigned long long *cnt = (unsigned long long*)(w2 + l.cnt), *off = (unsigned long long*)(w2 + l.off);
+    unsigned* dist = (unsigned*)(w2 + l.dist);
+    TieCtl* ctl = (TieCtl*)(w2 + l.ctl);
+    unsigned long long *keys0 = (unsigned long long*)(w2 + l.keys0), *keys1 = (unsigned long long*)(w2 + l.keys1);
+    unsigned *vals0 = (unsigned*)(w2 + l.vals0), *vals1 = (unsigned*)(w2 + l.vals1), *prow = (unsigned*)(w2 + l.prow);
+    // buffers of the D1 call that are still valid: levels, occupancy and the finished EDT of A at the start of `workspace`
+    unsigned char* lev = (unsigned char*)workspace;
+    const unsigned short* edt_a = (const unsigned short*)(lev + (size_t)B * nvox * 2);
+    const unsigned long long cap = (unsigned long long)max_pairs;
+    const int lines = D * H;
+    const unsigned vox_blocks = (unsigned)((nvox + 255) / 256);
+    const unsigned pblocks = (unsigned)((npts + 255) / 256);
+    PCC_CHECK_HIP(hipMemsetAsync(d2_ab, 0, (size_t)B * kT * 8, st));
+    PCC_CHECK_HIP(hipMemsetAsync(d2_ba, 0, (size_t)B * kT * 8, st));
+    PCC_CHECK_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int64_t), st));
+    // ---- B -> A
+    hipLaunchKernelGGL(k_tie_ba, dim3(vox_blocks, B), dim3(256), 0, st, lev, edt_a, pts, normals, block_start, nvox, H, W, ebar);
+    hipLaunchKernelGGL(k_d2_ba, dim3(nthr, B), dim3(256), 0, st, lev, ebar, tcount, nvox, d2_ba);
+    // ---- A -> B per chunk of thresholds
+    const bool fused = edt_zy_takes(D, H, W) && !getenv("PCC_EDT_OLD");      // the D1 call's switch: both parts take the same z/y kernels
+    for (int t0 = 0; t0 < nthr; t0 += l.TC) {
+        const int nt = nthr - t0 < l.TC ? nthr - t0 : l.TC;
+        const size_t slots = (size_t)nt * (size_t)npts;
+        if (fused) {
+            if (W <= 64 && H <= 64) hipLaunchKernelGGL((k_edt_zy<1, 64>), dim3(D, nt, B), dim3(64), 0, st, lev, tcount, l.TC, t0, D, H, W, g1);
+            else if (W <= 64) hipLaunchKernelGGL((k_edt_zy<1, 128>), dim3(D, nt, B), dim3(64), 0, st, lev, tcount, l.TC, t0, D, H, W, g1);
+            else hipLaunchKernelGGL((k_edt_zy<2, 128>), dim3(D, nt, B), dim3(64), 0, st, lev, tcount, l.TC, t0, D, H, W, g1);
+        } else {
+            hipLaunchKernelGGL(k_edt_z, dim3((lines + 255) / 256, nt, B), dim3(256), 0, st, lev, tcount, l.TC, t0, lines, W, g0);
+            hipLaunchKernelGGL(k_edt_axis, dim3(vox_blocks, nt, B), dim3(256), 0, st, g0, tcount, l.TC, t0, nvox, H, W, g1);
+        }
+        hipLaunchKernelGGL(k_tie_count, dim3(pblocks, nt), dim3(256), 0, st, g1, lev, tcount, l.TC, t0, pts, block_of, (long long)npts, D, H, W,
+                           cnt, dist);
+        size_t tmp = l.scan_tmp_bytes;
+        PCC_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum((void*)(w2 + l.scan_tmp), tmp, (const unsigned long long*)cnt, off, (int)slots, st));
+        hipLaunchKernelGGL(k_tie_total, dim3(1), dim3(1), 0, st, cnt, off, slots, cap, ctl, (long long*)status);
+        hipLaunchKernelGGL(k_tie_emit, dim3(pblocks, nt), dim3(256), 0, st, g1, lev, tcount, l.TC, t0, pts, block_of, (long long)npts, D, H, W,
+                           cnt, off, dist, ctl, cap, keys0, vals0, prow);
+        hipLaunchKernelGGL(k_tie_pad, dim3(256), dim3(256), 0, st, ctl, cap, keys0, vals0);
+        tmp = l.sort_tmp_bytes;
+        PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w2 + l.sort_tmp), tmp, keys0, keys1, vals0, vals1, (int)cap, 0, 48, st));
+        hipLaunchKernelGGL(k_tie_groups, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, keys1, vals1, prow, ctl, cap, pts, normals, H, W,
+                           perr);
+        hipLaunchKernelGGL(k_tie_row_mean, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, cnt, off, perr, ctl, slots, err);
+        hipLaunchKernelGGL(k_d2_ab, dim3(nt, B), dim3(256), 0, st, err, block_start, tcount, t0, (long long)npts, d2_ab);
+    }
+    hipLaunchKernelGGL(k_tie_finish, dim3((B * kT + 255) / 256), dim3(256), 0, st, (const long long*)status, B * kT, d2_ab, d2_ba);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}

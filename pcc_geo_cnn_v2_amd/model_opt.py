@@ -78,9 +78,36 @@ def metric_names(opt_metrics, max_deltas):
     return [f'{m}_{d}' for d in max_deltas for m in opt_metrics]
 
 
-def host_threshold_stats(block, x_hat, thresholds, normals=None):
+SEARCH_TIES = PM.TIES     # --search_ties: 'pick' = one neighbour per point (each engine's own choice), 'mean' = all equidistant ones
+
+
+def check_search_ties(ties, opt_metrics=None, with_normals=True):
+    """The tie rules of the D2 statistics of the threshold search.  'mean' only changes d2_* metrics: without one of them, or
+    without normals, it is refused instead of silently doing nothing."""
+    if ties not in SEARCH_TIES:
+        raise AssertionError(f'search_ties must be one of {SEARCH_TIES}, got {ties!r}')
+    if ties == 'mean' and opt_metrics is not None:
+        if not any(str(m).startswith('d2_') for m in opt_metrics):
+            raise AssertionError("search_ties 'mean' changes the d2_* statistics of the threshold search only: "
+                                 f'none of the opt_metrics {list(opt_metrics)} is a d2 metric, drop the flag or add one')
+        if not with_normals:
+            raise AssertionError("search_ties 'mean' needs normals (--input_normals or --estimate_normals): d2_* metrics read them")
+
+
+def host_threshold_stats(block, x_hat, thresholds, normals=None, ties='pick'):
     """Tallies of every non-empty leading level set of one block against the original points, with KD-trees.
-    Returns (tallies float64[T, 5], mean_tally float64[5]); T = number of leading non-empty level sets."""
+    Returns (tallies float64[T, 5], mean_tally float64[5]); T = number of leading non-empty level sets.
+    ties='mean': the plain restatement of the tie-averaged definition, PM.tie_mean_tally per level set and
+    for the mean point -- every level set evaluated, nothing pruned; the D1 slots are the same integers either way."""
+    check_search_ties(ties)
+    if ties == 'mean':
+        a = np.asarray(block)[:, :3]
+        tree_a = cKDTree(np.asarray(a, np.float64), balanced_tree=False)
+        cand, subsets = _level_subsets(x_hat, thresholds)
+        tallies = np.zeros((len(subsets), 5), np.float64)
+        for t, sel in enumerate(subsets):
+            tallies[t] = PM.tie_mean_tally(a, cand[sel], normals, tree_a)[:5]
+        return tallies, mean_point_tally(block if normals is None else np.hstack([a, normals]), normals is not None, ties='mean')
     a = block[:, :3]
     tree_a = cKDTree(a, balanced_tree=False)
     cand, subsets = _level_subsets(x_hat, thresholds)
@@ -266,13 +293,14 @@ def select_thresholds_from_stats(n_a, tallies, mean_tally, n_thresholds, resolut
 
 
 def compute_optimal_thresholds(block, x_hat, thresholds, resolution, normals=None, opt_metrics=['d1_mse'],
-                               max_deltas=[np.inf], fixed_threshold=False):
-    """The reference's entry point (model_opt.py:21): (names '{metric}_{max_delta}', threshold index per name)."""
+                               max_deltas=[np.inf], fixed_threshold=False, ties='pick'):
+    """The reference's entry point (model_opt.py:21): (names '{metric}_{max_delta}', threshold index per name).  ties='mean' (new):
+    the d2 statistics average over all equidistant nearest points (host_threshold_stats)."""
     validate_opt_metrics(opt_metrics, with_normals=normals is not None)
     assert len(max_deltas) > 0
     if fixed_threshold:
         return metric_names(opt_metrics, max_deltas), [len(thresholds) // 2] * (len(max_deltas) * len(opt_metrics))
-    tallies, mean_tally = host_threshold_stats(block, x_hat, thresholds, normals)
+    tallies, mean_tally = host_threshold_stats(block, x_hat, thresholds, normals, ties)
     return select_thresholds_from_stats(len(block), tallies, mean_tally, len(thresholds), resolution, opt_metrics, max_deltas)
 
 
@@ -336,8 +364,8 @@ class HostSearchPool:
                 fut.set_exception(e)
 
     def submit(self, job):
-        """job: ('decide', block, x_hat, thresholds, resolution, with_normals, opt_metrics, max_deltas) -> (names, best)
-                ('tally', block, x_hat, thresholds, with_normals)                                      -> (tallies, mean_tally)
+        """job: ('decide', block, x_hat, thresholds, resolution, with_normals, opt_metrics, max_deltas[, ties]) -> (names, best)
+                ('tally', block, x_hat, thresholds, with_normals[, ties])                              -> (tallies, mean_tally)
            (a bare 7-tuple is a 'decide' job).  Returns a concurrent.futures.Future."""
         from concurrent.futures import Future
         assert self.procs, 'pool is closed'
@@ -381,7 +409,7 @@ D2_SEARCH = None      # 'kdtree' | 'gpu': set by the CLIs' --d2_search; None = t
 _d2_logged = False
 
 
-def d2_on_gpu(mode=None):
+def d2_on_gpu(mode=None, ties='pick'):
     """Where the d2_* statistics of the adaptive search come from.  DEFAULT (round 5): scipy KD-trees in the host worker pool
     -- the reference's own neighbour picks (pc_metric.py:114: among equidistant nearest neighbours it takes whatever the tree traversal
     returns), hence the reference's decisions (pinned by tests/golden/model_opt_d2.npz).  OPT-IN (--d2_search gpu / PCC_D2_GPU=1): the
@@ -389,8 +417,13 @@ def d2_on_gpu(mode=None):
     where no tie occurs (tests/golden/model_opt_d2_tiefree.npz); on voxelised surfaces ties are the rule: measured (tools/d2_tie_table.py,
     DESIGN_HISTORY.md 3.8) the d2_mse decision differs on 82-89 % of the blocks of a 1024^3 cloud and the D2 PSNR of the d2-optimised stream,
     evaluated with the reference's metric, drops by 0.2-1.2 dB -- the search then minimises a function other than the one it is judged by.
-    d1_* metrics never depend on the pick and always come from the GPU."""
+    d1_* metrics never depend on the pick and always come from the GPU.
+    ties='mean' (--search_ties mean): both engines compute the same tie-averaged sums, so the GPU is the default and only an explicit
+    'kdtree' (argument, module default or PCC_D2_HOST) selects the host restatement, for checking; nothing is logged about differing
+    decisions."""
     global _d2_logged
+    if ties == 'mean':      # same precedence as 'pick' (argument, module default, environment: PCC_D2_HOST = kdtree), other default
+        return (mode or D2_SEARCH or ('kdtree' if os.environ.get('PCC_D2_HOST') is not None else 'gpu')) != 'kdtree'
     # precedence: the caller's model (`model.d2_search`, set by the CLI's --d2_search), the module default (tools, tests), the environment
     if mode is None and D2_SEARCH is None and os.environ.get('PCC_D2_HOST') is not None and os.environ.get('PCC_D2_GPU') is not None:
         logger.warning('PCC_D2_HOST and PCC_D2_GPU are both set: PCC_D2_HOST wins (kdtree)')
@@ -428,12 +461,43 @@ def d1_tallies_gpu(ctx, blocks, x_hat, thresholds):
     return out
 
 
-def d12_tallies_gpu(ctx, blocks, x_hat, thresholds):
+def _canonical_rows(block):
+    """The block's rows sorted by (x, y, z, nx, ny, nz): what ties='mean' uploads, so that the fixed summation orders of the kernels
+    do not depend on the row order of the input -- a permuted block gives the same bits, not only the same sums up to rounding."""
+    blk = np.asarray(block)
+    nrm = blk[:, blk.shape[1] - 3:]
+    return blk[np.lexsort((nrm[:, 2], nrm[:, 1], nrm[:, 0], blk[:, 2], blk[:, 1], blk[:, 0]))]
+
+
+def d12_tallies_gpu(ctx, blocks, x_hat, thresholds, ties='pick', max_pairs=None):
     """Per-block D1 AND D2 tallies on the GPU.  blocks: list of (n_i, 6) arrays, xyz + normals (the last three columns, as
-    model_types.get_normals_if takes them).  Returns [float64[T_i, 5]].  Ties between equidistant nearest neighbours go to the
-    lowest (x, y, z) -- the reference takes scipy's pick (pc_metric.py:114); D1 does not depend on the pick."""
+    model_types.get_normals_if takes them).  Returns [float64[T_i, 5]].  ties='pick': ties between equidistant nearest neighbours go
+    to the lowest (x, y, z) -- the reference takes scipy's pick (pc_metric.py:114); D1 does not depend on the pick.  ties='mean': D2
+    averages over ALL equidistant nearest points (ops.d12_threshold_stats_ties, float64 normals): the sums of
+    host_threshold_stats(ties='mean') up to float64 rounding, whatever the row order of the blocks."""
     import torch
     from . import ops
+    check_search_ties(ties)
+    if ties == 'mean':
+        blocks = [_canonical_rows(b) for b in blocks]
+        xyz = np.ascontiguousarray(np.concatenate([b[:, :3] for b in blocks]).astype(np.uint32).astype(np.int32))
+        nrm = np.ascontiguousarray(np.concatenate([b[:, b.shape[1] - 3:] for b in blocks]).astype(np.float64))
+        sizes = np.array([len(b) for b in blocks], np.int64)
+        bof = np.repeat(np.arange(len(blocks), dtype=np.int32), sizes)
+        start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        dev = ctx.device
+        thr = torch.from_numpy(np.asarray(thresholds).astype(np.float32)).to(dev)
+        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats_ties(
+            ctx, x_hat, thr, torch.from_numpy(xyz).to(dev), torch.from_numpy(bof).to(dev), torch.from_numpy(start).to(dev),
+            torch.from_numpy(nrm).to(dev), clip=True, max_pairs=max_pairs)
+        out = []
+        for i in range(len(blocks)):
+            T = int(tcount[i])
+            t = np.zeros((T, 5), np.float64)
+            t[:, PM.N_B], t[:, PM.D1_AB], t[:, PM.D1_BA] = n_b[i][:T], s_ab[i][:T], s_ba[i][:T]
+            t[:, PM.D2_AB], t[:, PM.D2_BA] = d2_ab[i][:T], d2_ba[i][:T]
+            out.append(t)
+        return out
     xyz = np.ascontiguousarray(np.concatenate([np.asarray(b)[:, :3] for b in blocks]).astype(np.uint32).astype(np.int32))
     nrm = np.ascontiguousarray(np.concatenate([np.asarray(b)[:, np.asarray(b).shape[1] - 3:] for b in blocks]).astype(np.float32))
     sizes = np.array([len(b) for b in blocks], np.int64)
@@ -454,47 +518,55 @@ def d12_tallies_gpu(ctx, blocks, x_hat, thresholds):
     return out
 
 
-def mean_point_tally(block, with_normals):
+def mean_point_tally(block, with_normals, ties='pick'):
     """Tally of the rounded mean point (the guard of model_opt.py:59-68) without a KD-tree: its nearest original point; among
     equidistant ones the lowest (x, y, z) in lexicographic order -- the tie rule of the GPU path (csrc/threshold_search.hip), whatever
-    order the block's points are stored in (a plain argmin is that rule only for sorted blocks)."""
+    order the block's points are stored in (a plain argmin is that rule only for sorted blocks).  ties='mean': the
+    tie-averaged rule, PM.tie_mean_tally(a, mean_point, normals)."""
     blk = np.asarray(block)
     if not with_normals:
         return mean_point_d1_tally(blk)
     a = blk[:, :3]
     mean_point = np.round(np.mean(a, axis=0))[np.newaxis, :]
+    if ties == 'mean':      # rows in canonical order, like the tallies: the guard's bits do not depend on the input's row order either
+        blk = _canonical_rows(blk)
+        return PM.tie_mean_tally(blk[:, :3], mean_point, blk[:, blk.shape[1] - 3:])[:5]
     d = PM.squared_norms(a - mean_point)
     near = np.flatnonzero(d == d.min())
     to_a = np.array([int(near[np.lexsort((a[near, 2], a[near, 1], a[near, 0]))[0]])], np.int64)
     return PM.pair_tally(a, mean_point, np.zeros(len(a), np.int64), to_a, blk[:, blk.shape[1] - 3:])
 
 
-def decide_from_tallies(blocks, d1, n_thresholds, resolution, opt_metrics, max_deltas, d2_stats=None, gpu_d2=False):
+def decide_from_tallies(blocks, d1, n_thresholds, resolution, opt_metrics, max_deltas, d2_stats=None, gpu_d2=False, ties='pick'):
     """Decisions of a chunk from the GPU's D1 tallies (d1_tallies_gpu), merged with the host pool's (tallies, mean_tally) per
     block when d2_* metrics are requested: their D2 slots go into the GPU's table; the D1 slots of both sources are the same
-    integers, which is asserted.  Returns (names, [best thresholds per block])."""
+    integers, which is asserted.  `ties`: the rule the D2 slots were computed by (d12_tallies_gpu(ties=) with gpu_d2, or the host
+    pool's 'tally' jobs).  Returns (names, [best thresholds per block])."""
     validate_opt_metrics(opt_metrics, with_normals=d2_stats is not None or gpu_d2)
     names, best = metric_names(list(opt_metrics), list(max_deltas)), []
     for i, blk in enumerate(blocks):
         # gpu_d2: the tallies of d12_tallies_gpu already hold their D2 slots; the guard point follows the same tie rule
-        tallies, mean_tally = d1[i], mean_point_tally(blk, gpu_d2)
+        tallies, mean_tally = d1[i], mean_point_tally(blk, gpu_d2, ties)      # (ties: the guard follows the rule of the tallies)
         if d2_stats is not None:
             host_t, host_mean = d2_stats[i]
             assert len(host_t) == len(tallies), 'host and GPU disagree on the number of non-empty level sets'
             assert np.array_equal(host_t[:, :3], tallies[:, :3]), 'host KD-tree and GPU distance-transform D1 sums differ'
             tallies[:, [PM.D2_AB, PM.D2_BA]] = host_t[:, [PM.D2_AB, PM.D2_BA]]
             mean_tally[[PM.D2_AB, PM.D2_BA]] = host_mean[[PM.D2_AB, PM.D2_BA]]
+            if ties == 'mean':      # the whole guard tally from the one function both engines use (mean_point_tally(ties='mean'))
+                mean_tally = np.array(host_mean, np.float64)
         names, bt = select_thresholds_from_stats(len(blk), tallies, mean_tally, n_thresholds, resolution, list(opt_metrics), list(max_deltas))
         best.append(bt)
     return names, best
 
 
 def compute_optimal_thresholds_gpu(ctx, blocks, x_hat, thresholds, resolution, opt_metrics=('d1_mse',),
-                                   max_deltas=(np.inf,), d2_stats=None):
+                                   max_deltas=(np.inf,), d2_stats=None, ties='pick'):
     """compute_optimal_thresholds for a batch of blocks with the KD-tree work of the d1_* metrics replaced by exact distance
     transforms on the GPU.  `d2_stats`: per block (tallies, mean_tally) from the host pool when d2_* metrics are requested -- or
-    a callable returning that list, evaluated after the GPU work has been issued.  Returns (names, [best thresholds per block])."""
+    a callable returning that list, evaluated after the GPU work has been issued; `ties`: the rule they were computed by.  Returns
+    (names, [best thresholds per block])."""
     d1 = d1_tallies_gpu(ctx, blocks, x_hat, thresholds)
     if callable(d2_stats):
         d2_stats = d2_stats()
-    return decide_from_tallies(blocks, d1, len(thresholds), resolution, opt_metrics, max_deltas, d2_stats)
+    return decide_from_tallies(blocks, d1, len(thresholds), resolution, opt_metrics, max_deltas, d2_stats, ties=ties)

@@ -490,7 +490,7 @@ class CompressionModel:
                 host = [(h[0], h[1][0]) for h in host]
             if item['d1'] is not None:
                 opt_metrics_ret, best_all = decide_from_tallies(chunk_, item['d1'], len(self.thresholds), resolution, opt_metrics, max_deltas, host,
-                                                                gpu_d2=item['gpu_d2'])
+                                                                gpu_d2=item['gpu_d2'], ties=item['ties'])
             else:
                 opt_metrics_ret, best_all = host[0][0], [bt for _, bt in host]
             # a block whose decode is empty at every threshold returns len(opt_metrics) entries (model_opt.py:35-36); with
@@ -529,12 +529,15 @@ class CompressionModel:
                 # table) a few chunks later, so the pool always holds several chunks' worth of blocks.
                 want_d2 = any(m.startswith('d2_') for m in opt_metrics)
                 on_gpu = gpu_search_supported(opt_metrics, dhw)
-                gpu_d2 = want_d2 and on_gpu and d2_on_gpu(getattr(self, 'd2_search', None))          # nearest-index transforms, stated tie rule: opt-in (DESIGN_HISTORY.md 3.8)
+                # search_ties 'mean' (DESIGN.md 4.6): the tie-averaged d2 statistics, the same sums on either engine -- from the GPU unless
+                # d2_search = 'kdtree' asks for the host restatement (every level set, nothing pruned: for checking)
+                ties = getattr(self, 'search_ties', 'pick') if want_d2 else 'pick'
+                gpu_d2 = want_d2 and on_gpu and d2_on_gpu(getattr(self, 'd2_search', None), ties)   # 'pick': nearest-index transforms, stated tie rule: opt-in (DESIGN_HISTORY.md 3.8)
                 strings = enc['finish']()
-                item = dict(chunk=chunk, x_hat=x_hat, futures=None, d1=None, gpu_d2=gpu_d2)
+                item = dict(chunk=chunk, x_hat=x_hat, futures=None, d1=None, gpu_d2=gpu_d2, ties=ties)
                 # (round 6) the host pool only builds the A->B trees of the thresholds that can still win a d2 metric: the workers get the
                 # GPU's exact D1 tallies as bounds (model_opt.host_threshold_stats_pruned); PCC_D2_NO_PRUNE=1: every threshold (A/B)
-                prune = on_gpu and want_d2 and not gpu_d2 and not os.environ.get('PCC_D2_NO_PRUNE')
+                prune = on_gpu and want_d2 and not gpu_d2 and ties == 'pick' and not os.environ.get('PCC_D2_NO_PRUNE')
                 if prune:
                     item['d1'] = d1_tallies_gpu(ctx, chunk, x_hat, self.thresholds)
                 if (want_d2 and not gpu_d2) or not on_gpu:
@@ -544,16 +547,16 @@ class CompressionModel:
                         jobs = [('tally_pruned', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, with_normals, item['d1'][j], resolution,
                                  list(opt_metrics), list(max_deltas)) for j in range(len(chunk))]
                     elif on_gpu:
-                        jobs = [('tally', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, with_normals) for j in range(len(chunk))]
+                        jobs = [('tally', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, with_normals, ties) for j in range(len(chunk))]
                     else:
                         jobs = [('decide', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, resolution, with_normals,
-                                 list(opt_metrics), list(max_deltas)) for j in range(len(chunk))]
+                                 list(opt_metrics), list(max_deltas), ties) for j in range(len(chunk))]
                     self.host_search_jobs = getattr(self, 'host_search_jobs', 0) + len(jobs)
                     self.last_host_job_kind = jobs[0][0] if jobs else None
                     pool = self._search_pool(len(blocks))
                     item['futures'] = [pool.submit(job) for job in jobs]
                 if on_gpu and item['d1'] is None:
-                    item['d1'] = (d12_tallies_gpu if gpu_d2 else d1_tallies_gpu)(ctx, chunk, x_hat, self.thresholds)
+                    item['d1'] = d12_tallies_gpu(ctx, chunk, x_hat, self.thresholds, ties=ties) if gpu_d2 else d1_tallies_gpu(ctx, chunk, x_hat, self.thresholds)
                 pending.append(item)
                 if len(pending) > SEARCH_LAG:
                     finalize_search(pending.pop(0))

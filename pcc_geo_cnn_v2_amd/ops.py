@@ -687,6 +687,80 @@ def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, cl
     return s_ab.cpu().numpy(), s_ba, n_b, tcount.cpu().numpy(), d2_ab.cpu().numpy(), d2_ba.cpu().numpy()
 
 
+class SearchTiePairOverflow(L.PccError):
+    """d12_threshold_stats_ties met more equidistant pairs in one chunk of thresholds than the stated capacity; `.pairs` suffices."""
+
+    def __init__(self, pairs, max_pairs):
+        super().__init__(f'd12_threshold_stats_ties: a chunk of thresholds needs {pairs} tie pairs, the workspace holds {max_pairs}; '
+                         f'pass max_pairs >= {pairs}')
+        self.pairs, self.max_pairs = int(pairs), int(max_pairs)
+
+
+def search_tie_pair_capacity(B, D, H, W, npts):
+    """Default pair capacity of d12_threshold_stats_ties (workspace rule): room for four equidistant voxels per row
+    and threshold on average over one chunk of thresholds, 4 npts chunk + 1024, capped at the engine's limit of 2^31 - 1 pairs."""
+    return min(4 * int(npts) * int(L.lib().pcc_d12_search_ties_chunk(B, D, H, W)) + 1024, (1 << 31) - 1)
+
+
+def d12_threshold_stats_ties_launch(ctx, x_hat, thr, pts, block_of, block_start, normals64, clip=True, max_pairs=None):
+    """d12_threshold_stats_ties without the host copies: the device tensors (s_ab, hsum, hcnt, tcount, d2_ab, d2_ba, status)."""
+    assert x_hat.dtype == torch.float32 and x_hat.is_contiguous() and x_hat.dim() == 4
+    assert pts.dtype == torch.int32 and pts.is_contiguous() and block_of.dtype == torch.int32 and block_of.is_contiguous()
+    assert pts.dim() == 2 and pts.shape[1] == 3 and pts.shape[0] > 0 and block_of.numel() == pts.shape[0]
+    assert normals64.dtype == torch.float64 and normals64.is_contiguous() and normals64.shape == pts.shape, \
+        'd12_threshold_stats_ties: normals must be (n,3) float64'
+    assert block_start.dtype == torch.int32 and block_start.is_contiguous() and thr.dtype == torch.float32 and thr.is_contiguous()
+    B, D, H, W = x_hat.shape
+    assert block_start.numel() == B + 1
+    lo, hi = pts.min(0).values.cpu(), pts.max(0).values.cpu()
+    assert int(lo.min()) >= 0 and bool((hi < torch.tensor([D, H, W])).all()), f'block-local coordinates outside the {(D, H, W)} grid'
+    n = pts.shape[0]
+    max_pairs = search_tie_pair_capacity(B, D, H, W, n) if max_pairs is None else int(max_pairs)
+    if not 1 <= max_pairs <= (1 << 31) - 1:
+        raise L.PccError(f'd12_threshold_stats_ties: max_pairs = {max_pairs} outside [1, 2^31)')
+    dev = x_hat.device
+    ws = torch.empty((L.lib().pcc_d1_search_workspace_bytes(B, D, H, W),), dtype=torch.uint8, device=dev)
+    ws2 = torch.empty((L.lib().pcc_d12_search_ties_workspace_bytes(B, D, H, W, n, max_pairs),), dtype=torch.uint8, device=dev)
+    s_ab = torch.empty((B, 256), dtype=torch.int64, device=dev)
+    hsum, hcnt = torch.empty_like(s_ab), torch.empty_like(s_ab)
+    d2_ab = torch.empty((B, 256), dtype=torch.float64, device=dev)
+    d2_ba = torch.empty_like(d2_ab)
+    tcount = torch.empty((B,), dtype=torch.int32, device=dev)
+    status = torch.empty((2,), dtype=torch.int64, device=dev)
+    L.check(L.lib().pcc_d12_threshold_stats_ties(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip), _ptr(pts), _ptr(block_of),
+                                                 _ptr(block_start), n, _ptr(normals64), max_pairs, _ptr(status), _ptr(ws), _ptr(ws2), _ptr(s_ab),
+                                                 _ptr(hsum), _ptr(hcnt), _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba), ctx.stream),
+            'pcc_d12_threshold_stats_ties')
+    return s_ab, hsum, hcnt, tcount, d2_ab, d2_ba, status
+
+
+def d12_threshold_stats_ties(ctx, x_hat, thr, pts, block_of, block_start, normals64, clip=True, max_pairs=None, return_status=False):
+    """d12_threshold_stats under the tie-averaged D2 definition (include/pcc_geo.h: pcc_d12_threshold_stats_ties): D2 of every
+    (block, threshold) averages over ALL equidistant nearest points, so it equals the host restatement
+    (model_opt.host_threshold_stats(ties='mean')) up to float64 rounding.  normals64 (n,3) float64 -- on the device like the rest.
+    The pair list of a chunk of thresholds holds max_pairs pairs (default search_tie_pair_capacity): with the default, a call that
+    needs more runs once more with the number the first run reported; an explicit max_pairs that is too small raises
+    SearchTiePairOverflow -- or, with return_status=True, returns what the engine wrote (D2 all NaN, D1 valid) with the status.
+    Returns (s_ab, s_ba, n_b, tcount, d2_ab, d2_ba) and, with return_status=True, (pairs needed, overflowed) appended."""
+    args = (ctx, x_hat, thr, pts, block_of, block_start, normals64, clip)
+    out = d12_threshold_stats_ties_launch(*args, max_pairs=max_pairs)
+    pairs, over = (int(v) for v in out[-1].cpu())
+    if over and not return_status:
+        if max_pairs is not None or pairs > (1 << 31) - 1:
+            B, D, H, W = x_hat.shape
+            raise SearchTiePairOverflow(pairs, search_tie_pair_capacity(B, D, H, W, pts.shape[0]) if max_pairs is None else max_pairs)
+        out = d12_threshold_stats_ties_launch(*args, max_pairs=pairs)
+        pairs, over = (int(v) for v in out[-1].cpu())
+        assert not over, 'd12_threshold_stats_ties: the reported pair capacity did not suffice'
+    s_ab, hsum, hcnt, tcount, d2_ab, d2_ba, _ = out
+    B = x_hat.shape[0]
+    hs, hc = hsum.cpu().numpy(), hcnt.cpu().numpy()
+    s_ba = np.concatenate([np.cumsum(hs[:, ::-1], 1)[:, ::-1][:, 1:], np.zeros((B, 1), np.int64)], 1)
+    n_b = np.concatenate([np.cumsum(hc[:, ::-1], 1)[:, ::-1][:, 1:], np.zeros((B, 1), np.int64)], 1)
+    res = (s_ab.cpu().numpy(), s_ba, n_b, tcount.cpu().numpy(), d2_ab.cpu().numpy(), d2_ba.cpu().numpy())
+    return res + ((pairs, bool(over)),) if return_status else res
+
+
 NORMALS_COORD_LIMIT = 1 << 21        # include/pcc_geo.h "point normals": coordinates are integers in [0, 2^21)
 
 

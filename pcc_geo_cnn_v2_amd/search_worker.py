@@ -26,17 +26,19 @@ def main():
         try:
             kind, args = (job[0], job[1:]) if isinstance(job[0], str) else ('decide', job)
             if kind == 'tally':
-                block, x_hat, thresholds, with_normals = args
-                out = ('ok',) + tuple(host_threshold_stats(block, x_hat, thresholds, normals_of(block, with_normals)))
+                block, x_hat, thresholds, with_normals = args[:4]
+                ties = args[4] if len(args) > 4 else 'pick'
+                out = ('ok',) + tuple(host_threshold_stats(block, x_hat, thresholds, normals_of(block, with_normals), ties))
             elif kind == 'tally_pruned':
                 block, x_hat, thresholds, with_normals, d1_gpu, resolution, opt_metrics, max_deltas = args
                 tallies, mean_tally, kept = host_threshold_stats_pruned(block, x_hat, thresholds, normals_of(block, with_normals), d1_gpu, resolution,
                                                                         opt_metrics, max_deltas)
                 out = ('ok', tallies, (mean_tally, kept))
             else:
-                block, x_hat, thresholds, resolution, with_normals, opt_metrics, max_deltas = args
+                block, x_hat, thresholds, resolution, with_normals, opt_metrics, max_deltas = args[:7]
                 names, best = compute_optimal_thresholds(block, x_hat, thresholds, resolution, normals=normals_of(block, with_normals),
-                                                         opt_metrics=opt_metrics, max_deltas=max_deltas, fixed_threshold=False)
+                                                         opt_metrics=opt_metrics, max_deltas=max_deltas, fixed_threshold=False,
+                                                         ties=args[7] if len(args) > 7 else 'pick')
                 out = ('ok', names, [int(b) for b in best])
         except BaseException as e:   # the parent re-raises
             out = ('err', f'{type(e).__name__}: {e}', None)
