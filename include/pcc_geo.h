@@ -532,6 +532,34 @@ int pcc_conv_repack_map(const pcc_conv_desc* d, int32_t* map);
 int pcc_conv_repack_weights_device(pcc_ctx* ctx, const pcc_conv_desc* d, const int32_t* map, const float* w, float* pk,
                                    void* stream);
 
+/* ---- training summaries (src/model_types.py:65-105) ------------------------------------------------
+ * pcc_tensor_histogram: the TensorFlow HistogramProto of a contiguous float32 device tensor in one pass.  Bucket limits are those of
+ * TensorFlow's histogram.cc: positive limits v = 1e-12, v *= 1.1 while v < 1e20 (774 values), then DBL_MAX; the table is
+ * [-reversed positives, 0.0, positives] (pcc_histogram_limits writes its PCC_HISTOGRAM_BUCKETS doubles, host).  A finite value v
+ * counts in bucket upper_bound(limits, (double)v); NaN and +-Inf count in `nonfinite` only.  min / max of an empty histogram are
+ * DBL_MAX / -DBL_MAX.  counts are integers; sum and sum_squares are double sums over pcc_tensor_histogram_slices(n) slices added in
+ * slice order: the same bytes on every call.  `out` (device, 8-byte aligned) receives one pcc_histogram; `workspace` (device) holds
+ * pcc_tensor_histogram_workspace_bytes() bytes.                                                                              */
+#define PCC_HISTOGRAM_BUCKETS 1551
+typedef struct {
+    uint64_t counts[PCC_HISTOGRAM_BUCKETS]; /* offset 0     */
+    uint64_t num;                           /* offset 12408: finite values */
+    uint64_t nonfinite;                     /* offset 12416 */
+    double min, max, sum, sum_squares;      /* offsets 12424, 12432, 12440, 12448; sizeof = 12456 */
+} pcc_histogram;
+int pcc_histogram_limits(double* limits);
+size_t pcc_tensor_histogram_workspace_bytes(void);
+int pcc_tensor_histogram_slices(size_t n);
+int pcc_tensor_histogram(pcc_ctx* ctx, const float* x, size_t n, pcc_histogram* out, void* workspace, void* stream);
+/* pcc_occupancy_scores: the confusion matrix of q(x_tilde) against q(x), q(v) = rint(clip(v, 0, 1)) rounding half to even (0.5 -> 0;
+ * NaN -> 0), as src/model_types.py:90-94 counts it; num_occupied = #(q(x) == 1) = tp + fn.  x_tilde_quant (device, n floats, may be
+ * NULL) receives q(x_tilde).  `out`: one pcc_occupancy on the device.                                                         */
+typedef struct {
+    uint64_t tp, tn, fp, fn, num_occupied;  /* offsets 0, 8, 16, 24, 32; sizeof = 40 */
+} pcc_occupancy;
+int pcc_occupancy_scores(pcc_ctx* ctx, const float* x, const float* x_tilde, size_t n, float* x_tilde_quant, pcc_occupancy* out,
+                         void* stream);
+
 /* ---- range coder (HOST) ----------------------------------------------------------------
  * Replaces tfc's C++ ops range_coding_ops.unbounded_index_range_encode/decode
  * (src/utils/patch_gaussian_conditional.py:27-31; src/model_types.py:291-292,382-387,404-407),

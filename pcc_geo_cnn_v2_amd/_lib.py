@@ -35,6 +35,7 @@ EXPORTS = [
     'pcc_mesh_sample_workspace_bytes', 'pcc_mesh_to_points', 'pcc_render_workspace_bytes', 'pcc_render_points',
     'pcc_conv_wgrad_workspace_bytes', 'pcc_conv_wgrad_slices', 'pcc_conv3d_wgrad', 'pcc_relu_backward', 'pcc_focal_loss_grad', 'pcc_conv_repack_map',
     'pcc_conv_repack_weights_device',
+    'pcc_histogram_limits', 'pcc_tensor_histogram_workspace_bytes', 'pcc_tensor_histogram_slices', 'pcc_tensor_histogram', 'pcc_occupancy_scores',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -67,6 +68,18 @@ class CodecDesc(C.Structure):
 class SymbolSink(C.Structure):
     _fields_ = [('zsym', C.c_void_p), ('ysym', C.c_void_p), ('idx', C.c_void_p), ('zsym_tile_max', C.c_void_p),
                 ('ysym_tile_max', C.c_void_p), ('sym_bytes', C.c_int32), ('idx_bytes', C.c_int32), ('channels_first', C.c_int32)]
+
+
+HISTOGRAM_BUCKETS = 1551
+
+
+class Histogram(C.Structure):            # pcc_histogram
+    _fields_ = [('counts', C.c_uint64 * HISTOGRAM_BUCKETS), ('num', C.c_uint64), ('nonfinite', C.c_uint64), ('min', C.c_double),
+                ('max', C.c_double), ('sum', C.c_double), ('sum_squares', C.c_double)]
+
+
+class Occupancy(C.Structure):            # pcc_occupancy
+    _fields_ = [(n, C.c_uint64) for n in ('tp', 'tn', 'fp', 'fn', 'num_occupied')]
 
 
 class PccError(RuntimeError):
@@ -160,6 +173,11 @@ def lib():
     L.pcc_focal_loss_grad.argtypes = [vp, vp, vp, sz, C.c_float, C.c_float, vp, vp, vp]
     L.pcc_conv_repack_map.argtypes = [C.POINTER(ConvDesc), vp]
     L.pcc_conv_repack_weights_device.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp]
+    L.pcc_histogram_limits.argtypes = [vp]
+    L.pcc_tensor_histogram_workspace_bytes.restype = sz
+    L.pcc_tensor_histogram_slices.argtypes = [sz]
+    L.pcc_tensor_histogram.argtypes = [vp, vp, sz, vp, vp, vp]
+    L.pcc_occupancy_scores.argtypes = [vp, vp, vp, sz, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

@@ -24,6 +24,8 @@ struct pcc_ctx {
     // its own in the workspace): grown on demand, one tensor per context like `scratch`
     unsigned* amax = nullptr;
     int amax_cap = 0;
+    // the positive histogram bucket limits on the device (summary.hip), uploaded at the first pcc_tensor_histogram
+    void* summary_limits = nullptr;
 };
 int pcc_ctx_amax(pcc_ctx* ctx, int n, unsigned** ptr);
 // Side channel of the fp16-split kernels (conv_wino_f16s.hip): in_amax[n] = fp32 bits of max |in| over block n as recorded by the

@@ -104,6 +104,7 @@ PCC_API int pcc_ctx_destroy(pcc_ctx* ctx) {
     if (ctx) pcc_profile_free(ctx);
     if (ctx && ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx && ctx->amax) (void)hipFree(ctx->amax);
+    if (ctx && ctx->summary_limits) (void)hipFree(ctx->summary_limits);
     delete ctx;
     return PCC_OK;
 }

@@ -639,6 +639,77 @@ def conv3d_wgrad(ctx, d, x, dout, dw, db=None, workspace=None):
     return dw, db
 
 
+def histogram_limits():
+    """The 1551 bucket limits as the library computes them (pcc_histogram_limits), float64."""
+    lim = np.empty(L.HISTOGRAM_BUCKETS, np.float64)
+    n = L.check(L.lib().pcc_histogram_limits(lim.ctypes.data_as(C.c_void_p)), 'pcc_histogram_limits')
+    assert n == L.HISTOGRAM_BUCKETS
+    return lim
+
+
+def _f32_flat(t, what):
+    assert t.dtype == torch.float32 and t.is_cuda, f'{what}: float32 device tensor expected'
+    return t.detach().contiguous().reshape(-1)
+
+
+def histogram_unpack(raw):
+    """One pcc_histogram (its bytes as a uint8 array) -> dict(counts uint64[1551], num, nonfinite, min, max, sum, sum_squares)."""
+    raw = np.ascontiguousarray(raw, np.uint8)
+    assert raw.size == C.sizeof(L.Histogram)
+    counts = raw[:8 * L.HISTOGRAM_BUCKETS].view(np.uint64).copy()
+    num, nonfinite = (int(v) for v in raw[8 * L.HISTOGRAM_BUCKETS:8 * L.HISTOGRAM_BUCKETS + 16].view(np.uint64))
+    mn, mx, sm, sq = (float(v) for v in raw[8 * L.HISTOGRAM_BUCKETS + 16:].view(np.float64))
+    return dict(counts=counts, num=num, nonfinite=nonfinite, min=mn, max=mx, sum=sm, sum_squares=sq)
+
+
+def tensor_histograms_launch(ctx, tensors):
+    """pcc_tensor_histogram of every tensor on the context's stream -> (len(tensors), sizeof(pcc_histogram)) uint8 on the device (the
+    calls share one workspace: they are ordered on one stream)."""
+    size = C.sizeof(L.Histogram)
+    out = torch.empty((len(tensors), size), dtype=torch.uint8, device=ctx.device)
+    ws = torch.empty((int(L.lib().pcc_tensor_histogram_workspace_bytes()),), dtype=torch.uint8, device=ctx.device)
+    keep = []
+    for i, t in enumerate(tensors):
+        flat = _f32_flat(t, 'tensor_histogram')
+        keep.append(flat)
+        L.check(L.lib().pcc_tensor_histogram(ctx.handle, _ptr(flat) if flat.numel() else None, flat.numel(),
+                                             C.c_void_p(out.data_ptr() + i * size), _ptr(ws), ctx.stream), 'pcc_tensor_histogram')
+    return out, keep
+
+
+def tensor_histograms(ctx, tensors):
+    """The histograms of several tensors after ONE device-to-host copy of their results."""
+    out, _keep = tensor_histograms_launch(ctx, tensors)
+    raw = out.cpu().numpy()
+    return [histogram_unpack(r) for r in raw]
+
+
+def tensor_histogram(ctx, t):
+    """TensorFlow-bucketed histogram of a float32 device tensor (pcc_tensor_histogram): dict(counts uint64[1551], num, nonfinite,
+    min, max, sum, sum_squares) on the host."""
+    return tensor_histograms(ctx, [t])[0]
+
+
+def occupancy_scores_launch(ctx, x, x_tilde, want_quant=False):
+    """pcc_occupancy_scores on the context's stream -> (5 int64 on the device: tp, tn, fp, fn, num_occupied; quantised x_tilde or None)."""
+    a, b = _f32_flat(x, 'occupancy_scores'), _f32_flat(x_tilde, 'occupancy_scores')
+    assert a.numel() == b.numel(), 'occupancy_scores: x and x_tilde differ in size'
+    out = torch.empty((C.sizeof(L.Occupancy) // 8,), dtype=torch.int64, device=ctx.device)
+    quant = torch.empty_like(b) if want_quant else None
+    L.check(L.lib().pcc_occupancy_scores(ctx.handle, _ptr(a) if a.numel() else None, _ptr(b) if b.numel() else None, a.numel(),
+                                         _ptr(quant), _ptr(out), ctx.stream), 'pcc_occupancy_scores')
+    return out, (None if quant is None else quant.reshape(x_tilde.shape))
+
+
+def occupancy_scores(ctx, x, x_tilde, want_quant=False):
+    """Confusion matrix of rint(clip(x_tilde, 0, 1)) against rint(clip(x, 0, 1)) (pcc_occupancy_scores): dict(tp, tn, fp, fn,
+    num_occupied) of Python ints after one device-to-host copy; with want_quant also the quantised x_tilde (float32 device tensor of
+    x_tilde's shape)."""
+    out, quant = occupancy_scores_launch(ctx, x, x_tilde, want_quant)
+    res = dict(zip(('tp', 'tn', 'fp', 'fn', 'num_occupied'), (int(v) for v in out.cpu().numpy().view(np.uint64))))
+    return (res, quant) if want_quant else res
+
+
 def d1_threshold_stats(ctx, x_hat, thr, pts, block_of, clip=True):
     """Exact D1 sums for every threshold of every block (see include/pcc_geo.h).  x_hat (B,D,H,W) float32,
     thr (T<=256,) float32, pts (n,3) int32 grouped by block, block_of (n,) int32 -- all on the device.

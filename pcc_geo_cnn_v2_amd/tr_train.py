@@ -2,10 +2,11 @@
 
   python -m pcc_geo_cnn_v2_amd.tr_train 'blocks/**/*.ply' checkpoint_dir --model_config c3p [--resolution 64 --batch_size 32
       --lmbda 1e-4 --alpha 0.9 --gamma 2.0 --max_steps 100000 --warm_start DIR --seed 42 --validation_interval 500
-      --validation_steps 10]
+      --validation_steps 10 --summary_interval 0]
 
 Blocks under a directory named `train` train, blocks under `test` validate (src/tr_train.py:26-32).  The checkpoint directory
-receives model.npz (what compress_octree / decompress_octree load), train_state.pt (resumed when present), log.jsonl and `done`.
+receives model.npz (what compress_octree / decompress_octree load), train_state.pt (resumed when present), log.jsonl and `done`;
+with --summary_interval N > 0 also TensorBoard event files under train/ and val/ (src/tr_train.py:45-47; tr_plots draws them).
 """
 import argparse
 import glob
@@ -29,6 +30,9 @@ def build_parser():
     ap.add_argument('--seed', type=int, default=42, help='Seed of the weights, the data order and the noise.')
     ap.add_argument('--validation_interval', type=int, default=500, help='Steps between validations.')
     ap.add_argument('--validation_steps', type=int, default=10, help='Batches per validation.')
+    ap.add_argument('--summary_interval', type=int, default=0,
+                    help='Write a TensorBoard summary (scalars and histograms) of every N-th training step to checkpoint_dir/train '
+                         'and of every validation batch to checkpoint_dir/val; 0: none.  The reference uses 100.')
     ap.add_argument('--data_format', default='channels_first', help='Accepted and ignored: the layout is NDHWC internally.')
     return ap
 
@@ -47,7 +51,7 @@ def main(argv=None):
     trainer = model.train(None, a.gamma, a.alpha, a.lmbda, checkpoint_dir=a.checkpoint_dir, train_blocks=load(train_files),
                           val_blocks=load(val_files), resolution=a.resolution, batch_size=a.batch_size, max_steps=a.max_steps,
                           seed=a.seed, validation_interval=a.validation_interval, validation_steps=a.validation_steps,
-                          warm_start=a.warm_start)
+                          warm_start=a.warm_start, summary_interval=a.summary_interval)
     trainer.run()
     return 0
 

@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from . import model_transforms as MT
 from . import ops
+from .utils import tf_summary
 
 # The split (bf16 x 3), two-piece fp16 and Winograd kernels read packed images that are not reorders of the taps: off for training,
 # so every conv runs an exact-fp32 family (conv_fwd, conv_tr2, conv_tr2m, conv_cin1, conv_cout1_mfma, conv_cout1) or the generic one.
@@ -266,24 +267,38 @@ class TrainGraph:
         y = (N, D // 8, H // 8, W // 8, F)
         return (y, (N, D // 16, H // 16, W // 16, F)) if self.v2 else (y,)
 
-    def loss(self, x, noise, lmbda, gamma=2.0, alpha=0.9):
+    def loss(self, x, noise, lmbda, gamma=2.0, alpha=0.9, tensors=False):
         """x (N, D, H, W) {0,1} float32 on the device; noise: tensors of latent_shapes(x.shape).  Returns dict of 0-d tensors:
-        loss = lmbda * fl + mbpov (src/model_types.py:266-268 / :355-358), fl, mbpov."""
+        loss = lmbda * fl + mbpov (src/model_types.py:266-268 / :355-358), fl, mbpov.  tensors=True adds what summarize() reads:
+        mbpov_y (V2: mbpov_z too; V1 reports mbpov as both mbpov/y and mbpov/total, src/model_types.py:270), num_occupied_voxels and
+        `tensors`, the detached tensors of the reference's histogram summaries by tag."""
         m, pctx = self.model, self.pctx
         y = _run(pctx, m.analysis_transform, x.unsqueeze(-1), self.convs)
-        denominator = -math.log(2) * torch.sum(x)
+        num_occupied = torch.sum(x)
+        denominator = -math.log(2) * num_occupied
         if self.v2:
             z = _run(pctx, m.hyper_analysis_transform, y, self.convs)
             z_tilde, z_lik = self.eb(z, noise[1])
             sigma = _run(pctx, m.hyper_synthesis_transform, z_tilde, self.convs)
             y_tilde, y_lik = gaussian_likelihood(y, sigma, noise[0], self.scale_bound)
-            mbpov = torch.sum(torch.log(y_lik)) / denominator + torch.sum(torch.log(z_lik)) / denominator
+            log_y, log_z = torch.log(y_lik), torch.log(z_lik)
+            mbpov_y, mbpov_z = torch.sum(log_y) / denominator, torch.sum(log_z) / denominator
+            mbpov = mbpov_y + mbpov_z
         else:
             y_tilde, y_lik = self.eb(y, noise[0])
-            mbpov = torch.sum(torch.log(y_lik)) / denominator
+            log_y = torch.log(y_lik)
+            mbpov = mbpov_y = torch.sum(log_y) / denominator
         x_tilde = _run(pctx, m.synthesis_transform, y_tilde, self.convs)
         fl = focal_loss(pctx, x, x_tilde[..., 0], gamma, alpha)
-        return dict(loss=lmbda * fl + mbpov, fl=fl, mbpov=mbpov)
+        out = dict(loss=lmbda * fl + mbpov, fl=fl, mbpov=mbpov)
+        if tensors:
+            t = dict(y=y, y_tilde=y_tilde, x=x, x_tilde=x_tilde, y_likelihoods=y_lik, log_y_likelihoods=log_y)
+            out.update(mbpov_y=mbpov_y.detach(), num_occupied_voxels=num_occupied.detach())
+            if self.v2:
+                t.update(z=z, z_tilde=z_tilde, sigma_tilde=sigma, z_likelihoods=z_lik, log_z_likelihoods=log_z)
+                out['mbpov_z'] = mbpov_z.detach()
+            out['tensors'] = {k: v.detach() for k, v in t.items()}
+        return out
 
     def export_weights(self):
         """The checkpoint dictionary compress_octree / decompress_octree load (same keys as init_checkpoint): conv weights, the
@@ -297,6 +312,63 @@ class TrainGraph:
             w[f'entropy_bottleneck/{k}'] = v
         self.model.set_weights(w)
         return self.model.get_weights()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# summaries (src/model_types.py:65-105)
+# ---------------------------------------------------------------------------------------------------------------------------------
+V1_HISTOGRAMS = ('y', 'y_tilde', 'x', 'x_tilde', 'x_tilde_quant', 'y_likelihoods', 'log_y_likelihoods')
+V2_HISTOGRAMS = ('z', 'z_tilde', 'sigma_tilde', 'z_likelihoods', 'log_z_likelihoods')
+BC_TAGS = ('bc/precision', 'bc/recall', 'bc/accuracy', 'bc/specificity', 'bc/f1_score')
+
+
+def binary_histogram(zeros, ones):
+    """The histogram of a tensor that holds `zeros` 0.0 and `ones` 1.0 and nothing else (x_tilde_quant, from the confusion matrix:
+    no pass over the tensor)."""
+    limits = tf_summary.default_bucket_limits()
+    counts = np.zeros(tf_summary.NUM_BUCKETS, np.uint64)
+    b0, b1 = np.searchsorted(limits, [0.0, 1.0], side='right')
+    counts[b0], counts[b1] = zeros, ones
+    n = zeros + ones
+    return dict(counts=counts, num=n, nonfinite=0, min=(0.0 if zeros else 1.0) if n else tf_summary.DBL_MAX,
+                max=(1.0 if ones else 0.0) if n else -tf_summary.DBL_MAX, sum=float(ones), sum_squares=float(ones))
+
+
+def binary_classification(tp, tn, fp, fn):
+    """src/model_types.py:95-99 in float32; 0 / 0 is NaN, as TensorFlow's division gives."""
+    tp, tn, fp, fn = (np.float32(v) for v in (tp, tn, fp, fn))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        precision = tp / (tp + fp)
+        recall = tp / (tp + fn)
+        accuracy = (tp + tn) / (tp + tn + fp + fn)
+        specificity = tn / (tn + fp)
+        f1 = (np.float32(2) * precision * recall) / (precision + recall)
+    return dict(zip(BC_TAGS, (float(v) for v in (precision, recall, accuracy, specificity, f1))))
+
+
+def summarize(pctx, out):
+    """{tag: float | histogram} of a TrainGraph.loss(..., tensors=True) result, tags and order of the reference's merged summary
+    (v1_summaries, v2_summaries, binary_classification_summaries).  Histograms by pcc_tensor_histogram (one device-to-host copy for
+    all of them), the scores from pcc_occupancy_scores; x_tilde_quant's histogram follows from the confusion matrix, its values
+    being 0 and 1 only.  A tensor that holds NaN or Inf raises ValueError naming its tag (tf.summary.histogram fails there too)."""
+    t = out['tensors']
+    v2 = 'z' in t
+    names = [k for k in V1_HISTOGRAMS + (V2_HISTOGRAMS if v2 else ()) if k != 'x_tilde_quant']
+    hists = dict(zip(names, ops.tensor_histograms(pctx, [t[k] for k in names])))
+    occ = ops.occupancy_scores(pctx, t['x'], t['x_tilde'])
+    for k in names:
+        if hists[k]['nonfinite']:
+            raise ValueError(f"summary histogram '{k}': {hists[k]['nonfinite']} values are NaN or Inf")
+    hists['x_tilde_quant'] = binary_histogram(occ['tn'] + occ['fn'], occ['tp'] + occ['fp'])
+    num = lambda k: float(out[k].detach())
+    s = {'loss': num('loss'), 'mbpov/y': num('mbpov_y'), 'mbpov/total': num('mbpov'), 'fl': num('fl'),
+         'num_occupied_voxels': num('num_occupied_voxels')}
+    s.update({k: hists[k] for k in V1_HISTOGRAMS})
+    if v2:
+        s.update({'z': hists['z'], 'z_tilde': hists['z_tilde'], 'mbpov/z': num('mbpov_z')})
+        s.update({k: hists[k] for k in V2_HISTOGRAMS[2:]})
+    s.update(binary_classification(occ['tp'], occ['tn'], occ['fp'], occ['fn']))
+    return s
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -364,11 +436,16 @@ class Trainer:
 
     train_state.pt (step, weights, both optimizers, noise generator, data order, best loss) is written atomically at every
     validation and at the end, so an interrupted run resumes from its last validation and replays the same steps.  A directory
-    that holds a model.npz but no train_state.pt is refused: training there from scratch would overwrite that model."""
+    that holds a model.npz but no train_state.pt is refused: training there from scratch would overwrite that model.
+
+    summary_interval N > 0 (the reference's value is 100; 0: off) writes TensorBoard event files where the reference does: the
+    summary of every training step whose counter before the step is a multiple of N to <dir>/train/ under step + 1
+    (src/tr_train.py:128,139-141), and one per validation batch i to <dir>/val/ under step + i (:104).  Every Trainer opens new
+    event files.  Summaries draw no random numbers and touch no weights: model.npz and log.jsonl do not depend on N."""
 
     def __init__(self, model, checkpoint_dir, train_blocks, val_blocks, resolution=64, batch_size=32, lmbda=1e-4, alpha=0.9,
                  gamma=2.0, max_steps=100000, seed=42, validation_interval=500, validation_steps=10, warm_start=None,
-                 device=None, log=print):
+                 device=None, log=print, summary_interval=0):
         self.model, self.dir = model, checkpoint_dir
         assert not (os.path.exists(os.path.join(checkpoint_dir, 'model.npz')) and not os.path.exists(self._state_path())), \
             f'{checkpoint_dir} holds a model.npz but no train_state.pt: not a training directory to resume (to start from that ' \
@@ -377,6 +454,8 @@ class Trainer:
         self.max_steps, self.seed = int(max_steps), int(seed)
         self.val_interval, self.val_steps = int(validation_interval), int(validation_steps)
         self.log = log
+        self.summary_interval = int(summary_interval)
+        assert self.summary_interval >= 0, 'summary_interval must be >= 0'
         self.pctx = training_context(device)
         R = int(resolution)
         if getattr(model, 'analysis_transform', None) is None:
@@ -392,13 +471,17 @@ class Trainer:
         self.gen.manual_seed(seed)
         self.step, self.best, self.best_step, self.last_val = 0, float('inf'), 0, None
         os.makedirs(checkpoint_dir, exist_ok=True)
+        self.train_writer = self.val_writer = None
+        if self.summary_interval:
+            self.train_writer = tf_summary.EventFileWriter(os.path.join(checkpoint_dir, 'train'))
+            self.val_writer = tf_summary.EventFileWriter(os.path.join(checkpoint_dir, 'val'))
         self._resume()
 
     def noise(self, x_shape, gen):
         return [torch.rand(s, generator=gen, device=self.pctx.device) - .5 for s in self.graph.latent_shapes(tuple(x_shape))]
 
-    def train_step(self, x):
-        out = self.graph.loss(x, self.noise(x.shape, self.gen), self.lmbda, self.gamma, self.alpha)
+    def train_step(self, x, tensors=False):
+        out = self.graph.loss(x, self.noise(x.shape, self.gen), self.lmbda, self.gamma, self.alpha, tensors=tensors)
         aux = self.graph.eb.aux_loss()
         self.main_opt.zero_grad(set_to_none=True)
         self.aux_opt.zero_grad(set_to_none=True)
@@ -416,9 +499,13 @@ class Trainer:
         gen.manual_seed(self.seed + 2)
         tot = 0.
         with torch.no_grad():
-            for _ in range(self.val_steps):
+            for i in range(self.val_steps):
                 x = data.next(self.pctx)
-                tot += float(self.graph.loss(x, self.noise(x.shape, gen), self.lmbda, self.gamma, self.alpha)['loss'])
+                out = self.graph.loss(x, self.noise(x.shape, gen), self.lmbda, self.gamma, self.alpha,
+                                      tensors=self.val_writer is not None)
+                tot += float(out['loss'])
+                if self.val_writer is not None:
+                    self.val_writer.add_summary(summarize(self.pctx, out), self.step + i)
         return tot / self.val_steps
 
     # ---- checkpoint directory
@@ -488,8 +575,11 @@ class Trainer:
             if self.step >= self.max_steps:
                 break
             x = self.train_data.next(self.pctx)
-            out = self.train_step(x)
+            get_summary = self.train_writer is not None and self.step % self.summary_interval == 0
+            out = self.train_step(x, tensors=True) if get_summary else self.train_step(x)
             self.step += 1
+            if get_summary:
+                self.train_writer.add_summary(summarize(self.pctx, out), self.step)
             self._log(dict(step=self.step, fl=float(out['fl']), mbpov=float(out['mbpov']), loss=float(out['loss']),
                            aux=float(out['aux'])))
         self._save_state()
