@@ -607,6 +607,51 @@ int pcc_pmf_to_quantized_cdf(const float* pmf, int32_t n, int32_t precision, int
 int64_t pcc_octree_bucket(const double* points, int64_t n, int32_t ncols, int32_t block_size, int32_t level,
                                      int64_t* order, int64_t* bucket_count);
 
+/* ---- octree anchor (new: a conventional geometry codec that runs on any cloud; NOT G-PCC, not a TMC13 stream) ----
+ * Quantise-and-prune octree coding with neighbour-dependent contexts (pcc_geo_cnn_v2_amd/anchor_octree.py holds the stream header
+ * and a numpy path that gives the same bytes).  Definition:
+ *   - scale num / den, 0 < num <= den < 2^31; q = (2 p num + den) / (2 den) per coordinate of the integer points (the cell index's
+ *     contract: [0, 2^21)), integer division; duplicates merged; depth D = bit_length(max q), at least 1 (the caller computes it:
+ *     quantisation is monotone, so max q comes from max p); decoded p = min((2 q den + num) / (2 num), resolution - 1);
+ *   - nodes of level l = the distinct key >> 3 (D - l) of the Morton keys (x << 2 | y << 1 | z per bit triple) of the quantised points,
+ *     ascending; occupancy byte: bit c set for child c = 4 dx + 2 dy + dz; n6: bit 0 / 1 = the -x / +x face neighbour of the node is
+ *     occupied at its own level, 2 / 3 = -y / +y, 4 / 5 = -z / +z, a neighbour outside [0, 2^l) counting as empty;
+ *   - the bytes are coded breadth first by an adaptive binary range coder (LZMA's: 11-bit probabilities from 1024, shift 5, 32-bit
+ *     range normalised below 2^24, carries through the cache byte, five flush bytes), child 0 first, decision c with model
+ *     256 t + m: m = 1, then 2 m + bit (the bits already coded in this byte), t = bit (c >> 2 & 1) of n6 | bit (2 + (c >> 1 & 1))
+ *     << 1 | bit (4 + (c & 1)) << 2 (the neighbours across the outer faces of child c's octant).  A byte is never 0: after seven
+ *     zeros the eighth decision is not coded.  PCC_ANCHOR_NO_CONTEXT codes with t = 0 (measurement only: such a payload needs the
+ *     same flag to decode).
+ * Host coder: the *_code_bits / *_decode_bits pair codes raw decisions (model[i] < 2048, bit[i]); pcc_anchor_encode codes n nodes (all
+ * levels, in order) into out[cap] and sets *out_len (PCC_ERR_SPACE when it does not fit: 2 n + 16 bytes always do);
+ * the decoder keeps its state in pcc_anchor_decoder_bytes caller-owned bytes, reads `data` (which must outlive it) level by level
+ * given each level's n6, and returns PCC_ERR_CORRUPT when the payload ends early; a payload is read to its last byte exactly.
+ * Device side (one stream, no host synchronisation): pcc_anchor_tree writes, for level l < D, its nodes' occ and n6 bytes at
+ * offset pcc_anchor_tree_level_offset(npts, l) = sum over j < l of min(npts, 8^j) of `occ` and `n6` (device, capacity
+ * pcc_anchor_tree_capacity(npts, D) bytes each), and hdr (device, int64[PCC_ANCHOR_HDR_WORDS]): hdr[l] = nodes of level l, hdr[D]
+ * = distinct quantised points.  pcc_anchor_expand writes the ascending child keys of one decoded level (nchildren = the sum of the
+ * popcounts of occ, which the caller knows) and, when n6 is non-NULL, their n6 at child_level.  pcc_anchor_points turns leaf keys
+ * into decoded points (n,3) int32.  Every index is checked against its count: wrong counts give wrong bytes, never an access
+ * outside the buffers.  The *_bytes / capacity functions return 0 (level_offset: -1) outside the contract.                     */
+#define PCC_ANCHOR_NO_CONTEXT 1
+#define PCC_ANCHOR_HDR_WORDS 32
+int pcc_anchor_code_bits(const uint16_t* model, const uint8_t* bit, int64_t n, uint8_t* out, int64_t cap, int64_t* out_len);
+int pcc_anchor_decode_bits(const uint8_t* data, int64_t len, const uint16_t* model, int64_t n, uint8_t* bit);
+int pcc_anchor_encode(const uint8_t* occ, const uint8_t* n6, int64_t n, int32_t flags, uint8_t* out, int64_t cap, int64_t* out_len);
+size_t pcc_anchor_decoder_bytes(void);
+int pcc_anchor_decoder_init(void* state, const uint8_t* data, int64_t len, int32_t flags);
+int pcc_anchor_decode_level(void* state, const uint8_t* n6, int64_t n, uint8_t* occ);
+int64_t pcc_anchor_decoder_consumed(const void* state);
+int64_t pcc_anchor_tree_capacity(int64_t npts, int32_t depth);
+int64_t pcc_anchor_tree_level_offset(int64_t npts, int32_t level);
+size_t pcc_anchor_tree_workspace_bytes(int64_t npts);
+int pcc_anchor_tree(pcc_ctx* ctx, const int32_t* pts, int64_t npts, int64_t num, int64_t den, int32_t depth, int64_t* hdr, uint8_t* occ,
+                    uint8_t* n6, void* workspace, void* stream);
+size_t pcc_anchor_expand_workspace_bytes(int64_t nparents);
+int pcc_anchor_expand(pcc_ctx* ctx, const uint64_t* parents, const uint8_t* occ, int64_t nparents, int32_t child_level, uint64_t* children,
+                      int64_t nchildren, uint8_t* n6, void* workspace, void* stream);
+int pcc_anchor_points(pcc_ctx* ctx, const uint64_t* keys, int64_t n, int64_t num, int64_t den, int32_t resolution, int32_t* pts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ PCC_CONV_BIAS, PCC_CONV_RELU, PCC_CONV_ADD, PCC_CONV_CLIP01, PCC_CONV_F16 = 1, 2
 PCC_CONV_IN16, PCC_CONV_OUT16, PCC_CONV_RES16 = 32, 64, 128          # fp16 storage inside the fp16 mode
 PCC_IMPL_AUTO, PCC_IMPL_GENERIC, PCC_IMPL_MFMA, PCC_IMPL_WINOGRAD, PCC_IMPL_SPLIT = 0, 1, 2, 3, 4
 PCC_ROUND_FLOOR_HALF, PCC_ROUND_HALF_EVEN = 0, 1
+PCC_ANCHOR_NO_CONTEXT, PCC_ANCHOR_HDR_WORDS = 1, 32      # include/pcc_geo.h "octree anchor"
 
 EXPORTS = [
     'pcc_abi_version', 'pcc_last_error', 'pcc_ctx_create', 'pcc_ctx_destroy', 'pcc_ctx_num_cu', 'pcc_ctx_get_numerics', 'pcc_ctx_set_numerics',
@@ -36,6 +37,9 @@ EXPORTS = [
     'pcc_conv_wgrad_workspace_bytes', 'pcc_conv_wgrad_slices', 'pcc_conv3d_wgrad', 'pcc_relu_backward', 'pcc_focal_loss_grad', 'pcc_conv_repack_map',
     'pcc_conv_repack_weights_device',
     'pcc_histogram_limits', 'pcc_tensor_histogram_workspace_bytes', 'pcc_tensor_histogram_slices', 'pcc_tensor_histogram', 'pcc_occupancy_scores',
+    'pcc_anchor_code_bits', 'pcc_anchor_decode_bits', 'pcc_anchor_encode', 'pcc_anchor_decoder_bytes', 'pcc_anchor_decoder_init',
+    'pcc_anchor_decode_level', 'pcc_anchor_decoder_consumed', 'pcc_anchor_tree_capacity', 'pcc_anchor_tree_level_offset',
+    'pcc_anchor_tree_workspace_bytes', 'pcc_anchor_tree', 'pcc_anchor_expand_workspace_bytes', 'pcc_anchor_expand', 'pcc_anchor_points',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -178,6 +182,26 @@ def lib():
     L.pcc_tensor_histogram_slices.argtypes = [sz]
     L.pcc_tensor_histogram.argtypes = [vp, vp, sz, vp, vp, vp]
     L.pcc_occupancy_scores.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    i64 = C.c_int64
+    L.pcc_anchor_code_bits.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64)]
+    L.pcc_anchor_decode_bits.argtypes = [vp, i64, vp, i64, vp]
+    L.pcc_anchor_encode.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(i64)]
+    L.pcc_anchor_decoder_bytes.restype = sz
+    L.pcc_anchor_decoder_init.argtypes = [vp, vp, i64, i32]
+    L.pcc_anchor_decode_level.argtypes = [vp, vp, i64, vp]
+    L.pcc_anchor_decoder_consumed.argtypes = [vp]
+    L.pcc_anchor_decoder_consumed.restype = i64
+    L.pcc_anchor_tree_capacity.argtypes = [i64, i32]
+    L.pcc_anchor_tree_capacity.restype = i64
+    L.pcc_anchor_tree_level_offset.argtypes = [i64, i32]
+    L.pcc_anchor_tree_level_offset.restype = i64
+    L.pcc_anchor_tree_workspace_bytes.argtypes = [i64]
+    L.pcc_anchor_tree_workspace_bytes.restype = sz
+    L.pcc_anchor_tree.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp]
+    L.pcc_anchor_expand_workspace_bytes.argtypes = [i64]
+    L.pcc_anchor_expand_workspace_bytes.restype = sz
+    L.pcc_anchor_expand.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp]
+    L.pcc_anchor_points.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

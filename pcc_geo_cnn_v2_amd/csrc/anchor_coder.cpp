@@ -1,0 +1,211 @@
+// Adaptive binary range coder of the octree anchor codec (include/pcc_geo.h "octree anchor"), host only.
+//
+// The coder is the LZMA one: 11-bit probabilities of a zero starting at 1024 and moving by 1/32 of the distance per decision, a
+// 32-bit range kept at or above 2^24 by shifting bytes out, a 33-bit `low` whose carry travels through the cache byte and the run of
+// 0xff bytes held back behind it.  The encoder ends with five shifts; the decoder starts with five reads, so a stream of N
+// normalisations is N + 5 bytes on both sides and a decoder that wants a byte past the end has met a cut or damaged stream.
+//
+// On top of it, an occupancy byte (never 0) is eight binary decisions, child 0 first.  Decision c uses model 256 * t + m: m = the
+// binary-tree node of the bits already coded in this byte (1, then 2m + bit: 255 values), t = three bits of the node's face-neighbour
+// mask n6 (bit 0 / 1: the -x / +x neighbour, 2 / 3: -y / +y, 4 / 5: -z / +z) -- the neighbours across the three outer faces of
+// child c's octant: bit (c >> 2 & 1) of the x pair, (c >> 1 & 1) of the y pair, (c & 1) of the z pair.  After seven zeros the
+// eighth decision is a one and is not coded.  This file shares nothing with range_coder.cpp (table-driven, multi-symbol).
+#include <cstdint>
+#include <cstring>
+#include <new>
+
+#include "../../include/pcc_geo.h"
+
+void pcc_set_error(const char* fmt, ...);
+#define PCC_API extern "C" __attribute__((visibility("default")))
+
+namespace {
+
+constexpr int kProbBits = 11, kMoveBits = 5;
+constexpr uint32_t kTop = 1u << 24;
+constexpr int kModels = 8 * 256;                  // 256 * t + m, m = 1 .. 255 (m = 0 unused)
+
+struct Encoder {
+    uint64_t low = 0;
+    uint32_t range = 0xffffffffu;
+    uint8_t cache = 0;
+    int64_t cache_size = 1;
+    uint8_t* out;
+    int64_t cap, len = 0;
+    bool overflow = false;
+
+    Encoder(uint8_t* o, int64_t c) : out(o), cap(c) {}
+    void put(uint8_t b) {
+        if (len < cap) out[len] = b; else overflow = true;
+        ++len;
+    }
+    void shift_low() {
+        if ((uint32_t)low < 0xff000000u || (low >> 32) != 0) {
+            const uint8_t carry = (uint8_t)(low >> 32);
+            uint8_t b = cache;
+            do {
+                put((uint8_t)(b + carry));
+                b = 0xff;
+            } while (--cache_size != 0);
+            cache = (uint8_t)(low >> 24);
+        }
+        ++cache_size;
+        low = (low & 0x00ffffffu) << 8;
+    }
+    void encode(uint16_t& p, int bit) {
+        const uint32_t bound = (range >> kProbBits) * p;
+        if (bit == 0) {
+            range = bound;
+            p = (uint16_t)(p + (((1u << kProbBits) - p) >> kMoveBits));
+        } else {
+            low += bound;
+            range -= bound;
+            p = (uint16_t)(p - (p >> kMoveBits));
+        }
+        while (range < kTop) {
+            range <<= 8;
+            shift_low();
+        }
+    }
+    void finish() {
+        for (int i = 0; i < 5; ++i) shift_low();
+    }
+};
+
+struct Decoder {
+    const uint8_t* in = nullptr;
+    int64_t len = 0, pos = 0;
+    uint32_t range = 0xffffffffu, code = 0;
+    bool past_end = false;
+    int32_t flags = 0;
+    uint16_t probs[kModels];
+
+    uint8_t get() {
+        if (pos < len) return in[pos++];
+        past_end = true;
+        return 0;
+    }
+    void init(const uint8_t* data, int64_t n, int32_t f) {
+        in = data; len = n; pos = 0; range = 0xffffffffu; code = 0; past_end = false; flags = f;
+        for (int i = 0; i < kModels; ++i) probs[i] = 1u << (kProbBits - 1);
+        uint8_t first = get();
+        for (int i = 0; i < 4; ++i) code = code << 8 | get();
+        if (first != 0) past_end = true;              // the encoder's first byte is its initial cache byte: always 0
+    }
+    int decode(uint16_t& p) {
+        const uint32_t bound = (range >> kProbBits) * p;
+        int bit;
+        if (code < bound) {
+            range = bound;
+            p = (uint16_t)(p + (((1u << kProbBits) - p) >> kMoveBits));
+            bit = 0;
+        } else {
+            code -= bound;
+            range -= bound;
+            p = (uint16_t)(p - (p >> kMoveBits));
+            bit = 1;
+        }
+        while (range < kTop) {
+            range <<= 8;
+            code = code << 8 | get();
+        }
+        return bit;
+    }
+};
+
+inline int tbits(int n6, int c) { return (n6 >> (c >> 2 & 1) & 1) | (n6 >> (2 + (c >> 1 & 1)) & 1) << 1 | (n6 >> (4 + (c & 1)) & 1) << 2; }
+
+}  // namespace
+
+/* raw decisions: model[i] in [0, 2048), bit[i] in {0, 1} */
+PCC_API int pcc_anchor_code_bits(const uint16_t* model, const uint8_t* bit, int64_t n, uint8_t* out, int64_t cap, int64_t* out_len) {
+    if (n < 0 || cap < 0 || !out_len || (n > 0 && (!model || !bit))) { pcc_set_error("pcc_anchor_code_bits: bad argument"); return PCC_ERR_ARG; }
+    uint16_t probs[kModels];
+    for (int i = 0; i < kModels; ++i) probs[i] = 1u << (kProbBits - 1);
+    Encoder e(out, cap);
+    for (int64_t i = 0; i < n; ++i) {
+        if (model[i] >= kModels || bit[i] > 1) { pcc_set_error("pcc_anchor_code_bits: decision %lld out of range", (long long)i); return PCC_ERR_ARG; }
+        e.encode(probs[model[i]], bit[i]);
+    }
+    e.finish();
+    *out_len = e.len;
+    if (e.overflow) { pcc_set_error("pcc_anchor_code_bits: %lld bytes do not fit %lld", (long long)e.len, (long long)cap); return PCC_ERR_SPACE; }
+    return PCC_OK;
+}
+
+PCC_API int pcc_anchor_decode_bits(const uint8_t* data, int64_t len, const uint16_t* model, int64_t n, uint8_t* bit) {
+    if (n < 0 || len < 0 || (len > 0 && !data) || (n > 0 && (!model || !bit))) { pcc_set_error("pcc_anchor_decode_bits: bad argument"); return PCC_ERR_ARG; }
+    Decoder* d = new (std::nothrow) Decoder;
+    if (!d) { pcc_set_error("pcc_anchor_decode_bits: out of memory"); return PCC_ERR_SPACE; }
+    d->init(data, len, 0);
+    int rc = PCC_OK;
+    for (int64_t i = 0; i < n && rc == PCC_OK; ++i) {
+        if (model[i] >= kModels) { pcc_set_error("pcc_anchor_decode_bits: model %lld out of range", (long long)i); rc = PCC_ERR_ARG; break; }
+        bit[i] = (uint8_t)d->decode(d->probs[model[i]]);
+        if (d->past_end) { pcc_set_error("pcc_anchor_decode_bits: the stream ends inside decision %lld", (long long)i); rc = PCC_ERR_CORRUPT; }
+    }
+    if (rc == PCC_OK && d->past_end) { pcc_set_error("pcc_anchor_decode_bits: the stream is cut or does not start with a zero byte"); rc = PCC_ERR_CORRUPT; }
+    delete d;
+    return rc;
+}
+
+/* all occupancy bytes of a tree, breadth first, in one coder run */
+PCC_API int pcc_anchor_encode(const uint8_t* occ, const uint8_t* n6, int64_t n, int32_t flags, uint8_t* out, int64_t cap, int64_t* out_len) {
+    if (n < 0 || cap < 0 || !out_len || (n > 0 && (!occ || !n6)) || (flags & ~PCC_ANCHOR_NO_CONTEXT)) {
+        pcc_set_error("pcc_anchor_encode: bad argument");
+        return PCC_ERR_ARG;
+    }
+    uint16_t probs[kModels];
+    for (int i = 0; i < kModels; ++i) probs[i] = 1u << (kProbBits - 1);
+    Encoder e(out, cap);
+    const bool ctx = !(flags & PCC_ANCHOR_NO_CONTEXT);
+    for (int64_t i = 0; i < n; ++i) {
+        const int b = occ[i], nb = ctx ? (n6[i] & 63) : 0;
+        if (b == 0) { pcc_set_error("pcc_anchor_encode: node %lld has no child", (long long)i); return PCC_ERR_ARG; }
+        int m = 1;
+        for (int c = 0; c < 8; ++c) {
+            if (c == 7 && m == 128) break;            // seven zeros: the eighth is a one
+            const int bit = b >> c & 1;
+            e.encode(probs[256 * tbits(nb, c) + m], bit);
+            m = 2 * m + bit;
+        }
+    }
+    e.finish();
+    *out_len = e.len;
+    if (e.overflow) { pcc_set_error("pcc_anchor_encode: %lld bytes do not fit %lld", (long long)e.len, (long long)cap); return PCC_ERR_SPACE; }
+    return PCC_OK;
+}
+
+PCC_API size_t pcc_anchor_decoder_bytes(void) { return sizeof(Decoder); }
+
+/* state: pcc_anchor_decoder_bytes() bytes owned by the caller; data must outlive the last pcc_anchor_decode_level */
+PCC_API int pcc_anchor_decoder_init(void* state, const uint8_t* data, int64_t len, int32_t flags) {
+    if (!state || len < 0 || (len > 0 && !data) || (flags & ~PCC_ANCHOR_NO_CONTEXT)) { pcc_set_error("pcc_anchor_decoder_init: bad argument"); return PCC_ERR_ARG; }
+    Decoder* d = new (state) Decoder;
+    d->init(data, len, flags);
+    if (d->past_end) { pcc_set_error("pcc_anchor_decoder_init: the payload is shorter than five bytes or does not start with a zero byte"); return PCC_ERR_CORRUPT; }
+    return PCC_OK;
+}
+
+PCC_API int pcc_anchor_decode_level(void* state, const uint8_t* n6, int64_t n, uint8_t* occ) {
+    if (!state || n < 0 || (n > 0 && (!n6 || !occ))) { pcc_set_error("pcc_anchor_decode_level: bad argument"); return PCC_ERR_ARG; }
+    Decoder* d = (Decoder*)state;
+    const bool ctx = !(d->flags & PCC_ANCHOR_NO_CONTEXT);
+    for (int64_t i = 0; i < n; ++i) {
+        const int nb = ctx ? (n6[i] & 63) : 0;
+        int m = 1;
+        for (int c = 0; c < 8; ++c) {
+            if (c == 7 && m == 128) { m = 257; break; }
+            m = 2 * m + d->decode(d->probs[256 * tbits(nb, c) + m]);
+        }
+        if (d->past_end) { pcc_set_error("pcc_anchor_decode_level: the stream ends inside node %lld of this level", (long long)i); return PCC_ERR_CORRUPT; }
+        // m = 256 + the bits with child 0 first as the HIGHEST bit: reverse them into bit c = child c
+        int b = 0;
+        for (int c = 0; c < 8; ++c) b |= (m >> (7 - c) & 1) << c;
+        occ[i] = (uint8_t)b;
+    }
+    return PCC_OK;
+}
+
+/* bytes of the payload read so far (the whole payload once the last level is decoded) */
+PCC_API int64_t pcc_anchor_decoder_consumed(const void* state) { return state ? ((const Decoder*)state)->pos : -1; }

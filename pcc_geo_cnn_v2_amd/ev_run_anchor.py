@@ -1,0 +1,138 @@
+"""The octree anchor (anchor_octree.py) over every cloud and rate of an experiment YAML: the baseline of ev_run_compare's RD curves and
+BD tables for clouds that have no published anchor.
+
+  python -m pcc_geo_cnn_v2_amd.ev_run_anchor experiment.yml
+
+It is NOT G-PCC.  It writes the tree ev_run_compare reads for an id listed under the YAML's mpeg_modes:
+
+  EXPERIMENT_DIR/gpcc/<anchor id>/<pc_name>/<rate>/<pc_name>.ply.bin                        the stream
+                                                   <pc_name>.ply.bin.decoded.ply            the decoded cloud
+                                                   <pc_name>.ply.bin.decoded.ply.color.ply  with the original's colours (map_color), if it has any
+                                                   report.json                              ev_report.build_report's dictionary
+
+so the user lists the id under mpeg_modes with a label of their own and under an eval mode; ev_run_compare does not change.  A label
+that contains "G-PCC" is refused.  Every decoded cloud is checked against the encoder's own reconstruction (anchor_octree.reconstruct).
+
+YAML keys, all optional: anchor_id (default 'octree-anchor'); anchor_rates, a mapping rate name -> [num, den]; anchor_device (or
+device): gpu (default) or host, where the tree and its contexts are computed; metrics_device, d2_ties, estimate_normals as in
+ev_run_experiment, which also resolves resolutions and normals the same way.
+
+The default rates r01 .. r06 = 1/8, 1/4, 1/2, 3/4, 7/8, 15/16 are the scales of the MPEG common test conditions for lossy octree
+geometry on 10-bit clouds AS RECALLED by the author of this step: nothing available to this project confirms them.  Give
+anchor_rates when the exact conditions matter.
+
+A step whose outputs exist is skipped, so the command resumes.  The GPU context, each cloud (points, normals, KD-tree / GPU index)
+and its quantisation input stay resident across the rates (ev_experiment.Resident); the reports of all rates of a cloud are measured
+in one pass.
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+import time
+
+import numpy as np
+
+from .utils import experiment as E
+
+logger = logging.getLogger(__name__)
+
+DEFAULT_ID = 'octree-anchor'
+DEFAULT_RATES = {'r01': (1, 8), 'r02': (1, 4), 'r03': (1, 2), 'r04': (3, 4), 'r05': (7, 8), 'r06': (15, 16)}
+FORBIDDEN_LABEL = 'G-PCC'
+
+
+def anchor_settings(exp):
+    """-> (anchor id, {rate: (num, den)}, device).  Raises for a bad scale or a label that claims to be G-PCC."""
+    from . import anchor_octree as A
+    anchor_id = exp.get('anchor_id', DEFAULT_ID)
+    rates = exp.get('anchor_rates') or DEFAULT_RATES
+    assert isinstance(rates, dict) and rates, 'anchor_rates: a mapping rate name -> [num, den]'
+    rates = {str(k): A.check_scale(tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in rates.items()}
+    device = exp.get('anchor_device', exp.get('device', 'gpu'))
+    A.check_device(device)
+    labels = [m.get('label', '') for m in exp.get('mpeg_modes') or () if m.get('id') == anchor_id]
+    labels += [m.get('label', '') for ev in exp.get('eval_modes') or () for m in ev.get('modes') or () if m.get('id') == anchor_id]
+    for label in labels:
+        if FORBIDDEN_LABEL.lower() in str(label).lower():
+            raise ValueError(f'label {label!r} of {anchor_id}: the octree anchor is not G-PCC and must not be labelled so')
+    return anchor_id, rates, device
+
+
+def rate_dir(exp, anchor_id, pc_name, rate):
+    return os.path.join(exp['EXPERIMENT_DIR'], 'gpcc', anchor_id, pc_name, rate)
+
+
+def run(exp, resident=None):
+    """Returns {'coded': n, 'reports': n}: the steps that ran (0, 0 when everything existed)."""
+    from . import anchor_octree as A
+    from .ev_experiment import Resident, _recolor, measure
+    from .utils import pc_io
+    assert os.path.isdir(exp['EXPERIMENT_DIR']), f"{exp['EXPERIMENT_DIR']} not found"
+    anchor_id, rates, device = anchor_settings(exp)
+    res = resident if resident is not None else Resident()
+    metrics_device, d2_ties = exp.get('metrics_device', 'host'), exp.get('d2_ties', 'pick')
+    done = {'coded': 0, 'reports': 0}
+    t0 = time.perf_counter()
+    for entry in exp['data']:
+        pc_name = entry['pc_name']
+        input_norm = None if exp.get('estimate_normals') else E.data_path(exp, entry.get('input_norm'))
+        original = res.original(E.data_path(exp, entry['input_pc']), input_norm, bool(exp.get('estimate_normals')))
+        resolution = E.cloud_resolution(exp, entry)
+        todo = []
+        for rate, scale in rates.items():
+            out = rate_dir(exp, anchor_id, pc_name, rate)
+            enc = os.path.join(out, pc_name + '.ply.bin')
+            dec, report = enc + '.decoded.ply', os.path.join(out, 'report.json')
+            col = dec + '.color.ply'
+            os.makedirs(out, exist_ok=True)
+            if os.path.exists(enc) and os.path.exists(dec):
+                logger.info(f'[{original.input_pc}] -> [{enc}, {dec}] (exists)')
+            else:
+                logger.info(f'[{original.input_pc}] -> [{enc}, {dec}] scale {scale[0]}/{scale[1]}')
+                ctx = res.ctx if device == 'gpu' else None
+                data = A.encode(original.points, resolution, scale, device, ctx)
+                pts = A.decode(data, device, ctx)
+                want = A.reconstruct(original.points, resolution, scale)
+                assert np.array_equal(pts, want), f'{pc_name} {rate}: the decoded cloud is not the encoder\'s reconstruction'
+                with open(enc + '.tmp', 'wb') as f:
+                    f.write(data)
+                pc_io.write_df(dec, pc_io.pa_to_df(pts))
+                os.replace(enc + '.tmp', enc)
+                done['coded'] += 1
+            if os.path.exists(col):
+                logger.info(f'[{dec}] -> [{col}] (exists)')
+            elif original.colors is not None:
+                logger.info(f'[{dec}] -> [{col}]')
+                _recolor(res, original, dec, col)
+            if not os.path.exists(report):
+                todo.append((dec, enc, report))
+        if todo:
+            logger.info(f"[{pc_name}] -> [{', '.join(t[2] for t in todo)}]")
+            reports = measure(res, original, [t[0] for t in todo], [t[1] for t in todo], resolution, metrics_device, d2_ties)
+            for (_, _, path), data in zip(todo, reports):
+                with open(path + '.tmp', 'w') as f:
+                    json.dump(data, f, sort_keys=True, indent=4)
+                os.replace(path + '.tmp', path)
+                done['reports'] += 1
+    logger.info(f'Done: {done} in {time.perf_counter() - t0:.2f} s')
+    return done
+
+
+def main(argv=None):
+    from . import want_hw_queues
+    want_hw_queues()        # before torch (the HIP runtime) loads
+    logging.basicConfig(level=logging.INFO, format='%(asctime)s.%(msecs)03d %(levelname)s %(module)s - %(funcName)s: %(message)s',
+                        datefmt='%Y-%m-%d %H:%M:%S')
+    p = argparse.ArgumentParser(prog='ev_run_anchor.py', description='Code every cloud of an experiment with the octree anchor (a conventional '
+                                'baseline; not G-PCC) at every rate and write the report tree ev_run_compare reads.',
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('experiment_path', help='Experiments file path.')
+    a = p.parse_args(argv)
+    run(E.load_experiment(a.experiment_path))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

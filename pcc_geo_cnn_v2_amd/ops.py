@@ -1191,6 +1191,140 @@ def error_map(ctx, index_a, b_points):
 
 
 # ---------------------------------------------------------------------------------------------
+# octree anchor (include/pcc_geo.h "octree anchor"; the codec is anchor_octree.py)
+# ---------------------------------------------------------------------------------------------
+def _u8(a):
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def anchor_code_bits(models, bits):
+    """The anchor's binary range coder on raw decisions: models (n) in [0, 2048), bits (n) in {0, 1} -> bytes (host)."""
+    m, b = np.ascontiguousarray(models, dtype=np.uint16), _u8(bits)
+    assert m.ndim == 1 and m.shape == b.shape, 'anchor_code_bits: models and bits must be 1-d and of one length'
+    out = np.empty(2 * m.size + 16, np.uint8)
+    n = C.c_int64()
+    L.check(L.lib().pcc_anchor_code_bits(m.ctypes.data, b.ctypes.data, m.size, out.ctypes.data, out.size, C.byref(n)), 'pcc_anchor_code_bits')
+    return out[:n.value].tobytes()
+
+
+def anchor_decode_bits(data, models):
+    m = np.ascontiguousarray(models, dtype=np.uint16)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    out = np.empty(m.size, np.uint8)
+    L.check(L.lib().pcc_anchor_decode_bits(buf.ctypes.data if buf.size else None, buf.size, m.ctypes.data, m.size, out.ctypes.data),
+            'pcc_anchor_decode_bits')
+    return out
+
+
+def anchor_encode_nodes(occ, n6, no_context=False):
+    """All occupancy bytes of a tree (breadth first) with their neighbour masks -> the payload bytes (host)."""
+    occ, n6 = _u8(occ), _u8(n6)
+    assert occ.ndim == 1 and occ.shape == n6.shape, 'anchor_encode_nodes: occ and n6 must be 1-d and of one length'
+    out = np.empty(2 * occ.size + 16, np.uint8)
+    n = C.c_int64()
+    L.check(L.lib().pcc_anchor_encode(occ.ctypes.data, n6.ctypes.data, occ.size, L.PCC_ANCHOR_NO_CONTEXT if no_context else 0, out.ctypes.data,
+                                      out.size, C.byref(n)), 'pcc_anchor_encode')
+    return out[:n.value].tobytes()
+
+
+class AnchorDecoder:
+    """The host decoder of one payload: level(n6) returns the occupancy bytes of the next level.  A payload that ends early raises
+    PccError."""
+
+    def __init__(self, payload, no_context=False):
+        self._data = np.frombuffer(bytes(payload), np.uint8)          # kept alive: the C state points into it
+        self._state = np.zeros(L.lib().pcc_anchor_decoder_bytes() + 8, np.uint8)
+        L.check(L.lib().pcc_anchor_decoder_init(self._state.ctypes.data, self._data.ctypes.data if self._data.size else None, self._data.size,
+                                                L.PCC_ANCHOR_NO_CONTEXT if no_context else 0), 'pcc_anchor_decoder_init')
+
+    def level(self, n6):
+        n6 = _u8(n6)
+        occ = np.empty(n6.size, np.uint8)
+        L.check(L.lib().pcc_anchor_decode_level(self._state.ctypes.data, n6.ctypes.data, n6.size, occ.ctypes.data), 'pcc_anchor_decode_level')
+        return occ
+
+    @property
+    def consumed(self):
+        return int(L.lib().pcc_anchor_decoder_consumed(self._state.ctypes.data))
+
+    def __len__(self):
+        return int(self._data.size)
+
+
+def anchor_tree_launch(ctx, points, num, den, depth):
+    """Enqueues the tree of anchor_octree.encode for an int32 (n,3) numpy cloud already checked by the caller; returns the pinned
+    host buffer the result is being copied into and a function that waits for it and returns (counts[depth + 1], occ, n6): the nodes
+    per level with the leaves last, and the bytes of all levels, breadth first.  Nothing is read back before that one copy."""
+    lib, dev = L.lib(), ctx.device
+    n, depth = int(points.shape[0]), int(depth)
+    cap = int(lib.pcc_anchor_tree_capacity(n, depth))
+    if cap <= 0:
+        raise L.PccError(f'anchor_tree: {n} points at depth {depth} are outside the contract')
+    hdr_bytes = 8 * L.PCC_ANCHOR_HDR_WORDS
+    pts_d = torch.from_numpy(points).to(dev, non_blocking=True)
+    out = torch.empty((hdr_bytes + 2 * cap,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):            # hipCUB sizes its temporary storage for the current device
+        ws = torch.empty((lib.pcc_anchor_tree_workspace_bytes(n),), dtype=torch.uint8, device=dev)
+    base = out.data_ptr()
+    L.check(lib.pcc_anchor_tree(ctx.handle, _ptr(pts_d), n, int(num), int(den), depth, C.c_void_p(base), C.c_void_p(base + hdr_bytes),
+                                C.c_void_p(base + hdr_bytes + cap), _ptr(ws), ctx.stream), 'pcc_anchor_tree')
+    pin = getattr(ctx, '_anchor_pin', None)             # one launch in flight per context: the pinned landing buffer is reused
+    if pin is None or pin.numel() < out.numel():
+        ctx._anchor_pin = pin = torch.empty((out.numel(),), dtype=torch.uint8, pin_memory=True)
+    host = pin[:out.numel()]
+    host.copy_(out, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(dev))
+    alive = (pts_d, out, ws)
+
+    def finish():
+        assert alive
+        done.synchronize()                  # pts_d, out and ws stay alive until here
+        raw = host.numpy()
+        counts = raw[:hdr_bytes].view(np.int64)[:depth + 1].copy()
+        offs = [int(lib.pcc_anchor_tree_level_offset(n, l)) for l in range(depth + 1)]
+        for l in range(depth):
+            if not 1 <= counts[l] <= offs[l + 1] - offs[l]:
+                raise L.PccError(f'anchor_tree: level {l} reports {counts[l]} nodes for a slot of {offs[l + 1] - offs[l]}')
+        occ = np.concatenate([raw[hdr_bytes + offs[l]:hdr_bytes + offs[l] + counts[l]] for l in range(depth)])
+        n6 = np.concatenate([raw[hdr_bytes + cap + offs[l]:hdr_bytes + cap + offs[l] + counts[l]] for l in range(depth)])
+        return counts, occ, n6
+    return finish
+
+
+def anchor_tree(ctx, points, num, den, depth):
+    return anchor_tree_launch(ctx, points, num, den, depth)()
+
+
+def anchor_expand(ctx, parents, occ, child_level, want_n6=True):
+    """One decoder step on the device: parents (device uint64 keys of a level, ascending; None for the root), occ (numpy uint8, the
+    level's decoded bytes) -> (child keys on the device, their n6 as numpy or None).  One copy in, one copy out."""
+    dev = ctx.device
+    occ = _u8(occ)
+    if parents is None:
+        parents = torch.zeros((1,), dtype=torch.int64, device=dev)
+    npar = int(parents.shape[0])
+    assert occ.shape == (npar,), 'anchor_expand: one occupancy byte per parent'
+    nch = int(np.unpackbits(occ).sum())
+    occ_d = torch.from_numpy(occ).to(dev)
+    children = torch.empty((nch,), dtype=torch.int64, device=dev)
+    n6 = torch.empty((nch,), dtype=torch.uint8, device=dev) if want_n6 else None
+    with torch.cuda.device(dev):
+        ws = torch.empty((L.lib().pcc_anchor_expand_workspace_bytes(npar),), dtype=torch.uint8, device=dev)
+    L.check(L.lib().pcc_anchor_expand(ctx.handle, _ptr(parents), _ptr(occ_d), npar, int(child_level), _ptr(children), nch, _ptr(n6), _ptr(ws),
+                                      ctx.stream), 'pcc_anchor_expand')
+    return children, (n6.cpu().numpy() if want_n6 else None)
+
+
+def anchor_points(ctx, keys, num, den, resolution):
+    """Leaf keys (device) -> the decoded (n,3) int32 points (numpy), in key order."""
+    n = int(keys.shape[0])
+    pts = torch.empty((n, 3), dtype=torch.int32, device=ctx.device)
+    L.check(L.lib().pcc_anchor_points(ctx.handle, _ptr(keys), n, int(num), int(den), int(resolution), _ptr(pts), ctx.stream), 'pcc_anchor_points')
+    return pts.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------
 class HostCdfTable:
