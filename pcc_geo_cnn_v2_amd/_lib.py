@@ -15,6 +15,7 @@ PCC_CONV_IN16, PCC_CONV_OUT16, PCC_CONV_RES16 = 32, 64, 128          # fp16 stor
 PCC_IMPL_AUTO, PCC_IMPL_GENERIC, PCC_IMPL_MFMA, PCC_IMPL_WINOGRAD, PCC_IMPL_SPLIT = 0, 1, 2, 3, 4
 PCC_ROUND_FLOOR_HALF, PCC_ROUND_HALF_EVEN = 0, 1
 PCC_ANCHOR_NO_CONTEXT, PCC_ANCHOR_HDR_WORDS = 1, 32      # include/pcc_geo.h "octree anchor"
+PCC_SURFACE_HDR_WORDS = 4                                # include/pcc_geo.h "surface anchor"
 
 EXPORTS = [
     'pcc_abi_version', 'pcc_last_error', 'pcc_ctx_create', 'pcc_ctx_destroy', 'pcc_ctx_num_cu', 'pcc_ctx_get_numerics', 'pcc_ctx_set_numerics',
@@ -40,6 +41,9 @@ EXPORTS = [
     'pcc_anchor_code_bits', 'pcc_anchor_decode_bits', 'pcc_anchor_encode', 'pcc_anchor_decoder_bytes', 'pcc_anchor_decoder_init',
     'pcc_anchor_decode_level', 'pcc_anchor_decoder_consumed', 'pcc_anchor_tree_capacity', 'pcc_anchor_tree_level_offset',
     'pcc_anchor_tree_workspace_bytes', 'pcc_anchor_tree', 'pcc_anchor_expand_workspace_bytes', 'pcc_anchor_expand', 'pcc_anchor_points',
+    'pcc_surface_encode_vertices', 'pcc_surface_decode_vertices', 'pcc_surface_leaves_workspace_bytes', 'pcc_surface_leaves',
+    'pcc_surface_edges_workspace_bytes', 'pcc_surface_edges', 'pcc_surface_vertices_workspace_bytes', 'pcc_surface_vertices',
+    'pcc_surface_count_workspace_bytes', 'pcc_surface_count', 'pcc_surface_reconstruct_workspace_bytes', 'pcc_surface_reconstruct',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -202,6 +206,16 @@ def lib():
     L.pcc_anchor_expand_workspace_bytes.restype = sz
     L.pcc_anchor_expand.argtypes = [vp, vp, vp, i64, i32, vp, i64, vp, vp, vp]
     L.pcc_anchor_points.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp]
+    L.pcc_surface_encode_vertices.argtypes = [vp, vp, vp, i64, i32, vp, i64, C.POINTER(i64)]
+    L.pcc_surface_decode_vertices.argtypes = [vp, i64, vp, i64, i32, vp, vp, C.POINTER(i64), C.POINTER(i64)]
+    for name in ('leaves', 'edges', 'vertices', 'count', 'reconstruct'):
+        f = getattr(L, f'pcc_surface_{name}_workspace_bytes')
+        f.argtypes, f.restype = [i64], sz
+    L.pcc_surface_leaves.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp]
+    L.pcc_surface_edges.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.pcc_surface_vertices.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp]
+    L.pcc_surface_count.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp]
+    L.pcc_surface_reconstruct.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

@@ -209,3 +209,77 @@ PCC_API int pcc_anchor_decode_level(void* state, const uint8_t* n6, int64_t n, u
 
 /* bytes of the payload read so far (the whole payload once the last level is decoded) */
 PCC_API int64_t pcc_anchor_decoder_consumed(const void* state) { return state ? ((const Decoder*)state)->pos : -1; }
+
+/* ---- vertex payload of the surface anchor (include/pcc_geo.h "surface anchor"): one coder run over the edge list.  Per
+ * edge: the flag under model 2 a + prev (a = the edge's axis = key & 3, prev = the previous edge's flag, 0 at the start); behind a set
+ * flag the k bits of t, most significant first, under model 8 + m, m = 1 then 2 m + bit.  The decisions depend on decoded bits, so
+ * this pair cannot go through pcc_anchor_decode_bits. */
+namespace {
+constexpr int kSurfaceFlagModels = 8;
+bool surface_args_ok(const uint64_t* keys, int64_t n, int32_t k) { return n >= 0 && k >= 2 && k <= 6 && (n == 0 || keys); }
+}  // namespace
+
+PCC_API int pcc_surface_encode_vertices(const uint64_t* edge_keys, const uint8_t* flags, const uint8_t* t, int64_t nedges, int32_t k, uint8_t* out,
+                                        int64_t cap, int64_t* out_len) {
+    if (!surface_args_ok(edge_keys, nedges, k) || cap < 0 || !out_len || (nedges > 0 && (!flags || !t))) {
+        pcc_set_error("pcc_surface_encode_vertices: bad argument");
+        return PCC_ERR_ARG;
+    }
+    uint16_t probs[kModels];
+    for (int i = 0; i < kModels; ++i) probs[i] = 1u << (kProbBits - 1);
+    Encoder e(out, cap);
+    int prev = 0;
+    for (int64_t i = 0; i < nedges; ++i) {
+        const int a = (int)(edge_keys[i] & 3), f = flags[i];
+        if (a > 2 || f > 1 || (f && t[i] >= (1 << k))) { pcc_set_error("pcc_surface_encode_vertices: edge %lld out of range", (long long)i); return PCC_ERR_ARG; }
+        e.encode(probs[2 * a + prev], f);
+        if (f) {
+            int m = 1;
+            for (int b = k - 1; b >= 0; --b) {
+                const int bit = t[i] >> b & 1;
+                e.encode(probs[kSurfaceFlagModels + m], bit);
+                m = 2 * m + bit;
+            }
+        }
+        prev = f;
+    }
+    e.finish();
+    *out_len = e.len;
+    if (e.overflow) { pcc_set_error("pcc_surface_encode_vertices: %lld bytes do not fit %lld", (long long)e.len, (long long)cap); return PCC_ERR_SPACE; }
+    return PCC_OK;
+}
+
+/* flags[nedges], t[nedges] (0 where the flag is 0); *nflags = the set flags, *consumed = the bytes of data read (the whole payload for a sound one) */
+PCC_API int pcc_surface_decode_vertices(const uint8_t* data, int64_t len, const uint64_t* edge_keys, int64_t nedges, int32_t k, uint8_t* flags,
+                                        uint8_t* t, int64_t* nflags, int64_t* consumed) {
+    if (!surface_args_ok(edge_keys, nedges, k) || len < 0 || (len > 0 && !data) || !nflags || !consumed || (nedges > 0 && (!flags || !t))) {
+        pcc_set_error("pcc_surface_decode_vertices: bad argument");
+        return PCC_ERR_ARG;
+    }
+    Decoder* d = new (std::nothrow) Decoder;
+    if (!d) { pcc_set_error("pcc_surface_decode_vertices: out of memory"); return PCC_ERR_SPACE; }
+    d->init(data, len, 0);
+    int rc = PCC_OK, prev = 0;
+    int64_t set = 0;
+    if (d->past_end) { pcc_set_error("pcc_surface_decode_vertices: the payload is shorter than five bytes or does not start with a zero byte"); rc = PCC_ERR_CORRUPT; }
+    for (int64_t i = 0; i < nedges && rc == PCC_OK; ++i) {
+        const int a = (int)(edge_keys[i] & 3);
+        if (a > 2) { pcc_set_error("pcc_surface_decode_vertices: edge %lld has axis 3", (long long)i); rc = PCC_ERR_ARG; break; }
+        const int f = d->decode(d->probs[2 * a + prev]);
+        int v = 0;
+        if (f) {
+            int m = 1;
+            for (int b = 0; b < k; ++b) m = 2 * m + d->decode(d->probs[kSurfaceFlagModels + m]);
+            v = m - (1 << k);
+            ++set;
+        }
+        if (d->past_end) { pcc_set_error("pcc_surface_decode_vertices: the stream ends inside edge %lld", (long long)i); rc = PCC_ERR_CORRUPT; break; }
+        flags[i] = (uint8_t)f;
+        t[i] = (uint8_t)v;
+        prev = f;
+    }
+    *nflags = set;
+    *consumed = d->pos;
+    delete d;
+    return rc;
+}

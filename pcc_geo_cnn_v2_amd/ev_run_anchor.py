@@ -21,6 +21,10 @@ The default rates r01 .. r06 = 1/8, 1/4, 1/2, 3/4, 7/8, 15/16 are the scales of 
 geometry on 10-bit clouds AS RECALLED by the author of this step: nothing available to this project confirms them.  Give
 anchor_rates when the exact conditions matter.
 
+--codec surface (or both) runs the surface anchor (anchor_surface.py; not G-PCC, not trisoup-conformant) the same way
+under its own id: YAML keys surface_anchor_id (default 'surface-anchor') and surface_rates, a mapping rate name -> node_log2 (default
+r01 .. r04 = 5, 4, 3, 2: four points, because the BD fits need four).  The default, --codec octree, writes what it always wrote.
+
 A step whose outputs exist is skipped, so the command resumes.  The GPU context, each cloud (points, normals, KD-tree / GPU index)
 and its quantisation input stay resident across the rates (ev_experiment.Resident); the reports of all rates of a cloud are measured
 in one pass.
@@ -40,6 +44,9 @@ logger = logging.getLogger(__name__)
 
 DEFAULT_ID = 'octree-anchor'
 DEFAULT_RATES = {'r01': (1, 8), 'r02': (1, 4), 'r03': (1, 2), 'r04': (3, 4), 'r05': (7, 8), 'r06': (15, 16)}
+SURFACE_DEFAULT_ID = 'surface-anchor'
+SURFACE_DEFAULT_RATES = {'r01': 5, 'r02': 4, 'r03': 3, 'r04': 2}
+CODECS = ('octree', 'surface', 'both')
 FORBIDDEN_LABEL = 'G-PCC'
 
 
@@ -52,26 +59,74 @@ def anchor_settings(exp):
     rates = {str(k): A.check_scale(tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in rates.items()}
     device = exp.get('anchor_device', exp.get('device', 'gpu'))
     A.check_device(device)
+    _check_labels(exp, anchor_id, 'octree')
+    return anchor_id, rates, device
+
+
+def _check_labels(exp, anchor_id, what):
     labels = [m.get('label', '') for m in exp.get('mpeg_modes') or () if m.get('id') == anchor_id]
     labels += [m.get('label', '') for ev in exp.get('eval_modes') or () for m in ev.get('modes') or () if m.get('id') == anchor_id]
     for label in labels:
         if FORBIDDEN_LABEL.lower() in str(label).lower():
-            raise ValueError(f'label {label!r} of {anchor_id}: the octree anchor is not G-PCC and must not be labelled so')
+            raise ValueError(f'label {label!r} of {anchor_id}: the {what} anchor is not G-PCC and must not be labelled so')
+
+
+def surface_settings(exp):
+    """-> (anchor id, {rate: node_log2}, device).  Raises for a bad node_log2 or a label that claims to be G-PCC."""
+    from . import anchor_surface as S
+    anchor_id = exp.get('surface_anchor_id', SURFACE_DEFAULT_ID)
+    rates = exp.get('surface_rates') or SURFACE_DEFAULT_RATES
+    assert isinstance(rates, dict) and rates, 'surface_rates: a mapping rate name -> node_log2'
+    rates = {str(k): S.check_node_log2(v) for k, v in rates.items()}
+    device = exp.get('anchor_device', exp.get('device', 'gpu'))
+    S.check_device(device)
+    _check_labels(exp, anchor_id, 'surface')
     return anchor_id, rates, device
+
+
+class _Octree:
+    """One codec of run(): its id, its rates and the three functions of a rate's parameter."""
+
+    def __init__(self, exp):
+        from . import anchor_octree as A
+        self.codec, (self.anchor_id, self.rates, self.device) = A, anchor_settings(exp)
+
+    def describe(self, scale):
+        return f'scale {scale[0]}/{scale[1]}'
+
+
+class _Surface(_Octree):
+    def __init__(self, exp):
+        from . import anchor_surface as S
+        self.codec, (self.anchor_id, self.rates, self.device) = S, surface_settings(exp)
+
+    def describe(self, node_log2):
+        return f'node_log2 {node_log2}'
 
 
 def rate_dir(exp, anchor_id, pc_name, rate):
     return os.path.join(exp['EXPERIMENT_DIR'], 'gpcc', anchor_id, pc_name, rate)
 
 
-def run(exp, resident=None):
-    """Returns {'coded': n, 'reports': n}: the steps that ran (0, 0 when everything existed)."""
-    from . import anchor_octree as A
-    from .ev_experiment import Resident, _recolor, measure
-    from .utils import pc_io
+def run(exp, resident=None, codec='octree'):
+    """Returns {'coded': n, 'reports': n}: the steps that ran (0, 0 when everything existed).  codec: one of CODECS."""
+    from .ev_experiment import Resident
+    assert codec in CODECS, f'codec must be one of {CODECS}, got {codec!r}'
     assert os.path.isdir(exp['EXPERIMENT_DIR']), f"{exp['EXPERIMENT_DIR']} not found"
-    anchor_id, rates, device = anchor_settings(exp)
+    anchors = [cls(exp) for name, cls in (('octree', _Octree), ('surface', _Surface)) if codec in (name, 'both')]     # every label checked first
+    assert len({a.anchor_id for a in anchors}) == len(anchors), 'anchor_id and surface_anchor_id must differ'
     res = resident if resident is not None else Resident()
+    done = {'coded': 0, 'reports': 0}
+    for anchor in anchors:
+        for key, n in _run_one(exp, res, anchor).items():
+            done[key] += n
+    return done
+
+
+def _run_one(exp, res, anchor):
+    from .ev_experiment import _recolor, measure
+    from .utils import pc_io
+    A, anchor_id, rates, device = anchor.codec, anchor.anchor_id, anchor.rates, anchor.device
     metrics_device, d2_ties = exp.get('metrics_device', 'host'), exp.get('d2_ties', 'pick')
     done = {'coded': 0, 'reports': 0}
     t0 = time.perf_counter()
@@ -90,7 +145,7 @@ def run(exp, resident=None):
             if os.path.exists(enc) and os.path.exists(dec):
                 logger.info(f'[{original.input_pc}] -> [{enc}, {dec}] (exists)')
             else:
-                logger.info(f'[{original.input_pc}] -> [{enc}, {dec}] scale {scale[0]}/{scale[1]}')
+                logger.info(f'[{original.input_pc}] -> [{enc}, {dec}] {anchor.describe(scale)}')
                 ctx = res.ctx if device == 'gpu' else None
                 data = A.encode(original.points, resolution, scale, device, ctx)
                 pts = A.decode(data, device, ctx)
@@ -129,8 +184,10 @@ def main(argv=None):
                                 'baseline; not G-PCC) at every rate and write the report tree ev_run_compare reads.',
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('experiment_path', help='Experiments file path.')
+    p.add_argument('--codec', choices=CODECS, default='octree', help='Which anchor to run: the octree anchor, the surface anchor (a triangle-soup '
+                   'class codec; not G-PCC, not trisoup-conformant) or both')
     a = p.parse_args(argv)
-    run(E.load_experiment(a.experiment_path))
+    run(E.load_experiment(a.experiment_path), codec=a.codec)
     return 0
 
 

@@ -1325,6 +1325,105 @@ def anchor_points(ctx, keys, num, den, resolution):
 
 
 # ---------------------------------------------------------------------------------------------
+# surface anchor (include/pcc_geo.h "surface anchor"; the codec is anchor_surface.py)
+# ---------------------------------------------------------------------------------------------
+def surface_encode_vertices(edge_keys, flags, t, k):
+    """The vertex payload: edge keys (n) uint64, flags (n) in {0, 1}, t (n) in [0, 2^k) -> bytes (host)."""
+    keys, flags, t = np.ascontiguousarray(edge_keys, dtype=np.uint64), _u8(flags), _u8(t)
+    assert keys.ndim == 1 and keys.shape == flags.shape == t.shape, 'surface_encode_vertices: one flag and one t per edge'
+    out = np.empty(8 * keys.size + 16, np.uint8)
+    n = C.c_int64()
+    L.check(L.lib().pcc_surface_encode_vertices(keys.ctypes.data, flags.ctypes.data, t.ctypes.data, keys.size, int(k), out.ctypes.data, out.size,
+                                                C.byref(n)), 'pcc_surface_encode_vertices')
+    return out[:n.value].tobytes()
+
+
+def surface_decode_vertices(data, edge_keys, k):
+    """-> (flags, t, set flags, bytes read) of a vertex payload over the given edge list (host); PccError when it ends early."""
+    keys = np.ascontiguousarray(edge_keys, dtype=np.uint64)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    flags, t = np.zeros(keys.size, np.uint8), np.zeros(keys.size, np.uint8)
+    nflags, consumed = C.c_int64(), C.c_int64()
+    L.check(L.lib().pcc_surface_decode_vertices(buf.ctypes.data if buf.size else None, buf.size, keys.ctypes.data, keys.size, int(k), flags.ctypes.data,
+                                                t.ctypes.data, C.byref(nflags), C.byref(consumed)), 'pcc_surface_decode_vertices')
+    return flags, t, nflags.value, consumed.value
+
+
+def _surface_ws(ctx, name, n):
+    nbytes = getattr(L.lib(), f'pcc_surface_{name}_workspace_bytes')(int(n))
+    if nbytes == 0:
+        raise L.PccError(f'surface_{name}: a count of {n} is outside the contract')
+    with torch.cuda.device(ctx.device):         # hipCUB sizes its temporary storage for the current device
+        return torch.empty((nbytes,), dtype=torch.uint8, device=ctx.device)
+
+
+def _surface_hdr(ctx):
+    return torch.zeros((L.PCC_SURFACE_HDR_WORDS,), dtype=torch.int64, device=ctx.device)
+
+
+def surface_leaves(ctx, points, k):
+    """int32 (n,3) numpy cloud already checked by the caller -> (Morton keys of its distinct points, leaf keys), device int64, ascending."""
+    n = int(points.shape[0])
+    pts_d = torch.from_numpy(points).to(ctx.device)
+    pkeys = torch.empty((n,), dtype=torch.int64, device=ctx.device)
+    leaves = torch.empty((n,), dtype=torch.int64, device=ctx.device)
+    hdr, ws = _surface_hdr(ctx), _surface_ws(ctx, 'leaves', n)
+    L.check(L.lib().pcc_surface_leaves(ctx.handle, _ptr(pts_d), n, int(k), _ptr(hdr), _ptr(pkeys), _ptr(leaves), _ptr(ws), ctx.stream),
+            'pcc_surface_leaves')
+    ndistinct, nleaves = (int(v) for v in hdr.cpu()[:2])
+    if not 1 <= nleaves <= ndistinct <= n:
+        raise L.PccError(f'surface_leaves: {ndistinct} distinct points and {nleaves} leaves from {n} points')
+    return pkeys[:ndistinct], leaves[:nleaves]
+
+
+def surface_edges(ctx, leaf_keys):
+    """Leaf keys (device int64, ascending) -> the edge list (device int64, ascending)."""
+    n = int(leaf_keys.shape[0])
+    hdr, ws = _surface_hdr(ctx), _surface_ws(ctx, 'edges', n)
+    edges = torch.empty((12 * n,), dtype=torch.int64, device=ctx.device)
+    L.check(L.lib().pcc_surface_edges(ctx.handle, _ptr(leaf_keys), n, _ptr(hdr), _ptr(edges), _ptr(ws), ctx.stream), 'pcc_surface_edges')
+    nedges = int(hdr.cpu()[0])
+    if not 1 <= nedges <= 12 * n:
+        raise L.PccError(f'surface_edges: {nedges} edges from {n} leaves')
+    return edges[:nedges]
+
+
+def surface_vertices(ctx, pkeys, k, edge_keys):
+    """Distinct point keys and the edge list (device) -> (flags, t) per edge, numpy uint8."""
+    n, nedges = int(pkeys.shape[0]), int(edge_keys.shape[0])
+    out = torch.empty((2, nedges), dtype=torch.uint8, device=ctx.device)
+    ws = _surface_ws(ctx, 'vertices', n)
+    L.check(L.lib().pcc_surface_vertices(ctx.handle, _ptr(pkeys), n, int(k), _ptr(edge_keys), nedges, _ptr(out[0]), _ptr(out[1]), _ptr(ws),
+                                         ctx.stream), 'pcc_surface_vertices')
+    out = out.cpu().numpy()
+    return out[0], out[1]
+
+
+def surface_reconstruct(ctx, leaf_keys, edge_keys, flags, t, k, resolution):
+    """Leaves, edge list (device int64) and the vertices (numpy uint8 per edge) -> the decoded (n,3) int32 cloud (numpy), in Morton order."""
+    dev = ctx.device
+    nleaves, nedges = int(leaf_keys.shape[0]), int(edge_keys.shape[0])
+    flags, t = _u8(flags), _u8(t)
+    assert flags.shape == t.shape == (nedges,), 'surface_reconstruct: one flag and one t per edge'
+    ft = torch.from_numpy(np.stack([flags, t])).to(dev)
+    pos = torch.empty((nleaves,), dtype=torch.int64, device=dev)
+    hdr, ws = _surface_hdr(ctx), _surface_ws(ctx, 'count', nleaves)
+    L.check(L.lib().pcc_surface_count(ctx.handle, _ptr(leaf_keys), nleaves, _ptr(edge_keys), _ptr(ft[0]), _ptr(ft[1]), nedges, int(k), _ptr(pos),
+                                      _ptr(hdr), _ptr(ws), ctx.stream), 'pcc_surface_count')
+    total = int(hdr.cpu()[0])
+    if not nleaves <= total < 1 << 31:
+        raise L.PccError(f'surface_reconstruct: {total} voxels from {nleaves} leaves')
+    pts = torch.empty((total, 3), dtype=torch.int32, device=dev)
+    ws = _surface_ws(ctx, 'reconstruct', total)
+    L.check(L.lib().pcc_surface_reconstruct(ctx.handle, _ptr(leaf_keys), nleaves, _ptr(edge_keys), _ptr(ft[0]), _ptr(ft[1]), nedges, int(k),
+                                            int(resolution), _ptr(pos), total, _ptr(pts), _ptr(hdr), _ptr(ws), ctx.stream), 'pcc_surface_reconstruct')
+    n = int(hdr.cpu()[0])
+    if not 1 <= n <= total:
+        raise L.PccError(f'surface_reconstruct: {n} distinct voxels of {total}')
+    return pts[:n].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------
 class HostCdfTable:
