@@ -285,6 +285,25 @@ int pcc_symbols_pack(pcc_ctx* ctx, const int32_t* src, int32_t N, int64_t vox, i
                      void* dst, int32_t dst_bytes, int32_t* tile_max, void* stream);
 int pcc_symbols_unpack(pcc_ctx* ctx, const void* src, int32_t src_bytes, int32_t N, int64_t vox, int32_t C,
                        int32_t channels_first, int32_t* dst, void* stream);
+/* The same two kernels with the element-wise step before / after them folded in: what pcc_codec_encode / _decode_hyper /
+ * _decode_main launch (one launch where the stand-alone calls need two).  Each gives, bit for bit, what the stand-alone call
+ * followed by pcc_symbols_pack (or pcc_symbols_unpack followed by pcc_dequantize) gives.  N blocks of (vox, C), NDHWC on the
+ * device side, dst / src in stream order as above.
+ * pcc_quantize_pack: pcc_quantize (v, medians (C) or NULL, mode -> sym int32, deq float32 or NULL; both NDHWC) and the packed,
+ *   truncated copy of sym in dst (dst_bytes 1, 2 or 4); tile_max (pcc_symbols_tiles entries, or NULL) receives max|sym| of every
+ *   64 x 64 tile, entry (n * ceil(vox/64) + voxel tile) * ceil(C/64) + channel tile.
+ * pcc_index_pack: pcc_scale_to_index (sigma, table of L in [1,256] entries -> idx int32 NDHWC) and the packed copy of idx in
+ *   dst.  An ascending table (what the reference builds) is searched in log2(L) steps, any other table is counted literally:
+ *   the result is the formula of pcc_scale_to_index either way.
+ * pcc_unpack_dequantize: pcc_symbols_unpack (src, src_bytes -> sym int32 NDHWC) and deq = float(sym) + medians[c]
+ *   (medians (C) or NULL; deq must not be NULL).                                                                            */
+int pcc_quantize_pack(pcc_ctx* ctx, const float* v, const float* medians, int32_t* sym, float* deq, int32_t N, int64_t vox,
+                      int32_t C, int32_t mode, int32_t channels_first, void* dst, int32_t dst_bytes, int32_t* tile_max,
+                      void* stream);
+int pcc_index_pack(pcc_ctx* ctx, const float* sigma, const float* table, int32_t L, int32_t* idx, int32_t N, int64_t vox,
+                   int32_t C, int32_t channels_first, void* dst, int32_t dst_bytes, void* stream);
+int pcc_unpack_dequantize(pcc_ctx* ctx, const void* src, int32_t src_bytes, int32_t N, int64_t vox, int32_t C,
+                          int32_t channels_first, int32_t* sym, const float* medians, float* deq, void* stream);
 
 /* ---- occupancy thresholding + order-preserving compaction ------------------------------
  * Replaces `np.argwhere(x_hat > thresholds[t]).astype(float32)` (src/model_types.py:209,233-234,

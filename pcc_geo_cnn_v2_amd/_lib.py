@@ -22,7 +22,7 @@ EXPORTS = [
     'pcc_conv_out_dims', 'pcc_conv_mfma_supported', 'pcc_conv_packed_floats', 'pcc_conv_pack_weights', 'pcc_conv_kernel_family',
     'pcc_conv3d', 'pcc_quantize', 'pcc_dequantize', 'pcc_scale_to_index', 'pcc_threshold_compact',
     'pcc_threshold_scratch_ints', 'pcc_voxelize', 'pcc_focal_loss', 'pcc_focal_scratch_floats',
-    'pcc_symbols_tiles', 'pcc_symbols_pack', 'pcc_symbols_unpack',
+    'pcc_symbols_tiles', 'pcc_symbols_pack', 'pcc_symbols_unpack', 'pcc_quantize_pack', 'pcc_index_pack', 'pcc_unpack_dequantize',
     'pcc_range_encode_batch', 'pcc_range_decode_batch', 'pcc_range_encode_batch_n', 'pcc_range_decode_batch_n', 'pcc_pmf_to_quantized_cdf',
     'pcc_d1_search_workspace_bytes', 'pcc_d1_threshold_stats', 'pcc_d12_search_workspace_bytes', 'pcc_d12_threshold_stats', 'pcc_octree_bucket',
     'pcc_d12_search_ties_chunk', 'pcc_d12_search_ties_workspace_bytes', 'pcc_d12_threshold_stats_ties',
@@ -238,6 +238,9 @@ def lib():
     L.pcc_symbols_tiles.restype = sz
     L.pcc_symbols_pack.argtypes = [vp, vp, i32, C.c_int64, i32, i32, vp, i32, vp, vp]
     L.pcc_symbols_unpack.argtypes = [vp, vp, i32, i32, C.c_int64, i32, i32, vp, vp]
+    L.pcc_quantize_pack.argtypes = [vp, vp, vp, vp, vp, i32, C.c_int64, i32, i32, i32, vp, i32, vp, vp]
+    L.pcc_index_pack.argtypes = [vp, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, i32, vp]
+    L.pcc_unpack_dequantize.argtypes = [vp, vp, i32, i32, C.c_int64, i32, i32, vp, vp, vp, vp]
     L.pcc_codec_decode_hyper.argtypes = [vp, C.POINTER(CodecDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, i32, C.POINTER(SymbolSink), vp]
     L.pcc_codec_decode_main.argtypes = [vp, C.POINTER(CodecDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_int64, vp,
                                         vp, sz, i32, C.POINTER(SymbolSink), vp]

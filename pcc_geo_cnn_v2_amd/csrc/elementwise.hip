@@ -590,7 +590,7 @@ PCC_API int pcc_symbols_pack(pcc_ctx* ctx, const int32_t* src, int32_t N, int64_
 }
 
 // quantiser + pack / scale fold + pack / unpack + dequantiser in one launch each (the codec graphs, network.hip)
-int pcc_quantize_pack(pcc_ctx* ctx, const float* v, const float* medians, int32_t* sym, float* deq, int32_t N, int64_t vox,
+PCC_API int pcc_quantize_pack(pcc_ctx* ctx, const float* v, const float* medians, int32_t* sym, float* deq, int32_t N, int64_t vox,
                       int32_t C, int32_t mode, int32_t channels_first, void* dst, int32_t dst_bytes, int32_t* tile_max,
                       void* stream) {
     PCC_REQUIRE(v && sym && (mode == PCC_ROUND_FLOOR_HALF || mode == PCC_ROUND_HALF_EVEN), "pcc_quantize_pack: bad argument");
@@ -599,7 +599,7 @@ int pcc_quantize_pack(pcc_ctx* ctx, const float* v, const float* medians, int32_
     return launch_pack<SRC_QUANT>(ctx, ps, N, vox, C, channels_first, dst, dst_bytes, tile_max, stream, "pcc_quantize_pack");
 }
 
-int pcc_index_pack(pcc_ctx* ctx, const float* sigma, const float* table, int32_t L, int32_t* idx, int32_t N, int64_t vox,
+PCC_API int pcc_index_pack(pcc_ctx* ctx, const float* sigma, const float* table, int32_t L, int32_t* idx, int32_t N, int64_t vox,
                    int32_t C, int32_t channels_first, void* dst, int32_t dst_bytes, void* stream) {
     PCC_REQUIRE(sigma && table && idx && L >= 1 && L <= 256, "pcc_index_pack: bad argument");
     PackSrc ps = {};
@@ -632,7 +632,7 @@ PCC_API int pcc_symbols_unpack(pcc_ctx* ctx, const void* src, int32_t src_bytes,
     return launch_unpack(ctx, src, src_bytes, N, vox, C, channels_first, dst, nullptr, nullptr, stream);
 }
 
-int pcc_unpack_dequantize(pcc_ctx* ctx, const void* src, int32_t src_bytes, int32_t N, int64_t vox, int32_t C,
+PCC_API int pcc_unpack_dequantize(pcc_ctx* ctx, const void* src, int32_t src_bytes, int32_t N, int64_t vox, int32_t C,
                           int32_t channels_first, int32_t* sym, const float* medians, float* deq, void* stream) {
     PCC_REQUIRE(deq, "pcc_unpack_dequantize: NULL argument");
     return launch_unpack(ctx, src, src_bytes, N, vox, C, channels_first, sym, medians, deq, stream);

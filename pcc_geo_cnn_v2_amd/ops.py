@@ -372,6 +372,52 @@ def symbols_unpack(ctx, src, ndhwc_shape, channels_first):
     return out
 
 
+def _out(t, shape, dtype, ref):
+    """a caller-supplied output tensor (tests pass views into guarded buffers) or a fresh one"""
+    if t is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=ref.device)
+    assert t.dtype == dtype and t.is_contiguous() and t.device == ref.device and tuple(t.shape) == tuple(shape)
+    return t
+
+
+def quantize_pack(ctx, v, medians, mode, channels_first, dst_ptr, dst_bytes, tile_max_ptr=None, want_deq=True, sym=None, deq=None):
+    """The quantiser fused with symbols_pack, as the encoder graph launches it (pcc_quantize_pack): (N, ..., C) float32 ->
+    (sym int32, deq float32 or None) like quantize(), and sym in stream order as dst_bytes-wide integers at dst_ptr."""
+    assert v.dtype == torch.float32 and v.is_contiguous() and v.device == ctx.device
+    N, Cc = v.shape[0], v.shape[-1]
+    sym = _out(sym, v.shape, torch.int32, v)
+    deq = _out(deq, v.shape, torch.float32, v) if want_deq else None
+    L.check(L.lib().pcc_quantize_pack(ctx.handle, _ptr(v), _ptr(medians), _ptr(sym), _ptr(deq), N, v[0].numel() // Cc, Cc, mode,
+                                      int(bool(channels_first)), C.c_void_p(dst_ptr), dst_bytes,
+                                      None if tile_max_ptr is None else C.c_void_p(tile_max_ptr), ctx.stream), 'pcc_quantize_pack')
+    return sym, deq
+
+
+def index_pack(ctx, sigma, table, channels_first, dst_ptr, dst_bytes, idx=None):
+    """scale_to_index fused with symbols_pack (pcc_index_pack): (N, ..., C) float32 sigma -> idx int32 of the same shape, and idx
+    in stream order as dst_bytes-wide integers at dst_ptr."""
+    assert sigma.dtype == torch.float32 and sigma.is_contiguous() and sigma.device == ctx.device and table.dtype == torch.float32
+    N, Cc = sigma.shape[0], sigma.shape[-1]
+    idx = _out(idx, sigma.shape, torch.int32, sigma)
+    L.check(L.lib().pcc_index_pack(ctx.handle, _ptr(sigma), _ptr(table), table.numel(), _ptr(idx), N, sigma[0].numel() // Cc, Cc,
+                                   int(bool(channels_first)), C.c_void_p(dst_ptr), dst_bytes, ctx.stream), 'pcc_index_pack')
+    return idx
+
+
+def unpack_dequantize(ctx, src, ndhwc_shape, channels_first, medians=None, sym=None, deq=None):
+    """symbols_unpack fused with dequantize, as the decoder graphs launch it (pcc_unpack_dequantize): stream-order device tensor
+    (uint8 / int16 / int32) of N blocks -> (sym int32, deq float32), both (N,D,H,W,C)."""
+    assert src.is_contiguous() and src.device == ctx.device and src.dtype in _ITEM
+    sym = _out(sym, ndhwc_shape, torch.int32, src)
+    deq = _out(deq, ndhwc_shape, torch.float32, src)
+    N, Cc = sym.shape[0], sym.shape[-1]
+    assert src.numel() == sym.numel()
+    L.check(L.lib().pcc_unpack_dequantize(ctx.handle, _ptr(src), _ITEM[src.dtype], N, sym[0].numel() // Cc, Cc,
+                                          int(bool(channels_first)), _ptr(sym), _ptr(medians), _ptr(deq), ctx.stream),
+            'pcc_unpack_dequantize')
+    return sym, deq
+
+
 def codec_encode(ctx, desc, x, thr=None, cap=None, symbols_ready=None, staging=None, scratch=None):
     """The GPU part of compress() (src/model_types.py:289-293 / :379-388) for a batch of blocks in ONE ABI call.
     x: (N,D,H,W) float32.  Returns dict of device tensors (NDHWC); with `thr` (N,) float32 also the encoder-side point
@@ -519,9 +565,10 @@ def mfma_supported(layer, x_shape):
     return L.lib().pcc_conv_mfma_supported(C.byref(d)) == 1
 
 
-def quantize(ctx, v, medians=None, mode=L.PCC_ROUND_FLOOR_HALF, want_sym=True, want_deq=True):
+def quantize(ctx, v, medians=None, mode=L.PCC_ROUND_FLOOR_HALF, want_sym=True, want_deq=True, channels=None):
+    """channels: the channel count when it is not v's last dimension (the channel of element i is i % channels)."""
     assert v.dtype == torch.float32 and v.is_contiguous()
-    Cn = v.shape[-1]
+    Cn = v.shape[-1] if channels is None else int(channels)
     sym = torch.empty(v.shape, dtype=torch.int32, device=v.device) if want_sym else None
     deq = torch.empty_like(v) if want_deq else None
     L.check(L.lib().pcc_quantize(ctx.handle, _ptr(v), _ptr(medians), _ptr(sym), _ptr(deq), v.numel(), Cn, mode,
@@ -529,11 +576,11 @@ def quantize(ctx, v, medians=None, mode=L.PCC_ROUND_FLOOR_HALF, want_sym=True, w
     return sym, deq
 
 
-def dequantize(ctx, sym, medians=None):
+def dequantize(ctx, sym, medians=None, channels=None):
     assert sym.dtype == torch.int32 and sym.is_contiguous()
     deq = torch.empty(sym.shape, dtype=torch.float32, device=sym.device)
-    L.check(L.lib().pcc_dequantize(ctx.handle, _ptr(sym), _ptr(medians), _ptr(deq), sym.numel(), sym.shape[-1],
-                                   ctx.stream), 'pcc_dequantize')
+    L.check(L.lib().pcc_dequantize(ctx.handle, _ptr(sym), _ptr(medians), _ptr(deq), sym.numel(),
+                                   sym.shape[-1] if channels is None else int(channels), ctx.stream), 'pcc_dequantize')
     return deq
 
 

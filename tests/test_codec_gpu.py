@@ -8,6 +8,7 @@ from pcc_geo_cnn_v2_amd import _lib as L
 from pcc_geo_cnn_v2_amd import ops
 from pcc_geo_cnn_v2_amd.model_configs import ModelConfigType
 
+import _pack_ref as PR
 import _stagecheck as SC
 
 pytestmark = pytest.mark.gpu
@@ -403,12 +404,18 @@ def test_symbols_pack_unpack_is_the_stream_order_permutation(ctx, shape, dtype, 
     vox = int(np.prod(shape[1:4]))
     ntiles = L.lib().pcc_symbols_tiles(B, vox, C)
     assert ntiles == B * ((vox + 63) // 64) * ((C + 63) // 64)
-    out = torch.zeros((B, C) + shape[1:4] if cf else shape, dtype=dtype, device=ctx.device)
-    tmax = torch.full((ntiles,), -1, dtype=torch.int32, device=ctx.device)
+    # both destinations between 64 sentinel elements on each side: a vector store running past a partial tile would show there
+    G = 64
+    obuf = torch.full((src.numel() + 2 * G,), 0x5A, dtype=dtype, device=ctx.device)
+    tbuf = torch.full((ntiles + 2 * G,), -1, dtype=torch.int32, device=ctx.device)
+    out, tmax = obuf[G:G + src.numel()].view((B, C) + shape[1:4] if cf else shape), tbuf[G:G + ntiles]
     ops.symbols_pack(ctx, src, cf, out.data_ptr(), out.element_size(), tmax.data_ptr())
     want = (src.permute(0, 4, 1, 2, 3).contiguous() if cf else src).to(dtype)
     assert torch.equal(out, want)
     assert int(tmax.max()) == int(src.abs().max()) and int(tmax.min()) >= 0
+    assert torch.equal(tmax.cpu(), torch.from_numpy(PR.tile_max(src.cpu().numpy())))       # every tile's own maximum, in tile order
+    assert bool((obuf[:G] == 0x5A).all()) and bool((obuf[-G:] == 0x5A).all()), 'written outside dst'
+    assert bool((tbuf[:G] == -1).all()) and bool((tbuf[-G:] == -1).all()), 'written outside tile_max'
     back = ops.symbols_unpack(ctx, out, shape, cf)
     assert torch.equal(back, src)
 
@@ -452,24 +459,74 @@ def test_last_layer_writes_the_occupancy_bits_of_the_fixed_threshold(ctx, res, b
     check(d, s2, False)
 
 
+def graph_models():
+    """Every ModelConfigType that runs on the batched codec graph: all its transforms are reference stacks with a packed network
+    (what CompressionModel._codec needs to return a pcc_codec_desc) and the model stages its symbols (_staging).  Read off the
+    classes, so that a new configuration joins -- or visibly leaves -- the parametrisation below by itself."""
+    names = []
+    for name, cfg in ModelConfigType.__members__.items():
+        cls = cfg.value.model_type.value
+        kinds = [v.value for k, v in cfg.value.model_params.items() if k.endswith('_transform_type')]
+        if hasattr(cls, '_staging') and hasattr(cls, '_codec') and all(getattr(t, 'NET_ID', None) is not None for t in kinds):
+            names.append(name)
+    return names
+
+
+def _graph_pack_check(ctx, name, B):
+    g = torch.Generator().manual_seed(9)
+    m = ModelConfigType[name].build(batch_size=B)
+    m.compress([1, 1, 32, 32, 32])
+    m.set_weights(scaled_weights(m, 2.2))
+    mc = m._ctx(ctx)
+    desc = m._codec(mc)
+    assert desc is not None, f'{name} is listed as a graph model but returns no codec descriptor'
+    v2 = desc.version == 2
+    x = (torch.rand((B, 32, 32, 32), generator=g) < 0.05).float().to(ctx.device)
+    stg = m._staging(mc, 7, B, [4, 4, 4], [2, 2, 2] if v2 else None)
+    t = ops.codec_encode(mc, desc, x, None, staging=stg)
+    if v2:
+        tab = m._dev(mc, 'scale_table', m.conditional_bottleneck.scale_table_f32)
+        assert torch.equal(t['indexes'], ops.scale_to_index(mc, t['sigma_hat'], tab))
+    stg.copy_out()
+    torch.cuda.synchronize()
+    if v2:
+        assert torch.equal(stg.idx, t['indexes'].permute(0, 4, 1, 2, 3).contiguous().to(torch.uint8).cpu())
+    assert torch.equal(stg.ysym, t['symbols'].permute(0, 4, 1, 2, 3).contiguous().to(torch.int16).cpu())
+    if v2:
+        assert torch.equal(stg.zsym, t['z_symbols'].permute(0, 4, 1, 2, 3).contiguous().to(torch.int16).cpu())
+        assert int(stg.ytm.max()) == int(t['symbols'].abs().max()) and int(stg.ztm.max()) == int(t['z_symbols'].abs().max())
+        assert torch.equal(stg.ztm, torch.from_numpy(PR.tile_max(t['z_symbols'].cpu().numpy())))
+    assert int(stg.ytm.max()) == int(t['symbols'].abs().max())
+    assert torch.equal(stg.ytm, torch.from_numpy(PR.tile_max(t['symbols'].cpu().numpy())))
+    # the quantisers folded into the pack launches give what the stand-alone kernel gives on the same y / z
+    med = m._dev(mc, 'medians', m.entropy_bottleneck.medians)
+    sym, deq = ops.quantize(mc, t['z'] if v2 else t['y'], med, m.round_mode)
+    assert torch.equal(sym, t['z_symbols'] if v2 else t['symbols']) and torch.equal(deq, t['z_hat'] if v2 else t['y_hat'])
+    if not v2:
+        return
+    sym, deq = ops.quantize(mc, t['y'], None, m.round_mode)
+    assert torch.equal(sym, t['symbols']) and torch.equal(deq, t['y_hat'])
+    # decoder side: the packed z symbols go back in, the unpack + dequantise and the index + pack launches must give the encoder's
+    # tensors and the encoder's staged rows
+    o, nb, shape, dt = stg.layout['zsym']
+    packed = stg.dev[o:o + nb].view(dt).reshape(shape).clone()
+    rows = torch.full(stg.layout['idx'][2], 0xA5, dtype=stg.idx_dtype, device=ctx.device)
+    d = ops.codec_decode_hyper(mc, desc, None, [32] * 3, packed=packed, channels_first=stg.channels_first, idx_packed=rows)
+    assert torch.equal(d['z_symbols'], t['z_symbols']) and torch.equal(d['z_hat'], t['z_hat'])
+    assert torch.equal(d['indexes'], t['indexes'])
+    assert torch.equal(rows.cpu(), stg.idx)
+
+
 def test_graph_packs_symbols_and_rows_exactly_as_the_stand_alone_kernels(ctx):
     """pcc_codec_encode folds the quantisers and the sigma -> CDF-row step into its pack launches (binary search on the ascending
     scale table the reference builds, patch_gaussian_conditional.py:104-116): the int32 tensors it returns must be what
     pcc_scale_to_index gives on the same sigma_hat, and the staging buffer must hold exactly their stream-order permutation in the
     narrow integer types, with the true max|symbol| in the tile maxima."""
-    g = torch.Generator().manual_seed(9)
-    m = ModelConfigType['c3p'].build(batch_size=2)
-    m.compress([1, 1, 32, 32, 32])
-    m.set_weights(scaled_weights(m, 2.2))
-    mc = m._ctx(ctx)
-    x = (torch.rand((2, 32, 32, 32), generator=g) < 0.05).float().to(ctx.device)
-    stg = m._staging(mc, 7, 2, [4, 4, 4], [2, 2, 2])
-    t = ops.codec_encode(mc, m._codec(mc), x, None, staging=stg)
-    tab = m._dev(mc, 'scale_table', m.conditional_bottleneck.scale_table_f32)
-    assert torch.equal(t['indexes'], ops.scale_to_index(mc, t['sigma_hat'], tab))
-    stg.copy_out()
-    torch.cuda.synchronize()
-    assert torch.equal(stg.idx, t['indexes'].permute(0, 4, 1, 2, 3).contiguous().to(torch.uint8).cpu())
-    assert torch.equal(stg.ysym, t['symbols'].permute(0, 4, 1, 2, 3).contiguous().to(torch.int16).cpu())
-    assert torch.equal(stg.zsym, t['z_symbols'].permute(0, 4, 1, 2, 3).contiguous().to(torch.int16).cpu())
-    assert int(stg.ytm.max()) == int(t['symbols'].abs().max()) and int(stg.ztm.max()) == int(t['z_symbols'].abs().max())
+    _graph_pack_check(ctx, 'c3p', 2)
+
+
+@pytest.mark.parametrize('name', graph_models())
+def test_graph_packs_symbols_and_rows_in_every_graph_model(ctx, name):
+    """the same on every configuration that runs on the codec graph (F = 32 in c1 / c2 / c3: no whole 64-channel tile), three 32^3
+    blocks, and -- hyperprior models -- through the decoder's unpack + dequantise and index + pack launches as well"""
+    _graph_pack_check(ctx, name, 3)
