@@ -712,6 +712,41 @@ int pcc_surface_reconstruct(pcc_ctx* ctx, const uint64_t* leaf_keys, int64_t nle
                             const uint8_t* t, int64_t nedges, int32_t k, int32_t resolution, const uint64_t* pos, int64_t total, int32_t* pts,
                             int64_t* hdr, void* workspace, void* stream);
 
+/* ---- colour anchor (new: an attribute codec for the colours of a voxelised cloud; NOT G-PCC, not RAHT-conformant) ----
+ * pcc_geo_cnn_v2_amd/anchor_color.py holds the stream header, the normative definition (integers only) and a numpy path that gives
+ * the same bytes.  An integer weighted-Haar lifting over the binary Morton tree of N pairwise distinct points: leaves = the points in
+ * ascending key order (the octree anchor's keys over D = depth bits per axis), values = YCoCg-R of their colours.  Leaf i >= 1 owns
+ * one coefficient at step s = the highest bit of key[i - 1] ^ key[i]; its node holds the leaves [p0, p1) that agree with key[i] above
+ * bit s, wL = i - p0, wR = p1 - i, w = wL + wR.  Forward, s ascending: h = val[i] - val[p0], val[p0] += floor(wR h / w); val[0]
+ * ends as the DC.  Quantiser: step = max(1, isqrt(Q Q w / (wL wR))), c = sgn(h) (2 |h| + step) / (2 step).  Inverse, s descending:
+ * aL = val[p0] - floor(wR c step / w), val[p0] = aL, val[i] = aL + c step; then RGB, clipped to [0, 255].  Coding order: steps
+ * descending, i ascending inside a step, channels Y, Co, Cg.
+ * Device side (one stream, no host synchronisation inside a call):
+ *   pcc_color_anchor_plan     points (n,3) int32 -> the plan, kept in `workspace` (pcc_color_anchor_workspace_bytes(npts) bytes, 0
+ *                             outside the contract) for the two calls below, and hdr (device, int64[PCC_COLOR_HDR_WORDS]): hdr[s] =
+ *                             coefficients of step s (s < 64), hdr[64] = adjacent equal keys (duplicate positions: the caller refuses);
+ *   pcc_color_anchor_forward  colours (n,3) uint8 RGB in the row order of the planned points -> coef (device, int16[3 (n - 1)]) in
+ *                             coding order and hdr[65 .. 67] = the DC triple; hdr[0 .. 64] are left as the plan wrote them;
+ *   pcc_color_anchor_inverse  coef (device) and dc (HOST, int32[3], Y in [0, 255], Co, Cg in [-255, 255]) -> colours (n,3) uint8 in
+ *                             the row order of the planned points.
+ * Every index is checked against its count.  Host coder (anchor_coder.cpp): one run of the octree anchor's binary coder over the
+ * coefficients in coding order given the per-step counts (nsteps = 3 D <= 63); g = 2 min(s / 3, 7) + (channel != Y); zero flag under
+ * 32 g + z (z = the previous coefficient of the channel was nonzero), sign under 32 g + 2, v = |c| < 512 as n = bit_length(v) - 1
+ * ones and a zero under 32 g + 3 + j, then the n low bits, MSB first, under 32 g + 12 + j.  PCC_ERR_SPACE when the bytes do not fit
+ * `cap` (48 ncoef + 16 always do).  The decoder returns PCC_ERR_CORRUPT for a ninth one-bit or a payload that ends early and reports
+ * the bytes it read.                                                                                                               */
+#define PCC_COLOR_HDR_WORDS 72
+size_t pcc_color_anchor_workspace_bytes(int64_t npts);
+int pcc_color_anchor_plan(pcc_ctx* ctx, const int32_t* pts, int64_t npts, int32_t depth, int64_t* hdr, void* workspace, void* stream);
+int pcc_color_anchor_forward(pcc_ctx* ctx, const uint8_t* colors, int64_t npts, int32_t depth, int32_t qstep, int64_t* hdr, int16_t* coef,
+                             void* workspace, void* stream);
+int pcc_color_anchor_inverse(pcc_ctx* ctx, const int16_t* coef, const int32_t* dc, int64_t npts, int32_t depth, int32_t qstep, uint8_t* colors,
+                             void* workspace, void* stream);
+int pcc_color_anchor_encode(const int16_t* coef, int64_t ncoef, const int64_t* counts, int32_t nsteps, uint8_t* out, int64_t cap,
+                            int64_t* out_len);
+int pcc_color_anchor_decode(const uint8_t* data, int64_t len, const int64_t* counts, int32_t nsteps, int16_t* coef, int64_t ncoef,
+                            int64_t* consumed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ PCC_IMPL_AUTO, PCC_IMPL_GENERIC, PCC_IMPL_MFMA, PCC_IMPL_WINOGRAD, PCC_IMPL_SPLI
 PCC_ROUND_FLOOR_HALF, PCC_ROUND_HALF_EVEN = 0, 1
 PCC_ANCHOR_NO_CONTEXT, PCC_ANCHOR_HDR_WORDS = 1, 32      # include/pcc_geo.h "octree anchor"
 PCC_SURFACE_HDR_WORDS = 4                                # include/pcc_geo.h "surface anchor"
+PCC_COLOR_HDR_WORDS = 72                                 # include/pcc_geo.h "colour anchor"
 
 EXPORTS = [
     'pcc_abi_version', 'pcc_last_error', 'pcc_ctx_create', 'pcc_ctx_destroy', 'pcc_ctx_num_cu', 'pcc_ctx_get_numerics', 'pcc_ctx_set_numerics',
@@ -44,6 +45,8 @@ EXPORTS = [
     'pcc_surface_encode_vertices', 'pcc_surface_decode_vertices', 'pcc_surface_leaves_workspace_bytes', 'pcc_surface_leaves',
     'pcc_surface_edges_workspace_bytes', 'pcc_surface_edges', 'pcc_surface_vertices_workspace_bytes', 'pcc_surface_vertices',
     'pcc_surface_count_workspace_bytes', 'pcc_surface_count', 'pcc_surface_reconstruct_workspace_bytes', 'pcc_surface_reconstruct',
+    'pcc_color_anchor_workspace_bytes', 'pcc_color_anchor_plan', 'pcc_color_anchor_forward', 'pcc_color_anchor_inverse',
+    'pcc_color_anchor_encode', 'pcc_color_anchor_decode',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -216,6 +219,13 @@ def lib():
     L.pcc_surface_vertices.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp]
     L.pcc_surface_count.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp]
     L.pcc_surface_reconstruct.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
+    L.pcc_color_anchor_workspace_bytes.argtypes = [i64]
+    L.pcc_color_anchor_workspace_bytes.restype = sz
+    L.pcc_color_anchor_plan.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.pcc_color_anchor_forward.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp]
+    L.pcc_color_anchor_inverse.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
+    L.pcc_color_anchor_encode.argtypes = [vp, i64, vp, i32, vp, i64, C.POINTER(i64)]
+    L.pcc_color_anchor_decode.argtypes = [vp, i64, vp, i32, vp, i64, C.POINTER(i64)]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

@@ -283,3 +283,96 @@ PCC_API int pcc_surface_decode_vertices(const uint8_t* data, int64_t len, const 
     delete d;
     return rc;
 }
+
+/* ---- coefficient payload of the colour anchor (include/pcc_geo.h "colour anchor"): one coder run over the coefficients
+ * in coding order -- steps descending (counts[s] coefficients at step s), three channels Y, Co, Cg each.  g = 2 min(s / 3, 7) + (channel
+ * != Y).  Zero flag (1 = nonzero) under model 32 g + z, z = the previous coefficient of the same channel was nonzero; behind a set
+ * flag the sign (1 = negative) under 32 g + 2, then v = |c| in [1, 512): n = bit_length(v) - 1 one-bits and a zero-bit, prefix bit
+ * j under 32 g + 3 + j, then the n low bits of v, most significant first, suffix bit j under 32 g + 12 + j. */
+namespace {
+constexpr int kColorSteps = 63, kColorMaxPrefix = 8;
+bool color_counts_ok(const int64_t* counts, int32_t nsteps, int64_t ncoef) {
+    if (nsteps < 0 || nsteps > kColorSteps || ncoef < 0 || (nsteps > 0 && !counts)) return false;
+    int64_t sum = 0;
+    for (int s = 0; s < nsteps; ++s) {
+        if (counts[s] < 0 || counts[s] > ncoef) return false;
+        sum += counts[s];
+    }
+    return sum == ncoef;
+}
+inline int color_group(int s, int ch) { return 2 * (s / 3 < 7 ? s / 3 : 7) + (ch != 0); }
+}  // namespace
+
+/* coef[3 ncoef] int16 in coding order, |c| < 512 */
+PCC_API int pcc_color_anchor_encode(const int16_t* coef, int64_t ncoef, const int64_t* counts, int32_t nsteps, uint8_t* out, int64_t cap,
+                                    int64_t* out_len) {
+    if (!color_counts_ok(counts, nsteps, ncoef) || cap < 0 || !out_len || (ncoef > 0 && !coef) || (cap > 0 && !out)) {
+        pcc_set_error("pcc_color_anchor_encode: bad argument");
+        return PCC_ERR_ARG;
+    }
+    uint16_t probs[kModels];
+    for (int i = 0; i < kModels; ++i) probs[i] = 1u << (kProbBits - 1);
+    Encoder e(out, cap);
+    int prev[3] = {0, 0, 0};
+    int64_t i = 0;
+    for (int s = nsteps - 1; s >= 0; --s)
+        for (int64_t k = 0; k < counts[s]; ++k, ++i)
+            for (int ch = 0; ch < 3; ++ch) {
+                const int c = coef[3 * i + ch], v = c < 0 ? -c : c, m = 32 * color_group(s, ch);
+                if (v >= (2 << kColorMaxPrefix)) { pcc_set_error("pcc_color_anchor_encode: coefficient %lld is %d", (long long)i, c); return PCC_ERR_ARG; }
+                e.encode(probs[m + prev[ch]], v != 0);
+                prev[ch] = v != 0;
+                if (!v) continue;
+                e.encode(probs[m + 2], c < 0);
+                int n = 0;
+                while ((v >> (n + 1)) != 0) ++n;
+                for (int j = 0; j < n; ++j) e.encode(probs[m + 3 + j], 1);
+                e.encode(probs[m + 3 + n], 0);
+                for (int j = 0; j < n; ++j) e.encode(probs[m + 12 + j], v >> (n - 1 - j) & 1);
+            }
+    e.finish();
+    *out_len = e.len;
+    if (e.overflow) { pcc_set_error("pcc_color_anchor_encode: %lld bytes do not fit %lld", (long long)e.len, (long long)cap); return PCC_ERR_SPACE; }
+    return PCC_OK;
+}
+
+/* *consumed = the bytes of data read (the whole payload for a sound one) */
+PCC_API int pcc_color_anchor_decode(const uint8_t* data, int64_t len, const int64_t* counts, int32_t nsteps, int16_t* coef, int64_t ncoef,
+                                    int64_t* consumed) {
+    if (!color_counts_ok(counts, nsteps, ncoef) || len < 0 || (len > 0 && !data) || !consumed || (ncoef > 0 && !coef)) {
+        pcc_set_error("pcc_color_anchor_decode: bad argument");
+        return PCC_ERR_ARG;
+    }
+    Decoder* d = new (std::nothrow) Decoder;
+    if (!d) { pcc_set_error("pcc_color_anchor_decode: out of memory"); return PCC_ERR_SPACE; }
+    d->init(data, len, 0);
+    int rc = PCC_OK, prev[3] = {0, 0, 0};
+    if (d->past_end) { pcc_set_error("pcc_color_anchor_decode: the payload is shorter than five bytes or does not start with a zero byte"); rc = PCC_ERR_CORRUPT; }
+    int64_t i = 0;
+    for (int s = nsteps - 1; s >= 0 && rc == PCC_OK; --s)
+        for (int64_t k = 0; k < counts[s] && rc == PCC_OK; ++k, ++i)
+            for (int ch = 0; ch < 3 && rc == PCC_OK; ++ch) {
+                const int m = 32 * color_group(s, ch);
+                int c = 0;
+                const int nz = d->decode(d->probs[m + prev[ch]]);
+                prev[ch] = nz;
+                if (nz) {
+                    const int neg = d->decode(d->probs[m + 2]);
+                    int n = 0;
+                    while (n <= kColorMaxPrefix && d->decode(d->probs[m + 3 + n])) ++n;
+                    if (n > kColorMaxPrefix) {
+                        pcc_set_error("pcc_color_anchor_decode: coefficient %lld has a prefix of more than %d ones", (long long)i, kColorMaxPrefix);
+                        rc = PCC_ERR_CORRUPT;
+                        break;
+                    }
+                    int v = 1;
+                    for (int j = 0; j < n; ++j) v = 2 * v + d->decode(d->probs[m + 12 + j]);
+                    c = neg ? -v : v;
+                }
+                if (d->past_end) { pcc_set_error("pcc_color_anchor_decode: the stream ends inside coefficient %lld", (long long)i); rc = PCC_ERR_CORRUPT; break; }
+                coef[3 * i + ch] = (int16_t)c;
+            }
+    *consumed = d->pos;
+    delete d;
+    return rc;
+}

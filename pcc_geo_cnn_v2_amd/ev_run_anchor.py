@@ -25,6 +25,19 @@ anchor_rates when the exact conditions matter.
 under its own id: YAML keys surface_anchor_id (default 'surface-anchor') and surface_rates, a mapping rate name -> node_log2 (default
 r01 .. r04 = 5, 4, 3, 2: four points, because the BD fits need four).  The default, --codec octree, writes what it always wrote.
 
+--color (off by default: without it every file written is what it always was) also codes the colours that map_color put on each
+decoded cloud with the colour anchor (anchor_color.py; not G-PCC, not RAHT-conformant).  YAML key color_rates, a
+mapping rate name -> qstep in 1 .. 255 (default r01 .. r06 = 48, 32, 24, 16, 8, 4: this project's choice, nobody's test conditions).
+A rate directory that has a .color.ply and an entry in color_rates gains
+
+                                                   <pc_name>.ply.bin.color.bin                         the colour stream
+                                                   <pc_name>.ply.bin.decoded.ply.coded.color.ply       the decoded cloud with the coded colours
+                                                   report_color.json                                   colour bytes and bits per input point, geometry +
+                                                                                                       colour bits per input point, ev_report --color's
+                                                                                                       y/u/v mse and psnr of the coded-colour cloud
+
+and the decoded colours are checked against anchor_color.reconstruct.  report.json is untouched.
+
 A step whose outputs exist is skipped, so the command resumes.  The GPU context, each cloud (points, normals, KD-tree / GPU index)
 and its quantisation input stay resident across the rates (ev_experiment.Resident); the reports of all rates of a cloud are measured
 in one pass.
@@ -46,6 +59,7 @@ DEFAULT_ID = 'octree-anchor'
 DEFAULT_RATES = {'r01': (1, 8), 'r02': (1, 4), 'r03': (1, 2), 'r04': (3, 4), 'r05': (7, 8), 'r06': (15, 16)}
 SURFACE_DEFAULT_ID = 'surface-anchor'
 SURFACE_DEFAULT_RATES = {'r01': 5, 'r02': 4, 'r03': 3, 'r04': 2}
+COLOR_DEFAULT_RATES = {'r01': 48, 'r02': 32, 'r03': 24, 'r04': 16, 'r05': 8, 'r06': 4}
 CODECS = ('octree', 'surface', 'both')
 FORBIDDEN_LABEL = 'G-PCC'
 
@@ -84,6 +98,14 @@ def surface_settings(exp):
     return anchor_id, rates, device
 
 
+def color_settings(exp):
+    """-> {rate: qstep} of --color.  Raises for a qstep outside 1 .. 255."""
+    from . import anchor_color as AC
+    rates = exp.get('color_rates') or COLOR_DEFAULT_RATES
+    assert isinstance(rates, dict) and rates, 'color_rates: a mapping rate name -> qstep'
+    return {str(k): AC.check_qstep(v) for k, v in rates.items()}
+
+
 class _Octree:
     """One codec of run(): its id, its rates and the three functions of a rate's parameter."""
 
@@ -108,27 +130,57 @@ def rate_dir(exp, anchor_id, pc_name, rate):
     return os.path.join(exp['EXPERIMENT_DIR'], 'gpcc', anchor_id, pc_name, rate)
 
 
-def run(exp, resident=None, codec='octree'):
-    """Returns {'coded': n, 'reports': n}: the steps that ran (0, 0 when everything existed).  codec: one of CODECS."""
+def run(exp, resident=None, codec='octree', color=False):
+    """Returns {'coded': n, 'reports': n}: the steps that ran (0, 0 when everything existed), with color=True also 'colors': n.
+    codec: one of CODECS."""
     from .ev_experiment import Resident
     assert codec in CODECS, f'codec must be one of {CODECS}, got {codec!r}'
     assert os.path.isdir(exp['EXPERIMENT_DIR']), f"{exp['EXPERIMENT_DIR']} not found"
     anchors = [cls(exp) for name, cls in (('octree', _Octree), ('surface', _Surface)) if codec in (name, 'both')]     # every label checked first
     assert len({a.anchor_id for a in anchors}) == len(anchors), 'anchor_id and surface_anchor_id must differ'
     res = resident if resident is not None else Resident()
-    done = {'coded': 0, 'reports': 0}
+    color_rates = color_settings(exp) if color else None
+    done = {'coded': 0, 'reports': 0, **({'colors': 0} if color else {})}
     for anchor in anchors:
-        for key, n in _run_one(exp, res, anchor).items():
+        for key, n in _run_one(exp, res, anchor, color_rates).items():
             done[key] += n
     return done
 
 
-def _run_one(exp, res, anchor):
+def _code_colors(res, original, device, enc, dec, col, report, qstep):
+    """The --color step of one rate directory: the colour stream, the coded-colour cloud and report_color.json."""
+    from . import anchor_color as AC
+    from . import ops
+    from .utils import pc_io
+    from .utils.pc_metric import color_table
+    pts, colors = pc_io.load_pc(col), pc_io.load_colors(col)
+    # a decoder's clip to the grid can put two points on one voxel: they carry one mapped colour, which is coded once
+    upts, first, inverse = np.unique(np.asarray(pts, np.int64), axis=0, return_index=True, return_inverse=True)
+    ctx = res.ctx if device == 'gpu' else None
+    data = AC.encode(upts, colors[first], qstep, device, ctx)
+    coded = AC.decode(data, upts, device, ctx)
+    assert np.array_equal(coded, AC.reconstruct(upts, colors[first], qstep)), f'{col}: the decoded colours are not the encoder\'s reconstruction'
+    coded = coded[inverse.reshape(-1)]
+    tally = ops.cloud_color_distortion(res.ctx, original.index, original.colors, np.asarray(pts, np.float64)[:, :3], coded)
+    n, geometry = len(original.points), os.stat(enc).st_size
+    out = {'color_qstep': qstep, 'color_total_size_in_bytes': len(data), 'color_bits_per_input_point': len(data) * 8 / n,
+           'total_bits_per_input_point': (geometry + len(data)) * 8 / n, 'input_point_count': n}
+    out.update({k: float(v) for k, v in color_table(tally, n, len(pts)).items()})
+    pc_io.write_df(dec + '.coded.color.ply', pc_io.pa_to_df(np.concatenate([np.asarray(pts, np.float64), coded], axis=1)))
+    with open(enc + '.color.bin.tmp', 'wb') as f:
+        f.write(data)
+    os.replace(enc + '.color.bin.tmp', enc + '.color.bin')
+    with open(report + '.tmp', 'w') as f:
+        json.dump(out, f, sort_keys=True, indent=4)
+    os.replace(report + '.tmp', report)
+
+
+def _run_one(exp, res, anchor, color_rates=None):
     from .ev_experiment import _recolor, measure
     from .utils import pc_io
     A, anchor_id, rates, device = anchor.codec, anchor.anchor_id, anchor.rates, anchor.device
     metrics_device, d2_ties = exp.get('metrics_device', 'host'), exp.get('d2_ties', 'pick')
-    done = {'coded': 0, 'reports': 0}
+    done = {'coded': 0, 'reports': 0, **({'colors': 0} if color_rates is not None else {})}
     t0 = time.perf_counter()
     for entry in exp['data']:
         pc_name = entry['pc_name']
@@ -161,6 +213,14 @@ def _run_one(exp, res, anchor):
             elif original.colors is not None:
                 logger.info(f'[{dec}] -> [{col}]')
                 _recolor(res, original, dec, col)
+            if color_rates is not None and rate in color_rates and os.path.exists(col):
+                creport = os.path.join(out, 'report_color.json')
+                if os.path.exists(creport):
+                    logger.info(f'[{col}] -> [{creport}] (exists)')
+                else:
+                    logger.info(f'[{col}] -> [{enc}.color.bin, {dec}.coded.color.ply, {creport}] qstep {color_rates[rate]}')
+                    _code_colors(res, original, device, enc, dec, col, creport, color_rates[rate])
+                    done['colors'] += 1
             if not os.path.exists(report):
                 todo.append((dec, enc, report))
         if todo:
@@ -186,8 +246,10 @@ def main(argv=None):
     p.add_argument('experiment_path', help='Experiments file path.')
     p.add_argument('--codec', choices=CODECS, default='octree', help='Which anchor to run: the octree anchor, the surface anchor (a triangle-soup '
                    'class codec; not G-PCC, not trisoup-conformant) or both')
+    p.add_argument('--color', default=False, action='store_true', help='Also code the colours map_color put on each decoded cloud with the colour '
+                   'anchor (not G-PCC, not RAHT-conformant) and write report_color.json beside report.json')
     a = p.parse_args(argv)
-    run(E.load_experiment(a.experiment_path), codec=a.codec)
+    run(E.load_experiment(a.experiment_path), codec=a.codec, color=a.color)
     return 0
 
 

@@ -1471,6 +1471,101 @@ def surface_reconstruct(ctx, leaf_keys, edge_keys, flags, t, k, resolution):
 
 
 # ---------------------------------------------------------------------------------------------
+# colour anchor (include/pcc_geo.h "colour anchor"; the codec is anchor_color.py)
+# ---------------------------------------------------------------------------------------------
+def _color_counts(counts):
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    assert counts.ndim == 1 and counts.size <= 63, 'colour anchor: one count per step, at most 63 steps'
+    return counts
+
+
+def color_anchor_encode_coefficients(coef, counts):
+    """Coefficients (n,3) int16 in coding order and the per-step counts -> the payload bytes (host)."""
+    coef, counts = np.ascontiguousarray(coef, dtype=np.int16), _color_counts(counts)
+    assert coef.ndim == 2 and coef.shape[1] == 3, 'color_anchor_encode_coefficients: coefficients must be (n, 3)'
+    n = C.c_int64()
+    for per_coef in (6, 48):                 # 48 bytes a coefficient always fit; the first try spares the memory
+        out = np.empty(per_coef * coef.shape[0] + 16, np.uint8)
+        rc = L.lib().pcc_color_anchor_encode(coef.ctypes.data, coef.shape[0], counts.ctypes.data, counts.size, out.ctypes.data, out.size, C.byref(n))
+        if rc != L.PCC_ERR_SPACE:
+            break
+    L.check(rc, 'pcc_color_anchor_encode')
+    return out[:n.value].tobytes()
+
+
+def color_anchor_decode_coefficients(data, counts, ncoef):
+    """-> (coefficients (ncoef,3) int16, bytes read) of a payload (host); PccError when it is damaged or ends early."""
+    counts = _color_counts(counts)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    coef = np.zeros((int(ncoef), 3), np.int16)
+    consumed = C.c_int64()
+    L.check(L.lib().pcc_color_anchor_decode(buf.ctypes.data if buf.size else None, buf.size, counts.ctypes.data, counts.size, coef.ctypes.data,
+                                            int(ncoef), C.byref(consumed)), 'pcc_color_anchor_decode')
+    return coef, consumed.value
+
+
+def _color_ws(ctx, n):
+    nbytes = L.lib().pcc_color_anchor_workspace_bytes(int(n))
+    if nbytes == 0:
+        raise L.PccError(f'color_anchor: {n} points are outside the contract')
+    with torch.cuda.device(ctx.device):         # hipCUB sizes its temporary storage for the current device
+        return torch.empty((nbytes,), dtype=torch.uint8, device=ctx.device)
+
+
+def _color_hdr(raw, n):
+    hdr = raw[:8 * L.PCC_COLOR_HDR_WORDS].view(np.int64)
+    counts, dups = hdr[:64].copy(), int(hdr[64])
+    if dups == 0 and (counts.min() < 0 or int(counts.sum()) != n - 1):
+        raise L.PccError(f'color_anchor: the per-step counts sum to {int(counts.sum())} for {n} points')
+    return counts, dups, hdr[65:68].copy()
+
+
+def color_anchor_plan(ctx, points, depth):
+    """int32 (n,3) numpy cloud already checked by the caller -> (the planned workspace for color_anchor_inverse (device), per-step
+    counts int64[64], number of adjacent equal keys: nonzero = duplicate positions).  One copy back."""
+    n = int(points.shape[0])
+    pts_d = torch.from_numpy(points).to(ctx.device)
+    hdr = torch.empty((L.PCC_COLOR_HDR_WORDS,), dtype=torch.int64, device=ctx.device)
+    ws = _color_ws(ctx, n)
+    L.check(L.lib().pcc_color_anchor_plan(ctx.handle, _ptr(pts_d), n, int(depth), _ptr(hdr), _ptr(ws), ctx.stream), 'pcc_color_anchor_plan')
+    counts, dups, _ = _color_hdr(hdr.cpu().numpy().view(np.uint8), n)
+    return ws, counts, dups
+
+
+def color_anchor_transform(ctx, points, colors, depth, qstep):
+    """Plan and forward transform of an int32 (n,3) cloud and its uint8 (n,3) colours, both already checked by the caller ->
+    (counts int64[64], adjacent equal keys, DC int64[3], coefficients (n - 1, 3) int16 in coding order).  Both calls are enqueued
+    before the one copy back."""
+    lib, dev = L.lib(), ctx.device
+    n = int(points.shape[0])
+    hdr_bytes = 8 * L.PCC_COLOR_HDR_WORDS
+    pts_d, col_d = torch.from_numpy(points).to(dev), torch.from_numpy(colors).to(dev)
+    out = torch.empty((hdr_bytes + 6 * (n - 1),), dtype=torch.uint8, device=dev)
+    ws = _color_ws(ctx, n)
+    base = out.data_ptr()
+    L.check(lib.pcc_color_anchor_plan(ctx.handle, _ptr(pts_d), n, int(depth), C.c_void_p(base), _ptr(ws), ctx.stream), 'pcc_color_anchor_plan')
+    L.check(lib.pcc_color_anchor_forward(ctx.handle, _ptr(col_d), n, int(depth), int(qstep), C.c_void_p(base),
+                                         C.c_void_p(base + hdr_bytes) if n > 1 else None, _ptr(ws), ctx.stream), 'pcc_color_anchor_forward')
+    raw = out.cpu().numpy()
+    counts, dups, dc = _color_hdr(raw, n)
+    return counts, dups, dc, raw[hdr_bytes:].view(np.int16).reshape(n - 1, 3).copy()
+
+
+def color_anchor_inverse(ctx, plan, coef, dc, n, depth, qstep):
+    """A workspace color_anchor_plan filled for the same n points, coefficients (n - 1, 3) int16 in coding order and the DC triple ->
+    the (n,3) uint8 colours (numpy) in the row order of the planned points."""
+    coef = np.ascontiguousarray(coef, dtype=np.int16)
+    assert coef.shape == (n - 1, 3), 'color_anchor_inverse: one coefficient triple per point but the first'
+    coef_d = torch.from_numpy(coef).to(ctx.device) if n > 1 else None
+    dc = np.ascontiguousarray(dc, dtype=np.int32)
+    assert dc.shape == (3,), 'color_anchor_inverse: the DC is a triple'
+    out = torch.empty((n, 3), dtype=torch.uint8, device=ctx.device)
+    L.check(L.lib().pcc_color_anchor_inverse(ctx.handle, _ptr(coef_d), dc.ctypes.data, int(n), int(depth), int(qstep), _ptr(out), _ptr(plan),
+                                             ctx.stream), 'pcc_color_anchor_inverse')
+    return out.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------
 # host range coder
 # ---------------------------------------------------------------------------------------------
 class HostCdfTable:
