@@ -618,6 +618,46 @@ int pcc_range_decode_batch_n(const pcc_cdf_table* t, int32_t n_streams, const ui
 /* tfc `pmf_to_quantized_cdf` (src/utils/patch_gaussian_conditional.py:87-89): pmf[n] -> cdf[n+1]. */
 int pcc_pmf_to_quantized_cdf(const float* pmf, int32_t n, int32_t precision, int32_t* cdf);
 
+/* ---- rANS coder (DEVICE): the opt-in "rans1" string format, a second format beside the range coder's ----------
+ * An interleaved rANS: 32-bit state in [2^16, 2^32), initial state 2^16, 16-bit words, 16-bit probabilities (any other
+ * `precision` of the table: PCC_ERR_ARG; so is a table with a frequency outside [1, 65535] -- then a lane moves at most one word
+ * per symbol).  A stream of n symbols uses L in {1, 2, .., 64} lanes, symbol i on lane i % L at step i / L.  Row of symbol i:
+ * index[i], or i % index_mod when index is NULL; with m = cdf_size[row] - 2, a value v with 0 <= v - offset[row] < m takes bin
+ * v - offset[row], any other takes bin m and its raw int32 goes to the escape list (overflow_width is not used).
+ * The decoder walks the steps upwards; after decoding its symbol a lane whose state fell below 2^16 reads one word from a single
+ * forward cursor, lanes in ascending order within a step.  String bytes (little-endian): one byte log2(L); the escape count as a
+ * LEB128 varint; L final states of 4 bytes; the words; the escapes, 4 bytes each.  n = 0 codes as the empty string.
+ * L (lanes = 0): with cost256(f) = 256 (16 - k) - ((r << 8) >> k) for f = 2^k + r and est = (sum of cost256 + 2047) >> 11, the
+ * largest power of two <= 64 with 128 L <= est, at least 1.  lanes > 0 forces that L (a power of two <= 64).
+ *
+ * One wave codes one stream.  Every pointer except `t` (host, as for the range coder; its arrays are uploaded once per context and
+ * table and kept) and status_host is a DEVICE pointer:
+ *   data / out   : int32 symbols, stream s at s * data_stride (out_stride) elements; index: int32 rows, stream s at s * index_stride
+ *                  (0: one row vector shared by all streams); n[s] <= n_max symbols per stream;
+ *   channels > 0 : the tensors are (n / channels, channels) in memory and the stream is channel-major: symbol i and its row are
+ *                  read (written) at element (i % vox) * channels + i / vox, vox = n / channels -- the codec's NDHWC tensors
+ *                  under data_format channels_first, without a permuted copy;
+ *   encoder      : string s at out + s * cap with cap >= pcc_rans_stream_cap(n_max) (= 1 + 10 + 4 * 64 + 6 n_max), its length in
+ *                  out_len[s]; status[s] != 0: a row outside the table / n[s] not a multiple of `channels` (the string is void);
+ *                  workspace of pcc_rans_workspace_bytes(n_streams, n_max) bytes;
+ *   decoder      : string s = str[off[s], off[s] + len[s]) inside the str_bytes bytes of `str`.  The kernel tests the header against
+ *                  len[s] and clamps every cursor, so a truncated or inconsistent string never reads outside itself; it sets
+ *                  status[s] != 0 when the string does not end exactly where its symbols do.  status_host (n_streams ints, may be
+ *                  NULL): the call waits for the stream and returns PCC_ERR_CORRUPT / PCC_ERR_ARG from the flags; NULL: the
+ *                  flags stay in status[] for the caller to fetch.
+ * pcc_rans_check_strings (HOST pointers): the same header test before the upload -- PCC_ERR_CORRUPT.                              */
+size_t pcc_rans_stream_cap(int64_t n);
+size_t pcc_rans_workspace_bytes(int32_t n_streams, int64_t n_max);
+int pcc_rans_check_strings(int32_t n_streams, const uint8_t* str, const int64_t* off, const int32_t* len, const int32_t* n);
+int pcc_rans_encode_batch(pcc_ctx* ctx, const pcc_cdf_table* t, int32_t n_streams, const int32_t* data, int64_t data_stride,
+                          const int32_t* index, int64_t index_stride, int32_t index_mod, int32_t channels, const int32_t* n,
+                          int32_t n_max, int32_t lanes, uint8_t* out, size_t cap, int32_t* out_len, int32_t* status,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int pcc_rans_decode_batch(pcc_ctx* ctx, const pcc_cdf_table* t, int32_t n_streams, const uint8_t* str, size_t str_bytes,
+                          const int64_t* off, const int32_t* len, const int32_t* index, int64_t index_stride, int32_t index_mod,
+                          int32_t channels, const int32_t* n, int32_t n_max, int32_t* out, int64_t out_stride, int32_t* status,
+                          int32_t* status_host, void* stream);
+
 /* ---- octree blocking, host (replaces the per-point loop of src/utils/octree_coding.py:82-108) ----------------------
  * Buckets `n` points (row-major doubles, `ncols` >= 3 columns, x y z first) into blocks of edge `block_size`:
  * bucket = Morton code of the block id over `level` bits per axis, x least significant.  order[n] receives the point

@@ -182,6 +182,7 @@ def compress(args):
     import torch
     from . import ops
     from .model_configs import ModelConfigType
+    from .model_syntax import coder_tag
     from .utils import pc_io
     from .utils.octree_coding import partition_octree
     T.mark('imports')
@@ -210,7 +211,8 @@ def compress(args):
     logger.info(f'Processing resolution {args.resolution} with octree level {args.octree_level} resulting in dense_tensor_shape '
                 f'{block_shape} and {sum(len(blocks) for blocks, _ in partitions)} blocks')
 
-    model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
+    model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision,
+                                                    entropy_coder=getattr(args, 'entropy_coder', 'range'))
     model.d2_search = getattr(args, 'd2_search', None)      # per model, not a module global
     model.search_ties = getattr(args, 'search_ties', 'pick')
     model.compress(np.concatenate(((1,), block_shape)))
@@ -232,7 +234,7 @@ def compress(args):
             if len(streams) != len(cloud.targets):
                 raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
             for n, target in enumerate(cloud.targets):
-                infos[n]['numerics_tag'] = sess.numerics_tag(args.precision)
+                infos[n]['numerics_tag'] = coder_tag(sess.numerics_tag(args.precision), model.entropy_coder)
                 _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
             logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
         T.mark('container_gzip_write')
@@ -294,6 +296,10 @@ def build_parser():
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'fp16'],
                         help='fp16: fp16 matrix instructions with fp32 accumulation on the conv layers (new; must match between '
                              'compress and decompress).')
+    parser.add_argument('--entropy_coder', default='range', choices=['range', 'rans'],
+                        help="String format (new): range = the host range coder (tfc's algorithm, the default: files unchanged), "
+                             'rans = the interleaved rANS coded on the GPU; the stream names it (numerics tag suffix /rans1), so '
+                             'decompress_octree needs no flag.')
     return parser
 
 

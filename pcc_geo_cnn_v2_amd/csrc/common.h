@@ -59,6 +59,7 @@ int pcc_block_amax(pcc_ctx* ctx, const float* x, int N, size_t per_block, unsign
 int pcc_ctx_scratch(pcc_ctx* ctx, size_t bytes, void** ptr);
 uint32_t pcc_numerics_from_env();
 void pcc_profile_free(pcc_ctx* ctx);
+void pcc_rans_free(pcc_ctx* ctx);      // the context's device CDF tables (rans_coder.hip)
 
 void pcc_set_error(const char* fmt, ...);
 

@@ -102,6 +102,7 @@ int pcc_ctx_amax(pcc_ctx* ctx, int n, unsigned** ptr) {
 
 PCC_API int pcc_ctx_destroy(pcc_ctx* ctx) {
     if (ctx) pcc_profile_free(ctx);
+    if (ctx) pcc_rans_free(ctx);
     if (ctx && ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx && ctx->amax) (void)hipFree(ctx->amax);
     if (ctx && ctx->summary_limits) (void)hipFree(ctx->summary_limits);

@@ -32,7 +32,7 @@ def decompress(args):
     import torch
     from . import ops, sharding
     from .model_configs import ModelConfigType
-    from .model_syntax import check_numerics_tag, load_compressed_file, read_gzip_tag
+    from .model_syntax import load_compressed_file, read_gzip_tag, stream_coder
     from .utils import pc_io
     from .utils.octree_coding import departition_octree
     T.mark('imports')
@@ -60,9 +60,11 @@ def decompress(args):
     T.mark('context', sess.device)
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
-    compressed_data = []
+    compressed_data, coders = [], []
     for file in args.input_files:
-        check_numerics_tag(read_gzip_tag(file), sess.numerics_tag(args.precision), ignore=args.ignore_numerics_tag)
+        # the stream names its entropy coder (tag suffix); the rest of the tag is compared as before
+        coders.append(stream_coder(read_gzip_tag(file), sess.numerics_tag(args.precision), getattr(args, 'entropy_coder', None),
+                                   ignore=args.ignore_numerics_tag))
         with gzip.open(file, 'rb') as f:
             compressed_data.append(load_compressed_file(f))
     T.mark('container_read_gunzip')
@@ -77,6 +79,7 @@ def decompress(args):
             zip(compressed_data, args.input_files, args.output_files)):
         logger.info(f'{i}/{len(args.input_files)} - Writing {ori_file} to {output_file} with {len(blocks)} blocks')
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
+        model.entropy_coder = coders[i]
         dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug)
         T.mark('decompress_blocks', sess.device)
         if args.debug and rank == 0:
@@ -123,6 +126,8 @@ def build_parser():
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'fp16'],
                         help='fp16: fp16 matrix instructions with fp32 accumulation on the conv layers (new; must match between '
                              'compress and decompress).')
+    parser.add_argument('--entropy_coder', default=None, choices=['range', 'rans'],
+                        help='Entropy coder of input files that carry no numerics tag (new; default range).  A tagged file names its own.')
     return parser
 
 

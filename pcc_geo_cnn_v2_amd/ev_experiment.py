@@ -173,6 +173,7 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
             fixed_threshold, metrics_device, d2_ties, batch_size):
     """compress_octree.compress for one cloud on the resident state: the same arguments, the same plan, the same writer."""
     from . import compress_octree as CO
+    from .model_syntax import coder_tag
     argv = ['--input_files', original.input_pc, '--output_files', *enc_pcs, '--checkpoint_dir', model_dir, '--model_config', model_config,
             '--opt_metrics', *opt_metrics, '--max_deltas', *[str(d) for d in max_deltas], '--resolution', str(resolution),
             '--octree_level', str(octree_level), '--metrics_device', metrics_device, '--d2_ties', d2_ties, '--batch_size', str(batch_size)]
@@ -192,6 +193,7 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
     box, block_shape = CO._block_grid(args.resolution, args.octree_level, args.data_format)
     blocks, binstr = original.partition(box, args.octree_level)
     model = res.model('enc', model_config, model_dir, args.batch_size, args.precision, block_shape)
+    model.entropy_coder = args.entropy_coder
     model.d2_search = args.d2_search
     model.search_ties = args.search_ties
     cloud = clouds[0]
@@ -202,20 +204,20 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
     if len(streams) != len(cloud.targets):
         raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
     for n, target in enumerate(cloud.targets):
-        infos[n]['numerics_tag'] = sess.numerics_tag(args.precision)
+        infos[n]['numerics_tag'] = coder_tag(sess.numerics_tag(args.precision), model.entropy_coder)
         CO._write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks,
                              debug_t_list)
 
 
 def _decode(res, enc_pcs, dec_pcs, model_dir, model_config, batch_size, precision='fp32'):
     """decompress_octree.decompress for some files on the resident state."""
-    from .model_syntax import check_numerics_tag, load_compressed_file, read_gzip_tag
+    from .model_syntax import load_compressed_file, read_gzip_tag, stream_coder
     from .utils import pc_io
     from .utils.octree_coding import departition_octree
     sess = res.ctx
     model = res.model('dec', model_config, model_dir, batch_size, precision)
     for enc, dec in zip(enc_pcs, dec_pcs):
-        check_numerics_tag(read_gzip_tag(enc), sess.numerics_tag(precision), ignore=False)
+        model.entropy_coder = stream_coder(read_gzip_tag(enc), sess.numerics_tag(precision))      # the stream names its coder
         with gzip.open(enc, 'rb') as f:
             resolution, level, binstr, blocks = load_compressed_file(f)
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)

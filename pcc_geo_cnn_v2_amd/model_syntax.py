@@ -132,6 +132,44 @@ def read_gzip_tag(path):
         return cstring().decode('latin-1') if flg & 0x10 else None
 
 
+# entropy coder of a stream -> what it appends to the numerics tag ('range', the default, appends nothing: its files are unchanged)
+CODER_SUFFIX = {'range': None, 'rans': 'rans1'}
+
+
+def coder_tag(tag, entropy_coder):
+    """The numerics tag of a stream written with `entropy_coder`."""
+    suffix = CODER_SUFFIX[entropy_coder]
+    return tag if suffix is None else f'{tag}/{suffix}'
+
+
+def split_coder_tag(tag):
+    """(numerics tag without the coder suffix, entropy coder) of a stream's tag; (tag, None) for a stream without a tag of ours.  An
+    unknown suffix is refused: the strings could not be parsed."""
+    if tag is None or not tag.startswith('pcc_geo_cnn_v2_amd/'):
+        return tag, None
+    parts = tag.split('/')
+    if len(parts) <= 4:
+        return tag, 'range'
+    suffix = '/'.join(parts[4:])
+    for coder, known in CODER_SUFFIX.items():
+        if known == suffix:
+            return '/'.join(parts[:4]), coder
+    raise RuntimeError(f'the stream was written with the entropy coder {suffix!r} ({tag}); this build reads '
+                       f'{sorted(k for k in CODER_SUFFIX.values() if k)} and the untagged range coder')
+
+
+def stream_coder(tag, expected, override=None, ignore=False):
+    """Decoder side: the entropy coder the stream names (an untagged stream: `override`, default 'range'); the rest of the tag is
+    compared with `expected` as check_numerics_tag does."""
+    base, coder = split_coder_tag(tag)
+    check_numerics_tag(base, expected, ignore=ignore)
+    if coder is None:
+        return override or 'range'
+    if override is not None and override != coder:
+        logger.warning('--entropy_coder %s ignored: the stream says %s', override, coder)
+    return coder
+
+
 def check_numerics_tag(tag, expected, ignore=False):
     """Decoder side.  No tag: a stream of the reference or of a build before the tag existed -- nothing to compare, logged.  Another
     tag: refuse (or warn with ignore=True) -- the decoded cloud could be silent garbage."""

@@ -131,6 +131,9 @@ def _host_dtypes(levels=64):
     return torch.int16, (torch.uint8 if levels <= 256 else torch.int32)
 
 
+ENTROPY_CODERS = ('range', 'rans')
+
+
 class _Pinned:
     """Cache of pinned host staging buffers keyed by (tag, shape, dtype)."""
 
@@ -168,8 +171,12 @@ class _Pinned:
 
 class CompressionModel:
     def __init__(self, n_thresholds=2 ** 8, data_format='channels_first', batch_size=32,
-                 round_mode=L.PCC_ROUND_FLOOR_HALF, coder_threads=0, seed=42, precision='fp32', search_threads=0):
+                 round_mode=L.PCC_ROUND_FLOOR_HALF, coder_threads=0, seed=42, precision='fp32', search_threads=0,
+                 entropy_coder='range'):
         assert precision in ('fp32', 'fp16'), "precision: 'fp32' (the reference's arithmetic) or 'fp16' (fp16 matrix instructions, fp32 accumulate)"
+        assert entropy_coder in ENTROPY_CODERS, f"entropy_coder: 'range' (the host range coder, tfc's bytes) or 'rans' (the device coder), not {entropy_coder!r}"
+        # which string format compress() writes and decompress() reads: part of the stream (the CLIs record it in the numerics tag)
+        self.entropy_coder = entropy_coder
         self.precision = precision
         self.thresholds = np.linspace(0, 1.0, n_thresholds)
         self.data_format = data_format
@@ -383,6 +390,52 @@ class CompressionModel:
         main.wait_event(arrived)
         dev.record_stream(main)
         return dev
+
+    # ---- entropy_coder='rans': the strings are coded on the device from the int32 (B,D,H,W,C) tensors as the codec leaves them.  Under
+    # channels_first the kernels walk them channel-major (`channels`), and the EntropyBottleneck rows are one cached row vector in
+    # that memory order; nothing is narrowed, staged in pinned rings or handed to the host coder pool.
+    def _rans_layout(self, ctx, n_per_block, eb):
+        """(index, index_mod, channels) of ops.rans_*: eb = the EntropyBottleneck's per-channel rows, else the caller's index tensor"""
+        F = self.num_filters
+        cf = self.data_format == 'channels_first'
+        if not eb:
+            return None, 0, F if cf else 0
+        if not cf:
+            return None, F, 0
+        name = ('rans_rows', n_per_block, F)
+        rows = self._dev_cache.get((ctx.device.index, name))
+        if rows is None:
+            rows = self._dev(ctx, name, np.tile(np.arange(F, dtype=np.int32), n_per_block // F))
+        return rows, 0, F
+
+    def _rans_encode(self, ctx, ready, jobs):
+        """jobs: (table, symbols, index or None, eb) per string kind.  The launches run on the side stream once `ready` (default: now,
+        on the main stream) has passed, beside the synthesis transform.  Returns fetch() -> one list of strings per job."""
+        main, side = torch.cuda.current_stream(ctx.device), self._side_stream(ctx)
+        if ready is None:
+            ready = torch.cuda.Event()
+            ready.record(main)
+        with torch.cuda.stream(side):
+            side.wait_event(ready)
+            launched = []
+            for table, sym, index, eb in jobs:
+                rows, mod, channels = self._rans_layout(ctx, sym[0].numel(), eb)
+                for t in (sym, index):
+                    if t is not None:
+                        t.record_stream(side)
+                launched.append(ops.rans_encode_launch(ctx, table, sym, None, rows if eb else index, mod, channels))
+
+        def fetch():
+            with torch.cuda.stream(side):           # (the copies wait for the side stream only, never for the main queue)
+                return [ops.rans_encode_fetch(out, meta) for out, meta in launched]
+        return fetch
+
+    def _rans_decode(self, ctx, table, strings, shape, index, eb):
+        """strings -> (symbols (B,D,H,W,C) int32 on the device, status flags for ops.rans_check_status), on the current stream"""
+        sym = torch.empty(tuple(shape), dtype=torch.int32, device=ctx.device)
+        n = sym[0].numel()
+        rows, mod, channels = self._rans_layout(ctx, n, eb)
+        return ops.rans_decode_batch(ctx, table, strings, [n] * len(strings), rows if eb else index, mod, channels, out=sym, check=False)
 
     def _unpack(self, ctx, packed, dhw):
         return ops.symbols_unpack(ctx, packed, (packed.shape[0],) + tuple(dhw) + (self.num_filters,), self.data_format == 'channels_first')
@@ -748,7 +801,8 @@ class CompressionModel:
             st = self._decode_phase_a(ctx, strings, dhw)
             # (round 5) the y range-decode of this chunk -- host work only -- starts now on a helper thread and is collected one iteration
             # later by stage_b, when both coders fit the usable cores side by side (the rule of the encoder's helper thread below)
-            yfut = self._helper_thread('ydec').submit(self._decode_phase_b_host, st) if threaded and hasattr(self, '_decode_phase_b_host') else None
+            host_coder = threaded and self.entropy_coder == 'range' and hasattr(self, '_decode_phase_b_host')      # (rans: no host part)
+            yfut = self._helper_thread('ydec').submit(self._decode_phase_b_host, st) if host_coder else None
             q_b.append((strings, enc['counts'], st, dhw, B, yfut))
             if len(q_b) > 1:
                 q_g.append(stage_b(q_b.pop(0)))
@@ -771,7 +825,8 @@ class CompressionModel:
                 enc = self._encode_batch(ctx, x, False, thr=self._thr_tensor(ctx, [thr_idx] * B), slot=k % 3)
                 # (only when both coders fit the usable cores side by side: with 32 streams per call on a 16-core container the two
                 # would just take turns, with scheduler jitter on top -- measured: 7-12 ms hiccups in the 64^3 headline)
-                enc['strings'] = self._coder_thread().submit(enc['finish']) if 2 * B <= _usable_cores() else _Immediate(enc['finish'])
+                on_thread = 2 * B <= _usable_cores() and self.entropy_coder == 'range'        # (rans: finish only fetches bytes)
+                enc['strings'] = self._coder_thread().submit(enc['finish']) if on_thread else _Immediate(enc['finish'])
                 k += 1
                 q_a.append((enc, dhw, B))
                 t1 = time.perf_counter()
@@ -913,7 +968,8 @@ class CompressionModelV1(CompressionModel):
         codec = self._codec(ctx)
         t = {}
         ready = None
-        stg = self._staging(ctx, slot, B, [v // 8 for v in x.shape[1:4]])
+        rans = self.entropy_coder == 'rans'
+        stg = None if rans else self._staging(ctx, slot, B, [v // 8 for v in x.shape[1:4]])
         if codec is not None:                      # analysis -> quantise -> synthesis (-> fixed threshold) in one ABI call
             ready = torch.cuda.Event()
             ready.record(self._side_stream(ctx, '_idx_stream'))      # creates the handle (on a stream that is idle now: a record costs the
@@ -924,8 +980,12 @@ class CompressionModelV1(CompressionModel):
             med = self._dev(ctx, 'medians', eb.medians)
             y = self.analysis_transform.forward_ndhwc(ctx, x.unsqueeze(-1))
             ysym, y_hat = ops.quantize(ctx, y, med, self.round_mode)
-            stg.pack(ctx, ysym)
-        ev = self._ship(ctx, stg, ready)
+            if not rans:
+                stg.pack(ctx, ysym)
+        if rans:
+            fetch = self._rans_encode(ctx, ready, [(eb.table, ysym, None, True)])
+        else:
+            ev = self._ship(ctx, stg, ready)
         if codec is None:
             x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
             if thr is not None:
@@ -933,6 +993,8 @@ class CompressionModelV1(CompressionModel):
         rows, mod = self._eb_rows(ysym[0].numel(), self.num_filters)
 
         def finish():
+            if rans:
+                return [(s,) for s in fetch()[0]]
             ev.synchronize()
             # a symbol beyond the narrow host type (never seen in practice) shows in the tile maxima: fetch that tensor as int32
             ys_src = stg.ysym if stg.sym_dtype == torch.int32 or int(stg.ytm.max()) <= 32767 else self._to_stream_order(ysym).cpu()
@@ -946,6 +1008,8 @@ class CompressionModelV1(CompressionModel):
     def _decode_phase_a(self, ctx, strings, dhw):
         B = len(strings)
         eb = self.entropy_bottleneck
+        if self.entropy_coder == 'rans':           # the strings go to the device as they are, in phase b
+            return dict(strings=strings)
         yshape = self._stream_shape(B, [v // 8 for v in dhw], self.num_filters)
         ysym_h, ysym_release = self._pinned.ring('dec_ysym', yshape, _host_dtypes()[0])
         n = int(np.prod(yshape[1:]))
@@ -955,18 +1019,28 @@ class CompressionModelV1(CompressionModel):
 
     def _decode_phase_b(self, ctx, st, dhw, debug, thr=None):
         eb = self.entropy_bottleneck
-        packed = self._symbols_to_device(ctx, st['ysym'], st['ysym_release'])
+        rans = self.entropy_coder == 'rans'
+        if rans:
+            B = len(st['strings'])
+            ysym, status = self._rans_decode(ctx, eb.table, [s[0] for s in st['strings']], (B,) + tuple(v // 8 for v in dhw) + (self.num_filters,),
+                                             None, True)
+            packed = None
+        else:
+            ysym, packed = None, self._symbols_to_device(ctx, st['ysym'], st['ysym_release'])
         codec = self._codec(ctx)
         if codec is not None:                      # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
-            t = ops.codec_decode_main(ctx, codec, None, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
+            t = ops.codec_decode_main(ctx, codec, ysym, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
             y_hat, x_hat = t['y_hat'], t['x_hat']
         else:
-            ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
+            if not rans:
+                ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
             y_hat = ops.dequantize(ctx, ysym, self._dev(ctx, 'medians', eb.medians))
             x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
             t = {}
             if thr is not None:
                 t['xyz'], t['counts'] = ops.threshold_compact(ctx, x_hat, thr, clip=False)
+        if rans:
+            ops.rans_check_status(status)           # (after the chunk's launches: the device works while the host waits for the flags)
         B = x_hat.shape[0]
         dbg = [{'y_hat': _np(y_hat[b:b + 1]), 'x_hat': _np(x_hat[b:b + 1].unsqueeze(-1))} for b in range(B)] if debug else [None] * B
         return dict(x_hat=x_hat, debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
@@ -1042,7 +1116,8 @@ class CompressionModelV2(CompressionModel):
         codec = self._codec(ctx)
         t = {}
         ready = None
-        stg = self._staging(ctx, slot, B, [v // 8 for v in x.shape[1:4]], [v // 16 for v in x.shape[1:4]])
+        rans = self.entropy_coder == 'rans'
+        stg = None if rans else self._staging(ctx, slot, B, [v // 8 for v in x.shape[1:4]], [v // 16 for v in x.shape[1:4]])
         if codec is not None:                      # the whole GPU part of compress() (model_types.py:379-388) in one ABI call
             ready = torch.cuda.Event()
             ready.record(self._side_stream(ctx, '_idx_stream'))      # creates the handle (on a stream that is idle now: a record costs the
@@ -1059,12 +1134,17 @@ class CompressionModelV2(CompressionModel):
             sigma = self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat)
             idx = ops.scale_to_index(ctx, sigma, tab)
             ysym, y_hat = ops.quantize(ctx, y, None, self.round_mode)
-            stg.pack(ctx, ysym, zsym, idx)
+            if not rans:
+                stg.pack(ctx, ysym, zsym, idx)
         # what crosses PCIe: ONE buffer per chunk -- symbols as int16, the 64 scale rows as uint8 (8.5 -> 3.3 MB per 32-block
         # chunk), packed in stream order by the library before `ready`, plus the per-tile max|symbol| that tells the host
         # afterwards whether a symbol exceeded int16 (then that tensor is fetched again as int32: never seen in practice).
         # The copy runs on a side stream so that it overlaps the synthesis transform.
-        ev = self._ship(ctx, stg, ready)
+        # entropy_coder='rans': nothing is narrowed or shipped; both strings are coded on the side stream from the int32 tensors.
+        if rans:
+            fetch = self._rans_encode(ctx, ready, [(gc.table, ysym, idx, False), (eb.table, zsym, None, True)])
+        else:
+            ev = self._ship(ctx, stg, ready)
         if codec is None:
             x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
             if thr is not None:
@@ -1072,6 +1152,8 @@ class CompressionModelV2(CompressionModel):
         rows, mod = self._eb_rows(zsym[0].numel(), F)
 
         def finish():
+            if rans:
+                return list(zip(*fetch()))
             ev.synchronize()  # symbols are on the host
             fits = stg.sym_dtype == torch.int32
             zs_src = stg.zsym if fits or int(stg.ztm.max()) <= 32767 else self._to_stream_order(zsym).cpu()
@@ -1092,6 +1174,18 @@ class CompressionModelV2(CompressionModel):
         """z_string -EB.decompress-> z_hat -HS-> sigma -> indexes (async D2H)."""
         B, F = len(strings), self.num_filters
         eb, gc = self.entropy_bottleneck, self.conditional_bottleneck
+        if self.entropy_coder == 'rans':
+            zsym, zstatus = self._rans_decode(ctx, eb.table, [s[1] for s in strings], (B,) + tuple(v // 16 for v in dhw) + (F,), None, True)
+            codec = self._codec(ctx)
+            if codec is not None:
+                t = ops.codec_decode_hyper(ctx, codec, zsym, dhw)
+                z_hat, sigma, idx = t['z_hat'], t['sigma_hat'], t['indexes']
+            else:
+                z_hat = ops.dequantize(ctx, zsym, self._dev(ctx, 'medians', eb.medians))
+                sigma = self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat)
+                idx = ops.scale_to_index(ctx, sigma, self._dev(ctx, 'scale_table', gc.scale_table_f32))
+            # the CDF rows stay on the device: phase b decodes the y strings there
+            return dict(strings=strings, z_hat=z_hat, sigma=sigma, idx=idx, zstatus=zstatus, device=ctx.device)
         zshape = self._stream_shape(B, [v // 16 for v in dhw], F)
         # per-slot cached pinned buffers (like the encoder's): nothing is allocated in the steady state
         zsym_h, zsym_release = self._pinned.ring('dec_zsym', zshape, _host_dtypes()[0])
@@ -1129,6 +1223,8 @@ class CompressionModelV2(CompressionModel):
         """The host part of phase b: wait for the CDF-row indexes, range-decode the y strings into a pinned buffer.  No GPU work is
         enqueued here, so roundtrip_stream may run it on a helper thread (the coder is sequential per stream: 2 ms per 8-block chunk
         of 128^3 blocks) while the calling thread keeps feeding the device."""
+        if self.entropy_coder == 'rans':           # nothing to do on the host
+            return None
         gc = self.conditional_bottleneck
         strings, idx_h = st['strings'], st['idx_h']
         B = len(strings)
@@ -1146,19 +1242,28 @@ class CompressionModelV2(CompressionModel):
         it already ran elsewhere."""
         strings = st['strings']
         B = len(strings)
-        ysym, ysym_release = self._decode_phase_b_host(st) if host is None else host
-        packed = self._symbols_to_device(ctx, ysym, ysym_release)
+        rans = self.entropy_coder == 'rans'
+        if rans:
+            ysym, status = self._rans_decode(ctx, self.conditional_bottleneck.table, [s[0] for s in strings], st['idx'].shape, st['idx'], False)
+            packed = None
+        else:
+            ysym, ysym_release = self._decode_phase_b_host(st) if host is None else host
+            ysym, packed = None, self._symbols_to_device(ctx, ysym, ysym_release)
         codec = self._codec(ctx)
         if codec is not None:                      # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
-            t = ops.codec_decode_main(ctx, codec, None, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
+            t = ops.codec_decode_main(ctx, codec, ysym, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
             ysym, y_hat, x_hat = t['symbols'], t['y_hat'], t['x_hat']
         else:
-            ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
+            if not rans:
+                ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
             y_hat = ops.dequantize(ctx, ysym, None)
             x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
             t = {}
             if thr is not None:
                 t['xyz'], t['counts'] = ops.threshold_compact(ctx, x_hat, thr, clip=False)
+        if rans:                                    # (after the chunk's launches: the device works while the host waits for the flags)
+            ops.rans_check_status(st['zstatus'])
+            ops.rans_check_status(status)
         dbg = [None] * B
         if debug:
             dbg = [{'z_hat': _np(st['z_hat'][b:b + 1]), 'sigma_hat': _np(st['sigma'][b:b + 1]),

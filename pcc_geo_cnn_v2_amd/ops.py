@@ -1748,3 +1748,123 @@ def pmf_to_quantized_cdf(pmf, precision=16):
     L.check(L.lib().pcc_pmf_to_quantized_cdf(pmf.ctypes.data_as(C.c_void_p), pmf.size, precision,
                                              cdf.ctypes.data_as(C.c_void_p)), 'pcc_pmf_to_quantized_cdf')
     return cdf
+
+
+# ---------------------------------------------------------------------------------------------
+# device rANS coder (the opt-in "rans1" string format, include/pcc_geo.h "rANS coder (DEVICE)")
+# ---------------------------------------------------------------------------------------------
+def rans_stream_cap(n):
+    return int(L.lib().pcc_rans_stream_cap(int(n)))
+
+
+def _rans_counts(ctx, n_list):
+    """symbols per stream on the device; one cached tensor per (streams, n) when all streams are as long (the codec's case)"""
+    n_list = [int(k) for k in n_list]
+    if len(set(n_list)) > 1:
+        return torch.tensor(n_list, dtype=torch.int32).to(ctx.device)
+    cache = ctx.__dict__.setdefault('_rans_counts', {}) if isinstance(ctx, Context) else ctx._base.__dict__.setdefault('_rans_counts', {})
+    key = (len(n_list), n_list[0])
+    if key not in cache:
+        cache[key] = torch.tensor(n_list, dtype=torch.int32).to(ctx.device)
+    return cache[key]
+
+
+def _rans_index(ctx, index, S, n_max):
+    """-> (tensor or None, elements between the rows of two streams): (S, ...) int32 device tensor, or ONE row vector for all streams"""
+    if index is None:
+        return None, 0
+    assert index.dtype == torch.int32 and index.is_contiguous() and index.device == ctx.device
+    if index.numel() == n_max and (index.dim() == 1 or S == 1):
+        return index, 0
+    assert index.shape[0] == S and index.numel() == S * n_max, f'rans: index of shape {tuple(index.shape)} for {S} streams of {n_max}'
+    return index, n_max
+
+
+def rans_encode_launch(ctx, table, data, n_list=None, index=None, index_mod=0, channels=0, lanes=0):
+    """Enqueues the encode of S streams on the current stream.  data: (S, ...) int32 device tensor, stream s = data[s] flattened (its
+    first n_list[s] elements; default all); index: int32 device rows of the same shape, or one 1-D vector shared by all streams, or
+    None with index_mod; channels > 0: data[s] is (vox, channels) in memory and the stream is channel-major (see the header).
+    lanes: 0 = the lane rule.  Returns (out (S, cap) uint8, meta (2, S) int32: lengths, status) -- rans_encode_fetch(out, meta)."""
+    assert data.dtype == torch.int32 and data.is_contiguous() and data.device == ctx.device and data.dim() >= 2
+    S = data.shape[0]
+    n_max = data[0].numel() if S else 0
+    n_list = [n_max] * S if n_list is None else [int(k) for k in n_list]
+    assert len(n_list) == S and all(0 <= k <= n_max for k in n_list)
+    cap = rans_stream_cap(n_max)
+    out = torch.empty((S, cap), dtype=torch.uint8, device=ctx.device)
+    meta = torch.zeros((2, S), dtype=torch.int32, device=ctx.device)
+    if S == 0:
+        return out, meta
+    idx, idx_stride = _rans_index(ctx, index, S, n_max)
+    ws = torch.empty((int(L.lib().pcc_rans_workspace_bytes(S, n_max)) + 16,), dtype=torch.uint8, device=ctx.device)
+    n_dev = _rans_counts(ctx, n_list)
+    L.check(L.lib().pcc_rans_encode_batch(ctx.handle, C.byref(table.struct), S, _ptr(data), n_max, _ptr(idx), idx_stride, index_mod, channels,
+                                          _ptr(n_dev), n_max, lanes, _ptr(out), cap, _ptr(meta[0]), _ptr(meta[1]), _ptr(ws), ws.numel(),
+                                          ctx.stream), 'pcc_rans_encode_batch')
+    return out, meta
+
+
+def rans_encode_fetch(out, meta):
+    """The strings of a rans_encode_launch: the lengths first, then only the used part of the byte buffer.  Waits for the device."""
+    if out.shape[0] == 0:
+        return []
+    m = meta.cpu().numpy()
+    if m[1].any():
+        raise AssertionError('pcc_rans_encode_batch: CDF row index out of range (or a stream that is no multiple of its channels)')
+    used = int(m[0].max())
+    b = out[:, :used].cpu().numpy() if used else np.zeros((out.shape[0], 0), np.uint8)
+    return [b[s, :int(m[0, s])].tobytes() for s in range(out.shape[0])]
+
+
+def rans_encode_batch(ctx, table, data, n_list=None, index=None, index_mod=0, channels=0, lanes=0):
+    """-> list of bytes (rans_encode_launch + rans_encode_fetch)"""
+    return rans_encode_fetch(*rans_encode_launch(ctx, table, data, n_list, index, index_mod, channels, lanes))
+
+
+def rans_check_status(status):
+    """the per-stream flags of a rans_decode_batch(check=False), fetched now: raises like the checked call"""
+    st = status.cpu().numpy()
+    if (st & 5).any():
+        raise AssertionError('pcc_rans_decode_batch: CDF row index out of range (or a stream that is no multiple of its channels)')
+    if st.any():
+        raise L.PccError(f'pcc_rans_decode_batch: string {int(np.flatnonzero(st)[0])} is corrupt (status {L.PCC_ERR_CORRUPT})')
+
+
+def rans_decode_batch(ctx, table, strings, n_list, index=None, index_mod=0, channels=0, out=None, check=True):
+    """strings: list of bytes -> (out, status).  The headers are checked on the host, then ONE pinned buffer (offsets, lengths, counts,
+    bytes) goes to the device on the current stream and one wave decodes each string into out[s] ((S, n_max) int32, or the caller's
+    (S, ...) int32 device tensor).  index / index_mod / channels: as for rans_encode_launch.  check: wait and raise PccError (status
+    PCC_ERR_CORRUPT) when a string did not decode; False: the flags stay in `status` (device int32) for rans_check_status."""
+    S = len(strings)
+    n_list = [int(k) for k in n_list]
+    assert len(n_list) == S
+    n_max = max(n_list) if out is None else (out[0].numel() if S else 0)
+    if out is None:
+        out = torch.zeros((S, n_max), dtype=torch.int32, device=ctx.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.device == ctx.device and out.shape[0] == S and all(k <= n_max for k in n_list)
+    status = torch.zeros((S,), dtype=torch.int32, device=ctx.device)
+    if S == 0:
+        return out, status
+    lens = np.fromiter((len(s_) for s_ in strings), np.int64, S)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    total = int(lens.sum())
+    head = 16 * S
+    host = torch.empty((head + total + 16,), dtype=torch.uint8, pin_memory=True)
+    h = host.numpy()
+    h[:8 * S].view(np.int64)[:] = offs
+    h[8 * S:12 * S].view(np.int32)[:] = lens
+    h[12 * S:16 * S].view(np.int32)[:] = n_list
+    h[head:head + total] = np.frombuffer(b''.join(strings), np.uint8)
+    h[head + total:] = 0
+    base = h.ctypes.data
+    L.check(L.lib().pcc_rans_check_strings(S, C.c_void_p(base + head), C.c_void_p(base), C.c_void_p(base + 8 * S), C.c_void_p(base + 12 * S)),
+            'pcc_rans_check_strings')
+    dev = host.to(ctx.device, non_blocking=True)
+    idx, idx_stride = _rans_index(ctx, index, S, n_max)
+    p = dev.data_ptr()
+    st_host = np.zeros(S, np.int32) if check else None
+    L.check(L.lib().pcc_rans_decode_batch(ctx.handle, C.byref(table.struct), S, C.c_void_p(p + head), total, C.c_void_p(p), C.c_void_p(p + 8 * S),
+                                          _ptr(idx), idx_stride, index_mod, channels, C.c_void_p(p + 12 * S), n_max, _ptr(out), n_max,
+                                          _ptr(status), None if st_host is None else st_host.ctypes.data_as(C.c_void_p), ctx.stream),
+            'pcc_rans_decode_batch')
+    return out, status
