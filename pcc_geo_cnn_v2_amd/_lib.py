@@ -115,8 +115,8 @@ def lib():
                        '(python -c "import __graft_entry__ as g; g.build()"). There is no CPU fallback.')
     L = C.CDLL(LIB_PATH)
     vp, i32, sz = C.c_void_p, C.c_int32, C.c_size_t
-    L.pcc_abi_version.restype = C.c_int
-    L.pcc_last_error.restype = C.c_char_p
+    L.pcc_abi_version.argtypes, L.pcc_abi_version.restype = [], C.c_int
+    L.pcc_last_error.argtypes, L.pcc_last_error.restype = [], C.c_char_p
     L.pcc_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.pcc_ctx_destroy.argtypes = [vp]
     L.pcc_ctx_num_cu.argtypes = [vp]
@@ -137,9 +137,11 @@ def lib():
     L.pcc_threshold_scratch_ints.restype = sz
     L.pcc_voxelize.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, i32, vp, vp]
     L.pcc_focal_loss.argtypes = [vp, vp, vp, sz, C.c_float, C.c_float, vp, vp, vp]
-    L.pcc_focal_scratch_floats.restype = sz
+    L.pcc_focal_scratch_floats.argtypes, L.pcc_focal_scratch_floats.restype = [], sz
     L.pcc_range_encode_batch.argtypes = [C.POINTER(CdfTable), i32, vp, vp, i32, vp, vp, vp, vp, i32]
     L.pcc_range_decode_batch.argtypes = [C.POINTER(CdfTable), i32, vp, vp, vp, i32, vp, vp, i32]
+    L.pcc_range_encode_batch_n.argtypes = [C.POINTER(CdfTable), i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32]
+    L.pcc_range_decode_batch_n.argtypes = [C.POINTER(CdfTable), i32, vp, vp, vp, i32, i32, vp, vp, i32, i32]
     L.pcc_pmf_to_quantized_cdf.argtypes = [vp, i32, i32, vp]
     L.pcc_d1_search_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.pcc_d1_search_workspace_bytes.restype = sz
@@ -186,7 +188,7 @@ def lib():
     L.pcc_conv_repack_map.argtypes = [C.POINTER(ConvDesc), vp]
     L.pcc_conv_repack_weights_device.argtypes = [vp, C.POINTER(ConvDesc), vp, vp, vp, vp]
     L.pcc_histogram_limits.argtypes = [vp]
-    L.pcc_tensor_histogram_workspace_bytes.restype = sz
+    L.pcc_tensor_histogram_workspace_bytes.argtypes, L.pcc_tensor_histogram_workspace_bytes.restype = [], sz
     L.pcc_tensor_histogram_slices.argtypes = [sz]
     L.pcc_tensor_histogram.argtypes = [vp, vp, sz, vp, vp, vp]
     L.pcc_occupancy_scores.argtypes = [vp, vp, vp, sz, vp, vp, vp]
@@ -194,7 +196,7 @@ def lib():
     L.pcc_anchor_code_bits.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64)]
     L.pcc_anchor_decode_bits.argtypes = [vp, i64, vp, i64, vp]
     L.pcc_anchor_encode.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(i64)]
-    L.pcc_anchor_decoder_bytes.restype = sz
+    L.pcc_anchor_decoder_bytes.argtypes, L.pcc_anchor_decoder_bytes.restype = [], sz
     L.pcc_anchor_decoder_init.argtypes = [vp, vp, i64, i32]
     L.pcc_anchor_decode_level.argtypes = [vp, vp, i64, vp]
     L.pcc_anchor_decoder_consumed.argtypes = [vp]

@@ -107,12 +107,6 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
 _SIDE_STREAMS = {}
 
 
-def _usable_cores():
-    """Cores this process may really use: the affinity mask, capped by the cgroup CPU quota (a container that sees 256 cores may
-    be throttled to 16 CPUs' worth of time per period -- running more threads than that gets the whole process paused)."""
-    return ops.usable_cores()
-
-
 class _Immediate:
     """A future-like wrapper that runs its function when the result is asked for (the caller's thread)."""
 
@@ -301,7 +295,7 @@ class CompressionModel:
         from .model_opt import HostSearchPool
         # default: the cores this process may run on, at most 64 (measured on a 256-thread box whose container gets far fewer: 64
         # workers 17.5 s per 190-block cloud with d2 metrics, 128 workers 23.6 s -- the KD-tree work is host-bound)
-        usable = _usable_cores() * 4          # (KD-tree queries wait on memory: 64 workers on a 16-CPU quota measured best)
+        usable = ops.usable_cores() * 4          # (KD-tree queries wait on memory: 64 workers on a 16-CPU quota measured best)
         want = max(1, min(n_jobs, self.search_threads or min(usable, 64)))
         pool = getattr(self, '_host_search_pool', None)
         if pool is None or len(pool.procs) < want:
@@ -820,12 +814,12 @@ class CompressionModel:
             for x in dense_chunks:
                 B, dhw = x.shape[0], tuple(x.shape[1:4])
                 if threaded is None:
-                    threaded = (2 * B <= _usable_cores() or bool(os.environ.get('PCC_FORCE_HELPER_THREADS'))) and not os.environ.get('PCC_NO_HELPER_THREADS')
+                    threaded = (2 * B <= ops.usable_cores() or bool(os.environ.get('PCC_FORCE_HELPER_THREADS'))) and not os.environ.get('PCC_NO_HELPER_THREADS')
                 t0 = time.perf_counter()
                 enc = self._encode_batch(ctx, x, False, thr=self._thr_tensor(ctx, [thr_idx] * B), slot=k % 3)
                 # (only when both coders fit the usable cores side by side: with 32 streams per call on a 16-core container the two
                 # would just take turns, with scheduler jitter on top -- measured: 7-12 ms hiccups in the 64^3 headline)
-                on_thread = 2 * B <= _usable_cores() and self.entropy_coder == 'range'        # (rans: finish only fetches bytes)
+                on_thread = 2 * B <= ops.usable_cores() and self.entropy_coder == 'range'        # (rans: finish only fetches bytes)
                 enc['strings'] = self._coder_thread().submit(enc['finish']) if on_thread else _Immediate(enc['finish'])
                 k += 1
                 q_a.append((enc, dhw, B))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import _metrics_ref as R
+from _ops_patch import patch_ops
 from pcc_geo_cnn_v2_amd import ev_report, model_opt, ops
 from pcc_geo_cnn_v2_amd.estimate_normals import normals_frame
 from pcc_geo_cnn_v2_amd.utils import pc_io, pc_metric
@@ -83,11 +84,11 @@ def test_empty_candidates_give_none_and_launch_nothing(ctx, monkeypatch):
     a, b = PAIRS['uniform']
     calls = []
     real = ops.cloud_distortion_launch
-    monkeypatch.setattr(ops, 'cloud_distortion_launch', lambda *x, **k: calls.append(1) or real(*x, **k))
+    patch_ops(monkeypatch, 'cloud_distortion_launch', lambda *x, **k: calls.append(1) or real(*x, **k))
     assert pc_metric.cloud_metrics_batch_gpu(ctx, a, [np.zeros((0, 3))], 1023) == [None]
     assert calls == []
     built = []
-    monkeypatch.setattr(ops, 'CloudIndex', lambda *x, **k: built.append(1))
+    patch_ops(monkeypatch, 'CloudIndex', lambda *x, **k: built.append(1))
     assert pc_metric.cloud_metrics_batch_gpu(ctx, a, [np.zeros((0, 3)), []], 1023) == [None, None]
     assert built == []
     monkeypatch.undo()

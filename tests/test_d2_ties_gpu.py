@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import _ties_ref as R
+from _ops_patch import patch_ops
 from pcc_geo_cnn_v2_amd import _lib as L
 from pcc_geo_cnn_v2_amd import ops
 from pcc_geo_cnn_v2_amd.utils import pc_io, pc_metric
@@ -113,10 +114,10 @@ def test_pair_capacity_overflow_is_reported_not_truncated(ctx):
 def test_default_capacity_overflow_runs_again_with_the_reported_count(ctx, monkeypatch):
     a, b, n = CASES['single_b']                                            # every original point votes for the one decoded point
     want = ops.cloud_distortion(ctx, a, b, n, ties='mean')
-    monkeypatch.setattr(ops, 'tie_pair_capacity', lambda n_a: 7)           # a sizing rule this input exceeds
+    patch_ops(monkeypatch, 'tie_pair_capacity', lambda n_a: 7)           # a sizing rule this input exceeds
     calls = []
     real = ops.cloud_distortion_launch
-    monkeypatch.setattr(ops, 'cloud_distortion_launch', lambda *x, **k: calls.append(k.get('max_pairs')) or real(*x, **k))
+    patch_ops(monkeypatch, 'cloud_distortion_launch', lambda *x, **k: calls.append(k.get('max_pairs')) or real(*x, **k))
     assert np.array_equal(ops.cloud_distortion(ctx, a, b, n, ties='mean'), want)
     assert calls == [None, len(a)]
     calls.clear()

@@ -14,6 +14,7 @@ import torch
 
 import _search_ties_ref as S
 import _ties_ref as R
+from _ops_patch import patch_ops
 from pcc_geo_cnn_v2_amd import model_opt, ops
 from pcc_geo_cnn_v2_amd.model_syntax import load_compressed_file
 from pcc_geo_cnn_v2_amd.utils import pc_io
@@ -159,7 +160,7 @@ def test_pair_capacity_overflow_is_reported_and_the_default_path_reruns(ctx, mon
     exact = ops.d12_threshold_stats_ties(*args, max_pairs=pairs, return_status=True)
     assert exact[-1] == (pairs, False)
     # the default path: a default capacity that is too small is followed by one run with the reported count
-    monkeypatch.setattr(ops, 'search_tie_pair_capacity', lambda *a: 1000)
+    patch_ops(monkeypatch, 'search_tie_pair_capacity', lambda *a: 1000)
     rerun = _gpu(ctx, blocks, x_hat)
     for a, b in zip(full, rerun):
         assert a.tobytes() == b.tobytes()

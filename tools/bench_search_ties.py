@@ -59,7 +59,7 @@ def _recording_launch(*a, **kw):
     return out
 
 
-ops.d12_threshold_stats_ties_launch = _recording_launch
+ops.d12_threshold_stats_ties_launch = ops.search.d12_threshold_stats_ties_launch = _recording_launch      # callers outside and inside the package
 
 
 def cloud(kind):
