@@ -658,6 +658,42 @@ int pcc_rans_decode_batch(pcc_ctx* ctx, const pcc_cdf_table* t, int32_t n_stream
                           int32_t channels, const int32_t* n, int32_t n_max, int32_t* out, int64_t out_stride, int32_t* status,
                           int32_t* status_host, void* stream);
 
+/* ---- occupancy coder (DEVICE): the "occ1" string format, the lossless layer on top of the y/z strings -----------
+ * One string codes the true occupancy of a block of n <= 2^28 voxels given x_hat (fp32, voxel i in C order), which encoder and
+ * decoder hold with the same bits.  Bucket of voxel i, K = 32: 0 unless x_hat > 0 (NaN, -0, negatives); 31 if x_hat >= 1; else
+ * min(30, 1 + (int)(x_hat * 30.0f)) -- one fp32 multiply, then truncation.  With tot[b] / on[b] the voxels / occupied voxels of
+ * bucket b, every bucket with tot[b] > 0 has, in ascending b, one uint16 entry: 0 when on[b] == 0 (its voxels are not coded), else
+ * f = clamp((on * 65536 + tot / 2) / tot, 1, 65535) in 64-bit integers.  Coded symbols: the voxels of the buckets with a non-zero
+ * entry, in ascending i (m of them); bit 1 has freq f and start 65536 - f, bit 0 has freq 65536 - f and start 0.  Coder: rans1's
+ * (above) without escapes -- state in [2^16, 2^32), initial state 2^16, 16-bit words, symbol j on lane j % L at step j / L, the
+ * decoder walks the steps upwards with one forward word cursor, ascending lanes within a step; L by the same lane rule over the
+ * coded freqs (m = 0: L = 1), lanes > 0 forces it.  String bytes (little-endian): one byte log2 L; the entries; L final states of
+ * 4 bytes; the words.  n = 0 codes as the empty string.  A decoder accepts a string only if its length is 1 + 2 used + 4 L +
+ * 2 n_words with n_words <= m (used = the buckets with tot > 0), every lane ends in 2^16 and the cursor ends at n_words.
+ *
+ * One workgroup codes one block.  x_hat, occ, out, out_len, status, str, off, len, occ_out and workspace are DEVICE pointers;
+ * status_host is a host pointer.  Block s reads x_hat + s * x_hat_stride and occ + s * occ_stride (elements; the voxeliser's float
+ * grid, occupied = != 0).
+ *   encoder : string s at out + s * cap with cap >= pcc_occ_stream_cap(n) (= 1 + 2 * 32 + 4 * 64 + 2 n), its length in out_len[s],
+ *             status[s] = 0; workspace of pcc_occ_workspace_bytes(n_streams, n) bytes.
+ *   decoder : string s = str[off[s], off[s] + len[s]) inside the str_bytes bytes of `str`; occ_out + s * out_stride receives n
+ *             floats, 0 or 1, and nothing outside them is written whatever the string says.  Every read of the string is made under
+ *             the length test; status[s] != 0 when the string is not accepted (the grid is then undefined).  status_host
+ *             (n_streams ints, may be NULL): the call waits for the stream and returns PCC_ERR_CORRUPT / PCC_ERR_ARG from the
+ *             flags; NULL: the flags stay in status[] for the caller to fetch.  The same workspace size as the encoder's.
+ * pcc_occ_check_strings (HOST pointers) reads the first byte of each string only: log2 L <= 6 and a length that leaves
+ * len - 1 - 4 L even, non-negative and at most 2 (32 + n) -- PCC_ERR_CORRUPT.  `used` and m depend on x_hat, so only the device can
+ * validate a string fully.                                                                                                      */
+size_t pcc_occ_stream_cap(int64_t n);
+size_t pcc_occ_workspace_bytes(int32_t n_streams, int64_t n);
+int pcc_occ_check_strings(int32_t n_streams, const uint8_t* str, const int64_t* off, const int32_t* len, int64_t n);
+int pcc_occ_encode_batch(pcc_ctx* ctx, const float* x_hat, int64_t x_hat_stride, const float* occ, int64_t occ_stride, int32_t n_streams,
+                         int64_t n, int32_t lanes, uint8_t* out, size_t cap, int32_t* out_len, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int pcc_occ_decode_batch(pcc_ctx* ctx, const float* x_hat, int64_t x_hat_stride, int32_t n_streams, int64_t n, const uint8_t* str,
+                         size_t str_bytes, const int64_t* off, const int32_t* len, float* occ_out, int64_t out_stride, int32_t* status,
+                         int32_t* status_host, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- octree blocking, host (replaces the per-point loop of src/utils/octree_coding.py:82-108) ----------------------
  * Buckets `n` points (row-major doubles, `ncols` >= 3 columns, x y z first) into blocks of edge `block_size`:
  * bucket = Morton code of the block id over `level` bits per axis, x least significant.  order[n] receives the point

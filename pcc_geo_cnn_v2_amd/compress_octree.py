@@ -4,6 +4,7 @@
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
          [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu] [--d2_ties pick|mean] [--search_ties pick|mean]
+         [--entropy_coder range|rans] [--lossless]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
@@ -12,6 +13,8 @@ the files.  `--num_filters` is accepted and ignored, like in the reference (SURV
 normals of the D2 metrics come from the GPU (include/pcc_geo.h "point normals") instead of an `--input_normals` file.
 `--metrics_device gpu` is new: the whole-cloud metrics of the final candidate selection run on the GPU (include/pcc_geo.h "cloud
 metrics", neighbour ties to the lowest row) instead of scipy KD-trees; single process only.
+`--lossless` is new: every block carries one more string that codes its true occupancy under the decoder's x_hat, so
+decompress_octree returns the input voxels exactly; the y/z strings stay the lossy base; single process only.
 """
 import argparse
 import json
@@ -115,6 +118,13 @@ def check_metrics_device(metrics_device, world):
                              'host, drop the flag or run on one GPU')
 
 
+def check_lossless(lossless, world):
+    """--lossless codes the occupancy layer in one process; the sharded path moves the y/z strings alone."""
+    if lossless and world > 1:
+        raise AssertionError(f'--lossless is single-process only (world size {world}): the sharded path does not carry the occupancy '
+                             'strings, drop the flag or run on one GPU')
+
+
 def check_d2_ties(d2_ties, world):
     """--d2_ties mean averages the whole-cloud D2 over all equidistant nearest points in one process; tie sets are not sharded."""
     from .utils.pc_metric import check_ties
@@ -165,6 +175,13 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
             record['d2_ties'] = args.d2_ties
         if getattr(args, 'search_ties', 'pick') != 'pick':
             record['search_ties'] = args.search_ties
+        if getattr(args, 'lossless', False):
+            # the last string of every block is the occupancy layer; the rate of the exact cloud counts the whole file as written
+            n_points = sum(len(b) for b in blocks)
+            record['lossless'] = True
+            record['base_bytes'] = sum(len(x) for strings, _ in streams for x in strings[:-1])
+            record['occ_bytes'] = sum(len(strings[-1]) for strings, _ in streams)
+            record['bits_per_input_point_lossless'] = 8.0 * os.path.getsize(target) / max(n_points, 1)
         json.dump(record, fh, sort_keys=True, indent=4)
     if decoded_path is not None:
         pc_io.write_df(decoded_path, pc_io.pa_to_df(info['blocks_full']))
@@ -182,12 +199,14 @@ def compress(args):
     import torch
     from . import ops
     from .model_configs import ModelConfigType
-    from .model_syntax import coder_tag
+    from .model_syntax import stream_tag
     from .utils import pc_io
     from .utils.octree_coding import partition_octree
     T.mark('imports')
 
     clouds, with_normals = _plan(args)
+    lossless = getattr(args, 'lossless', False)
+    check_lossless(lossless, int(os.environ.get('WORLD_SIZE', '1')))      # (before the process group and the GPU are touched)
     rank, world, local = _join_process_group()
     check_metrics_device(getattr(args, 'metrics_device', 'host'), world)
     check_d2_ties(getattr(args, 'd2_ties', 'pick'), world)
@@ -212,7 +231,7 @@ def compress(args):
                 f'{block_shape} and {sum(len(blocks) for blocks, _ in partitions)} blocks')
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision,
-                                                    entropy_coder=getattr(args, 'entropy_coder', 'range'))
+                                                    entropy_coder=getattr(args, 'entropy_coder', 'range'), lossless=lossless)
     model.d2_search = getattr(args, 'd2_search', None)      # per model, not a module global
     model.search_ties = getattr(args, 'search_ties', 'pick')
     model.compress(np.concatenate(((1,), block_shape)))
@@ -234,7 +253,7 @@ def compress(args):
             if len(streams) != len(cloud.targets):
                 raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
             for n, target in enumerate(cloud.targets):
-                infos[n]['numerics_tag'] = coder_tag(sess.numerics_tag(args.precision), model.entropy_coder)
+                infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless)
                 _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
             logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
         T.mark('container_gzip_write')
@@ -274,7 +293,8 @@ def build_parser():
                              '--d2_ties mean reports.  Needs a d2 metric '
                              'in --opt_metrics and normals.')
     parser.add_argument('--dec_files', nargs='*',
-                        help='Decoded files. Allows compression/decompression in a single execution.')
+                        help='Decoded files. Allows compression/decompression in a single execution.  Under --lossless they still hold the '
+                             'lossy base candidate (what decompress_octree --base_only writes).')
     parser.add_argument('--checkpoint_dir', help='Directory where to save/load model checkpoints.', required=True)
     parser.add_argument('--model_config', help='Model used: c1, c2, c3, c3p.', required=True)
     # the reference's default (compress_octree.py:156); translated to d1_mse in compress(), see there
@@ -300,6 +320,11 @@ def build_parser():
                         help="String format (new): range = the host range coder (tfc's algorithm, the default: files unchanged), "
                              'rans = the interleaved rANS coded on the GPU; the stream names it (numerics tag suffix /rans1), so '
                              'decompress_octree needs no flag.')
+    parser.add_argument('--lossless', default=False, action='store_true',
+                        help='Add the occupancy layer (new): one more string per block codes its true occupancy under the decoded x_hat, '
+                             'so decompress_octree returns the input voxels exactly and --base_only the lossy cloud.  The stream names the '
+                             'layer (numerics tag suffix /occ1); .enc.metric.json gains lossless, base_bytes, occ_bytes and '
+                             'bits_per_input_point_lossless (8 x file size / input points).  Single process only.')
     return parser
 
 

@@ -17,11 +17,9 @@
 #include <vector>
 
 #include "common.h"
+#include "rans_common.h"
 
 namespace {
-
-constexpr int kMaxLanes = 64;
-constexpr uint32_t kLow = 1u << 16;
 
 struct DevTable {
     const int32_t* cdf;
@@ -29,18 +27,6 @@ struct DevTable {
     const int32_t* offset;
     int32_t rows, stride;
 };
-
-// flags of the per-stream status word
-constexpr int32_t kBadRow = 1, kCorrupt = 2, kBadShape = 4;
-
-__device__ __forceinline__ int lane_id() { return (int)threadIdx.x; }
-__device__ __forceinline__ int prefix_rank(uint64_t mask) { return __popcll(mask & ((1ull << lane_id()) - 1ull)); }
-
-__device__ __forceinline__ int32_t cost256(uint32_t f) {
-    const int k = 31 - __clz((int)f);
-    const uint32_t r = f - (1u << k);
-    return 256 * (16 - k) - (int32_t)((r << 8) >> k);
-}
 
 // where symbol i of a stream lies in memory: as it is, or -- channels > 0: the tensor is (vox, channels) in memory and the stream is
 // channel-major -- at (i % vox) * channels + i / vox
@@ -69,21 +55,6 @@ __device__ __forceinline__ Bin bin_of(const DevTable& t, int32_t row, int32_t v)
     const uint32_t lo = (uint32_t)c[0], hi = (uint32_t)c[1];
     return Bin{lo, hi - lo, esc};
 }
-
-__device__ __forceinline__ int64_t wave_sum(int64_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off);
-    return v;
-}
-
-__device__ __forceinline__ int32_t wave_or(int32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v |= __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ void put16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
-__device__ __forceinline__ void put32(uint8_t* p, uint32_t v) { put16(p, v); put16(p + 2, v >> 16); }
 
 __global__ __launch_bounds__(64) void rans_encode_kernel(DevTable t, const int32_t* __restrict__ data, int64_t data_stride,
                                                          const int32_t* __restrict__ index, int64_t index_stride, int32_t index_mod,
@@ -120,11 +91,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(DevTable t, const int32
     cost = wave_sum(cost);
     n_esc = wave_sum(n_esc);
     const int64_t est = (cost + 2047) >> 11;
-    int L = forced;
-    if (L == 0) {
-        L = 1;
-        while (L < kMaxLanes && 128 * (2 * L) <= est) L *= 2;
-    }
+    const int L = forced ? forced : lane_rule(est);
     __syncthreads();                                                     // (one wave: orders the bins written above before pass 2 reads them)
 
     // pass 2: steps descending; the words of step t lie before those of step t + 1, ascending lane order inside a step
@@ -247,7 +214,6 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(DevTable t, const uint8
     const int L = h.L;
     const uint8_t* pw = sp + h.hdr + 4 * L;
     const uint8_t* pe = pw + 2 * h.n_words;
-    auto get16 = [](const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); };
     uint32_t x = kLow;
     if (lane < L) x = get16(sp + h.hdr + 4 * lane) | (get16(sp + h.hdr + 4 * lane + 2) << 16);
     int64_t wcur = 0, ecur = 0;

@@ -1,7 +1,7 @@
 """Decoder CLI -- same flags and files as /root/reference/src/decompress_octree.py:148-182.
 
   python -m pcc_geo_cnn_v2_amd.decompress_octree --input_files a.ply.bin --output_files a.dec.ply \\
-         --checkpoint_dir models/c3p/1.00e-04 --model_config c3p [--debug]
+         --checkpoint_dir models/c3p/1.00e-04 --model_config c3p [--debug] [--base_only]
 
 `--debug` reloads the encoder-side dumps (`.enc.data.npz`, `.enc.blocks/`) and checks every intermediate
 and the decoded blocks for exact equality.  The reference needs up to 100 retries there because its GPU
@@ -32,7 +32,7 @@ def decompress(args):
     import torch
     from . import ops, sharding
     from .model_configs import ModelConfigType
-    from .model_syntax import load_compressed_file, read_gzip_tag, stream_coder
+    from .model_syntax import load_compressed_file, read_gzip_tag, stream_layers
     from .utils import pc_io
     from .utils.octree_coding import departition_octree
     T.mark('imports')
@@ -61,10 +61,17 @@ def decompress(args):
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
     compressed_data, coders = [], []
+    base_only = getattr(args, 'base_only', False)
     for file in args.input_files:
-        # the stream names its entropy coder (tag suffix); the rest of the tag is compared as before
-        coders.append(stream_coder(read_gzip_tag(file), sess.numerics_tag(args.precision), getattr(args, 'entropy_coder', None),
-                                   ignore=args.ignore_numerics_tag))
+        # the stream names its entropy coder and its layers (tag suffixes); the rest of the tag is compared as before
+        coder, layers = stream_layers(read_gzip_tag(file), sess.numerics_tag(args.precision), getattr(args, 'entropy_coder', None),
+                                      ignore=args.ignore_numerics_tag)
+        coders.append(coder)
+        if base_only and 'occ1' not in layers:
+            logger.warning('--base_only has no effect on %s: the stream carries no occupancy layer', file)
+        if args.debug and 'occ1' in layers and not base_only:
+            raise AssertionError(f'--debug compares the decoded blocks with the encoder dumps, which hold the lossy candidate: pass --base_only '
+                                 f'to check {file}')
         with gzip.open(file, 'rb') as f:
             compressed_data.append(load_compressed_file(f))
     T.mark('container_read_gunzip')
@@ -80,7 +87,7 @@ def decompress(args):
         logger.info(f'{i}/{len(args.input_files)} - Writing {ori_file} to {output_file} with {len(blocks)} blocks')
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
         model.entropy_coder = coders[i]
-        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug)
+        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug, layers='base' if base_only else 'all')
         T.mark('decompress_blocks', sess.device)
         if args.debug and rank == 0:
             dec_blocks_enc = read_pcs(len(blocks), ori_file + '.enc.blocks')
@@ -126,6 +133,9 @@ def build_parser():
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'fp16'],
                         help='fp16: fp16 matrix instructions with fp32 accumulation on the conv layers (new; must match between '
                              'compress and decompress).')
+    parser.add_argument('--base_only', default=False, action='store_true',
+                        help='Write the lossy decode of a file that carries the occupancy layer (compress_octree --lossless; new).  Such a '
+                             'file decodes to the exact input voxels by default; without the layer the flag does nothing.')
     parser.add_argument('--entropy_coder', default=None, choices=['range', 'rans'],
                         help='Entropy coder of input files that carry no numerics tag (new; default range).  A tagged file names its own.')
     return parser

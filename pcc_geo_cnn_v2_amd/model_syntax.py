@@ -53,7 +53,9 @@ def save_compressed_file(binstr, data_b_list, resolution, octree_level, strict=F
     for strings, threshold_idx in data_b_list:
         out.append(_field(threshold_idx, 8, strict, 'threshold index'))
         for payload in strings:
-            out += _U16.pack(_field(len(payload), 16, strict, 'string length'))
+            # (the last of the strings of a lossless stream is the occupancy layer: at most 1 bit per voxel, so a block of 64^3 always fits)
+            out += _U16.pack(_field(len(payload), 16, strict, 'string length (the container holds at most 65535 bytes per string; under '
+                                    '--lossless the occupancy string of a block larger than 64^3 voxels may not fit: raise --octree_level)'))
             out += payload
     return bytes(out)
 
@@ -156,6 +158,37 @@ def split_coder_tag(tag):
             return '/'.join(parts[:4]), coder
     raise RuntimeError(f'the stream was written with the entropy coder {suffix!r} ({tag}); this build reads '
                        f'{sorted(k for k in CODER_SUFFIX.values() if k)} and the untagged range coder')
+
+
+# layers on top of the y/z strings -> the final part of the tag that names them
+LAYER_SUFFIX = {'occ1': 'occ1'}
+
+
+def stream_tag(tag, entropy_coder, lossless=False):
+    """The numerics tag of a stream written with `entropy_coder`, with the occupancy layer named as a final '/occ1' part."""
+    tag = coder_tag(tag, entropy_coder)
+    return f'{tag}/occ1' if lossless else tag
+
+
+def split_stream_tag(tag):
+    """(numerics tag without coder and layer parts, entropy coder, tuple of layers) of a stream's tag; (tag, None, ()) for a stream
+    without a tag of ours.  Unknown parts are refused like split_coder_tag refuses them."""
+    if tag is None or not tag.startswith('pcc_geo_cnn_v2_amd/'):
+        return tag, None, ()
+    parts = tag.split('/')
+    layers = ()
+    if len(parts) > 4 and parts[-1] in LAYER_SUFFIX:
+        layers, parts = (LAYER_SUFFIX[parts[-1]],), parts[:-1]
+    base, coder = split_coder_tag('/'.join(parts))
+    return base, coder, layers
+
+
+def stream_layers(tag, expected, override=None, ignore=False):
+    """Decoder side: (entropy coder, layers) the stream names; the rest of the tag is compared as stream_coder does."""
+    base, coder, layers = split_stream_tag(tag)
+    if coder is None:
+        return stream_coder(tag, expected, override, ignore), layers
+    return stream_coder(coder_tag(base, coder), expected, override, ignore), layers
 
 
 def stream_coder(tag, expected, override=None, ignore=False):

@@ -166,11 +166,14 @@ class _Pinned:
 class CompressionModel:
     def __init__(self, n_thresholds=2 ** 8, data_format='channels_first', batch_size=32,
                  round_mode=L.PCC_ROUND_FLOOR_HALF, coder_threads=0, seed=42, precision='fp32', search_threads=0,
-                 entropy_coder='range'):
+                 entropy_coder='range', lossless=False):
         assert precision in ('fp32', 'fp16'), "precision: 'fp32' (the reference's arithmetic) or 'fp16' (fp16 matrix instructions, fp32 accumulate)"
         assert entropy_coder in ENTROPY_CODERS, f"entropy_coder: 'range' (the host range coder, tfc's bytes) or 'rans' (the device coder), not {entropy_coder!r}"
         # which string format compress() writes and decompress() reads: part of the stream (the CLIs record it in the numerics tag)
         self.entropy_coder = entropy_coder
+        # lossless: every block carries one more string, LAST, that codes its true occupancy under the decoder's x_hat ("occ1", DESIGN.md
+        # 4.19); the y/z strings and the threshold byte in front of it are what they are without it.  The CLIs name the layer in the tag.
+        self.lossless = bool(lossless)
         self.precision = precision
         self.thresholds = np.linspace(0, 1.0, n_thresholds)
         self.data_format = data_format
@@ -557,6 +560,9 @@ class CompressionModel:
             x = self._voxelize(ctx, chunk, dhw)
             enc = self._encode_batch(ctx, x, debug, thr=self._thr_tensor(ctx, [half] * len(chunk)) if fixed_threshold else None)
             x_hat = enc['x_hat']
+            # the occupancy layer: the chunk's dense input under the x_hat the decoder will compute (same bits: the numerics tag); the
+            # threshold search below neither sees nor changes it
+            occ_job = ops.occ_encode_launch(ctx, x_hat, x) if self.lossless else None
             if fixed_threshold:
                 # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 for every metric
                 n_m = len(max_deltas) * len(opt_metrics)
@@ -607,6 +613,8 @@ class CompressionModel:
                 pending.append(item)
                 if len(pending) > SEARCH_LAG:
                     finalize_search(pending.pop(0))
+            if occ_job is not None:
+                strings = [tuple(ss) + (o,) for ss, o in zip(strings, ops.occ_encode_fetch(*occ_job))]
             strings_list.extend(strings)
             debug_t_list.extend(enc['debug'])
         while pending:
@@ -626,6 +634,8 @@ class CompressionModel:
         from .utils.pc_metric import check_ties
         rank, world = sharding.world_info()
         check_ties(d2_ties, world)
+        if self.lossless and world > 1:
+            raise AssertionError('lossless is single-process only: the sharded path moves the y/z strings alone')
         if metrics_device not in METRICS_DEVICES:
             raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
         if metrics_device == 'gpu' and world > 1:
@@ -857,17 +867,21 @@ class CompressionModel:
                         except Exception:
                             pass
 
-    def decompress_blocks(self, sess, blocks, x_shape, debug=False):
+    def decompress_blocks(self, sess, blocks, x_shape, debug=False, layers='all'):
         """Uses the decompression model to decompress a point cloud (model_types.py:220-238).
-        Software pipeline over chunks: the host range decoder of chunk k overlaps the synthesis of k-1."""
+        Software pipeline over chunks: the host range decoder of chunk k overlaps the synthesis of k-1.
+        layers: 'all' decodes the occupancy string of a lossless stream (one string more per block than the model's y/z strings)
+        against x_hat and returns the exact input voxels, the threshold byte is ignored; 'base' is the lossy decode of the same stream,
+        as if the layer were not there.  A stream without the layer decodes the same under both."""
         from . import sharding
+        assert layers in ('all', 'base'), f"layers: 'all' or 'base', not {layers!r}"
         rank, world = sharding.world_info()
         if world > 1 and not getattr(self, '_in_shard', False):
             # contiguous shards; the decoded float32 points go to rank 0 with one (counts, rows) gather -- the other ranks
             # return None (rank 0 writes the file, decompress_octree.py:111-113)
             lo, hi = sharding.shard_range(len(blocks), rank, world)
-            self._in_shard = True
-            try:
+            self._in_shard = layers              # (truthy; the shard's own call below reads its layers from here: the signature it is
+            try:                                 #  called with stays the four arguments it always had)
                 local, dbg = self.decompress_blocks(sess, blocks[lo:hi], x_shape, debug)
             finally:
                 self._in_shard = False
@@ -880,15 +894,27 @@ class CompressionModel:
                 return None, dbg
             off = np.concatenate([[0], np.cumsum(counts)])
             return [flat[off[j]:off[j + 1]] for j in range(len(blocks))], dbg
+        if getattr(self, '_in_shard', False):
+            layers = self._in_shard
         ctx = self._ctx(sess)
         dhw = self._spatial(x_shape)
         chunks = [blocks[c0:c0 + self.batch_size] for c0 in range(0, len(blocks), self.batch_size)]
+        n_base = 1 if isinstance(self, CompressionModelV1) else 2
+        exact = layers == 'all' and len(blocks) > 0 and len(blocks[0][0]) == n_base + 1
         state = [None] * len(chunks)
         results = [None] * len(chunks)
         for k in range(len(chunks) + 1):
             if k < len(chunks):
                 state[k] = self._decode_phase_a(ctx, [s for s, _ in chunks[k]], dhw)
-            if k >= 1:
+            if k >= 1 and exact:
+                B = len(chunks[k - 1])
+                dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=None)
+                occ, status = ops.occ_decode_batch(ctx, dec['x_hat'], [s[n_base] for s, _ in chunks[k - 1]], check=False)
+                xyz, counts = ops.threshold_compact(ctx, occ, self._dev(ctx, ('thr_occ', B), np.full(B, 0.5, np.float32)), clip=False)
+                ops.occ_check_status(status)                            # (after the chunk's launches)
+                results[k - 1] = (xyz, counts, dec['debug'])
+                state[k - 1] = None
+            elif k >= 1:
                 thr_idx = [int(t) for _, t in chunks[k - 1]]
                 dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=self._thr_tensor(ctx, thr_idx))
                 xyz, counts = dec['xyz'], dec['counts']                 # the decoder does not clip (:232-233)

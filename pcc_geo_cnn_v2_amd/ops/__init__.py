@@ -30,4 +30,5 @@ from .anchors import (  # noqa: F401
 from .coders import (  # noqa: F401
     HostCdfTable, _np_i32, _np_host, _uniform_dtype, _SYM, _ROW, _rows_2d, _row_ptrs, _pp, _sz, range_encode_batch,
     range_decode_batch, pmf_to_quantized_cdf, rans_stream_cap, _rans_counts, _rans_index, rans_encode_launch, rans_encode_fetch,
-    rans_encode_batch, rans_check_status, rans_decode_batch)
+    rans_encode_batch, rans_check_status, rans_decode_batch, occ_stream_cap, occ_encode_launch, occ_encode_fetch, occ_encode_batch,
+    occ_check_status, occ_decode_batch)

@@ -302,3 +302,103 @@ def rans_decode_batch(ctx, table, strings, n_list, index=None, index_mod=0, chan
                                           _ptr(status), None if st_host is None else st_host.ctypes.data_as(C.c_void_p), ctx.stream),
             'pcc_rans_decode_batch')
     return out, status
+
+
+# ---------------------------------------------------------------------------------------------
+# device occupancy coder (the "occ1" string format, include/pcc_geo.h "occupancy coder (DEVICE)")
+# ---------------------------------------------------------------------------------------------
+def occ_stream_cap(n):
+    return int(L.lib().pcc_occ_stream_cap(int(n)))
+
+
+def _occ_grid(ctx, t, what):
+    """(S, ...) fp32 device tensor whose rows are contiguous -> (streams, voxels per stream, elements between two rows)"""
+    assert t.dtype == torch.float32 and t.device == ctx.device and t.dim() >= 2, f'{what}: an (S, ...) float32 tensor on the context\'s device'
+    S = t.shape[0]
+    n = t[0].numel() if S else 0
+    assert S == 0 or t[0].is_contiguous(), f'{what}: the voxels of a block must be contiguous'
+    stride = t.stride(0) if S > 1 else n
+    assert stride >= n
+    return S, n, stride
+
+
+def occ_encode_launch(ctx, x_hat, occ, lanes=0):
+    """Enqueues the encode of S blocks on the current stream.  x_hat, occ: (S, ...) float32 device tensors of the same shape, block s =
+    row s flattened (rows may be further apart than their voxels: a slice of a larger tensor); occupied = occ != 0.  lanes: 0 = the
+    lane rule.  Returns (out (S, cap) uint8, meta (2, S) int32: lengths, status) -- occ_encode_fetch(out, meta)."""
+    S, n, xs = _occ_grid(ctx, x_hat, 'occ_encode_launch: x_hat')
+    S2, n2, os_ = _occ_grid(ctx, occ, 'occ_encode_launch: occ')
+    assert (S, n) == (S2, n2), f'occ_encode_launch: x_hat {tuple(x_hat.shape)} and occ {tuple(occ.shape)}'
+    cap = occ_stream_cap(n)
+    out = torch.empty((S, cap), dtype=torch.uint8, device=ctx.device)
+    meta = torch.zeros((2, S), dtype=torch.int32, device=ctx.device)
+    if S == 0 or n == 0:                            # (an empty block codes as b'': lengths 0, nothing to launch)
+        return out, meta
+    ws = _workspace(ctx, int(L.lib().pcc_occ_workspace_bytes(S, n)) + 16)
+    L.check(L.lib().pcc_occ_encode_batch(ctx.handle, _ptr(x_hat), xs, _ptr(occ), os_, S, n, lanes, _ptr(out), cap, _ptr(meta[0]), _ptr(meta[1]),
+                                         _ptr(ws), ws.numel(), ctx.stream), 'pcc_occ_encode_batch')
+    return out, meta
+
+
+def occ_encode_fetch(out, meta):
+    """The strings of an occ_encode_launch: the lengths first, then only the used part of the byte buffer.  Waits for the device."""
+    if out.shape[0] == 0:
+        return []
+    m = meta.cpu().numpy()
+    if m[1].any():
+        raise AssertionError('pcc_occ_encode_batch: bad voxel count')
+    used = int(m[0].max())
+    b = out[:, :used].cpu().numpy() if used else np.zeros((out.shape[0], 0), np.uint8)
+    return [b[s, :int(m[0, s])].tobytes() for s in range(out.shape[0])]
+
+
+def occ_encode_batch(ctx, x_hat, occ, lanes=0):
+    """-> list of bytes (occ_encode_launch + occ_encode_fetch)"""
+    return occ_encode_fetch(*occ_encode_launch(ctx, x_hat, occ, lanes))
+
+
+def occ_check_status(status):
+    """the per-stream flags of an occ_decode_batch(check=False), fetched now: raises like the checked call"""
+    st = status.cpu().numpy()
+    if (st & 4).any():
+        raise AssertionError('pcc_occ_decode_batch: bad voxel count')
+    if st.any():
+        raise L.PccError(f'pcc_occ_decode_batch: string {int(np.flatnonzero(st)[0])} is corrupt (status {L.PCC_ERR_CORRUPT})')
+
+
+def occ_decode_batch(ctx, x_hat, strings, out=None, check=True):
+    """strings: list of bytes, one per row of x_hat ((S, ...) float32 device tensor, the decoder's own) -> (out, status).  The lane
+    bytes and lengths are checked on the host, then ONE pinned buffer (offsets, lengths, bytes) goes to the device on the current
+    stream and one workgroup decodes each string into out[s]: float32 0 / 1 of x_hat's shape (or the caller's tensor of that shape).
+    check: wait and raise PccError (status PCC_ERR_CORRUPT) when a string did not decode; False: the flags stay in `status` (device
+    int32) for occ_check_status."""
+    S, n, xs = _occ_grid(ctx, x_hat, 'occ_decode_batch: x_hat')
+    assert len(strings) == S
+    if out is None:
+        out = torch.empty(tuple(x_hat.shape), dtype=torch.float32, device=ctx.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.device == ctx.device and out.shape == x_hat.shape
+    status = torch.zeros((S,), dtype=torch.int32, device=ctx.device)
+    if S == 0:
+        return out, status
+    lens = np.fromiter((len(s_) for s_ in strings), np.int64, S)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    total = int(lens.sum())
+    head = 12 * S + (-12 * S) % 16
+    host = torch.empty((head + total + 16,), dtype=torch.uint8, pin_memory=True)
+    h = host.numpy()
+    h[:8 * S].view(np.int64)[:] = offs
+    h[8 * S:12 * S].view(np.int32)[:] = lens
+    h[head:head + total] = np.frombuffer(b''.join(strings), np.uint8)
+    h[head + total:] = 0
+    base = h.ctypes.data
+    L.check(L.lib().pcc_occ_check_strings(S, C.c_void_p(base + head), C.c_void_p(base), C.c_void_p(base + 8 * S), n), 'pcc_occ_check_strings')
+    if n == 0:                                      # (the check above took nothing but empty strings)
+        return out, status
+    dev = host.to(ctx.device, non_blocking=True)
+    ws = _workspace(ctx, int(L.lib().pcc_occ_workspace_bytes(S, n)) + 16)
+    p = dev.data_ptr()
+    st_host = np.zeros(S, np.int32) if check else None
+    L.check(L.lib().pcc_occ_decode_batch(ctx.handle, _ptr(x_hat), xs, S, n, C.c_void_p(p + head), total, C.c_void_p(p), C.c_void_p(p + 8 * S),
+                                         _ptr(out), n, _ptr(status), None if st_host is None else st_host.ctypes.data_as(C.c_void_p),
+                                         _ptr(ws), ws.numel(), ctx.stream), 'pcc_occ_decode_batch')
+    return out, status
