@@ -329,8 +329,14 @@ int pcc_voxelize(pcc_ctx* ctx, const int32_t* pts, const int32_t* block_of, int6
  *   s_ab[b][t]  = sum over the original points a of block b of min_{v in B_t} |a - v|^2        (d1_sum_AB)
  *   hsum[b][k]  = sum over voxels of level k of min_a |v - a|^2;  d1_sum_BA(t) = sum_{k>t} hsum[b][k]
  *   hcnt[b][k]  = number of voxels of level k;                    |B_t|        = sum_{k>t} hcnt[b][k]
- *   tcount[b]   (int32, (B,)) = number of thresholds whose decoded set is non-empty.
+ *   tcount[b]   (int32, (B,)) = number of thresholds whose decoded set is non-empty = the largest level of the block.
  * All sums are integers, so the host reproduces the reference's float64 metrics bit for bit.
+ * Levels are held as uint8, so the thresholds computed are t < min(tcount[b], 255).  tcount[b] == 256 (nthr == 256 and a voxel above
+ * thr[255]: clip == 0 with x_hat above the last threshold, or thresholds that end below 1) reports a level the engine cannot hold:
+ * the voxel is counted at level 255 (hsum / hcnt[b][255]), threshold 255 is not computed, s_ab[b][255] and -- in the two D2
+ * calls below -- d2_ab / d2_ba[b][255] stay zero and are NOT the statistics of B_255; everything at t < 255, and every other block, is
+ * as defined above.  The Python wrappers raise PccError naming such blocks.  With clip != 0 and thresholds up to 1.0 (the
+ * encoder's) no float32, infinities and NaN included, has a level above 255.
  * pts: (npts,3) int32 block-local coordinates, block_of: (npts,) int32; thr: nthr <= 256 increasing float32
  * thresholds (device).  clip != 0 applies np.clip(x_hat,0,1) first (the encoder does, model_types.py:202).
  * Blocks up to 128^3.  `workspace`: pcc_d1_search_workspace_bytes(B,D,H,W) bytes of device memory.             */

@@ -19,6 +19,14 @@ namespace {
 constexpr unsigned short kInf = 0xFFFF;   // no set voxel on the line / plane seen so far
 constexpr int kT = 256;
 
+// Thresholds of block b that the engines compute.  Levels are stored as uint8, so a level of 256 (nthr == 256 and a voxel above thr[255])
+// is held as 255 and the level set of t = 255 cannot be formed: tcount[b] == 256 reports it, t = 255 is then not computed and every
+// output at [b][255] stays zero (include/pcc_geo.h).  tcount[b] <= 255 otherwise, and nothing changes.
+__device__ __forceinline__ int live_thresholds(const int* __restrict__ tcount, int b) {
+    const int n = tcount[b];
+    return n < kT ? n : kT - 1;
+}
+
 __global__ void __launch_bounds__(256) k_levels(const float* __restrict__ x, const float* __restrict__ thr, int nthr,
                                                 int clip, size_t nvox, unsigned char* __restrict__ lev,
                                                 int* __restrict__ maxlev) {
@@ -62,7 +70,7 @@ __global__ void __launch_bounds__(256) k_occupancy(const int* __restrict__ pts, 
 __global__ void __launch_bounds__(256) k_edt_z(const unsigned char* __restrict__ lev, const int* __restrict__ tcount,
                                                int tmax, int t0, int lines, int W, unsigned short* __restrict__ out) {
     const int b = blockIdx.z, tl = blockIdx.y, t = t0 + tl;      // tl: slot inside the resident chunk of `tmax` thresholds
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     const int line = blockIdx.x * blockDim.x + threadIdx.x;
     if (line >= lines) return;
     const unsigned char* l = lev + ((size_t)b * lines + line) * W;
@@ -87,7 +95,7 @@ __global__ void __launch_bounds__(256) k_edt_z(const unsigned char* __restrict__
 __global__ void __launch_bounds__(256) k_edt_axis(const unsigned short* __restrict__ in, const int* __restrict__ tcount,
                                                   int tmax, int t0, size_t nvox, int L, int astride, unsigned short* __restrict__ out) {
     const int b = blockIdx.z, tl = blockIdx.y, t = t0 + tl;
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nvox) return;
     const size_t base = ((size_t)b * tmax + tl) * nvox;
@@ -133,7 +141,7 @@ template <int NW, int HM>      // NW = 64-bit words per line (W <= 64 NW), HM = 
 __global__ void __launch_bounds__(64) k_edt_zy(const unsigned char* __restrict__ lev, const int* __restrict__ tcount, int tmax, int t0,
                                                int D, int H, int W, unsigned short* __restrict__ out) {
     const int x = blockIdx.x, tl = blockIdx.y, b = blockIdx.z, t = t0 + tl;
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     __shared__ unsigned long long mask[HM][NW];
     __shared__ unsigned char sv[HM][64];         // envelope stack of lane z: positions y' ...
     __shared__ unsigned short sF[HM][64];        // ... and F = f + y'^2 (<= 2 * 127^2)
@@ -200,7 +208,7 @@ __global__ void __launch_bounds__(256) k_edt_points(const unsigned short* __rest
     int b = -1;
     if (i < npts) {
         b = block_of[i];
-        if (t < tcount[b]) {
+        if (t < live_thresholds(tcount, b)) {
             const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
             const size_t hw = (size_t)H * W;
             const unsigned short* c = g + ((size_t)b * tmax + tl) * D * hw + (size_t)ya * W + za;
@@ -363,7 +371,7 @@ constexpr unsigned short kNo16 = 0xFFFF;
 __global__ void __launch_bounds__(256) k_ft_z(const unsigned char* __restrict__ lev, const int* __restrict__ tcount, int tmax, int t0,
                                               int lines, int W, unsigned char* __restrict__ out) {
     const int b = blockIdx.z, tl = blockIdx.y, t = t0 + tl;
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     const int line = blockIdx.x * blockDim.x + threadIdx.x;
     if (line >= lines) return;
     const unsigned char* l = lev + ((size_t)b * lines + line) * W;
@@ -385,7 +393,7 @@ __global__ void __launch_bounds__(256) k_ft_z(const unsigned char* __restrict__ 
 __global__ void __launch_bounds__(256) k_ft_y(const unsigned char* __restrict__ in, const int* __restrict__ tcount, int tmax, int t0,
                                               size_t nvox, int H, int W, unsigned short* __restrict__ out) {
     const int b = blockIdx.z, tl = blockIdx.y, t = t0 + tl;
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nvox) return;
     const size_t base = ((size_t)b * tmax + tl) * nvox;
@@ -482,7 +490,7 @@ __global__ void __launch_bounds__(256) k_d2_ba(const unsigned char* __restrict__
                                                const int* __restrict__ tcount, size_t nvox, double* __restrict__ d2_ba) {
     __shared__ double sh[256];
     const int t = blockIdx.x, b = blockIdx.y;
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     double s = 0.0;
     for (size_t i = threadIdx.x; i < nvox; i += 256)
         if (lev[(size_t)b * nvox + i] > t) s += e[(size_t)b * nvox + i];
@@ -499,7 +507,7 @@ __global__ void __launch_bounds__(256) k_ft_points(const unsigned short* __restr
     unsigned long long key = ~0ull;
     if (i < npts) {
         const int b = block_of[i];
-        if (t < tcount[b]) {
+        if (t < live_thresholds(tcount, b)) {
             const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
             const size_t hw = (size_t)H * W;
             const unsigned short* c = g + ((size_t)b * tmax + tl) * D * hw + (size_t)ya * W + za;
@@ -555,7 +563,7 @@ __global__ void __launch_bounds__(256) k_d2_ab(const double* __restrict__ err, c
                                                int t0, long long npts, double* __restrict__ d2_ab) {
     __shared__ double sh[256];
     const int tl = blockIdx.x, b = blockIdx.y, t = t0 + tl;
-    if (t >= tcount[b]) return;
+    if (t >= live_thresholds(tcount, b)) return;
     double s = 0.0;
     for (long long i = block_start[b] + threadIdx.x; i < block_start[b + 1]; i += 256) s += err[(size_t)tl * npts + i];
     s = block_sum_256(s, sh);
@@ -792,7 +800,7 @@ __global__ void __launch_bounds__(256) k_tie_count(const unsigned short* __restr
     unsigned d2 = 0;
     const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
     const bool inside = xa >= 0 && xa < D && ya >= 0 && ya < H && za >= 0 && za < W;      // (k_occupancy's rule: a row outside the grid takes no part)
-    if (inside && t < tcount[b]) {
+    if (inside && t < live_thresholds(tcount, b)) {
         const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
         const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
         d2 = tie_x_pass(c, hw, xa, D);

@@ -23,25 +23,35 @@ def _search_outputs(x_hat, d2):
     return out + [torch.empty((B, 256), dtype=torch.float64, device=dev) for _ in range(2 if d2 else 0)]
 
 
-def _search_results(s_ab, hsum, hcnt, tcount, *d2):
+def _search_results(who, s_ab, hsum, hcnt, tcount, *d2):
     """The device outputs of a search as numpy: (s_ab, s_ba, n_b, tcount, *d2) with s_ba, n_b the suffix sums of the level
-    histograms over the levels k > t."""
+    histograms over the levels k > t.  tcount[b] == 256 (256 thresholds and a voxel above the last one: a level the engine's uint8
+    grid cannot hold, include/pcc_geo.h) raises PccError naming the blocks; its `.results` is the tuple this would have returned,
+    whose entries at t < 255 are valid."""
     suffix = lambda h: np.concatenate([np.cumsum(h[:, ::-1], 1)[:, ::-1][:, 1:], np.zeros((h.shape[0], 1), np.int64)], 1)
     s_ba, n_b = suffix(hsum.cpu().numpy()), suffix(hcnt.cpu().numpy())
-    return (s_ab.cpu().numpy(), s_ba, n_b, tcount.cpu().numpy()) + tuple(t.cpu().numpy() for t in d2)
+    res = (s_ab.cpu().numpy(), s_ba, n_b, tcount.cpu().numpy()) + tuple(t.cpu().numpy() for t in d2)
+    over = np.flatnonzero(res[3] >= 256)
+    if len(over):
+        err = L.PccError(f'{who}: block(s) {over.tolist()} hold a voxel above all 256 thresholds (level 256): threshold 255 is not '
+                         'computed for them; clip x_hat to a range the last threshold covers, or pass at most 255 thresholds')
+        err.blocks, err.results = over.tolist(), res
+        raise err
+    return res
 
 
 def d1_threshold_stats(ctx, x_hat, thr, pts, block_of, clip=True):
     """Exact D1 sums for every threshold of every block (see include/pcc_geo.h).  x_hat (B,D,H,W) float32,
     thr (T<=256,) float32, pts (n,3) int32 grouped by block, block_of (n,) int32 -- all on the device.
-    Returns int64 numpy arrays s_ab (B,256), s_ba (B,256), n_b (B,256) indexed by threshold, and tcount (B,)."""
+    Returns int64 numpy arrays s_ab (B,256), s_ba (B,256), n_b (B,256) indexed by threshold, and tcount (B,).  Like the two D2
+    searches below it raises PccError when a block holds a voxel above all of 256 thresholds (_search_results)."""
     B, D, H, W = _search_args(x_hat, thr, pts, block_of)
     ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
     s_ab, hsum, hcnt, tcount = out = _search_outputs(x_hat, d2=False)
     L.check(L.lib().pcc_d1_threshold_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip),
                                            _ptr(pts), _ptr(block_of), pts.shape[0], _ptr(ws), _ptr(s_ab), _ptr(hsum),
                                            _ptr(hcnt), _ptr(tcount), ctx.stream), 'pcc_d1_threshold_stats')
-    return _search_results(*out)
+    return _search_results('d1_threshold_stats', *out)
 
 
 def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, clip=True):
@@ -55,7 +65,7 @@ def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, cl
     L.check(L.lib().pcc_d12_threshold_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip), _ptr(pts), _ptr(block_of),
                                             _ptr(block_start), pts.shape[0], _ptr(normals), _ptr(ws), _ptr(ws2), _ptr(s_ab), _ptr(hsum), _ptr(hcnt),
                                             _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba), ctx.stream), 'pcc_d12_threshold_stats')
-    return _search_results(*out)
+    return _search_results('d12_threshold_stats', *out)
 
 
 class SearchTiePairOverflow(_PairOverflow):
@@ -110,5 +120,5 @@ def d12_threshold_stats_ties(ctx, x_hat, thr, pts, block_of, block_start, normal
         out = d12_threshold_stats_ties_launch(*args, max_pairs=pairs)
         pairs, over = (int(v) for v in out[-1].cpu())
         assert not over, 'd12_threshold_stats_ties: the reported pair capacity did not suffice'
-    res = _search_results(*out[:-1])
+    res = _search_results('d12_threshold_stats_ties', *out[:-1])
     return res + ((pairs, bool(over)),) if return_status else res
