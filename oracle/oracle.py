@@ -445,7 +445,7 @@ def search_tallies_lowest_index(block, x_hat, thresholds):
     """Brute-force restatement of the per-threshold statistics of /root/reference/src/model_opt.py:33-56 with
     /root/reference/src/utils/pc_metric.py:76-131, for one block: rows (|B_t|, d1_sum_AB, d1_sum_BA, d2_sum_AB, d2_sum_BA) of
     the leading non-empty level sets B_t = argwhere(clip(x_hat) > thr[t]).  Where the reference takes whatever neighbour
-    scipy's KD-tree returns among equidistant ones (pc_metric.py:114), this restatement -- like csrc/threshold_search.hip -- takes
+    scipy's KD-tree returns among equidistant ones (pc_metric.py:114), this restatement -- like csrc/search_d2.hip -- takes
     the one with the lowest (x, y, z) in lexicographic order.  block: (n, 6) = xyz + normals.  O(n |B_t|) memory: small cases."""
     a = np.asarray(block)[:, :3].astype(np.float64)
     n_a = np.asarray(block)[:, 3:6].astype(np.float32).astype(np.float64)       # (float32 normals, promoted like the product path)

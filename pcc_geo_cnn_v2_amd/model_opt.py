@@ -11,7 +11,7 @@ eligibility, guard) on whole columns of `pc_metric.metrics_table`.  Where the ta
     same for every threshold, so the B->A neighbours of all voxels are queried ONCE (on B_0, the largest level set) and sliced
     per threshold; one tree per level set remains for A->B (which neighbour scipy's tree returns among equidistant ones decides
     the D2 numbers, so that tree must be the one the reference builds: same points, same order, balanced_tree=False);
-  * `ops.d1_threshold_stats` (csrc/threshold_search.hip): exact squared Euclidean distance transforms on the GPU -- D1 only;
+  * `ops.d1_threshold_stats` (csrc/search_d1.hip): exact squared Euclidean distance transforms on the GPU -- D1 only;
   * both: d1_* columns from the GPU, d2_* columns from the host pool (`HostSearchPool`, groups=('d2',)).
 
 The comparisons `x_hat > t` are done in float32 like the reference under its pinned numpy 1.18.
@@ -400,7 +400,7 @@ class HostSearchPool:
 
 
 def gpu_search_supported(opt_metrics, dhw):
-    """The GPU search (csrc/threshold_search.hip) covers grids up to 128^3: the d1_* metrics by exact distance transforms, the
+    """The GPU search (csrc/search_d1.hip, csrc/search_d2.hip) covers grids up to 128^3: the d1_* metrics by exact distance transforms, the
     d2_* metrics (round 4) by nearest-index transforms with a stated tie rule (d2_on_gpu)."""
     return max(dhw) <= 128
 
@@ -413,7 +413,7 @@ def d2_on_gpu(mode=None, ties='pick'):
     """Where the d2_* statistics of the adaptive search come from.  DEFAULT (round 5): scipy KD-trees in the host worker pool
     -- the reference's own neighbour picks (pc_metric.py:114: among equidistant nearest neighbours it takes whatever the tree traversal
     returns), hence the reference's decisions (pinned by tests/golden/model_opt_d2.npz).  OPT-IN (--d2_search gpu / PCC_D2_GPU=1): the
-    nearest-index transforms of csrc/threshold_search.hip, 8-18x faster per cloud, ties to the lowest (x, y, z).  The two agree exactly
+    nearest-index transforms of csrc/search_d2.hip, 8-18x faster per cloud, ties to the lowest (x, y, z).  The two agree exactly
     where no tie occurs (tests/golden/model_opt_d2_tiefree.npz); on voxelised surfaces ties are the rule: measured (tools/d2_tie_table.py,
     DESIGN_HISTORY.md 3.8) the d2_mse decision differs on 82-89 % of the blocks of a 1024^3 cloud and the D2 PSNR of the d2-optimised stream,
     evaluated with the reference's metric, drops by 0.2-1.2 dB -- the search then minimises a function other than the one it is judged by.
@@ -441,7 +441,7 @@ def d2_on_gpu(mode=None, ties='pick'):
 
 
 def d1_tallies_gpu(ctx, blocks, x_hat, thresholds):
-    """Per-block D1 tallies from exact distance transforms on the GPU (csrc/threshold_search.hip).  blocks: list of
+    """Per-block D1 tallies from exact distance transforms on the GPU (csrc/search_d1.hip).  blocks: list of
     (n_i, >=3) arrays; x_hat: (B,D,H,W) float32 device tensor (clipped inside, like model_types.py:202).
     Returns [float64[T_i, 5]] -- the d2 slots are zero."""
     import torch
@@ -520,7 +520,7 @@ def d12_tallies_gpu(ctx, blocks, x_hat, thresholds, ties='pick', max_pairs=None)
 
 def mean_point_tally(block, with_normals, ties='pick'):
     """Tally of the rounded mean point (the guard of model_opt.py:59-68) without a KD-tree: its nearest original point; among
-    equidistant ones the lowest (x, y, z) in lexicographic order -- the tie rule of the GPU path (csrc/threshold_search.hip), whatever
+    equidistant ones the lowest (x, y, z) in lexicographic order -- the tie rule of the GPU path (csrc/search_d2.hip), whatever
     order the block's points are stored in (a plain argmin is that rule only for sorted blocks).  ties='mean': the
     tie-averaged rule, PM.tie_mean_tally(a, mean_point, normals)."""
     blk = np.asarray(block)

@@ -1,4 +1,4 @@
-"""Adversarial blocks for the per-block threshold search (csrc/threshold_search.hip) and a brute-force reference that evaluates every
+"""Adversarial blocks for the per-block threshold search (csrc/search_d1.hip, csrc/search_d2.hip) and a brute-force reference that evaluates every
 DISTINCT level set once.
 
 The search is exact by design (integer squared distances in uint16 grids, uint8 levels, packed sort keys, a linear-time envelope with
@@ -31,12 +31,12 @@ T256 = np.linspace(0, 1.0, 256).astype(np.float32)        # the product's thresh
 
 # ---- chunk sizes: thresholds resident at a time ---------------------------------------------------------------------------------------
 def d1_chunk(B, nvox):
-    """chunk_thresholds(B, nvox) of csrc/threshold_search.hip: two uint16 grids per (block, threshold) within 1 GiB, in [8, 256]."""
+    """chunk_thresholds(B, nvox) of csrc/search_common.h: two uint16 grids per (block, threshold) within 1 GiB, in [8, 256]."""
     return int(min(256, max(8, (1 << 30) // (B * nvox * 2 * 2))))
 
 
 def d2_chunk(B, nvox, npts):
-    """d2_layout(...).TC of csrc/threshold_search.hip: 3 bytes per voxel and 32 bytes per row within 1 GiB, in [4, 64]."""
+    """d2_layout(...).TC of csrc/search_d2.hip: 3 bytes per voxel and 32 bytes per row within 1 GiB, in [4, 64]."""
     return int(min(64, max(4, (1 << 30) // (B * nvox * 3 + npts * 32 + 1))))
 
 

@@ -60,7 +60,7 @@ def test_numerics_switch_table_matches_the_header():
     for fn in os.listdir(csrc):
         if fn.endswith(('.hip', '.cpp', '.h')) and fn != 'ctx.hip':
             for m in re.finditer(r'getenv\("(PCC_[A-Z0-9_]+)"\)', open(os.path.join(csrc, fn)).read()):
-                # (PCC_EDT_OLD selects between two kernels that produce the same integers -- tests/test_round6_gpu.py -- it is not a numerics switch)
+                # (PCC_EDT_OLD selects between two kernels that produce the same integers -- tests/test_threshold_search_gpu.py -- it is not a numerics switch)
                     assert m.group(1) in ('PCC_NO_THR_FUSE', 'PCC_EDT_OLD'), f'{fn} reads {m.group(1)} per call: numerics switches live in pcc_ctx'
     assert int(re.search(r'#define PCC_KERNEL_FAMILY (\d+)', hdr).group(1)) >= 5
 

@@ -237,3 +237,58 @@ def test_adaptive_encode_with_d2_metrics_issues_no_host_job(ctx, monkeypatch):
     host = model.encode_block_range(ctx, blocks, 32, with_normals=True, opt_metrics=['d1_mse', 'd2_mse'], max_deltas=[np.inf])
     assert model.host_search_jobs == len(blocks)
     assert out[0] == host[0] and [t[0] for t in out[1]] == [t[0] for t in host[1]]          # strings and the d1 decisions are the same
+
+
+# ------------------------------------------------------------------------------------------------------------ fused z / y passes (round 6)
+def _edt_case(ctx, shape):
+    """Device arguments (x_hat, thr, pts, block_of) of a search on random levels with empty planes and lines and about 2 % occupancy,
+    then block_start and unit float64 normals from the same generator for the D2 engines."""
+    B, D, H, W = shape
+    rng = np.random.default_rng(B * 1000 + W)
+    x = rng.random((B, D, H, W), dtype=np.float32) ** 6                   # few voxels above the high thresholds
+    x[0, : D // 2] = 0.0                                                  # empty planes and lines
+    x[-1, :, :, : W // 3] *= 0.01
+    pts, bof = [], []
+    for b in range(B):
+        p = np.argwhere(rng.random((D, H, W)) < 0.02).astype(np.int32)
+        pts.append(p); bof.append(np.full(len(p), b, np.int32))
+    start = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int32)
+    pts, bof = np.ascontiguousarray(np.vstack(pts)), np.concatenate(bof)          # (np.argwhere hands out a transposed view)
+    nrm = rng.standard_normal((len(pts), 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    thr = torch.from_numpy(np.linspace(0, 1.0, 256).astype(np.float32)).to(ctx.device)
+    dev = lambda a: torch.from_numpy(a).to(ctx.device)
+    return (ctx, dev(x), thr, dev(pts), dev(bof)), (dev(start), dev(nrm))
+
+
+@pytest.mark.parametrize('shape', [(3, 64, 64, 64), (2, 128, 128, 128), (2, 32, 48, 80), (2, 16, 24, 40), (1, 8, 128, 64)])
+def test_fused_linear_time_distance_passes_give_the_integers_of_the_two_kernel_form(ctx, shape, monkeypatch):
+    """search_d1.hip k_edt_zy (round 6): the z and y passes of the squared Euclidean distance transform of every level set in one
+    kernel -- bit masks for the z distances, a lower envelope of parabolas along y with exact integer cross-multiplied comparisons --
+    must give the sums of the two brute-force kernels (PCC_EDT_OLD=1) bit for bit: sparse and dense level sets, empty lines and planes,
+    64^3 and 128^3 blocks (one and two mask words), edges that are not powers of two, and a shape the fused kernel does not take
+    (W % 16 != 0: both runs then use the old kernels).  The search these sums feed restates /root/reference/src/model_opt.py:33-73."""
+    args, _ = _edt_case(ctx, shape)
+    monkeypatch.delenv('PCC_EDT_OLD', raising=False)
+    new = ops.d1_threshold_stats(*args)
+    monkeypatch.setenv('PCC_EDT_OLD', '1')
+    old = ops.d1_threshold_stats(*args)
+    for a, b in zip(new, old):
+        assert np.array_equal(a, b)
+    assert new[3].max() > 200 and new[0].any()
+
+
+@pytest.mark.parametrize('shape', [(2, 8, 16, 32), (1, 4, 80, 16), (1, 4, 8, 128)])
+def test_tie_averaged_engine_gives_the_same_bits_under_either_form_of_the_distance_passes(ctx, shape, monkeypatch):
+    """The tie-averaged D2 engine (search_d2.hip) takes its z / y passes from the same dispatcher as the D1 engine (search_d1.hip,
+    pcc_search_edt_zy): with PCC_EDT_OLD=1 every array it returns and its status equal the fused run's -- exactly, since nothing in the
+    engine uses float atomics and the kernels behind the z / y passes are the same.  One mask word with stack 64, stack 128, two words."""
+    args, d2 = _edt_case(ctx, shape)
+    monkeypatch.delenv('PCC_EDT_OLD', raising=False)
+    new = ops.d12_threshold_stats_ties(*args, *d2, return_status=True)
+    monkeypatch.setenv('PCC_EDT_OLD', '1')
+    old = ops.d12_threshold_stats_ties(*args, *d2, return_status=True)
+    assert new[-1] == old[-1] and not new[-1][1], (new[-1], old[-1])
+    for a, b in zip(new[:-1], old[:-1]):
+        assert np.array_equal(a, b)
+    assert new[3].max() > 200 and np.isfinite(new[4]).all() and new[4].any() and new[5].any()

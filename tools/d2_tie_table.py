@@ -1,4 +1,4 @@
-"""GPU box: what the GPU D2 tie rule (lowest (x, y, z) among equidistant nearest neighbours, csrc/threshold_search.hip) changes against the
+"""GPU box: what the GPU D2 tie rule (lowest (x, y, z) among equidistant nearest neighbours, csrc/search_d2.hip) changes against the
 reference's picks (scipy KD-tree traversal, /root/reference/src/utils/pc_metric.py:109-131) -- VERDICT r04 item 5.
 
  (1) tests/golden/model_opt_d2.npz (four voxelised-shell blocks, every level set tied) and model_opt_d2_tiefree.npz (six blocks without
