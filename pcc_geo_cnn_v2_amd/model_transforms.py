@@ -144,11 +144,29 @@ class SequentialLayer(Layer):
         if net is not None:
             return ops.network_forward(ctx, net, x, final_flags)       # the whole transform in one ABI call
         for i, layer in enumerate(self._layers):
+            if i == len(self._layers) - 2 and self._final_in16(ctx, layer, x):
+                # fp16 mode: the last block hands over in fp16 to the final 16 -> 1 transposed conv, as csrc/network.hip plans it
+                t = layer.forward_ndhwc(ctx, x, out16=True)
+                return ops.conv3d_fp16_storage(ctx, t, self._layers[-1].layer, None, in16=True, out16=False, flags=final_flags)
             if final_flags and i == len(self._layers) - 1:
                 x = layer.forward_ndhwc(ctx, x, flags=final_flags)
             else:
                 x = layer.forward_ndhwc(ctx, x)
         return x
+
+    def _final_in16(self, ctx, block, x):
+        """csrc/network.hip (pcc_network_forward, `final_in16`): in the fp16 mode the output of the last block stays fp16 when its only
+        consumer is the final 16 -> 1 k3 stride-1 transposed conv."""
+        import ctypes as C
+        fin = self._layers[-1]
+        if not (isinstance(block, ResidualLayer) and isinstance(fin, _ConvBase) and block.fp16_storage(ctx, x)):
+            return False
+        if not (fin.transposed and fin.filters == 1 and fin.k == 3 and fin.stride == 1 and fin.layer is not None and fin.impl == L.PCC_IMPL_AUTO
+                and block._layers[-1].filters == 16):
+            return False
+        N, D, H, W, _ = ops.conv_out_shape(block._layers[0].layer, x.shape)
+        d = fin.layer.desc(N, D, H, W, L.PCC_CONV_F16 | L.PCC_CONV_IN16)
+        return L.lib().pcc_conv_mfma_supported(C.byref(d)) == 1
 
     def conv_layers(self):
         return [c for layer in self._layers for c in layer.conv_layers()]
@@ -161,7 +179,42 @@ class ResidualLayer(Layer):
         self.residual_mode = residual_mode
         self.data_format = normalize_data_format(data_format)
 
-    def forward_ndhwc(self, ctx, x, flags=0):
+    def fp16_storage(self, ctx, x):
+        """csrc/network.hip's plan of the fp16 mode (pcc_network_forward, `storage`), restated for the layer-by-layer path so that both
+        give the same bits: inside an AnalysisBlock / SynthesisBlock of width 16, 32 or 64 whose grid is a multiple of 16 the two
+        intermediate tensors live in HBM as fp16 -- the stride-2 conv hands over in fp16 (PCC_CONV_OUT16), the two k3 stride-1 convs
+        run on conv_f16.hip (PCC_CONV_IN16), the last one adds the fp16 residual and writes fp32."""
+        import ctypes as C
+        if not (getattr(ctx, 'conv_flags', 0) & L.PCC_CONV_F16) or self.residual_mode != 'add' or len(self._layers) != 3:
+            return False
+        if any(not isinstance(c, _ConvBase) or c.layer is None or c.impl != L.PCC_IMPL_AUTO for c in self._layers):
+            return False
+        first, mid, last = self._layers
+        N, D, H, W, _ = x.shape
+        if not (first.k == 3 and first.stride == 2 and first.filters in (16, 32, 64) and H % 2 == 0 and W % 2 == 0):
+            return False
+        _, oD, oH, oW, _ = ops.conv_out_shape(first.layer, x.shape)
+        if oH % 16 or oW % 16:
+            return False
+        d0 = first.layer.desc(N, D, H, W, L.PCC_CONV_F16)
+        if L.lib().pcc_conv_mfma_supported(C.byref(d0)) != 1:          # (a layer on the generic path cannot hand over in fp16)
+            return False
+        for c in (mid, last):      # pcc_f16_eligible (csrc/conv_f16.hip)
+            l = c.layer
+            if not (l.k == 3 and l.stride == 1 and l.cin == l.cout and l.cin in (16, 32, 64) and oH * oW * l.cin * 4 < 2 ** 31):
+                return False
+            d = l.desc(N, oD, oH, oW, L.PCC_CONV_F16 | L.PCC_CONV_IN16)
+            if L.lib().pcc_conv_mfma_supported(C.byref(d)) != 1:
+                return False
+        return True
+
+    def forward_ndhwc(self, ctx, x, flags=0, out16=False):
+        if self.fp16_storage(ctx, x):
+            first, mid, last = self._layers
+            t1 = ops.conv3d_fp16_storage(ctx, x, first.layer, None, in16=False, out16=True)
+            t = ops.conv3d_fp16_storage(ctx, t1, mid.layer, None, out16=True)
+            return ops.conv3d_fp16_storage(ctx, t, last.layer, t1, out16=out16, flags=flags)
+        assert not out16
         t1 = self._layers[0].forward_ndhwc(ctx, x)
         t = t1
         for layer in self._layers[1:-1]:
