@@ -440,25 +440,43 @@ def d2_on_gpu(mode=None, ties='pick'):
     return mode == 'gpu'
 
 
+def _upload_blocks(ctx, blocks, thresholds, normals=None):
+    """What every GPU tally call reads, on ctx's device: (thresholds float32, xyz int32 (n,3), block of every row int32, first row of
+    every block int32 (B+1), normals in dtype `normals`) of the concatenated blocks; the last two only when `normals` is given."""
+    import torch
+    blocks = [np.asarray(b) for b in blocks]
+    # C-contiguous (n,3): np.argwhere-style inputs are transposed views and would otherwise stay Fortran-ordered
+    xyz = np.ascontiguousarray(np.concatenate([b[:, :3] for b in blocks]).astype(np.uint32).astype(np.int32))
+    sizes = np.array([len(b) for b in blocks], np.int64)
+    bof = np.repeat(np.arange(len(blocks), dtype=np.int32), sizes)
+    arrays = [np.asarray(thresholds).astype(np.float32), xyz, bof]
+    if normals is not None:
+        arrays += [np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32),
+                   np.ascontiguousarray(np.concatenate([b[:, b.shape[1] - 3:] for b in blocks]).astype(normals))]
+    return [torch.from_numpy(a).to(ctx.device) for a in arrays]
+
+
+def _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab=None, d2_ba=None):
+    """[float64[T_i, 5]] per block from the kernels' (B, n_thresholds) outputs; the d2 slots stay zero without d2 sums."""
+    out = []
+    for i in range(len(tcount)):
+        T = int(tcount[i])
+        t = np.zeros((T, 5), np.float64)
+        t[:, PM.N_B], t[:, PM.D1_AB], t[:, PM.D1_BA] = n_b[i][:T], s_ab[i][:T], s_ba[i][:T]
+        if d2_ab is not None:
+            t[:, PM.D2_AB], t[:, PM.D2_BA] = d2_ab[i][:T], d2_ba[i][:T]
+        out.append(t)
+    return out
+
+
 def d1_tallies_gpu(ctx, blocks, x_hat, thresholds):
     """Per-block D1 tallies from exact distance transforms on the GPU (csrc/search_d1.hip).  blocks: list of
     (n_i, >=3) arrays; x_hat: (B,D,H,W) float32 device tensor (clipped inside, like model_types.py:202).
     Returns [float64[T_i, 5]] -- the d2 slots are zero."""
-    import torch
     from . import ops
-    # C-contiguous (n,3): np.argwhere-style inputs are transposed views and would otherwise stay Fortran-ordered
-    pts = np.ascontiguousarray(np.concatenate([np.asarray(b)[:, :3] for b in blocks]).astype(np.uint32).astype(np.int32))
-    bof = np.concatenate([np.full(len(b), i, np.int32) for i, b in enumerate(blocks)])
-    thr = torch.from_numpy(np.asarray(thresholds).astype(np.float32)).to(ctx.device)
-    s_ab, s_ba, n_b, tcount = ops.d1_threshold_stats(ctx, x_hat, thr, torch.from_numpy(pts).to(ctx.device),
-                                                     torch.from_numpy(bof).to(ctx.device), clip=True)
-    out = []
-    for i in range(len(blocks)):
-        T = int(tcount[i])
-        t = np.zeros((T, 5), np.float64)
-        t[:, PM.N_B], t[:, PM.D1_AB], t[:, PM.D1_BA] = n_b[i][:T], s_ab[i][:T], s_ba[i][:T]
-        out.append(t)
-    return out
+    thr, xyz, bof = _upload_blocks(ctx, blocks, thresholds)
+    s_ab, s_ba, n_b, tcount = ops.d1_threshold_stats(ctx, x_hat, thr, xyz, bof, clip=True)
+    return _tally_tables(tcount, n_b, s_ab, s_ba)
 
 
 def _canonical_rows(block):
@@ -475,47 +493,15 @@ def d12_tallies_gpu(ctx, blocks, x_hat, thresholds, ties='pick', max_pairs=None)
     to the lowest (x, y, z) -- the reference takes scipy's pick (pc_metric.py:114); D1 does not depend on the pick.  ties='mean': D2
     averages over ALL equidistant nearest points (ops.d12_threshold_stats_ties, float64 normals): the sums of
     host_threshold_stats(ties='mean') up to float64 rounding, whatever the row order of the blocks."""
-    import torch
     from . import ops
     check_search_ties(ties)
     if ties == 'mean':
-        blocks = [_canonical_rows(b) for b in blocks]
-        xyz = np.ascontiguousarray(np.concatenate([b[:, :3] for b in blocks]).astype(np.uint32).astype(np.int32))
-        nrm = np.ascontiguousarray(np.concatenate([b[:, b.shape[1] - 3:] for b in blocks]).astype(np.float64))
-        sizes = np.array([len(b) for b in blocks], np.int64)
-        bof = np.repeat(np.arange(len(blocks), dtype=np.int32), sizes)
-        start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-        dev = ctx.device
-        thr = torch.from_numpy(np.asarray(thresholds).astype(np.float32)).to(dev)
-        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats_ties(
-            ctx, x_hat, thr, torch.from_numpy(xyz).to(dev), torch.from_numpy(bof).to(dev), torch.from_numpy(start).to(dev),
-            torch.from_numpy(nrm).to(dev), clip=True, max_pairs=max_pairs)
-        out = []
-        for i in range(len(blocks)):
-            T = int(tcount[i])
-            t = np.zeros((T, 5), np.float64)
-            t[:, PM.N_B], t[:, PM.D1_AB], t[:, PM.D1_BA] = n_b[i][:T], s_ab[i][:T], s_ba[i][:T]
-            t[:, PM.D2_AB], t[:, PM.D2_BA] = d2_ab[i][:T], d2_ba[i][:T]
-            out.append(t)
-        return out
-    xyz = np.ascontiguousarray(np.concatenate([np.asarray(b)[:, :3] for b in blocks]).astype(np.uint32).astype(np.int32))
-    nrm = np.ascontiguousarray(np.concatenate([np.asarray(b)[:, np.asarray(b).shape[1] - 3:] for b in blocks]).astype(np.float32))
-    sizes = np.array([len(b) for b in blocks], np.int64)
-    bof = np.repeat(np.arange(len(blocks), dtype=np.int32), sizes)
-    start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    dev = ctx.device
-    thr = torch.from_numpy(np.asarray(thresholds).astype(np.float32)).to(dev)
-    s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats(
-        ctx, x_hat, thr, torch.from_numpy(xyz).to(dev), torch.from_numpy(bof).to(dev), torch.from_numpy(start).to(dev),
-        torch.from_numpy(nrm).to(dev), clip=True)
-    out = []
-    for i in range(len(blocks)):
-        T = int(tcount[i])
-        t = np.zeros((T, 5), np.float64)
-        t[:, PM.N_B], t[:, PM.D1_AB], t[:, PM.D1_BA] = n_b[i][:T], s_ab[i][:T], s_ba[i][:T]
-        t[:, PM.D2_AB], t[:, PM.D2_BA] = d2_ab[i][:T], d2_ba[i][:T]
-        out.append(t)
-    return out
+        thr, xyz, bof, start, nrm = _upload_blocks(ctx, [_canonical_rows(b) for b in blocks], thresholds, np.float64)
+        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats_ties(ctx, x_hat, thr, xyz, bof, start, nrm, clip=True, max_pairs=max_pairs)
+    else:
+        thr, xyz, bof, start, nrm = _upload_blocks(ctx, blocks, thresholds, np.float32)
+        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats(ctx, x_hat, thr, xyz, bof, start, nrm, clip=True)
+    return _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab, d2_ba)
 
 
 def mean_point_tally(block, with_normals, ties='pick'):

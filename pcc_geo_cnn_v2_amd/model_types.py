@@ -11,6 +11,9 @@ MI355X-first differences (results identical):
   * the encoder obtains z_hat / y_hat from the quantiser directly instead of range-decoding the
     string it just produced (model_types.py:383,387): the values are identical by construction.
 `sess` in the reference's signatures is an `ops.Context` here (None = the default GPU context).
+Here: the whole-cloud selection, the models, their batch graph and the block loops of one process.  Beside it: _stream_io.py (pinned
+buffers, copy streams and the copies on them), block_search.py (the schedule of the adaptive threshold search), sharded_blocks.py (the
+block loops over the ranks of torch.distributed).
 """
 import logging
 import os
@@ -27,10 +30,11 @@ from . import _lib as L
 from . import model_transforms as MT
 from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
-from .model_opt import d1_tallies_gpu, d12_tallies_gpu, d2_on_gpu, decide_from_tallies, gpu_search_supported, metric_names
+from ._stream_io import _Immediate, _Pinned, _host_dtypes, gather_points, indexes_to_host, on_side_stream, ship, side_stream, symbols_to_device, to_host
+from .block_search import SearchSchedule
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
-from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu, finish_metrics
+from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu
 
 logger = logging.getLogger(__name__)
 
@@ -104,66 +108,29 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
             for _, m, met in rank_candidates(opt_metrics, cand_metrics, opt_groups)]
 
 
-_SIDE_STREAMS = {}
-
-
-class _Immediate:
-    """A future-like wrapper that runs its function when the result is asked for (the caller's thread)."""
-
-    def __init__(self, fn):
-        self.fn = fn
-
-    def result(self):
-        return self.fn()
-
-
-def _host_dtypes(levels=64):
-    """(symbol dtype, CDF-row dtype) of the host staging buffers: int16 / uint8 (uint8 rows cover scale tables of up to 256
-    levels; larger tables keep int32 rows); PCC_WIDE_SYMBOLS=1 keeps int32 for both (A/B runs)."""
-    if os.environ.get('PCC_WIDE_SYMBOLS'):
-        return torch.int32, torch.int32
-    return torch.int16, (torch.uint8 if levels <= 256 else torch.int32)
-
-
 ENTROPY_CODERS = ('range', 'rans')
 
 
-class _Pinned:
-    """Cache of pinned host staging buffers keyed by (tag, shape, dtype)."""
+def _np(t):
+    return t.detach().cpu().numpy()
 
-    def __init__(self):
-        self._b = {}
-        self._rings = {}
 
-    def get(self, tag, shape, dtype):
-        key = (tag, tuple(shape), dtype)
-        if key not in self._b:
-            self._b[key] = torch.empty(tuple(shape), dtype=dtype, pin_memory=True)
-        return self._b[key]
-
-    def ring(self, tag, shape, dtype, depth=4):
-        """Next buffer of a ring of `depth` pinned buffers (the decoder's staging buffers: a chunk's buffer is still the source
-        of an asynchronous host->device copy while the host already fills the next chunk's).  Returns (buffer, release):
-        call release(stream) after enqueuing the last device operation that reads the buffer; the ring waits for that event
-        before it hands the buffer out again -- no pinned allocation (a device-synchronising call) in the steady state."""
-        key = (tag, tuple(shape), dtype)
-        r = self._rings.setdefault(key, {'next': 0, 'buf': [None] * depth, 'busy': [None] * depth})
-        i = r['next']
-        r['next'] = (i + 1) % depth
-        if r['busy'][i] is not None:
-            r['busy'][i].synchronize()
-            r['busy'][i] = None
-        if r['buf'][i] is None:
-            r['buf'][i] = torch.empty(tuple(shape), dtype=dtype, pin_memory=True)
-
-        def release(stream):
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            r['busy'][i] = ev
-        return r['buf'][i], release
+def _debug_dicts(B, debug, tensors, keys):
+    """Per block the device tensors `keys` of `tensors` as numpy arrays (batch dimension kept; x_hat with its channel axis), or None per
+    block without `debug`."""
+    if not debug:
+        return [None] * B
+    return [{k: _np((tensors[k].unsqueeze(-1) if k == 'x_hat' else tensors[k])[b:b + 1]) for k in keys} for b in range(B)]
 
 
 class CompressionModel:
+    """What V1 and V2 share: the block loops and the structure of the batch graph.  A subclass states, as data: `n_strings` (strings per
+    block, without the occupancy layer), `codec_abi` (the version of the batched-graph ABI), `encode_debug_keys` / `decode_debug_keys`;
+    and, as methods, its transforms and entropy models and the steps of the batch graph that differ (`_analysis_layerwise`,
+    `_string_jobs`, `_decode_phase_a`, `_decode_phase_b_host`, `_y_rans_decode`, `_y_medians`)."""
+    n_strings = codec_abi = None
+    encode_debug_keys = decode_debug_keys = ()
+
     def __init__(self, n_thresholds=2 ** 8, data_format='channels_first', batch_size=32,
                  round_mode=L.PCC_ROUND_FLOOR_HALF, coder_threads=0, seed=42, precision='fp32', search_threads=0,
                  entropy_coder='range', lossless=False):
@@ -183,9 +150,19 @@ class CompressionModel:
         self.search_threads = search_threads      # worker processes of the host KD-tree threshold search (0 = min(cores, 64))
         self.seed = seed
         self.x_shape = None
+        # the adaptive threshold search (block_search.py): set by the CLIs' --search_ties / --d2_search
+        self.search_ties = 'pick'
+        self.d2_search = None                     # None: model_opt.D2_SEARCH, then the environment (model_opt.d2_on_gpu)
+        # ... and what it counts: blocks handed to the host pool, the kind of the last ones, A->B trees built / level sets ('tally_pruned')
+        self.host_search_jobs = self.search_trees_built = self.search_trees_total = 0
+        self.last_host_job_kind = None
+        self._host_search_pool = None
+        self._helper_pools = {}
         self._pinned = _Pinned()
         self._dev_cache = {}
         self._host_cache = {}
+        self._stagings = {}
+        self._codec_cache = (None,)
 
     # ------------------------------------------------------------------ helpers
     def _bind_transforms(self, **kinds):
@@ -215,45 +192,16 @@ class CompressionModel:
         assert len(x_shape) == 5
         return tuple(x_shape[2:5]) if self.data_format == 'channels_first' else tuple(x_shape[1:4])
 
-    def _side_stream(self, ctx, which='_copy_stream'):
-        """Copy streams beside the main one.  Work on one stream runs in order, so copies with different dependencies get
-        different streams: '_copy_stream' (encoder symbols and decoded points to the host: each waits for an event of the main
-        stream), '_up_stream' (decoder symbols to the device: no GPU-side dependency, they run as soon as the host has decoded
-        them), '_idx_stream' (the decoder's CDF-row indexes to the host)."""
-        # one set per device for the whole process (streams are a runtime resource: every model on the device shares them)
-        key = (ctx.device.index, which)
-        if key not in _SIDE_STREAMS:
-            _SIDE_STREAMS[key] = torch.cuda.Stream(ctx.device)
-        return _SIDE_STREAMS[key]
-
     def _staging(self, ctx, slot, B, y_dhw, z_dhw=None):
         """Per pipeline slot: the device + pinned staging buffers of one encode (ops.SymbolStaging), cached."""
         sym_t, row_t = _host_dtypes(len(getattr(self, 'scale_table', ())) or 64)
         F = self.num_filters
         key = (ctx.device.index, slot, B, tuple(y_dhw), None if z_dhw is None else tuple(z_dhw), sym_t, self.data_format)
-        cache = self.__dict__.setdefault('_stagings', {})
-        if key not in cache:
-            cache[key] = ops.SymbolStaging(ctx.device, B, self._stream_shape(B, y_dhw, F),
-                                           None if z_dhw is None else self._stream_shape(B, z_dhw, F), F, sym_t, row_t,
-                                           self.data_format == 'channels_first')
-        return cache[key]
-
-    def _ship(self, ctx, staging, ready=None):
-        """ONE device->pinned-host copy of a packed staging buffer on the side stream (no kernel runs there: the permutation
-        into stream order, the narrowing and the max|symbol| tiles were written in order on the main stream by the library);
-        returns the event the host has to wait for.  `ready`: event after which the staging buffer is final (default: now,
-        on the main stream)."""
-        main = torch.cuda.current_stream(ctx.device)
-        side = self._side_stream(ctx)
-        if ready is None:
-            ready = torch.cuda.Event()
-            ready.record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
-            staging.copy_out()
-            done = torch.cuda.Event()
-            done.record(side)
-        return done
+        if key not in self._stagings:
+            self._stagings[key] = ops.SymbolStaging(ctx.device, B, self._stream_shape(B, y_dhw, F),
+                                                    None if z_dhw is None else self._stream_shape(B, z_dhw, F), F, sym_t, row_t,
+                                                    self.data_format == 'channels_first')
+        return self._stagings[key]
 
     # ---- symbol order of the range-coded streams.  tfc 1.3 codes each batch item's tensor flattened in ITS memory order:
     # with the reference's default data_format='channels_first' (model_types.py:180,254,377) that is (C,D,H,W), i.e.
@@ -300,7 +248,7 @@ class CompressionModel:
         # workers 17.5 s per 190-block cloud with d2 metrics, 128 workers 23.6 s -- the KD-tree work is host-bound)
         usable = ops.usable_cores() * 4          # (KD-tree queries wait on memory: 64 workers on a 16-CPU quota measured best)
         want = max(1, min(n_jobs, self.search_threads or min(usable, 64)))
-        pool = getattr(self, '_host_search_pool', None)
+        pool = self._host_search_pool
         if pool is None or len(pool.procs) < want:
             if pool is not None:
                 pool.close()
@@ -308,20 +256,13 @@ class CompressionModel:
         return pool
 
     def _helper_thread(self, name):
-        """Single helper threads of roundtrip_stream besides the encoder's: 'ydec' (the decoder's y range-decode), 'gather' (point lists
-        to the host).  One thread each: the jobs of a kind complete in submission order."""
-        pools = self.__dict__.setdefault('_helper_pools', {})
-        if name not in pools:
+        """Single helper threads: 'coder' (host range-coder work of roundtrip_stream's encoder that may overlap the calling thread's),
+        'ydec' (its decoder's y range-decode), 'gather' (point lists to the host), 'tree' (compress_blocks' KD-tree over the original
+        cloud).  One thread each: the jobs of a kind complete in submission order."""
+        if name not in self._helper_pools:
             from concurrent.futures import ThreadPoolExecutor
-            pools[name] = ThreadPoolExecutor(max_workers=1, thread_name_prefix=f'pcc-{name}')
-        return pools[name]
-
-    def _coder_thread(self):
-        """One helper thread for host range-coder work that may overlap the calling thread's (roundtrip_stream)."""
-        if getattr(self, '_coder_pool', None) is None:
-            from concurrent.futures import ThreadPoolExecutor
-            self._coder_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='pcc-coder')
-        return self._coder_pool
+            self._helper_pools[name] = ThreadPoolExecutor(max_workers=1, thread_name_prefix=f'pcc-{name}')
+        return self._helper_pools[name]
 
     def _thr_tensor(self, ctx, thr_idx):
         """float32 thresholds of the blocks of a chunk as a device tensor."""
@@ -339,6 +280,8 @@ class CompressionModel:
         """x_hat (B,D,H,W) device; thr_idx list of ints -> (xyz (B,cap,3), counts (B,)) device tensors."""
         return ops.threshold_compact(ctx, x_hat, self._thr_tensor(ctx, thr_idx), clip=clip)
 
+    _gather_points = staticmethod(gather_points)
+
     def _codec(self, ctx):
         """pcc_codec_desc of this model on ctx's GPU (the batched-graph ABI), or None when a transform is not one of the
         plain reference stacks (then the per-layer path is used)."""
@@ -348,14 +291,16 @@ class CompressionModel:
             if nets[prefix] is None:
                 return None
         key = (ctx.device.index,) + tuple(id(n) for n in nets.values())
-        if getattr(self, '_codec_cache', (None,))[0] != key:
-            v2 = isinstance(self, CompressionModelV2)
+        if self._codec_cache[0] != key:
             med = self._dev(ctx, 'medians', self.entropy_bottleneck.medians)
-            tab = self._dev(ctx, 'scale_table', self.conditional_bottleneck.scale_table_f32) if v2 else None
+            tab = self._scale_table_dev(ctx)
             # the NetworkWeights objects are kept alive with the entry: their id()s are the key and must not be recycled
-            self._codec_cache = (key, ops.codec_desc(ctx, 2 if v2 else 1, self.num_filters, nets, med, tab, self.round_mode),
+            self._codec_cache = (key, ops.codec_desc(ctx, self.codec_abi, self.num_filters, nets, med, tab, self.round_mode),
                                  list(nets.values()))
         return self._codec_cache[1][0]
+
+    def _scale_table_dev(self, ctx):
+        return None                                # (a model with a conditional bottleneck has one)
 
     def _range_decode(self, table, strings, n, index_list, index_mod, sym_h):
         """Range-decodes one stream per block into the narrow pinned buffer `sym_h` (B, ...) in stream order; returns sym_h, or
@@ -372,21 +317,20 @@ class CompressionModel:
             wide = ops.range_decode_batch(table, strings, [n] * B, index_list, index_mod, self.coder_threads)
             return torch.from_numpy(np.stack(wide).reshape(sym_h.shape))
 
-    def _symbols_to_device(self, ctx, sym_host, release):
-        """Stream-order host symbols -> the device, as they are (one host->device copy of the narrow integers: half the PCIe
-        bytes of int32).  The copy runs on the SIDE stream -- a copy on the main stream would hold back every kernel queued
-        behind it for its 20-60 us, and the decoder calls of a chunk are enqueued long before the GPU gets to them -- on a
-        stream of their own (nothing there ever waits for the GPU), and the main stream only waits for the copy's event.  The library unpacks the symbols into the int32 (B,D,H,W,C) tensor inside the
-        decoder call (pcc_symbol_io); the per-layer path calls ops.symbols_unpack."""
-        main, side = torch.cuda.current_stream(ctx.device), self._side_stream(ctx, '_up_stream')
-        with torch.cuda.stream(side):
-            dev = sym_host.to(ctx.device, non_blocking=True)
-            release(side)
-            arrived = torch.cuda.Event()
-            arrived.record(side)
-        main.wait_event(arrived)
-        dev.record_stream(main)
-        return dev
+    def _range_decode_eb(self, tag, strings, shape):
+        """One EntropyBottleneck-coded stream per block -> (stream-order symbols in the next pinned buffer of ring `tag`, its release)."""
+        # per-slot cached pinned buffers (like the encoder's): nothing is allocated in the steady state
+        sym_h, release = self._pinned.ring(tag, shape, _host_dtypes()[0])
+        n = int(np.prod(shape[1:]))
+        rows, mod = self._eb_rows(n, self.num_filters)
+        return self._range_decode(self.entropy_bottleneck.table, strings, n, rows, mod, sym_h), release
+
+    def _host_symbols(self, staging, kind, sym):
+        """The staged stream-order symbols of tensor `kind` ('y' | 'z') for the host coder.  A symbol beyond the narrow host type (never
+        seen in practice) shows in the tile maxima: then `sym`, the int32 tensor on the device, is fetched instead."""
+        narrow, tile_max = getattr(staging, f'{kind}sym'), getattr(staging, f'{kind}tm')
+        fits = staging.sym_dtype == torch.int32 or int(tile_max.max()) <= 32767
+        return narrow if fits else self._to_stream_order(sym).cpu()
 
     # ---- entropy_coder='rans': the strings are coded on the device from the int32 (B,D,H,W,C) tensors as the codec leaves them.  Under
     # channels_first the kernels walk them channel-major (`channels`), and the EntropyBottleneck rows are one cached row vector in
@@ -406,62 +350,43 @@ class CompressionModel:
         return rows, 0, F
 
     def _rans_encode(self, ctx, ready, jobs):
-        """jobs: (table, symbols, index or None, eb) per string kind.  The launches run on the side stream once `ready` (default: now,
-        on the main stream) has passed, beside the synthesis transform.  Returns fetch() -> one list of strings per job."""
-        main, side = torch.cuda.current_stream(ctx.device), self._side_stream(ctx)
-        if ready is None:
-            ready = torch.cuda.Event()
-            ready.record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
+        """jobs: (kind, table, symbols, index or None) per string (`_string_jobs`); no index = the EntropyBottleneck's rows.  The launches run on the side
+        stream once `ready` (default: now, on the main stream) has passed, beside the synthesis transform.  Returns fetch() -> one
+        list of strings per job."""
+        with on_side_stream(ctx, after=ready) as side:
             launched = []
-            for table, sym, index, eb in jobs:
-                rows, mod, channels = self._rans_layout(ctx, sym[0].numel(), eb)
+            for _, table, sym, index in jobs:
+                rows, mod, channels = self._rans_layout(ctx, sym[0].numel(), index is None)
                 for t in (sym, index):
                     if t is not None:
                         t.record_stream(side)
-                launched.append(ops.rans_encode_launch(ctx, table, sym, None, rows if eb else index, mod, channels))
+                launched.append(ops.rans_encode_launch(ctx, table, sym, None, rows if index is None else index, mod, channels))
 
         def fetch():
             with torch.cuda.stream(side):           # (the copies wait for the side stream only, never for the main queue)
                 return [ops.rans_encode_fetch(out, meta) for out, meta in launched]
         return fetch
 
-    def _rans_decode(self, ctx, table, strings, shape, index, eb):
-        """strings -> (symbols (B,D,H,W,C) int32 on the device, status flags for ops.rans_check_status), on the current stream"""
+    def _rans_decode(self, ctx, table, strings, shape, index=None):
+        """strings -> (symbols (B,D,H,W,C) int32 on the device, status flags for ops.rans_check_status), on the current stream; no
+        index = the EntropyBottleneck's rows"""
         sym = torch.empty(tuple(shape), dtype=torch.int32, device=ctx.device)
         n = sym[0].numel()
-        rows, mod, channels = self._rans_layout(ctx, n, eb)
-        return ops.rans_decode_batch(ctx, table, strings, [n] * len(strings), rows if eb else index, mod, channels, out=sym, check=False)
+        rows, mod, channels = self._rans_layout(ctx, n, index is None)
+        return ops.rans_decode_batch(ctx, table, strings, [n] * len(strings), rows if index is None else index, mod, channels, out=sym, check=False)
 
     def _unpack(self, ctx, packed, dhw):
         return ops.symbols_unpack(ctx, packed, (packed.shape[0],) + tuple(dhw) + (self.num_filters,), self.data_format == 'channels_first')
 
-    def _gather_points(self, xyz, counts, ctx=None, ready=None):
-        """Point lists to the host.  When `ready` (an event recorded after the compaction kernels) is given, the
-        copies run on the side stream and wait only for that event, so the host never drains the main queue."""
-        if ready is None or ctx is None:
-            cnt = counts.cpu().numpy()
-            parts = [xyz[b, :int(cnt[b])] for b in range(len(cnt))]
-            flat = torch.cat(parts).cpu().numpy() if len(parts) else np.zeros((0, 3), np.float32)
-        else:
-            side = self._side_stream(ctx)
-            with torch.cuda.stream(side):
-                side.wait_event(ready)
-                xyz.record_stream(side)
-                counts.record_stream(side)
-                cnt = counts.cpu().numpy()
-                parts = [xyz[b, :int(cnt[b])] for b in range(len(cnt))]
-                flat = torch.cat(parts).cpu().numpy() if len(parts) else np.zeros((0, 3), np.float32)
-        out, p = [], 0
-        for n in cnt:
-            out.append(flat[p:p + int(n)].copy())
-            p += int(n)
-        return out
-
     # ------------------------------------------------------------------ weights / checkpoints
     def _transforms(self):
         raise NotImplementedError
+
+    def train(self, x, gamma, alpha, lmbda, **trainer_args):
+        """The training model (src/model_types.py:250-277 / :327-369) as a train.Trainer: `x` is unused (the trainer
+        voxelises its own batches from `train_blocks` / `val_blocks`); see train.Trainer for the other arguments."""
+        from .train import Trainer
+        return Trainer(self, gamma=gamma, alpha=alpha, lmbda=lmbda, **trainer_args)
 
     def init_weights(self, seed=None):
         """Seeded Glorot-uniform kernels / zero biases (Keras defaults) and tfc default entropy models:
@@ -477,7 +402,7 @@ class CompressionModel:
         medians / scale table tensors and the pcc_codec_desc, which holds raw device pointers to them."""
         self._dev_cache.clear()
         self._codec_cache = (None,)
-        self.__dict__.pop('_stagings', None)
+        self._stagings = {}
 
     def get_weights(self):
         out = {}
@@ -515,117 +440,46 @@ class CompressionModel:
                            max_deltas=(np.inf,), fixed_threshold=False, debug=False):
         """The per-block part of compress_blocks (model_types.py:192-212) for a list of blocks: returns
         (strings per block, best-threshold list per block, candidate point lists per block, metric names,
-        debug).  This is the unit that shards across GPUs (sharding.py)."""
+        debug).  This is the unit that shards across GPUs (sharded_blocks.py)."""
         ctx = self._ctx(sess)
         dhw = self._spatial(self.x_shape)
         if not fixed_threshold:
             # once per call what the reference asserts per block (model_opt.py:22-24): unknown metric names, d2_* without normals
             from .utils.pc_metric import validate_opt_metrics
             validate_opt_metrics(opt_metrics, with_normals)
-        strings_list, threshold_list, debug_t_list, x_hat_list = [], [], [], []
-        opt_metrics_ret = metric_names(opt_metrics, max_deltas)
+        strings_list, debug_t_list = [], []
+        # adaptive search (model_opt.py:33-73): every chunk's x_hat goes to the schedule, the decisions come a few chunks later
+        search = SearchSchedule(self, ctx, dhw, len(blocks), resolution, with_normals, opt_metrics, max_deltas)
         half = len(self.thresholds) // 2
-        SEARCH_LAG = 8            # chunks whose x_hat (batch x 1 MiB) stays on the GPU while their host jobs are in the pool
-        pending = []
-
-        def finalize_search(item):
-            """decisions + candidate point lists of one chunk whose tallies (GPU) / host results are complete"""
-            nonlocal opt_metrics_ret
-            chunk_, x_hat_ = item['chunk'], item['x_hat']
-            n_m = len(max_deltas) * len(opt_metrics)
-            host = [f.result() for f in item['futures']] if item['futures'] is not None else None
-            if host is not None and host and isinstance(host[0][1], tuple):      # 'tally_pruned' jobs: (tallies, (mean_tally, thresholds evaluated exactly))
-                self.search_trees_built = getattr(self, 'search_trees_built', 0) + sum(h[1][1] for h in host)
-                self.search_trees_total = getattr(self, 'search_trees_total', 0) + sum(len(h[0]) for h in host)
-                host = [(h[0], h[1][0]) for h in host]
-            if item['d1'] is not None:
-                opt_metrics_ret, best_all = decide_from_tallies(chunk_, item['d1'], len(self.thresholds), resolution, opt_metrics, max_deltas, host,
-                                                                gpu_d2=item['gpu_d2'], ties=item['ties'])
-            else:
-                opt_metrics_ret, best_all = host[0][0], [bt for _, bt in host]
-            # a block whose decode is empty at every threshold returns len(opt_metrics) entries (model_opt.py:35-36); with
-            # more than one max_delta the reference's zip(*...) would silently drop the other candidates of the WHOLE
-            # cloud -- here the 'emit nothing' index is repeated instead
-            best_all = [list(bt) + [bt[-1]] * (n_m - len(bt)) for bt in best_all]
-            per_metric = []
-            for m in range(n_m):
-                xyz, counts = self._extract_points(ctx, x_hat_, [bt[m] for bt in best_all], clip=True)
-                per_metric.append(self._gather_points(xyz, counts))
-            for j in range(len(chunk_)):
-                threshold_list.append(list(best_all[j]))
-                x_hat_list.append([per_metric[m][j] for m in range(n_m)])
-
         for c0 in range(0, len(blocks), self.batch_size):
             chunk = blocks[c0:c0 + self.batch_size]
             x = self._voxelize(ctx, chunk, dhw)
             enc = self._encode_batch(ctx, x, debug, thr=self._thr_tensor(ctx, [half] * len(chunk)) if fixed_threshold else None)
-            x_hat = enc['x_hat']
             # the occupancy layer: the chunk's dense input under the x_hat the decoder will compute (same bits: the numerics tag); the
             # threshold search below neither sees nor changes it
-            occ_job = ops.occ_encode_launch(ctx, x_hat, x) if self.lossless else None
+            occ_job = ops.occ_encode_launch(ctx, enc['x_hat'], x) if self.lossless else None
+            strings = enc['finish']()
             if fixed_threshold:
                 # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 for every metric
                 n_m = len(max_deltas) * len(opt_metrics)
-                xyz, counts = enc['xyz'], enc['counts']
-                strings = enc['finish']()
-                pts = self._gather_points(xyz, counts)
+                pts = self._gather_points(enc['xyz'], enc['counts'])
                 for j in range(len(chunk)):
-                    threshold_list.append([half] * n_m)
-                    x_hat_list.append([pts[j]] * n_m)
+                    search.thresholds.append([half] * n_m)
+                    search.points.append([pts[j]] * n_m)
             else:
-                # adaptive search (model_opt.py:33-73).  d1_* metrics: exact distance transforms on the GPU, with or without
-                # normals in the input.  d2_* metrics: the reference's numbers depend on WHICH of several equidistant nearest
-                # neighbours scipy's KD-tree returns (measured: another tie rule moves d2_mse by up to 60 % and the chosen
-                # threshold in 2 of 6 blocks), so those tallies come from the same KD-trees on the host -- one block per
-                # worker process of a persistent pool (the reference runs the blocks one after the other).  The host jobs of a
-                # chunk are only QUEUED here; the GPU goes on with the next chunks and the decisions are taken (on the merged
-                # table) a few chunks later, so the pool always holds several chunks' worth of blocks.
-                want_d2 = any(m.startswith('d2_') for m in opt_metrics)
-                on_gpu = gpu_search_supported(opt_metrics, dhw)
-                # search_ties 'mean' (DESIGN.md 4.6): the tie-averaged d2 statistics, the same sums on either engine -- from the GPU unless
-                # d2_search = 'kdtree' asks for the host restatement (every level set, nothing pruned: for checking)
-                ties = getattr(self, 'search_ties', 'pick') if want_d2 else 'pick'
-                gpu_d2 = want_d2 and on_gpu and d2_on_gpu(getattr(self, 'd2_search', None), ties)   # 'pick': nearest-index transforms, stated tie rule: opt-in (DESIGN_HISTORY.md 3.8)
-                strings = enc['finish']()
-                item = dict(chunk=chunk, x_hat=x_hat, futures=None, d1=None, gpu_d2=gpu_d2, ties=ties)
-                # (round 6) the host pool only builds the A->B trees of the thresholds that can still win a d2 metric: the workers get the
-                # GPU's exact D1 tallies as bounds (model_opt.host_threshold_stats_pruned); PCC_D2_NO_PRUNE=1: every threshold (A/B)
-                prune = on_gpu and want_d2 and not gpu_d2 and ties == 'pick' and not os.environ.get('PCC_D2_NO_PRUNE')
-                if prune:
-                    item['d1'] = d1_tallies_gpu(ctx, chunk, x_hat, self.thresholds)
-                if (want_d2 and not gpu_d2) or not on_gpu:
-                    xh = np.clip(x_hat.cpu().numpy(), 0.0, 1.0)
-                    # blocks go over in their own dtype: the worker computes exactly what the in-process call would
-                    if prune:
-                        jobs = [('tally_pruned', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, with_normals, item['d1'][j], resolution,
-                                 list(opt_metrics), list(max_deltas)) for j in range(len(chunk))]
-                    elif on_gpu:
-                        jobs = [('tally', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, with_normals, ties) for j in range(len(chunk))]
-                    else:
-                        jobs = [('decide', np.ascontiguousarray(chunk[j]), xh[j], self.thresholds, resolution, with_normals,
-                                 list(opt_metrics), list(max_deltas), ties) for j in range(len(chunk))]
-                    self.host_search_jobs = getattr(self, 'host_search_jobs', 0) + len(jobs)
-                    self.last_host_job_kind = jobs[0][0] if jobs else None
-                    pool = self._search_pool(len(blocks))
-                    item['futures'] = [pool.submit(job) for job in jobs]
-                if on_gpu and item['d1'] is None:
-                    item['d1'] = d12_tallies_gpu(ctx, chunk, x_hat, self.thresholds, ties=ties) if gpu_d2 else d1_tallies_gpu(ctx, chunk, x_hat, self.thresholds)
-                pending.append(item)
-                if len(pending) > SEARCH_LAG:
-                    finalize_search(pending.pop(0))
+                search.add(chunk, enc['x_hat'])
             if occ_job is not None:
                 strings = [tuple(ss) + (o,) for ss, o in zip(strings, ops.occ_encode_fetch(*occ_job))]
             strings_list.extend(strings)
             debug_t_list.extend(enc['debug'])
-        while pending:
-            finalize_search(pending.pop(0))
-        return strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list
+        search.drain()
+        return strings_list, search.thresholds, search.points, search.names, debug_t_list
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
                         need_points=True, metrics_device='host', d2_ties='pick'):
         """Uses the compression model to compress a point cloud (model_types.py:184-218).  Under torch.distributed (one
-        process per GPU) the block list is sharded (sharding.py): rank 0 returns the complete result, the other ranks
+        process per GPU) the block list is sharded (sharded_blocks.py): rank 0 returns the complete result, the other ranks
         return (None, metadata without point lists, local debug list).  `need_points=False` skips the gather of the
         decoded candidate point lists to rank 0 (they are only needed for --dec_files / --debug).  metrics_device='gpu'
         (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree.  d2_ties='mean' (single process
@@ -644,118 +498,23 @@ class CompressionModel:
         # encode: it is built on a helper thread while the GPU codes the blocks (0.11 s of a 614 k-point cloud's 0.30 s; scipy builds
         # without the GIL).  Same constructor call as before: the same tree, the same neighbour picks.  The GPU metrics need no tree.
         host_metrics = metrics_device == 'host'
-        self._tree_future = self._helper_thread('tree').submit(cKDTree, points[:, :3]) if len(points) and host_metrics else None
-        if world == 1:
-            try:
-                strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
-                    sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug)
-            finally:
-                tree = self._tree_future.result() if self._tree_future is not None else None
-                self._tree_future = None
-            # block -> opt metric to opt metric -> block
-            threshold_list = list(zip(*threshold_list))
-            x_hat_list = list(zip(*x_hat_list))
-            metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
-                                                  metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess),
-                                                  d2_ties=d2_ties)
-            data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
-            return data_list, metadata, debug_t_list
-        return self._compress_blocks_sharded(sess, blocks, binstr, points, resolution, level, with_normals, opt_metrics,
-                                             max_deltas, fixed_threshold, debug, need_points)
-
-    def _compress_blocks_sharded(self, sess, blocks, binstr, points, resolution, level, with_normals, opt_metrics,
-                                 max_deltas, fixed_threshold, debug, need_points):
-        from . import sharding
-        from .utils.octree_coding import block_origins
-        rank, world = sharding.world_info()
-        lo, hi = sharding.shard_range(len(blocks), rank, world)
+        tree_future = self._helper_thread('tree').submit(cKDTree, points[:, :3]) if len(points) and host_metrics else None
+        if world > 1:
+            from .sharded_blocks import compress_blocks_sharded
+            return compress_blocks_sharded(self, sess, blocks, binstr, points, resolution, level, with_normals, opt_metrics,
+                                           max_deltas, fixed_threshold, debug, need_points, tree_future)
         try:
-            strings_l, thr_l, xhat_l, names, debug_t_list = self.encode_block_range(
-                sess, blocks[lo:hi], resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug)
+            strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
+                sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug)
         finally:
-            fut, self._tree_future = getattr(self, '_tree_future', None), None
-            tree_a = fut.result() if fut is not None else None
-        if tree_a is None:
-            tree_a = cKDTree(points[:, :3])
-        n_str = 1 if isinstance(self, CompressionModelV1) else 2
-        n_m = len(max_deltas) * len(opt_metrics)
-        if names is None or not len(blocks[lo:hi]):
-            names = metric_names(opt_metrics, max_deltas)
-        # What crosses ranks (sharding.py).  Per block one int64 row: string lengths, threshold index and candidate point count per metric.
-        # The D1/D2 numbers of every candidate (select_best_per_opt_metric, src/model_types.py:128-176) come from per-rank partial tallies
-        # of the pairs a rank OWNS (its decoded point is the nearest one to an original point: MIN over ranks of `d2 * world + rank`).
-        origins = block_origins(binstr, [0, 0, 0], [resolution] * 3, level)[lo:hi]
-        p1, p1_n = points[:, :3], get_normals_if(points, with_normals)
-        cand_global = []
-        for m in range(n_m):
-            parts = [np.asarray(xhat_l[j][m], np.float64).reshape(-1, 3) + np.asarray(origins[j], np.float64) for j in range(hi - lo)]
-            cand_global.append(np.vstack(parts) if parts else np.zeros((0, 3)))
-        width = n_str + 2 * n_m
-        rows = np.zeros((hi - lo, width), np.int64)
-        for j in range(hi - lo):
-            rows[j, :n_str] = [len(x) for x in strings_l[j]]
-            rows[j, n_str:n_str + n_m] = thr_l[j][:n_m]
-            rows[j, n_str + n_m:] = [len(x) for x in xhat_l[j][:n_m]]
-        per_rank = sharding.shard_sizes(len(blocks), world)      # known to every rank: no size exchange anywhere below
-        first = np.concatenate([[0], np.cumsum(per_rank)])
-        my_strings = b''.join(x for ss in strings_l for x in ss)
-        if 8 * len(p1) * n_m * world <= int(os.environ.get('PCC_KEY_GATHER_MAX_BYTES', 64 << 20)):
-            # TWO collectives per cloud: (1) ONE all_gather of the rows with the MIN keys of all candidates riding as extra
-            # rows (sharding.PiggybackGroup: every rank takes the MIN itself), (2) ONE all_gather of bytes: strings + the partial tallies
-            grp = sharding.PiggybackGroup(rows, per_rank)
-            part_tallies, have = cloud_metrics_batch(p1, cand_global, resolution - 1, p1_n, tree_a, grp, partial=True)
-            table = grp.table
-            tb = np.ascontiguousarray(part_tallies, np.float64).tobytes()
-            payloads = sharding.all_gather_bytes(my_strings + tb, counts=[int(table[first[r]:first[r + 1], :n_str].sum()) + len(tb) for r in range(world)])
-            blobs = [p[:len(p) - len(tb)] for p in payloads]
-            tallies = np.zeros_like(part_tallies, dtype=np.float64)
-            for p in payloads:          # rank order: every rank gets the same doubles
-                tallies += np.frombuffer(p[len(p) - len(tb):], np.float64).reshape(part_tallies.shape)
-        else:
-            # a cloud whose keys (8 B per original point and candidate) are too many to move `world` times: THREE collectives -- (1) ONE
-            # all_reduce(MIN) of the keys, (2) ONE all_gather of the rows + T rows with the bit patterns of the partial tallies (summed in
-            # rank order), (3) ONE padded uint8 gather of the strings to rank 0
-            part_tallies, have = cloud_metrics_batch(p1, cand_global, resolution - 1, p1_n, tree_a, sharding.RankGroup(), partial=True)
-            T = -(-part_tallies.size // width)
-            send = np.zeros((hi - lo + T, width), np.int64)
-            send[:hi - lo] = rows
-            send[hi - lo:].reshape(-1)[:part_tallies.size] = np.ascontiguousarray(part_tallies, np.float64).reshape(-1).view(np.int64)
-            gathered = sharding.all_gather_rows(send, counts=[n + T for n in per_rank])
-            ends = np.cumsum([n + T for n in per_rank])
-            table = np.concatenate([gathered[e - n - T:e - T] for e, n in zip(ends, per_rank)], 0)
-            tallies = np.zeros_like(part_tallies, dtype=np.float64)
-            for e in ends:
-                tallies += gathered[e - T:e].reshape(-1)[:part_tallies.size].view(np.float64).reshape(part_tallies.shape)
-            blobs = sharding.gather_bytes(my_strings, counts=[int(table[first[r]:first[r + 1], :n_str].sum()) for r in range(world)])
-        assert table.shape[0] == len(blocks)
-        # the selection is replicated: every rank holds the summed tallies
-        cand_metrics = finish_metrics(len(p1), tallies, have, resolution - 1, p1_n is not None)
-        metadata = [{'idx': m, 'metrics': met} for _, m, met in rank_candidates(names, cand_metrics)]
-        # (4) the reconstruction of the selected candidates on rank 0 (only for --dec_files / --debug)
-        if need_points:
-            for md in metadata:
-                m = md['idx']
-                n_pts = table[:, n_str + n_m + m]
-                flat = sharding.gather_rows(np.vstack([np.asarray(xhat_l[j][m], np.float32).reshape(-1, 3) for j in range(hi - lo)])
-                                            if hi > lo else np.zeros((0, 3), np.float32),
-                                            counts=[int(n_pts[first[r]:first[r + 1]].sum()) for r in range(world)])
-                if rank == 0:
-                    off = np.concatenate([[0], np.cumsum(n_pts)])
-                    md['x_hat_list'] = tuple(flat[off[j]:off[j + 1]] for j in range(len(blocks)))
-                    md['blocks_depart'] = departition_octree(md['x_hat_list'], binstr, [0, 0, 0], [resolution] * 3, level)
-                    md['blocks_full'] = np.vstack(md['blocks_depart'])
-        if rank != 0:
-            return None, metadata, debug_t_list
-        # rank 0: split the gathered strings back into per-block tuples, block order == rank order
-        strings_list, raw, pos = [], b''.join(blobs), 0
-        for j in range(len(blocks)):
-            ss = []
-            for k in range(n_str):
-                ss.append(raw[pos:pos + int(table[j, k])])
-                pos += int(table[j, k])
-            strings_list.append(tuple(ss))
-        assert pos == len(raw)
-        data_list = [list(zip(strings_list, [int(t) for t in table[:, n_str + md['idx']]])) for md in metadata]
+            tree = tree_future.result() if tree_future is not None else None
+        # block -> opt metric to opt metric -> block
+        threshold_list = list(zip(*threshold_list))
+        x_hat_list = list(zip(*x_hat_list))
+        metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
+                                              metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess),
+                                              d2_ties=d2_ties)
+        data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
         return data_list, metadata, debug_t_list
 
     def roundtrip_stream(self, sess, dense_chunks, thr_idx=None, gather=True):
@@ -789,14 +548,11 @@ class CompressionModel:
             strings, cnt_e, xyz_d, cnt_d, ready = item
             if threaded:
                 torch.cuda.set_device(ctx.device)
-            pts = self._gather_points(xyz_d, cnt_d, ctx, ready) if gather else None
-            with torch.cuda.stream(self._side_stream(ctx)):     # never a blocking copy on the main stream
-                self._side_stream(ctx).wait_event(ready)
-                cnt_e.record_stream(self._side_stream(ctx))
-                ce = cnt_e.cpu().numpy()
-                if not gather:
-                    cnt_d.record_stream(self._side_stream(ctx))
-                    pts = cnt_d.cpu().numpy()
+            if gather:
+                pts = self._gather_points(xyz_d, cnt_d, ctx, ready)
+                ce, = to_host(ctx, ready, cnt_e)
+            else:
+                ce, pts = to_host(ctx, ready, cnt_e, cnt_d)
             return strings, ce, pts
 
         def stage_a(item):
@@ -805,7 +561,7 @@ class CompressionModel:
             st = self._decode_phase_a(ctx, strings, dhw)
             # (round 5) the y range-decode of this chunk -- host work only -- starts now on a helper thread and is collected one iteration
             # later by stage_b, when both coders fit the usable cores side by side (the rule of the encoder's helper thread below)
-            host_coder = threaded and self.entropy_coder == 'range' and hasattr(self, '_decode_phase_b_host')      # (rans: no host part)
+            host_coder = threaded and self.entropy_coder == 'range' and 'host' not in st      # (rans: no host part; 'host': done in phase a)
             yfut = self._helper_thread('ydec').submit(self._decode_phase_b_host, st) if host_coder else None
             q_b.append((strings, enc['counts'], st, dhw, B, yfut))
             if len(q_b) > 1:
@@ -830,7 +586,7 @@ class CompressionModel:
                 # (only when both coders fit the usable cores side by side: with 32 streams per call on a 16-core container the two
                 # would just take turns, with scheduler jitter on top -- measured: 7-12 ms hiccups in the 64^3 headline)
                 on_thread = 2 * B <= ops.usable_cores() and self.entropy_coder == 'range'        # (rans: finish only fetches bytes)
-                enc['strings'] = self._coder_thread().submit(enc['finish']) if on_thread else _Immediate(enc['finish'])
+                enc['strings'] = self._helper_thread('coder').submit(enc['finish']) if on_thread else _Immediate(enc['finish'])
                 k += 1
                 q_a.append((enc, dhw, B))
                 t1 = time.perf_counter()
@@ -868,38 +624,25 @@ class CompressionModel:
                             pass
 
     def decompress_blocks(self, sess, blocks, x_shape, debug=False, layers='all'):
-        """Uses the decompression model to decompress a point cloud (model_types.py:220-238).
-        Software pipeline over chunks: the host range decoder of chunk k overlaps the synthesis of k-1.
+        """Uses the decompression model to decompress a point cloud (model_types.py:220-238).  Under torch.distributed the block list
+        is sharded and rank 0 returns the points (sharded_blocks.py).
         layers: 'all' decodes the occupancy string of a lossless stream (one string more per block than the model's y/z strings)
         against x_hat and returns the exact input voxels, the threshold byte is ignored; 'base' is the lossy decode of the same stream,
         as if the layer were not there.  A stream without the layer decodes the same under both."""
         from . import sharding
         assert layers in ('all', 'base'), f"layers: 'all' or 'base', not {layers!r}"
-        rank, world = sharding.world_info()
-        if world > 1 and not getattr(self, '_in_shard', False):
-            # contiguous shards; the decoded float32 points go to rank 0 with one (counts, rows) gather -- the other ranks
-            # return None (rank 0 writes the file, decompress_octree.py:111-113)
-            lo, hi = sharding.shard_range(len(blocks), rank, world)
-            self._in_shard = layers              # (truthy; the shard's own call below reads its layers from here: the signature it is
-            try:                                 #  called with stays the four arguments it always had)
-                local, dbg = self.decompress_blocks(sess, blocks[lo:hi], x_shape, debug)
-            finally:
-                self._in_shard = False
-            per_rank = sharding.shard_sizes(len(blocks), world)
-            first = np.concatenate([[0], np.cumsum(per_rank)])
-            counts = sharding.all_gather_rows(np.array([[len(b)] for b in local], np.int64).reshape(-1, 1), counts=per_rank)[:, 0]
-            flat = sharding.gather_rows(np.vstack(local).astype(np.float32) if len(local) else np.zeros((0, 3), np.float32),
-                                        counts=[int(counts[first[r]:first[r + 1]].sum()) for r in range(world)])
-            if rank != 0:
-                return None, dbg
-            off = np.concatenate([[0], np.cumsum(counts)])
-            return [flat[off[j]:off[j + 1]] for j in range(len(blocks))], dbg
-        if getattr(self, '_in_shard', False):
-            layers = self._in_shard
+        if sharding.world_info()[1] > 1:
+            from .sharded_blocks import decompress_blocks_sharded
+            return decompress_blocks_sharded(self, sess, blocks, x_shape, debug, layers)
+        return self.decompress_block_range(sess, blocks, x_shape, debug, layers)
+
+    def decompress_block_range(self, sess, blocks, x_shape, debug=False, layers='all'):
+        """decompress_blocks for a list of blocks on this process' GPU: the unit that shards across GPUs.
+        Software pipeline over chunks: the host range decoder of chunk k overlaps the synthesis of k-1."""
         ctx = self._ctx(sess)
         dhw = self._spatial(x_shape)
         chunks = [blocks[c0:c0 + self.batch_size] for c0 in range(0, len(blocks), self.batch_size)]
-        n_base = 1 if isinstance(self, CompressionModelV1) else 2
+        n_base = self.n_strings
         exact = layers == 'all' and len(blocks) > 0 and len(blocks[0][0]) == n_base + 1
         state = [None] * len(chunks)
         results = [None] * len(chunks)
@@ -926,12 +669,97 @@ class CompressionModel:
             debug_t_list.extend(dbg)
         return dec_blocks, debug_t_list
 
+    # ------------------------------------------------------------------ batched graph.  With a pcc_codec_desc (`_codec`) the GPU part
+    # of each phase is ONE ABI call; otherwise the same steps run layer by layer.  Both leave the same tensors under the same names.
+    def _synthesis_layerwise(self, ctx, t, thr, clip):
+        """t['y_hat'] -S-> t['x_hat'] [-> thresholded points t['xyz'], t['counts']], layer by layer"""
+        t['x_hat'] = self.synthesis_transform.forward_ndhwc(ctx, t['y_hat'])[..., 0].contiguous()
+        if thr is not None:
+            t['xyz'], t['counts'] = ops.threshold_compact(ctx, t['x_hat'], thr, clip=clip)
 
-def _np(t):
-    return t.detach().cpu().numpy()
+    def _encode_batch(self, ctx, x, debug, thr=None, slot=0):
+        """The compress graph of a chunk x (B,D,H,W): returns x_hat (and, with `thr`, the encoder-side points xyz / counts), the per-block
+        debug dicts and finish() -> the strings per block, which waits for the symbols and codes them."""
+        B, dhw = x.shape[0], x.shape[1:4]
+        codec = self._codec(ctx)
+        ready = None
+        rans = self.entropy_coder == 'rans'
+        stg = None if rans else self._staging(ctx, slot, B, [v // 8 for v in dhw], [v // 16 for v in dhw] if self.n_strings == 2 else None)
+        if codec is not None:                      # the whole GPU part of compress() (model_types.py:289-293 / :379-388) in one ABI call
+            ready = torch.cuda.Event()
+            ready.record(side_stream(ctx, '_idx_stream'))            # creates the handle (on a stream that is idle now: a record costs the
+                                                                     # main queue a few microseconds); re-recorded by the library on the main stream
+            t = ops.codec_encode(ctx, codec, x.contiguous(), thr, symbols_ready=ready, staging=stg)
+        else:
+            t = self._analysis_layerwise(ctx, x)
+        jobs = self._string_jobs(t)
+        if codec is None and not rans:
+            stg.pack(ctx, *(t[k] for k in ('symbols', 'z_symbols', 'indexes') if k in t))
+        # what crosses PCIe: ONE buffer per chunk -- symbols as int16, the 64 scale rows as uint8 (8.5 -> 3.3 MB per 32-block
+        # chunk), packed in stream order by the library before `ready`, plus the per-tile max|symbol| that tells the host
+        # afterwards whether a symbol exceeded int16 (then that tensor is fetched again as int32: never seen in practice).
+        # The copy runs on a side stream so that it overlaps the synthesis transform.
+        # entropy_coder='rans': nothing is narrowed or shipped; the strings are coded on the side stream from the int32 tensors.
+        if rans:
+            fetch = self._rans_encode(ctx, ready, jobs)
+        else:
+            ev = ship(ctx, stg, ready)
+        if codec is None:
+            self._synthesis_layerwise(ctx, t, thr, clip=True)
+        eb_rows = {kind: self._eb_rows(sym[0].numel(), self.num_filters) for kind, _, sym, index in jobs if index is None}
+
+        def finish():
+            if rans:
+                return list(zip(*fetch()))
+            ev.synchronize()  # symbols are on the host
+            coded = []
+            for kind, table, sym, index in jobs:
+                rows, mod = eb_rows[kind] if index is None else (stg.idx.view(B, -1), 0)
+                coded.append(ops.range_encode_batch(table, self._host_symbols(stg, kind, sym).view(B, -1), rows, mod, self.coder_threads))
+            return list(zip(*coded))  # strings = (y_string,) / (y_string, z_string), model_types.py:293,389
+
+        dbg = _debug_dicts(B, debug, t, self.encode_debug_keys)
+        return dict(x_hat=t['x_hat'], finish=finish, debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
+
+    def _decode_phase_a(self, ctx, strings, dhw):
+        """What can be decoded of a chunk before its predecessor's synthesis is enqueued -> the state phase b continues from"""
+        raise NotImplementedError
+
+    def _decode_phase_b_host(self, st):
+        """The host part of phase b, (stream-order y symbols on the host, their ring release), when phase a has not left it under
+        'host' already.  No GPU work is enqueued here, so roundtrip_stream may run it on a helper thread."""
+        return st['host']
+
+    def _decode_phase_b(self, ctx, st, dhw, debug, thr=None, host=None):
+        """y_string -> y symbols -> y_hat -S-> x_hat [-> thresholded points].  host: the result of _decode_phase_b_host when it already
+        ran elsewhere."""
+        rans = self.entropy_coder == 'rans'
+        if rans:
+            ysym, status = self._y_rans_decode(ctx, st, dhw)
+            packed = None
+        else:
+            ysym, packed = None, symbols_to_device(ctx, *(self._decode_phase_b_host(st) if host is None else host))
+        codec = self._codec(ctx)
+        if codec is not None:                      # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
+            t = ops.codec_decode_main(ctx, codec, ysym, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
+        else:
+            if not rans:
+                ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
+            t = dict(symbols=ysym, y_hat=ops.dequantize(ctx, ysym, self._y_medians(ctx)))
+            self._synthesis_layerwise(ctx, t, thr, clip=False)
+        if rans:                                    # (after the chunk's launches: the device works while the host waits for the flags)
+            for flags in (st.get('zstatus'), status):
+                if flags is not None:
+                    ops.rans_check_status(flags)
+        dbg = _debug_dicts(len(st['strings']), debug, {**st, **t}, self.decode_debug_keys)      # (st: what phase a decoded)
+        return dict(x_hat=t['x_hat'], debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
 
 
 class CompressionModelV1(CompressionModel):
+    n_strings, codec_abi = 1, 1
+    encode_debug_keys = ('y', 'symbols', 'y_hat', 'x_hat')
+    decode_debug_keys = ('y_hat', 'x_hat')
+
     def __init__(self, num_filters=32,
                  analysis_transform_type=TransformType.AnalysisTransformV1,
                  synthesis_transform_type=TransformType.SynthesisTransformV1, *args, **kwargs):
@@ -939,12 +767,6 @@ class CompressionModelV1(CompressionModel):
         self._bind_transforms(analysis=analysis_transform_type, synthesis=synthesis_transform_type)
         self.entropy_bottleneck = None
         super().__init__(*args, **kwargs)
-
-    def train(self, x, gamma, alpha, lmbda, **trainer_args):
-        """The training model (src/model_types.py:250-277 / :327-369) as a train.Trainer: `x` is unused (the trainer
-        voxelises its own batches from `train_blocks` / `val_blocks`); see train.Trainer for the other arguments."""
-        from .train import Trainer
-        return Trainer(self, gamma=gamma, alpha=alpha, lmbda=lmbda, **trainer_args)
 
     def _transforms(self):
         t = []
@@ -981,92 +803,35 @@ class CompressionModelV1(CompressionModel):
         self.synthesis_transform = self.synthesis_transform_class(self.num_filters, data_format=self.data_format)
         self.init_weights()
 
-    # ---- batched graph
-    def _encode_batch(self, ctx, x, debug, thr=None, slot=0):
-        B = x.shape[0]
-        eb = self.entropy_bottleneck
-        codec = self._codec(ctx)
-        t = {}
-        ready = None
-        rans = self.entropy_coder == 'rans'
-        stg = None if rans else self._staging(ctx, slot, B, [v // 8 for v in x.shape[1:4]])
-        if codec is not None:                      # analysis -> quantise -> synthesis (-> fixed threshold) in one ABI call
-            ready = torch.cuda.Event()
-            ready.record(self._side_stream(ctx, '_idx_stream'))      # creates the handle (on a stream that is idle now: a record costs the
-                                                                     # main queue a few microseconds); re-recorded by the library on the main stream
-            t = ops.codec_encode(ctx, codec, x.contiguous(), thr, symbols_ready=ready, staging=stg)
-            y, ysym, y_hat, x_hat = t['y'], t['symbols'], t['y_hat'], t['x_hat']
-        else:
-            med = self._dev(ctx, 'medians', eb.medians)
-            y = self.analysis_transform.forward_ndhwc(ctx, x.unsqueeze(-1))
-            ysym, y_hat = ops.quantize(ctx, y, med, self.round_mode)
-            if not rans:
-                stg.pack(ctx, ysym)
-        if rans:
-            fetch = self._rans_encode(ctx, ready, [(eb.table, ysym, None, True)])
-        else:
-            ev = self._ship(ctx, stg, ready)
-        if codec is None:
-            x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
-            if thr is not None:
-                t['xyz'], t['counts'] = ops.threshold_compact(ctx, x_hat, thr, clip=True)
-        rows, mod = self._eb_rows(ysym[0].numel(), self.num_filters)
+    # ---- batched graph: x -A-> y -EB-> y_string ; y_hat -S-> x_hat
+    def _y_medians(self, ctx):
+        return self._dev(ctx, 'medians', self.entropy_bottleneck.medians)
 
-        def finish():
-            if rans:
-                return [(s,) for s in fetch()[0]]
-            ev.synchronize()
-            # a symbol beyond the narrow host type (never seen in practice) shows in the tile maxima: fetch that tensor as int32
-            ys_src = stg.ysym if stg.sym_dtype == torch.int32 or int(stg.ytm.max()) <= 32767 else self._to_stream_order(ysym).cpu()
-            ys = ops.range_encode_batch(eb.table, ys_src.view(B, -1), rows, mod, self.coder_threads)
-            return [(s,) for s in ys]
+    def _analysis_layerwise(self, ctx, x):
+        y = self.analysis_transform.forward_ndhwc(ctx, x.unsqueeze(-1))
+        ysym, y_hat = ops.quantize(ctx, y, self._y_medians(ctx), self.round_mode)
+        return dict(y=y, symbols=ysym, y_hat=y_hat)
 
-        dbg = [{'y': _np(y[b:b + 1]), 'symbols': _np(ysym[b:b + 1]), 'y_hat': _np(y_hat[b:b + 1]),
-                'x_hat': _np(x_hat[b:b + 1].unsqueeze(-1))} for b in range(B)] if debug else [None] * B
-        return dict(x_hat=x_hat, finish=finish, debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
+    def _string_jobs(self, t):
+        return [('y', self.entropy_bottleneck.table, t['symbols'], None)]
 
     def _decode_phase_a(self, ctx, strings, dhw):
-        B = len(strings)
-        eb = self.entropy_bottleneck
         if self.entropy_coder == 'rans':           # the strings go to the device as they are, in phase b
             return dict(strings=strings)
-        yshape = self._stream_shape(B, [v // 8 for v in dhw], self.num_filters)
-        ysym_h, ysym_release = self._pinned.ring('dec_ysym', yshape, _host_dtypes()[0])
-        n = int(np.prod(yshape[1:]))
-        rows, mod = self._eb_rows(n, self.num_filters)
-        return dict(ysym=self._range_decode(eb.table, [s[0] for s in strings], n, rows, mod, ysym_h),
-                    ysym_release=ysym_release)
+        yshape = self._stream_shape(len(strings), [v // 8 for v in dhw], self.num_filters)
+        return dict(strings=strings, host=self._range_decode_eb('dec_ysym', [s[0] for s in strings], yshape))
 
-    def _decode_phase_b(self, ctx, st, dhw, debug, thr=None):
-        eb = self.entropy_bottleneck
-        rans = self.entropy_coder == 'rans'
-        if rans:
-            B = len(st['strings'])
-            ysym, status = self._rans_decode(ctx, eb.table, [s[0] for s in st['strings']], (B,) + tuple(v // 8 for v in dhw) + (self.num_filters,),
-                                             None, True)
-            packed = None
-        else:
-            ysym, packed = None, self._symbols_to_device(ctx, st['ysym'], st['ysym_release'])
-        codec = self._codec(ctx)
-        if codec is not None:                      # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
-            t = ops.codec_decode_main(ctx, codec, ysym, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
-            y_hat, x_hat = t['y_hat'], t['x_hat']
-        else:
-            if not rans:
-                ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
-            y_hat = ops.dequantize(ctx, ysym, self._dev(ctx, 'medians', eb.medians))
-            x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
-            t = {}
-            if thr is not None:
-                t['xyz'], t['counts'] = ops.threshold_compact(ctx, x_hat, thr, clip=False)
-        if rans:
-            ops.rans_check_status(status)           # (after the chunk's launches: the device works while the host waits for the flags)
-        B = x_hat.shape[0]
-        dbg = [{'y_hat': _np(y_hat[b:b + 1]), 'x_hat': _np(x_hat[b:b + 1].unsqueeze(-1))} for b in range(B)] if debug else [None] * B
-        return dict(x_hat=x_hat, debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
+    def _y_rans_decode(self, ctx, st, dhw):
+        B = len(st['strings'])
+        return self._rans_decode(ctx, self.entropy_bottleneck.table, [s[0] for s in st['strings']],
+                                 (B,) + tuple(v // 8 for v in dhw) + (self.num_filters,))
 
 
 class CompressionModelV2(CompressionModel):
+    n_strings, codec_abi = 2, 2
+    encode_debug_keys = ('y', 'z', 'z_symbols', 'z_hat', 'sigma_hat', 'indexes', 'symbols', 'y_hat', 'x_hat')
+    decode_debug_keys = ('z_hat', 'sigma_hat', 'indexes', 'symbols', 'y_hat', 'x_hat')
+
     def __init__(self, num_filters=32,
                  analysis_transform_type=TransformType.AnalysisTransformV1,
                  synthesis_transform_type=TransformType.SynthesisTransformV1,
@@ -1079,12 +844,6 @@ class CompressionModelV2(CompressionModel):
         self.scale_table = scale_table(scales_min, scales_max, scales_levels)
         self.entropy_bottleneck = self.conditional_bottleneck = None
         super().__init__(*args, **kwargs)
-
-    def train(self, x, gamma, alpha, lmbda, **trainer_args):
-        """The training model (src/model_types.py:250-277 / :327-369) as a train.Trainer: `x` is unused (the trainer
-        voxelises its own batches from `train_blocks` / `val_blocks`); see train.Trainer for the other arguments."""
-        from .train import Trainer
-        return Trainer(self, gamma=gamma, alpha=alpha, lmbda=lmbda, **trainer_args)
 
     def _transforms(self):
         t = []
@@ -1129,123 +888,70 @@ class CompressionModelV2(CompressionModel):
         self.init_weights()
 
     # ---- batched graph: x -A-> y -HA-> z -EB-> z_string ; z_hat -HS-> sigma ; (y, sigma) -GC-> y_string ; y_hat -S-> x_hat
-    def _encode_batch(self, ctx, x, debug, thr=None, slot=0):
-        B = x.shape[0]
-        F = self.num_filters
-        eb, gc = self.entropy_bottleneck, self.conditional_bottleneck
+    def _y_medians(self, ctx):
+        return None                                # (the conditional bottleneck quantises y around zero)
+
+    def _scale_table_dev(self, ctx):
+        return self._dev(ctx, 'scale_table', self.conditional_bottleneck.scale_table_f32)
+
+    def _scales_layerwise(self, ctx, t):
+        """t['z_hat'] -HS-> t['sigma_hat'] -> t['indexes'] (the CDF row of every y symbol), layer by layer"""
+        t['sigma_hat'] = self.hyper_synthesis_transform.forward_ndhwc(ctx, t['z_hat'])
+        t['indexes'] = ops.scale_to_index(ctx, t['sigma_hat'], self._scale_table_dev(ctx))
+        return t
+
+    def _analysis_layerwise(self, ctx, x):
+        med = self._dev(ctx, 'medians', self.entropy_bottleneck.medians)
+        y = self.analysis_transform.forward_ndhwc(ctx, x.unsqueeze(-1))
+        z = self.hyper_analysis_transform.forward_ndhwc(ctx, y)
+        zsym, z_hat = ops.quantize(ctx, z, med, self.round_mode)
+        t = self._scales_layerwise(ctx, dict(y=y, z=z, z_symbols=zsym, z_hat=z_hat))
+        t['symbols'], t['y_hat'] = ops.quantize(ctx, y, None, self.round_mode)
+        return t
+
+    def _string_jobs(self, t):
+        return [('y', self.conditional_bottleneck.table, t['symbols'], t['indexes']), ('z', self.entropy_bottleneck.table, t['z_symbols'], None)]
+
+    def _hyper_decode(self, ctx, dhw, zsym=None, zpacked=None, idx_packed=None):
+        """z symbols (int32 on the device) or `zpacked` (stream-order symbols as the host->device copy delivered them) -> z_hat,
+        sigma_hat, indexes; idx_packed: device tensor that also receives the indexes in stream order, for the host coder."""
         codec = self._codec(ctx)
-        t = {}
-        ready = None
-        rans = self.entropy_coder == 'rans'
-        stg = None if rans else self._staging(ctx, slot, B, [v // 8 for v in x.shape[1:4]], [v // 16 for v in x.shape[1:4]])
-        if codec is not None:                      # the whole GPU part of compress() (model_types.py:379-388) in one ABI call
-            ready = torch.cuda.Event()
-            ready.record(self._side_stream(ctx, '_idx_stream'))      # creates the handle (on a stream that is idle now: a record costs the
-                                                                     # main queue a few microseconds); re-recorded by the library on the main stream
-            t = ops.codec_encode(ctx, codec, x.contiguous(), thr, symbols_ready=ready, staging=stg)
-            y, z, zsym, z_hat, sigma, idx, ysym, y_hat, x_hat = (t[k] for k in ('y', 'z', 'z_symbols', 'z_hat', 'sigma_hat',
-                                                                                'indexes', 'symbols', 'y_hat', 'x_hat'))
-        else:
-            med = self._dev(ctx, 'medians', eb.medians)
-            tab = self._dev(ctx, 'scale_table', gc.scale_table_f32)
-            y = self.analysis_transform.forward_ndhwc(ctx, x.unsqueeze(-1))
-            z = self.hyper_analysis_transform.forward_ndhwc(ctx, y)
-            zsym, z_hat = ops.quantize(ctx, z, med, self.round_mode)
-            sigma = self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat)
-            idx = ops.scale_to_index(ctx, sigma, tab)
-            ysym, y_hat = ops.quantize(ctx, y, None, self.round_mode)
-            if not rans:
-                stg.pack(ctx, ysym, zsym, idx)
-        # what crosses PCIe: ONE buffer per chunk -- symbols as int16, the 64 scale rows as uint8 (8.5 -> 3.3 MB per 32-block
-        # chunk), packed in stream order by the library before `ready`, plus the per-tile max|symbol| that tells the host
-        # afterwards whether a symbol exceeded int16 (then that tensor is fetched again as int32: never seen in practice).
-        # The copy runs on a side stream so that it overlaps the synthesis transform.
-        # entropy_coder='rans': nothing is narrowed or shipped; both strings are coded on the side stream from the int32 tensors.
-        if rans:
-            fetch = self._rans_encode(ctx, ready, [(gc.table, ysym, idx, False), (eb.table, zsym, None, True)])
-        else:
-            ev = self._ship(ctx, stg, ready)
-        if codec is None:
-            x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
-            if thr is not None:
-                t['xyz'], t['counts'] = ops.threshold_compact(ctx, x_hat, thr, clip=True)
-        rows, mod = self._eb_rows(zsym[0].numel(), F)
-
-        def finish():
-            if rans:
-                return list(zip(*fetch()))
-            ev.synchronize()  # symbols are on the host
-            fits = stg.sym_dtype == torch.int32
-            zs_src = stg.zsym if fits or int(stg.ztm.max()) <= 32767 else self._to_stream_order(zsym).cpu()
-            ys_src = stg.ysym if fits or int(stg.ytm.max()) <= 32767 else self._to_stream_order(ysym).cpu()
-            zs = ops.range_encode_batch(eb.table, zs_src.view(B, -1), rows, mod, self.coder_threads)
-            ys = ops.range_encode_batch(gc.table, ys_src.view(B, -1), stg.idx.view(B, -1), 0, self.coder_threads)
-            return list(zip(ys, zs))  # strings = (y_string, z_string), model_types.py:389
-
-        dbg = [None] * B
-        if debug:
-            dbg = [{'y': _np(y[b:b + 1]), 'z': _np(z[b:b + 1]), 'z_symbols': _np(zsym[b:b + 1]),
-                    'z_hat': _np(z_hat[b:b + 1]), 'sigma_hat': _np(sigma[b:b + 1]), 'indexes': _np(idx[b:b + 1]),
-                    'symbols': _np(ysym[b:b + 1]), 'y_hat': _np(y_hat[b:b + 1]), 'x_hat': _np(x_hat[b:b + 1].unsqueeze(-1))}
-                   for b in range(B)]
-        return dict(x_hat=x_hat, finish=finish, debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
+        cf = self.data_format == 'channels_first'
+        if codec is not None:                      # unpack z -> dequantise -> hyper-synthesis -> indexes -> pack, one ABI call
+            return ops.codec_decode_hyper(ctx, codec, zsym, dhw, packed=zpacked, channels_first=cf, idx_packed=idx_packed)
+        if zpacked is not None:
+            zsym = self._unpack(ctx, zpacked, [v // 16 for v in dhw])
+        t = self._scales_layerwise(ctx, dict(z_hat=ops.dequantize(ctx, zsym, self._dev(ctx, 'medians', self.entropy_bottleneck.medians))))
+        if idx_packed is not None:
+            ops.symbols_pack(ctx, t['indexes'], cf, idx_packed.data_ptr(), idx_packed.element_size())
+        return t
 
     def _decode_phase_a(self, ctx, strings, dhw):
         """z_string -EB.decompress-> z_hat -HS-> sigma -> indexes (async D2H)."""
         B, F = len(strings), self.num_filters
-        eb, gc = self.entropy_bottleneck, self.conditional_bottleneck
+        zstrings = [s[1] for s in strings]
         if self.entropy_coder == 'rans':
-            zsym, zstatus = self._rans_decode(ctx, eb.table, [s[1] for s in strings], (B,) + tuple(v // 16 for v in dhw) + (F,), None, True)
-            codec = self._codec(ctx)
-            if codec is not None:
-                t = ops.codec_decode_hyper(ctx, codec, zsym, dhw)
-                z_hat, sigma, idx = t['z_hat'], t['sigma_hat'], t['indexes']
-            else:
-                z_hat = ops.dequantize(ctx, zsym, self._dev(ctx, 'medians', eb.medians))
-                sigma = self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat)
-                idx = ops.scale_to_index(ctx, sigma, self._dev(ctx, 'scale_table', gc.scale_table_f32))
+            zsym, zstatus = self._rans_decode(ctx, self.entropy_bottleneck.table, zstrings, (B,) + tuple(v // 16 for v in dhw) + (F,))
+            t = self._hyper_decode(ctx, dhw, zsym)
             # the CDF rows stay on the device: phase b decodes the y strings there
-            return dict(strings=strings, z_hat=z_hat, sigma=sigma, idx=idx, zstatus=zstatus, device=ctx.device)
-        zshape = self._stream_shape(B, [v // 16 for v in dhw], F)
-        # per-slot cached pinned buffers (like the encoder's): nothing is allocated in the steady state
-        zsym_h, zsym_release = self._pinned.ring('dec_zsym', zshape, _host_dtypes()[0])
-        nz = int(np.prod(zshape[1:]))
-        rows, mod = self._eb_rows(nz, F)
-        zpacked = self._symbols_to_device(ctx, self._range_decode(eb.table, [s[1] for s in strings], nz, rows, mod, zsym_h), zsym_release)
+            return dict(strings=strings, z_hat=t['z_hat'], sigma_hat=t['sigma_hat'], indexes=t['indexes'], zstatus=zstatus, device=ctx.device)
+        zsym_h, zsym_release = self._range_decode_eb('dec_zsym', zstrings, self._stream_shape(B, [v // 16 for v in dhw], F))
+        zpacked = symbols_to_device(ctx, zsym_h, zsym_release)
         # the 64 scale rows leave in stream order, one byte each
         row_t = _host_dtypes(len(self.scale_table))[1]
-        cf = self.data_format == 'channels_first'
         idx_s = torch.empty(self._stream_shape(B, [v // 8 for v in dhw], F), dtype=row_t, device=ctx.device)
-        codec = self._codec(ctx)
-        if codec is not None:                      # unpack z -> dequantise -> hyper-synthesis -> indexes -> pack, one ABI call
-            t = ops.codec_decode_hyper(ctx, codec, None, dhw, packed=zpacked, channels_first=cf, idx_packed=idx_s)
-            z_hat, sigma, idx = t['z_hat'], t['sigma_hat'], t['indexes']
-        else:
-            zsym = self._unpack(ctx, zpacked, [v // 16 for v in dhw])
-            z_hat = ops.dequantize(ctx, zsym, self._dev(ctx, 'medians', eb.medians))
-            sigma = self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat)
-            idx = ops.scale_to_index(ctx, sigma, self._dev(ctx, 'scale_table', gc.scale_table_f32))
-            ops.symbols_pack(ctx, idx, cf, idx_s.data_ptr(), idx_s.element_size())
+        t = self._hyper_decode(ctx, dhw, zpacked=zpacked, idx_packed=idx_s)
         # (the host reads idx_h synchronously in phase b, long before the ring comes round: no release event needed)
         idx_h, _ = self._pinned.ring('dec_idx', idx_s.shape, row_t)
-        packed = torch.cuda.Event()
-        packed.record(torch.cuda.current_stream(ctx.device))
-        side = self._side_stream(ctx, '_idx_stream')
-        with torch.cuda.stream(side):               # (not on the main stream: the copy would delay the kernels queued behind it)
-            side.wait_event(packed)
-            idx_s.record_stream(side)
-            idx_h.copy_(idx_s, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        return dict(strings=strings, idx_h=idx_h, ev=ev, z_hat=z_hat, sigma=sigma, idx=idx, zsym_h=zsym_h, device=ctx.device)
+        ev = indexes_to_host(ctx, idx_s, idx_h)
+        return dict(strings=strings, idx_h=idx_h, ev=ev, z_hat=t['z_hat'], sigma_hat=t['sigma_hat'], indexes=t['indexes'], zsym_h=zsym_h,
+                    device=ctx.device)
 
     def _decode_phase_b_host(self, st):
-        """The host part of phase b: wait for the CDF-row indexes, range-decode the y strings into a pinned buffer.  No GPU work is
-        enqueued here, so roundtrip_stream may run it on a helper thread (the coder is sequential per stream: 2 ms per 8-block chunk
-        of 128^3 blocks) while the calling thread keeps feeding the device."""
+        """Wait for the CDF-row indexes, range-decode the y strings into a pinned buffer (the coder is sequential per stream: 2 ms per
+        8-block chunk of 128^3 blocks; on roundtrip_stream's helper thread the calling thread keeps feeding the device meanwhile)."""
         if self.entropy_coder == 'rans':           # nothing to do on the host
             return None
-        gc = self.conditional_bottleneck
         strings, idx_h = st['strings'], st['idx_h']
         B = len(strings)
         # may run on the 'ydec' helper thread: pinned allocations below must be made with THIS model's device current (a helper thread
@@ -1255,41 +961,10 @@ class CompressionModelV2(CompressionModel):
         st['ev'].synchronize()
         ysym_h, ysym_release = self._pinned.ring('dec_ysym', idx_h.shape, _host_dtypes()[0])
         n = int(np.prod(idx_h.shape[1:]))
-        return self._range_decode(gc.table, [s[0] for s in strings], n, idx_h.view(B, -1), 0, ysym_h), ysym_release
+        return self._range_decode(self.conditional_bottleneck.table, [s[0] for s in strings], n, idx_h.view(B, -1), 0, ysym_h), ysym_release
 
-    def _decode_phase_b(self, ctx, st, dhw, debug, thr=None, host=None):
-        """(y_string, indexes) -GC.decompress-> y_hat -S-> x_hat [-> thresholded points].  host: the result of _decode_phase_b_host when
-        it already ran elsewhere."""
-        strings = st['strings']
-        B = len(strings)
-        rans = self.entropy_coder == 'rans'
-        if rans:
-            ysym, status = self._rans_decode(ctx, self.conditional_bottleneck.table, [s[0] for s in strings], st['idx'].shape, st['idx'], False)
-            packed = None
-        else:
-            ysym, ysym_release = self._decode_phase_b_host(st) if host is None else host
-            ysym, packed = None, self._symbols_to_device(ctx, ysym, ysym_release)
-        codec = self._codec(ctx)
-        if codec is not None:                      # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
-            t = ops.codec_decode_main(ctx, codec, ysym, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
-            ysym, y_hat, x_hat = t['symbols'], t['y_hat'], t['x_hat']
-        else:
-            if not rans:
-                ysym = self._unpack(ctx, packed, [v // 8 for v in dhw])
-            y_hat = ops.dequantize(ctx, ysym, None)
-            x_hat = self.synthesis_transform.forward_ndhwc(ctx, y_hat)[..., 0].contiguous()
-            t = {}
-            if thr is not None:
-                t['xyz'], t['counts'] = ops.threshold_compact(ctx, x_hat, thr, clip=False)
-        if rans:                                    # (after the chunk's launches: the device works while the host waits for the flags)
-            ops.rans_check_status(st['zstatus'])
-            ops.rans_check_status(status)
-        dbg = [None] * B
-        if debug:
-            dbg = [{'z_hat': _np(st['z_hat'][b:b + 1]), 'sigma_hat': _np(st['sigma'][b:b + 1]),
-                    'indexes': _np(st['idx'][b:b + 1]), 'symbols': _np(ysym[b:b + 1]), 'y_hat': _np(y_hat[b:b + 1]),
-                    'x_hat': _np(x_hat[b:b + 1].unsqueeze(-1))} for b in range(B)]
-        return dict(x_hat=x_hat, debug=dbg, xyz=t.get('xyz'), counts=t.get('counts'))
+    def _y_rans_decode(self, ctx, st, dhw):
+        return self._rans_decode(ctx, self.conditional_bottleneck.table, [s[0] for s in st['strings']], st['indexes'].shape, st['indexes'])
 
 
 class ModelType(Enum):

@@ -37,20 +37,17 @@ def fake_encode_two_metrics(self, sess, blocks, resolution, with_normals=False, 
 
 
 def fake_decompress(model, blocks):
-    """decompress_blocks with the GPU part replaced: each 'compressed block' decodes to its own points."""
-    from pcc_geo_cnn_v2_amd import sharding
+    """decompress_blocks with the GPU part (the decode of one rank's shard) replaced: each 'compressed block' decodes to its own points."""
     from pcc_geo_cnn_v2_amd.model_types import CompressionModel
-    orig = CompressionModel.decompress_blocks
+    orig = CompressionModel.decompress_block_range
 
-    def local(self, sess, blks, x_shape, debug=False):
-        if sharding.world_info()[1] > 1 and not getattr(self, '_in_shard', False):
-            return orig(self, sess, blks, x_shape, debug)
+    def local(self, sess, blks, x_shape, debug=False, layers='all'):
         return [np.asarray(b)[:, :3].astype(np.float32) for b in blks], [None] * len(blks)
-    CompressionModel.decompress_blocks = local
+    CompressionModel.decompress_block_range = local
     try:
         out = model.decompress_blocks(None, blocks, [16, 16, 16])
     finally:
-        CompressionModel.decompress_blocks = orig
+        CompressionModel.decompress_block_range = orig
     return out[0]
 
 
@@ -107,8 +104,6 @@ def main():
     res['calls_two_big'] = list(calls)
     res['two_big'] = dict(data_list=dl3, idx=[m['idx'] for m in md3], metrics=[m['metrics'] for m in md3])
     # 4. decompress_blocks: decoded points to rank 0
-    CompressionModel._in_shard = False
-    model.decompress_local = True
     del calls[:]
     res['dec'] = fake_decompress(model, blocks)
     res['calls_dec'] = list(calls)

@@ -1,0 +1,119 @@
+"""CPU: what the block loops of model_types.py read as data -- the engines of the adaptive threshold search per (metrics, grid, ties, d2
+engine, PCC_D2_NO_PRUNE) and the number of strings a model writes per block."""
+import io
+import itertools
+import json
+import os
+
+import _codec_pins as CP
+import _family_cases as FC
+
+from pcc_geo_cnn_v2_amd import model_syntax
+from pcc_geo_cnn_v2_amd.block_search import search_plan
+from pcc_geo_cnn_v2_amd.model_configs import ModelConfigType
+from pcc_geo_cnn_v2_amd.model_types import ModelType
+
+METRICS = {'d1': ['d1_mse'], 'd2': ['d2_mse'], 'd1+d2': ['d1_mse', 'd2_mse']}
+
+# (metrics, grid edge, ties, d2 engine, PCC_D2_NO_PRUNE set) -> (GPU tally call, host job kind, tie rule of the D2 statistics): every row
+# written out, as encode_block_range branched before the plan was a function
+PLAN = {
+    ('d1', 64, 'pick', 'kdtree', False): ('d1', None, 'pick'),
+    ('d1', 64, 'pick', 'kdtree', True): ('d1', None, 'pick'),
+    ('d1', 64, 'pick', 'gpu', False): ('d1', None, 'pick'),
+    ('d1', 64, 'pick', 'gpu', True): ('d1', None, 'pick'),
+    ('d1', 64, 'mean', 'kdtree', False): ('d1', None, 'pick'),
+    ('d1', 64, 'mean', 'kdtree', True): ('d1', None, 'pick'),
+    ('d1', 64, 'mean', 'gpu', False): ('d1', None, 'pick'),
+    ('d1', 64, 'mean', 'gpu', True): ('d1', None, 'pick'),
+    ('d1', 128, 'pick', 'kdtree', False): ('d1', None, 'pick'),
+    ('d1', 128, 'pick', 'kdtree', True): ('d1', None, 'pick'),
+    ('d1', 128, 'pick', 'gpu', False): ('d1', None, 'pick'),
+    ('d1', 128, 'pick', 'gpu', True): ('d1', None, 'pick'),
+    ('d1', 128, 'mean', 'kdtree', False): ('d1', None, 'pick'),
+    ('d1', 128, 'mean', 'kdtree', True): ('d1', None, 'pick'),
+    ('d1', 128, 'mean', 'gpu', False): ('d1', None, 'pick'),
+    ('d1', 128, 'mean', 'gpu', True): ('d1', None, 'pick'),
+    ('d1', 256, 'pick', 'kdtree', False): (None, 'decide', 'pick'),
+    ('d1', 256, 'pick', 'kdtree', True): (None, 'decide', 'pick'),
+    ('d1', 256, 'pick', 'gpu', False): (None, 'decide', 'pick'),
+    ('d1', 256, 'pick', 'gpu', True): (None, 'decide', 'pick'),
+    ('d1', 256, 'mean', 'kdtree', False): (None, 'decide', 'pick'),
+    ('d1', 256, 'mean', 'kdtree', True): (None, 'decide', 'pick'),
+    ('d1', 256, 'mean', 'gpu', False): (None, 'decide', 'pick'),
+    ('d1', 256, 'mean', 'gpu', True): (None, 'decide', 'pick'),
+    ('d2', 64, 'pick', 'kdtree', False): ('d1', 'tally_pruned', 'pick'),
+    ('d2', 64, 'pick', 'kdtree', True): ('d1', 'tally', 'pick'),
+    ('d2', 64, 'pick', 'gpu', False): ('d12', None, 'pick'),
+    ('d2', 64, 'pick', 'gpu', True): ('d12', None, 'pick'),
+    ('d2', 64, 'mean', 'kdtree', False): ('d1', 'tally', 'mean'),
+    ('d2', 64, 'mean', 'kdtree', True): ('d1', 'tally', 'mean'),
+    ('d2', 64, 'mean', 'gpu', False): ('d12', None, 'mean'),
+    ('d2', 64, 'mean', 'gpu', True): ('d12', None, 'mean'),
+    ('d2', 128, 'pick', 'kdtree', False): ('d1', 'tally_pruned', 'pick'),
+    ('d2', 128, 'pick', 'kdtree', True): ('d1', 'tally', 'pick'),
+    ('d2', 128, 'pick', 'gpu', False): ('d12', None, 'pick'),
+    ('d2', 128, 'pick', 'gpu', True): ('d12', None, 'pick'),
+    ('d2', 128, 'mean', 'kdtree', False): ('d1', 'tally', 'mean'),
+    ('d2', 128, 'mean', 'kdtree', True): ('d1', 'tally', 'mean'),
+    ('d2', 128, 'mean', 'gpu', False): ('d12', None, 'mean'),
+    ('d2', 128, 'mean', 'gpu', True): ('d12', None, 'mean'),
+    ('d2', 256, 'pick', 'kdtree', False): (None, 'decide', 'pick'),
+    ('d2', 256, 'pick', 'kdtree', True): (None, 'decide', 'pick'),
+    ('d2', 256, 'pick', 'gpu', False): (None, 'decide', 'pick'),
+    ('d2', 256, 'pick', 'gpu', True): (None, 'decide', 'pick'),
+    ('d2', 256, 'mean', 'kdtree', False): (None, 'decide', 'mean'),
+    ('d2', 256, 'mean', 'kdtree', True): (None, 'decide', 'mean'),
+    ('d2', 256, 'mean', 'gpu', False): (None, 'decide', 'mean'),
+    ('d2', 256, 'mean', 'gpu', True): (None, 'decide', 'mean'),
+    ('d1+d2', 64, 'pick', 'kdtree', False): ('d1', 'tally_pruned', 'pick'),
+    ('d1+d2', 64, 'pick', 'kdtree', True): ('d1', 'tally', 'pick'),
+    ('d1+d2', 64, 'pick', 'gpu', False): ('d12', None, 'pick'),
+    ('d1+d2', 64, 'pick', 'gpu', True): ('d12', None, 'pick'),
+    ('d1+d2', 64, 'mean', 'kdtree', False): ('d1', 'tally', 'mean'),
+    ('d1+d2', 64, 'mean', 'kdtree', True): ('d1', 'tally', 'mean'),
+    ('d1+d2', 64, 'mean', 'gpu', False): ('d12', None, 'mean'),
+    ('d1+d2', 64, 'mean', 'gpu', True): ('d12', None, 'mean'),
+    ('d1+d2', 128, 'pick', 'kdtree', False): ('d1', 'tally_pruned', 'pick'),
+    ('d1+d2', 128, 'pick', 'kdtree', True): ('d1', 'tally', 'pick'),
+    ('d1+d2', 128, 'pick', 'gpu', False): ('d12', None, 'pick'),
+    ('d1+d2', 128, 'pick', 'gpu', True): ('d12', None, 'pick'),
+    ('d1+d2', 128, 'mean', 'kdtree', False): ('d1', 'tally', 'mean'),
+    ('d1+d2', 128, 'mean', 'kdtree', True): ('d1', 'tally', 'mean'),
+    ('d1+d2', 128, 'mean', 'gpu', False): ('d12', None, 'mean'),
+    ('d1+d2', 128, 'mean', 'gpu', True): ('d12', None, 'mean'),
+    ('d1+d2', 256, 'pick', 'kdtree', False): (None, 'decide', 'pick'),
+    ('d1+d2', 256, 'pick', 'kdtree', True): (None, 'decide', 'pick'),
+    ('d1+d2', 256, 'pick', 'gpu', False): (None, 'decide', 'pick'),
+    ('d1+d2', 256, 'pick', 'gpu', True): (None, 'decide', 'pick'),
+    ('d1+d2', 256, 'mean', 'kdtree', False): (None, 'decide', 'mean'),
+    ('d1+d2', 256, 'mean', 'kdtree', True): (None, 'decide', 'mean'),
+    ('d1+d2', 256, 'mean', 'gpu', False): (None, 'decide', 'mean'),
+    ('d1+d2', 256, 'mean', 'gpu', True): (None, 'decide', 'mean'),
+}
+
+
+def test_search_plan_reproduces_every_branch_of_the_block_loop():
+    product = list(itertools.product(METRICS, (64, 128, 256), ('pick', 'mean'), ('kdtree', 'gpu'), (False, True)))
+    assert sorted(product) == sorted(PLAN) and len(PLAN) == 72
+    for key in product:
+        metrics, edge, ties, engine, no_prune = key
+        assert tuple(search_plan(METRICS[metrics], (edge,) * 3, ties, engine == 'gpu', no_prune)) == PLAN[key], key
+    # one edge above 128 is enough to leave the GPU search (model_opt.gpu_search_supported)
+    assert tuple(search_plan(['d1_mse'], (64, 64, 256))) == (None, 'decide', 'pick')
+
+
+def test_n_strings_is_the_number_of_strings_per_block_in_the_committed_streams():
+    with open(FC.GOLDEN) as fh:
+        listing = CP.load_listing(json.load(fh)['family'])
+    per_model = {}
+    for e in listing['streams'].values():
+        path = os.path.join(CP.streams_dir(listing['family']), e['file'])
+        blocks = model_syntax.load_compressed_file(io.BytesIO(CP.payload_of(path)))[3]
+        per_model.setdefault(e['model'], set()).update(len(strings) - int(e['lossless']) for strings, _ in blocks)
+    assert per_model == {'c1': {1}, 'c3p': {2}}
+    by_type = {ModelType.v1.value: per_model['c1'], ModelType.v2.value: per_model['c3p']}      # (c2, c3: the model class of c3p)
+    for cfg in ModelConfigType:
+        model = cfg.build()
+        assert {model.n_strings} == per_model.get(cfg.name, by_type[type(model)]), cfg.name
+        assert model.codec_abi == model.n_strings

@@ -530,3 +530,26 @@ def test_graph_packs_symbols_and_rows_in_every_graph_model(ctx, name):
     """the same on every configuration that runs on the codec graph (F = 32 in c1 / c2 / c3: no whole 64-channel tile), three 32^3
     blocks, and -- hyperprior models -- through the decoder's unpack + dequantise and index + pack launches as well"""
     _graph_pack_check(ctx, name, 3)
+
+
+@pytest.mark.parametrize('coder', ['range', 'rans'])
+@pytest.mark.parametrize('name', ['c1', 'c3p'])
+def test_block_loops_code_what_the_batch_path_codes(ctx, name, coder):
+    """The three block loops against the batch path that tests/golden/family_bits.json pins: roundtrip_stream yields the strings of
+    _encode_batch(...)['finish']() on the same chunks, and its decoded points are those of decompress_blocks on these strings."""
+    res, B, half = 16, 2, 128
+    m = ModelConfigType[name].build(batch_size=B, entropy_coder=coder)
+    m.compress([1, 1, res, res, res])
+    m.set_weights(scaled_weights(m, 2.2))
+    chunks = [m._voxelize(ctx, make_blocks(B, res, seed=s), (res,) * 3) for s in (21, 22, 23)]
+    thr = m._thr_tensor(ctx, [half] * B)
+    want = [m._encode_batch(ctx, x, False, thr=thr)['finish']() for x in chunks]
+    got = list(m.roundtrip_stream(ctx, chunks, thr_idx=half))
+    assert len(got) == len(chunks) and all(len(s) == m.n_strings and all(s) for ss in want for s in ss)
+    strings = [tuple(s) for ss, _, _ in got for s in ss]
+    assert strings == [tuple(s) for ss in want for s in ss]
+    points = [p for _, _, plist in got for p in plist]
+    dec, _ = m.decompress_blocks(ctx, [(s, half) for s in strings], [res] * 3)
+    assert len(dec) == len(points) == B * len(chunks) and sum(len(p) for p in points) > 0
+    for a, b in zip(dec, points):
+        assert np.array_equal(a, b)

@@ -24,7 +24,7 @@ print(f'{len(pts)} points, {len(blocks)} blocks, host cores {os.cpu_count()}, us
 def run(mets, host_only=False):
     if host_only:
         keep = model_opt.gpu_search_supported
-        import pcc_geo_cnn_v2_amd.model_types as MTY
+        import pcc_geo_cnn_v2_amd.block_search as MTY
         MTY.gpu_search_supported = lambda *a: False
     torch.cuda.synchronize(); t0 = time.perf_counter()
     out = model.encode_block_range(ctx, blocks, R, with_normals=True, opt_metrics=mets, max_deltas=[np.inf])
@@ -57,6 +57,6 @@ for tag, env in (('pruned (default)', None), ('PCC_D2_NO_PRUNE=1', '1')):
     model.search_trees_built = model.search_trees_total = 0
     run(['d1_mse', 'd2_mse'])
     t, thr_ = run(['d1_mse', 'd2_mse'])
-    print(f"kdtree search, {tag}: {t:.2f} s / cloud; A->B trees built {getattr(model, 'search_trees_built', 0)} of {getattr(model, 'search_trees_total', 0)} (two runs)")
+    print(f"kdtree search, {tag}: {t:.2f} s / cloud; A->B trees built {model.search_trees_built} of {model.search_trees_total} (two runs)")
     globals()['thr_' + ('p' if env is None else 'f')] = thr_
 print('decisions equal:', thr_p == thr_f)

@@ -104,5 +104,5 @@ os.makedirs(os.path.dirname(args.output), exist_ok=True)
 with open(args.output, 'w') as fh:
     json.dump(out, fh, indent=1, sort_keys=True)
 print(json.dumps(out, indent=1, sort_keys=True))
-if hasattr(model, '_host_search_pool'):
+if model._host_search_pool is not None:
     model._host_search_pool.close()
