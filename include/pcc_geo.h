@@ -317,6 +317,22 @@ int pcc_threshold_compact(pcc_ctx* ctx, const float* x, int32_t B, int32_t D, in
                           int64_t cap, int32_t* scratch, void* stream);
 size_t pcc_threshold_scratch_ints(int32_t B, int32_t D, int32_t H, int32_t W);
 
+/* ---- top-k selection: count-matched thresholding ------------------------------------------------
+ * Block b keeps the k[b] voxels with the highest score instead of those above a threshold.  x: B blocks of n = D*H*W float32, block b at
+ * x + b * x_stride (elements, >= n); k: device array of B int32, a negative entry counts as 0.  Per block:
+ *   key(i) = 0 unless x[i] > 0 (NaN, -0, +0, negatives), else the 32 raw bits of x[i]; nothing is clipped;
+ *   P = #{i : key(i) > 0}, k_eff = clamp(k, 0, P): a voxel with a non-positive score is never emitted;
+ *   the k_eff voxels that come first by (key descending, i ascending) are taken: all above the k_eff-th largest key T and, of those
+ *   equal to T, the ones with the lowest i.
+ * xyz, counts, cap as in pcc_threshold_compact: the taken voxels in ascending i as float32 rows (x slowest), counts[b] = k_eff, which may
+ * exceed cap: then only the first cap rows are written.  The result is a function of the block's scores and k alone (integer
+ * histograms: no dependence on B, the stride, the position in the batch or the launch geometry).  workspace: device memory of
+ * pcc_topk_workspace_bytes(B, n) bytes (0 for an n above 2^28).  B = 0 or n = 0: nothing is launched, counts = 0.  PCC_ERR_ARG: a NULL
+ * pointer, a workspace that is too small, n > 2^28, B > 65535.                                                                        */
+size_t pcc_topk_workspace_bytes(int32_t B, int64_t n);
+int pcc_topk_compact(pcc_ctx* ctx, const float* x, int64_t x_stride, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* k,
+                     float* xyz, int32_t* counts, int64_t cap, void* workspace, size_t workspace_bytes, void* stream);
+
 /* sparse_to_dense (src/model_types.py:108-114): scatter ones.  pts: int32 (npts,3) local block
  * coordinates, block_of[i] = destination block; dense must be zero-filled B*D*H*W float32.       */
 int pcc_voxelize(pcc_ctx* ctx, const int32_t* pts, const int32_t* block_of, int64_t npts,

@@ -4,7 +4,7 @@
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
          [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu] [--d2_ties pick|mean] [--search_ties pick|mean]
-         [--entropy_coder range|rans] [--lossless]
+         [--entropy_coder range|rans] [--lossless] [--count_threshold [RHO]]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
@@ -15,6 +15,9 @@ normals of the D2 metrics come from the GPU (include/pcc_geo.h "point normals") 
 metrics", neighbour ties to the lowest row) instead of scipy KD-trees; single process only.
 `--lossless` is new: every block carries one more string that codes its true occupancy under the decoder's x_hat, so
 decompress_octree returns the input voxels exactly; the y/z strings stay the lossy base; single process only.
+`--count_threshold [RHO]` is new: count-matched thresholding instead of the threshold search: every block carries one more
+string with k = round(RHO x its input points) (RHO = 1 when omitted) and decompress_octree keeps its k highest-scoring voxels; single
+process only.
 """
 import argparse
 import json
@@ -125,6 +128,27 @@ def check_lossless(lossless, world):
                              'strings, drop the flag or run on one GPU')
 
 
+def check_count_threshold(args, world):
+    """--count_threshold replaces the threshold search and its tie rules, and codes in one process; the sharded path moves the y/z strings
+    alone.  From the parsed arguments, before the process group and the GPU are touched."""
+    rho = getattr(args, 'count_threshold', None)
+    if rho is None:
+        return
+    if not (np.isfinite(rho) and rho > 0):
+        raise AssertionError(f'--count_threshold: the scale must be a finite number above 0, got {rho}')
+    if getattr(args, 'fixed_threshold', False):
+        raise AssertionError('--count_threshold and --fixed_threshold are two policies for the same decision, drop one of the two flags')
+    if getattr(args, 'lossless', False):
+        raise AssertionError('--count_threshold and --lossless: a stream carries the point counts or the occupancy layer, drop one of the two flags')
+    if getattr(args, 'search_ties', 'pick') == 'mean':
+        raise AssertionError('--count_threshold runs no threshold search, drop --search_ties mean')
+    if getattr(args, 'd2_search', None) == 'gpu':
+        raise AssertionError('--count_threshold runs no threshold search, drop --d2_search gpu')
+    if world > 1:
+        raise AssertionError(f'--count_threshold is single-process only (world size {world}): the sharded path does not carry the count '
+                             'strings, drop the flag or run on one GPU')
+
+
 def check_d2_ties(d2_ties, world):
     """--d2_ties mean averages the whole-cloud D2 over all equidistant nearest points in one process; tie sets are not sharded."""
     from .utils.pc_metric import check_ties
@@ -175,6 +199,10 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
             record['d2_ties'] = args.d2_ties
         if getattr(args, 'search_ties', 'pick') != 'pick':
             record['search_ties'] = args.search_ties
+        if getattr(args, 'count_threshold', None) is not None:
+            record['threshold_policy'] = 'count'
+            record['count_scale'] = float(args.count_threshold)
+            record['count_bytes'] = sum(len(strings[-1]) for strings, _ in streams)      # (4 per block)
         if getattr(args, 'lossless', False):
             # the last string of every block is the occupancy layer; the rate of the exact cloud counts the whole file as written
             n_points = sum(len(b) for b in blocks)
@@ -204,8 +232,10 @@ def compress(args):
     from .utils.octree_coding import partition_octree
     T.mark('imports')
 
+    check_count_threshold(args, int(os.environ.get('WORLD_SIZE', '1')))     # (first: its message names the flag, not what _plan meets)
     clouds, with_normals = _plan(args)
     lossless = getattr(args, 'lossless', False)
+    count_scale = getattr(args, 'count_threshold', None)
     check_lossless(lossless, int(os.environ.get('WORLD_SIZE', '1')))      # (before the process group and the GPU are touched)
     rank, world, local = _join_process_group()
     check_metrics_device(getattr(args, 'metrics_device', 'host'), world)
@@ -247,13 +277,14 @@ def compress(args):
         streams, infos, debug_t_list = model.compress_blocks(
             sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
             max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
-            metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'))
+            metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'),
+            **({} if count_scale is None else {'count_scale': count_scale}))
         T.mark('compress_blocks', sess.device)
         if rank == 0:       # the other ranks only took part in the collectives
             if len(streams) != len(cloud.targets):
                 raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
             for n, target in enumerate(cloud.targets):
-                infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless)
+                infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless, count_scale is not None)
                 _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
             logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
         T.mark('container_gzip_write')
@@ -325,6 +356,12 @@ def build_parser():
                              'so decompress_octree returns the input voxels exactly and --base_only the lossy cloud.  The stream names the '
                              'layer (numerics tag suffix /occ1); .enc.metric.json gains lossless, base_bytes, occ_bytes and '
                              'bits_per_input_point_lossless (8 x file size / input points).  Single process only.')
+    parser.add_argument('--count_threshold', nargs='?', type=float, const=1.0, default=None, metavar='RHO',
+                        help='Count-matched thresholding (new) instead of the threshold search: every block carries one more string, its '
+                             'point count k = floor(RHO x input points + 0.5) (RHO = 1 when omitted), and decompress_octree keeps its k '
+                             'highest-scoring voxels.  The stream names the layer (numerics tag suffix /cnt1); .enc.metric.json gains '
+                             'threshold_policy, count_scale and count_bytes.  Not with --fixed_threshold, --lossless, --search_ties mean or '
+                             '--d2_search gpu; single process only.')
     return parser
 
 

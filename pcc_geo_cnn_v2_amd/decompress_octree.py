@@ -3,6 +3,9 @@
   python -m pcc_geo_cnn_v2_amd.decompress_octree --input_files a.ply.bin --output_files a.dec.ply \\
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p [--debug] [--base_only]
 
+The stream names its layer in the numerics tag: '/occ1' (compress_octree --lossless) decodes to the exact input voxels, '/cnt1'
+(--count_threshold) to each block's k highest-scoring voxels; `--base_only` decodes either by the threshold byte alone.
+
 `--debug` reloads the encoder-side dumps (`.enc.data.npz`, `.enc.blocks/`) and checks every intermediate
 and the decoded blocks for exact equality.  The reference needs up to 100 retries there because its GPU
 results are not reproducible (decompress_octree.py:69-131); this implementation is bit-deterministic, so a
@@ -60,14 +63,15 @@ def decompress(args):
     T.mark('context', sess.device)
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
-    compressed_data, coders = [], []
+    compressed_data, coders, counted = [], [], []
     base_only = getattr(args, 'base_only', False)
     for file in args.input_files:
         # the stream names its entropy coder and its layers (tag suffixes); the rest of the tag is compared as before
         coder, layers = stream_layers(read_gzip_tag(file), sess.numerics_tag(args.precision), getattr(args, 'entropy_coder', None),
                                       ignore=args.ignore_numerics_tag)
         coders.append(coder)
-        if base_only and 'occ1' not in layers:
+        counted.append('cnt1' in layers)
+        if base_only and not layers:
             logger.warning('--base_only has no effect on %s: the stream carries no occupancy layer', file)
         if args.debug and 'occ1' in layers and not base_only:
             raise AssertionError(f'--debug compares the decoded blocks with the encoder dumps, which hold the lossy candidate: pass --base_only '
@@ -87,7 +91,7 @@ def decompress(args):
         logger.info(f'{i}/{len(args.input_files)} - Writing {ori_file} to {output_file} with {len(blocks)} blocks')
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
         model.entropy_coder = coders[i]
-        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug, layers='base' if base_only else 'all')
+        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug, layers='base' if base_only else 'count' if counted[i] else 'all')
         T.mark('decompress_blocks', sess.device)
         if args.debug and rank == 0:
             dec_blocks_enc = read_pcs(len(blocks), ori_file + '.enc.blocks')
@@ -135,7 +139,8 @@ def build_parser():
                              'compress and decompress).')
     parser.add_argument('--base_only', default=False, action='store_true',
                         help='Write the lossy decode of a file that carries the occupancy layer (compress_octree --lossless; new).  Such a '
-                             'file decodes to the exact input voxels by default; without the layer the flag does nothing.')
+                             'file decodes to the exact input voxels by default; without the layer the flag does nothing.  On a file '
+                             'written with --count_threshold it writes the decode by the threshold byte (the fixed-threshold cloud).')
     parser.add_argument('--entropy_coder', default=None, choices=['range', 'rans'],
                         help='Entropy coder of input files that carry no numerics tag (new; default range).  A tagged file names its own.')
     return parser

@@ -2,7 +2,7 @@
 
   python -m pcc_geo_cnn_v2_amd.ev_experiment --output_dir OUT --model_dir models/c3p/1.00e-04 --model_config c3p --pc_name loot
       --input_pc loot.ply [--input_norm loot_n.ply | --estimate_normals] --resolution 1024 [--octree_level 4]
-      --opt_metrics d1_mse d2_mse --max_deltas inf [--fixed_threshold] [--no_merge_coding] [--metrics_device host|gpu]
+      --opt_metrics d1_mse d2_mse --max_deltas inf [--fixed_threshold | --count_threshold [RHO]] [--no_merge_coding] [--metrics_device host|gpu]
       [--d2_ties pick|mean] [--consistency assert|warn]
 
 Files in OUT, per optimisation group g (d1 always; d2 only when a d2_* metric is asked for, which needs normals):
@@ -170,10 +170,10 @@ def _progress(src, dst, comment=''):
 
 
 def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution, octree_level, opt_metrics, max_deltas,
-            fixed_threshold, metrics_device, d2_ties, batch_size):
+            fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold=None):
     """compress_octree.compress for one cloud on the resident state: the same arguments, the same plan, the same writer."""
     from . import compress_octree as CO
-    from .model_syntax import coder_tag
+    from .model_syntax import stream_tag
     argv = ['--input_files', original.input_pc, '--output_files', *enc_pcs, '--checkpoint_dir', model_dir, '--model_config', model_config,
             '--opt_metrics', *opt_metrics, '--max_deltas', *[str(d) for d in max_deltas], '--resolution', str(resolution),
             '--octree_level', str(octree_level), '--metrics_device', metrics_device, '--d2_ties', d2_ties, '--batch_size', str(batch_size)]
@@ -185,7 +185,10 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
         argv += ['--dec_files', *dec_pcs]
     if fixed_threshold:
         argv += ['--fixed_threshold']
+    if count_threshold is not None:
+        argv += ['--count_threshold', repr(float(count_threshold))]
     args = CO.build_parser().parse_args(argv)
+    CO.check_count_threshold(args, 1)
     clouds, with_normals = CO._plan(args)
     CO.check_metrics_device(args.metrics_device, 1)
     CO.check_d2_ties(args.d2_ties, 1)
@@ -200,28 +203,29 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
     streams, infos, debug_t_list = model.compress_blocks(
         sess, blocks, binstr, original.geometry, args.resolution, args.octree_level, with_normals=with_normals,
         opt_metrics=args.opt_metrics, max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=False,
-        need_points=cloud.decoded is not None, metrics_device=args.metrics_device, d2_ties=args.d2_ties)
+        need_points=cloud.decoded is not None, metrics_device=args.metrics_device, d2_ties=args.d2_ties,
+        **({} if args.count_threshold is None else {'count_scale': args.count_threshold}))
     if len(streams) != len(cloud.targets):
         raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
     for n, target in enumerate(cloud.targets):
-        infos[n]['numerics_tag'] = coder_tag(sess.numerics_tag(args.precision), model.entropy_coder)
+        infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, count=args.count_threshold is not None)
         CO._write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks,
                              debug_t_list)
 
 
 def _decode(res, enc_pcs, dec_pcs, model_dir, model_config, batch_size, precision='fp32'):
     """decompress_octree.decompress for some files on the resident state."""
-    from .model_syntax import load_compressed_file, read_gzip_tag, stream_coder
+    from .model_syntax import load_compressed_file, read_gzip_tag, stream_layers
     from .utils import pc_io
     from .utils.octree_coding import departition_octree
     sess = res.ctx
     model = res.model('dec', model_config, model_dir, batch_size, precision)
     for enc, dec in zip(enc_pcs, dec_pcs):
-        model.entropy_coder = stream_coder(read_gzip_tag(enc), sess.numerics_tag(precision))      # the stream names its coder
+        model.entropy_coder, layers = stream_layers(read_gzip_tag(enc), sess.numerics_tag(precision))      # the stream names its coder and layer
         with gzip.open(enc, 'rb') as f:
             resolution, level, binstr, blocks = load_compressed_file(f)
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
-        dec_blocks, _ = model.decompress_blocks(sess, blocks, x_shape, debug=False)
+        dec_blocks, _ = model.decompress_blocks(sess, blocks, x_shape, debug=False, layers='count' if 'cnt1' in layers else 'all')
         dec_blocks = departition_octree(dec_blocks, binstr, [0, 0, 0], x_shape * (2 ** level), level)
         pa = np.vstack(dec_blocks) if len(dec_blocks) else np.zeros((0, 3))
         pc_io.write_df(dec, pc_io.pa_to_df(pa))
@@ -282,7 +286,8 @@ def enc_dec_diff(enc_pc, report):
 
 def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input_norm=None, estimate_normals=False,
                    opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, no_merge_coding=False, metrics_device='host',
-                   d2_ties='pick', consistency='assert', resolution=None, octree_level=4, batch_size=32, normals_k=16, resident=None):
+                   d2_ties='pick', consistency='assert', resolution=None, octree_level=4, batch_size=32, normals_k=16, resident=None,
+                   count_threshold=None):
     """See the module docstring.  Returns {group: report dictionary} of the reports that exist afterwards."""
     from .utils.experiment import opt_groups
     from .utils.pc_metric import validate_opt_metrics
@@ -309,7 +314,7 @@ def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input
     else:
         _progress(input_pc, enc_pcs)
         _encode(res, original, enc_pcs, None if no_merge_coding else dec_pcs, model_dir, model_config, resolution, octree_level,
-                opt_metrics, max_deltas, fixed_threshold, metrics_device, d2_ties, batch_size)
+                opt_metrics, max_deltas, fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold)
 
     # decoding: whatever the encoder did not leave behind
     todo = [(e, d) for e, d in zip(enc_pcs, dec_pcs) if not os.path.exists(d)]
@@ -374,6 +379,8 @@ def build_parser():
     p.add_argument('--opt_metrics', nargs='+', help=f'Optimization metrics used. Available: {avail_opt_metrics}', required=True)
     p.add_argument('--max_deltas', nargs='+', type=float, help='Max deltas tested during optimization.', required=True)
     p.add_argument('--fixed_threshold', help='Enable fixed thresholding.', default=False, action='store_true')
+    p.add_argument('--count_threshold', nargs='?', type=float, const=1.0, default=None, metavar='RHO',
+                   help='Count-matched thresholding instead of the threshold search, passed to the compress step (new)')
     p.add_argument('--num_parallel', type=int, default=1, help='Accepted and ignored: the steps run in this process')
     p.add_argument('--no_stream_redirection', default=False, action='store_true', help='Accepted and ignored')
     p.add_argument('--no_merge_coding', help='Do not merge encoding and decoding.', default=False, action='store_true')
@@ -401,7 +408,7 @@ def main(argv=None):
             resolution = int(yaml.safe_load(f)['resolution']) + 1
     run_experiment(a.output_dir, a.model_dir, a.model_config, a.pc_name, a.input_pc, a.input_norm, a.estimate_normals, a.opt_metrics,
                    a.max_deltas, a.fixed_threshold, a.no_merge_coding, a.metrics_device, a.d2_ties, a.consistency, resolution,
-                   a.octree_level, a.batch_size)
+                   a.octree_level, a.batch_size, count_threshold=a.count_threshold)
     return 0
 
 

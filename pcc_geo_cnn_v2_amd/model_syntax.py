@@ -160,14 +160,27 @@ def split_coder_tag(tag):
                        f'{sorted(k for k in CODER_SUFFIX.values() if k)} and the untagged range coder')
 
 
-# layers on top of the y/z strings -> the final part of the tag that names them
-LAYER_SUFFIX = {'occ1': 'occ1'}
+# layers on top of the y/z strings -> the final part of the tag that names them; a stream carries at most one
+LAYER_SUFFIX = {'occ1': 'occ1', 'cnt1': 'cnt1'}
+
+_COUNT = struct.Struct('<I')             # the "cnt1" string of a block: how many voxels the decoder keeps
 
 
-def stream_tag(tag, entropy_coder, lossless=False):
-    """The numerics tag of a stream written with `entropy_coder`, with the occupancy layer named as a final '/occ1' part."""
+def count_to_bytes(k):
+    return _COUNT.pack(int(k))
+
+
+def count_from_bytes(payload):
+    """The count string of a block -> k, or None when it is not exactly 4 bytes long."""
+    return _COUNT.unpack(payload)[0] if len(payload) == _COUNT.size else None
+
+
+def stream_tag(tag, entropy_coder, lossless=False, count=False):
+    """The numerics tag of a stream written with `entropy_coder`, with its layer named as a final part: '/occ1' the occupancy layer,
+    '/cnt1' the per-block point counts."""
+    assert not (lossless and count), 'a stream carries the occupancy layer or the point counts, not both'
     tag = coder_tag(tag, entropy_coder)
-    return f'{tag}/occ1' if lossless else tag
+    return f'{tag}/occ1' if lossless else f'{tag}/cnt1' if count else tag
 
 
 def split_stream_tag(tag):

@@ -32,6 +32,7 @@ from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
 from ._stream_io import _Immediate, _Pinned, _host_dtypes, gather_points, indexes_to_host, on_side_stream, ship, side_stream, symbols_to_device, to_host
 from .block_search import SearchSchedule
+from .model_syntax import count_from_bytes, count_to_bytes
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
 from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu
@@ -109,6 +110,26 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
 
 
 ENTROPY_CODERS = ('range', 'rans')
+
+
+def block_count(n_rows, count_scale, n_voxels):
+    """Count-matched thresholding: how many voxels the decoder keeps of a block with `n_rows` input rows under the scale
+    rho = `count_scale`: min(n_voxels, floor(rho * n_rows + 0.5)), in float64."""
+    return int(min(np.float64(n_voxels), np.floor(np.float64(count_scale) * np.float64(n_rows) + 0.5)))
+
+
+def check_count_scale(count_scale, fixed_threshold, lossless, world=1):
+    """What count-matched thresholding excludes; None (off) passes."""
+    if count_scale is None:
+        return
+    if not (isinstance(count_scale, (int, float, np.floating)) and np.isfinite(count_scale) and count_scale > 0):
+        raise AssertionError(f'count_scale must be a finite float above 0, got {count_scale!r}')
+    if fixed_threshold:
+        raise AssertionError('count_scale and fixed_threshold are two policies for the same decision: pick one')
+    if lossless:
+        raise AssertionError('count_scale and lossless: a stream carries the point counts or the occupancy layer, not both')
+    if world > 1:
+        raise AssertionError('count_scale is single-process only: the sharded path moves the y/z strings alone')
 
 
 def _np(t):
@@ -437,12 +458,17 @@ class CompressionModel:
 
     # ------------------------------------------------------------------ block loops
     def encode_block_range(self, sess, blocks, resolution, with_normals=False, opt_metrics=('d1_mse',),
-                           max_deltas=(np.inf,), fixed_threshold=False, debug=False):
+                           max_deltas=(np.inf,), fixed_threshold=False, debug=False, count_scale=None):
         """The per-block part of compress_blocks (model_types.py:192-212) for a list of blocks: returns
         (strings per block, best-threshold list per block, candidate point lists per block, metric names,
-        debug).  This is the unit that shards across GPUs (sharded_blocks.py)."""
+        debug).  This is the unit that shards across GPUs (sharded_blocks.py).
+        count_scale = rho: count-matched thresholding instead of the search: every block carries one more string, LAST,
+        with k = block_count(its input rows, rho, voxels); its candidate is the k highest-scoring voxels of x_hat (ops.topk_compact) and
+        its threshold byte the fixed one."""
         ctx = self._ctx(sess)
         dhw = self._spatial(self.x_shape)
+        check_count_scale(count_scale, fixed_threshold, self.lossless)
+        counted = count_scale is not None
         if not fixed_threshold:
             # once per call what the reference asserts per block (model_opt.py:22-24): unknown metric names, d2_* without normals
             from .utils.pc_metric import validate_opt_metrics
@@ -458,9 +484,13 @@ class CompressionModel:
             # the occupancy layer: the chunk's dense input under the x_hat the decoder will compute (same bits: the numerics tag); the
             # threshold search below neither sees nor changes it
             occ_job = ops.occ_encode_launch(ctx, enc['x_hat'], x) if self.lossless else None
+            if counted:
+                ks = [block_count(len(b), count_scale, int(np.prod(dhw))) for b in chunk]
+                enc['xyz'], enc['counts'] = ops.topk_compact(ctx, enc['x_hat'], torch.tensor(ks, dtype=torch.int32).to(ctx.device, non_blocking=True))
             strings = enc['finish']()
-            if fixed_threshold:
-                # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 for every metric
+            if fixed_threshold or counted:
+                # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 for every metric; under count_scale the
+                # byte is the same and the candidate is the top-k one
                 n_m = len(max_deltas) * len(opt_metrics)
                 pts = self._gather_points(enc['xyz'], enc['counts'])
                 for j in range(len(chunk)):
@@ -470,6 +500,8 @@ class CompressionModel:
                 search.add(chunk, enc['x_hat'])
             if occ_job is not None:
                 strings = [tuple(ss) + (o,) for ss, o in zip(strings, ops.occ_encode_fetch(*occ_job))]
+            if counted:
+                strings = [tuple(ss) + (count_to_bytes(k),) for ss, k in zip(strings, ks)]
             strings_list.extend(strings)
             debug_t_list.extend(enc['debug'])
         search.drain()
@@ -477,19 +509,21 @@ class CompressionModel:
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
-                        need_points=True, metrics_device='host', d2_ties='pick'):
+                        need_points=True, metrics_device='host', d2_ties='pick', count_scale=None):
         """Uses the compression model to compress a point cloud (model_types.py:184-218).  Under torch.distributed (one
         process per GPU) the block list is sharded (sharded_blocks.py): rank 0 returns the complete result, the other ranks
         return (None, metadata without point lists, local debug list).  `need_points=False` skips the gather of the
         decoded candidate point lists to rank 0 (they are only needed for --dec_files / --debug).  metrics_device='gpu'
         (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree.  d2_ties='mean' (single process
-        only): the whole-cloud D2 averages over all equidistant nearest points; the per-block threshold search is not affected."""
+        only): the whole-cloud D2 averages over all equidistant nearest points; the per-block threshold search is not affected.
+        count_scale (single process only): see encode_block_range."""
         from . import sharding
         from .utils.pc_metric import check_ties
         rank, world = sharding.world_info()
         check_ties(d2_ties, world)
         if self.lossless and world > 1:
             raise AssertionError('lossless is single-process only: the sharded path moves the y/z strings alone')
+        check_count_scale(count_scale, fixed_threshold, self.lossless, world)
         if metrics_device not in METRICS_DEVICES:
             raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
         if metrics_device == 'gpu' and world > 1:
@@ -505,7 +539,8 @@ class CompressionModel:
                                            max_deltas, fixed_threshold, debug, need_points, tree_future)
         try:
             strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
-                sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug)
+                sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug,
+                **({} if count_scale is None else {'count_scale': count_scale}))
         finally:
             tree = tree_future.result() if tree_future is not None else None
         # block -> opt metric to opt metric -> block
@@ -628,9 +663,11 @@ class CompressionModel:
         is sharded and rank 0 returns the points (sharded_blocks.py).
         layers: 'all' decodes the occupancy string of a lossless stream (one string more per block than the model's y/z strings)
         against x_hat and returns the exact input voxels, the threshold byte is ignored; 'base' is the lossy decode of the same stream,
-        as if the layer were not there.  A stream without the layer decodes the same under both."""
+        as if the layer were not there.  A stream without the layer decodes the same under both.  'count' reads the extra string as the
+        block's point count k ("cnt1") and returns the k highest-scoring voxels of x_hat; 'base' on such a stream is the
+        decode by the threshold byte."""
         from . import sharding
-        assert layers in ('all', 'base'), f"layers: 'all' or 'base', not {layers!r}"
+        assert layers in ('all', 'base', 'count'), f"layers: 'all', 'base' or 'count', not {layers!r}"
         if sharding.world_info()[1] > 1:
             from .sharded_blocks import decompress_blocks_sharded
             return decompress_blocks_sharded(self, sess, blocks, x_shape, debug, layers)
@@ -644,6 +681,7 @@ class CompressionModel:
         chunks = [blocks[c0:c0 + self.batch_size] for c0 in range(0, len(blocks), self.batch_size)]
         n_base = self.n_strings
         exact = layers == 'all' and len(blocks) > 0 and len(blocks[0][0]) == n_base + 1
+        ks = self._block_counts(blocks, int(np.prod(dhw))) if layers == 'count' else None
         state = [None] * len(chunks)
         results = [None] * len(chunks)
         for k in range(len(chunks) + 1):
@@ -657,6 +695,13 @@ class CompressionModel:
                 ops.occ_check_status(status)                            # (after the chunk's launches)
                 results[k - 1] = (xyz, counts, dec['debug'])
                 state[k - 1] = None
+            elif k >= 1 and ks is not None:
+                c0 = (k - 1) * self.batch_size
+                dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=None)
+                kt = torch.tensor(ks[c0:c0 + len(chunks[k - 1])], dtype=torch.int32).to(ctx.device, non_blocking=True)
+                xyz, counts = ops.topk_compact(ctx, dec['x_hat'], kt)
+                results[k - 1] = (xyz, counts, dec['debug'])
+                state[k - 1] = None
             elif k >= 1:
                 thr_idx = [int(t) for _, t in chunks[k - 1]]
                 dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=self._thr_tensor(ctx, thr_idx))
@@ -668,6 +713,18 @@ class CompressionModel:
             dec_blocks.extend(self._gather_points(xyz, counts))
             debug_t_list.extend(dbg)
         return dec_blocks, debug_t_list
+
+    def _block_counts(self, blocks, n_voxels):
+        """The count strings of a "cnt1" stream (the string behind the model's y/z strings of every block) -> k per block, read before
+        anything is launched.  The stream is not trusted: a count above the block's voxels is the same request as all of them."""
+        ks = []
+        for b, (strings, _) in enumerate(blocks):
+            k = count_from_bytes(strings[self.n_strings]) if len(strings) == self.n_strings + 1 else None
+            if k is None:
+                raise L.PccError(f'block {b}: {len(strings)} strings, the last of {len(strings[-1]) if len(strings) else 0} bytes: a count stream '
+                                 f'carries {self.n_strings + 1} strings per block, the last of 4 bytes (status {L.PCC_ERR_CORRUPT})')
+            ks.append(min(k, n_voxels))
+        return ks
 
     # ------------------------------------------------------------------ batched graph.  With a pcc_codec_desc (`_codec`) the GPU part
     # of each phase is ONE ABI call; otherwise the same steps run layer by layer.  Both leave the same tensors under the same names.

@@ -10,7 +10,7 @@ from .conv import (  # noqa: F401
     mfma_supported)
 from .codec import (  # noqa: F401
     codec_desc, _ITEM, SymbolStaging, symbols_pack, symbols_unpack, _out, quantize_pack, index_pack, unpack_dequantize,
-    codec_encode, _packed_io, codec_decode_hyper, codec_decode_main, quantize, dequantize, scale_to_index, threshold_compact, voxelize)
+    codec_encode, _packed_io, codec_decode_hyper, codec_decode_main, quantize, dequantize, scale_to_index, threshold_compact, topk_compact, voxelize)
 from .training import (  # noqa: F401
     focal_loss, focal_loss_grad, relu_backward, dual_desc, conv_repack_map, conv_repack_device, conv_wgrad_slices, conv3d_wgrad,
     histogram_limits, _f32_flat, histogram_unpack, tensor_histograms_launch, tensor_histograms, tensor_histogram, occupancy_scores_launch,

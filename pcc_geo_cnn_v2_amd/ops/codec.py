@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._context import _ptr
+from ._context import _ptr, _workspace
 
 
 def codec_desc(ctx, version, filters, nets, medians=None, scale_table=None, round_mode=L.PCC_ROUND_FLOOR_HALF):
@@ -293,6 +293,30 @@ def threshold_compact(ctx, x, thr, clip=False, cap=None):
     scratch = torch.empty((L.lib().pcc_threshold_scratch_ints(B, D, H, W),), dtype=torch.int32, device=x.device)
     L.check(L.lib().pcc_threshold_compact(ctx.handle, _ptr(x), B, D, H, W, _ptr(thr), int(clip), _ptr(xyz),
                                           _ptr(counts), cap, _ptr(scratch), ctx.stream), 'pcc_threshold_compact')
+    return xyz, counts
+
+
+def topk_compact(ctx, x, k, cap=None):
+    """Count-matched thresholding (include/pcc_geo.h "top-k selection"): block b keeps its k[b] highest-scoring voxels
+    (scores <= 0 never; ties at the cut to the lowest voxel index).  x: (B,D,H,W) float32 on the context's device, each block contiguous,
+    blocks at least D*H*W elements apart (a slice of a wider buffer is fine); k: (B,) int32 device tensor.  Returns (xyz (B,cap,3),
+    counts (B,)) like threshold_compact: points in voxel order, counts[b] = min(max(k[b], 0), positive voxels of b)."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.device == ctx.device, 'topk_compact: x is a (B,D,H,W) float32 tensor on the context\'s device'
+    B, D, H, W = x.shape
+    n = D * H * W
+    assert B == 0 or n == 0 or x[0].is_contiguous(), 'topk_compact: the voxels of a block must be contiguous'
+    stride = x.stride(0) if B > 1 and n > 0 else n
+    assert stride >= n, 'topk_compact: blocks overlap'
+    assert k.dtype == torch.int32 and tuple(k.shape) == (B,) and k.is_contiguous() and k.device == ctx.device, \
+        'topk_compact: k is a (B,) int32 tensor on the context\'s device'
+    cap = n if cap is None else int(cap)
+    xyz = torch.empty((B, cap, 3), dtype=torch.float32, device=x.device)
+    counts = torch.zeros((B,), dtype=torch.int32, device=x.device)
+    if B == 0 or n == 0:
+        return xyz, counts
+    ws = _workspace(ctx, int(L.lib().pcc_topk_workspace_bytes(B, n)), 'topk_compact: more than 2^28 voxels per block')
+    L.check(L.lib().pcc_topk_compact(ctx.handle, _ptr(x), stride, B, D, H, W, _ptr(k), _ptr(xyz), _ptr(counts), cap, _ptr(ws), ws.numel(),
+                                     ctx.stream), 'pcc_topk_compact')
     return xyz, counts
 
 
