@@ -140,6 +140,7 @@ __global__ void k_level(long long n, int twice_points_per_cell, IndexHdr* H) {
 }
 
 size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+bool valid_n(int64_t n) { return n > 0 && n < ((int64_t)1 << 31); }      // a point count an index (and an int-sized hipCUB call) takes
 
 struct IndexLayout {
     size_t hdr, codes, recs, pts, codes0, rows0, rows1, sort_tmp, sort_tmp_bytes, total;

@@ -11,12 +11,12 @@
 //
 // Search: the cell index of cell_index.h (built by pcc_cloud_index_build), one lane per query, queries in the query cloud's
 // Morton order (its index records), as k_query<true> of cloud_metrics.hip.  Tally: the per-point terms are written by row and
-// summed by k_ctally / k_cfinish in an order fixed by the sizes; nothing synchronises with the host.
+// summed by k_ctally / k_cfinish in an order fixed by the sizes (the grid and the tree of cloud_tally.h); nothing synchronises with
+// the host.
 #include "cell_index.h"
+#include "cloud_tally.h"
 
 namespace {
-
-constexpr int kColorBlocks = 1024;    // upper bound of the partials of one direction (fixed per n: the sum order depends on n only)
 
 // ---- map -----------------------------------------------------------------------------------------------------------------------
 
@@ -55,20 +55,16 @@ __global__ void __launch_bounds__(256) k_map(const IndexHdr* __restrict__ H, con
 
 // ---- distortion ----------------------------------------------------------------------------------------------------------------
 
-// every point at the smallest squared distance so far: their count and exact colour sums
-struct TieSet {
+struct ColourSums {                   // over the tie set: the exact sums of R, G, B
     const uint8_t* colours;
-    unsigned long long d2 = ~0ull;
-    unsigned long long count = 0, s[3] = {0, 0, 0};
-    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
-        if (d > d2) return;
-        if (d < d2) { d2 = d; count = 0; s[0] = s[1] = s[2] = 0; }
-        ++count;
+    unsigned long long s[3] = {0, 0, 0};
+    __device__ __forceinline__ void reset() { s[0] = s[1] = s[2] = 0; }
+    __device__ __forceinline__ void add(unsigned r) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) s[c] += colours[3 * (long long)r + c];
     }
-    __device__ __forceinline__ unsigned long long bound() const { return d2; }
 };
+using TieSet = TieVisitor<ColourSums>;
 
 // One lane per query record of the source cloud against the destination index: terms[3 * row ..] = (eY^2, eU^2, eV^2).
 __global__ void __launch_bounds__(256) k_cterms(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
@@ -81,13 +77,13 @@ __global__ void __launch_bounds__(256) k_cterms(const IndexHdr* __restrict__ H, 
         const int4 q = qrecs[t];
         const int qc[3] = {q.x, q.y, q.z};
         TieSet init;
-        init.colours = colours;
+        init.over.colours = colours;
         const TieSet ties = search(g, qc, 0, init);
         const long long row = q.w;
         const double cnt = (double)ties.count;                  // exact: count < 2^31, sums < 2^39
-        const double dR = (double)qcolours[3 * row] - (double)ties.s[0] / cnt;
-        const double dG = (double)qcolours[3 * row + 1] - (double)ties.s[1] / cnt;
-        const double dB = (double)qcolours[3 * row + 2] - (double)ties.s[2] / cnt;
+        const double dR = (double)qcolours[3 * row] - (double)ties.over.s[0] / cnt;
+        const double dG = (double)qcolours[3 * row + 1] - (double)ties.over.s[1] / cnt;
+        const double dB = (double)qcolours[3 * row + 2] - (double)ties.over.s[2] / cnt;
         const double eY = (0.2126 * dR + 0.7152 * dG) + 0.0722 * dB;
         const double eU = (-0.1146 * dR - 0.3854 * dG) + 0.5 * dB;
         const double eV = (0.5 * dR - 0.4542 * dG) - 0.0458 * dB;
@@ -97,58 +93,40 @@ __global__ void __launch_bounds__(256) k_cterms(const IndexHdr* __restrict__ H, 
     }
 }
 
-// Grid-stride over the rows with a grid fixed by n, then a fixed tree in the workgroup: partial[3 * block ..].
+// Grid-stride over the rows on tally_blocks(n) workgroups, then the fixed tree in each: partial[3 * block ..].
 __global__ void __launch_bounds__(256) k_ctally(const double* __restrict__ terms, long long n, double* __restrict__ partial) {
-    __shared__ double s[3][256];
-    double acc[3] = {0.0, 0.0, 0.0};
+    __shared__ Slots<double, 3> sh[256];
+    Slots<double, 3> acc = {{0.0, 0.0, 0.0}};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += terms[3 * i + c];
+        for (int c = 0; c < 3; ++c) acc.v[c] += terms[3 * i + c];
     }
-    const int t = threadIdx.x;
+    const Slots<double, 3> sum = tree256(acc, sh, EachSlot<Sum>());
+    if (threadIdx.x == 0) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) s[c][t] = acc[c];
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (t < w) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s[c][t] += s[c][t + w];
-        }
-        __syncthreads();
+        for (int c = 0; c < 3; ++c) partial[3 * blockIdx.x + c] = sum.v[c];
     }
-    if (t < 3) partial[3 * blockIdx.x + t] = s[t][0];
 }
 
 // one workgroup: the partials of A -> B (ga of them) and B -> A (gb), each direction summed in a fixed order
 __global__ void __launch_bounds__(256) k_cfinish(const double* __restrict__ pab, int ga, const double* __restrict__ pba, int gb,
                                                  double* __restrict__ tally) {
-    __shared__ double s[6][256];
-    const int t = threadIdx.x;
+    __shared__ Slots<double, 6> sh[256];
+    Slots<double, 6> acc = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
     for (int side = 0; side < 2; ++side) {
         const double* p = side ? pba : pab;
         const int g = side ? gb : ga;
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (int b = t; b < g; b += 256) {
+        for (int b = threadIdx.x; b < g; b += 256) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += p[3 * b + c];
+            for (int c = 0; c < 3; ++c) acc.v[3 * side + c] += p[3 * b + c];
         }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[3 * side + c][t] = acc[c];
     }
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (t < w) {
+    const Slots<double, 6> sum = tree256(acc, sh, EachSlot<Sum>());
+    if (threadIdx.x == 0) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) s[k][t] += s[k][t + w];
-        }
-        __syncthreads();
+        for (int k = 0; k < 6; ++k) tally[k] = sum.v[k];
     }
-    if (t < 6) tally[t] = s[t][0];
-}
-
-int color_blocks(long long n) {
-    const long long b = (n + 255) / 256;
-    return (int)(b < kColorBlocks ? b : kColorBlocks);
 }
 
 struct ColorLayout {
@@ -157,16 +135,14 @@ struct ColorLayout {
 
 ColorLayout color_layout(long long na, long long nb) {
     ColorLayout l;
-    size_t o = 0;
-    l.terms_a = o; o += al256((size_t)na * 24);
-    l.terms_b = o; o += al256((size_t)nb * 24);
-    l.pab = o; o += al256(kColorBlocks * 24);
-    l.pba = o; o += al256(kColorBlocks * 24);
-    l.total = o;
+    Carver w;
+    l.terms_a = w.take((size_t)na * 24);
+    l.terms_b = w.take((size_t)nb * 24);
+    l.pab = w.take(kTallyBlocks * 24);
+    l.pba = w.take(kTallyBlocks * 24);
+    l.total = w.o;
     return l;
 }
-
-bool valid_n(int64_t n) { return n > 0 && n < ((int64_t)1 << 31); }
 
 }  // namespace
 
@@ -212,7 +188,7 @@ PCC_API int pcc_cloud_color_distortion(pcc_ctx* ctx, const void* index_a, int64_
                        a_colours, A.n, terms_a);
     hipLaunchKernelGGL(k_cterms, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, a_colours, B.recs,
                        b_colours, B.n, terms_b);
-    const int ta = color_blocks(na), tb = color_blocks(nb);
+    const int ta = tally_blocks(na), tb = tally_blocks(nb);
     hipLaunchKernelGGL(k_ctally, dim3(ta), dim3(256), 0, st, (const double*)terms_a, (long long)na, pab);
     hipLaunchKernelGGL(k_ctally, dim3(tb), dim3(256), 0, st, (const double*)terms_b, (long long)nb, pba);
     hipLaunchKernelGGL(k_cfinish, dim3(1), dim3(256), 0, st, (const double*)pab, ta, (const double*)pba, tb, tally);

@@ -14,32 +14,42 @@
 // Query (k_query), one lane per query: the index search from Chebyshev radius 0, keeping the best (squared distance, row) pair.
 // Tally: a stable radix sort of (to_b[i], i) makes every decoded point's original points a segment in increasing i (k_segments,
 // k_bnormals: one sequential float64 sum per segment, numpy bincount's order); k_tally reduces each direction into per-block
-// partials, k_finish adds the partials in a fixed order.  The only atomics are the index build's integer ones (bounding box,
+// partials, k_finish adds the partials in a fixed order (the grid and the tree of cloud_tally.h).  The only atomics are the index build's integer ones (bounding box,
 // coordinate sums, histogram); nothing synchronises with the host: the same inputs give the same bits on every call.
 #include <hipcub/hipcub.hpp>
 
 #include "cell_index.h"
+#include "cloud_tally.h"
 
 namespace {
 
-constexpr int kTallyBlocks = 1024;    // upper bound of the partials of one direction (fixed per n: the sum order depends on n only)
-
-struct Partial {                      // one workgroup's share of one direction
+struct Partial {                      // one direction's sums and maxima: a thread's, a workgroup's (in the workspace), the cloud's
     unsigned long long d1_lo, d1_hi;  // exact sum of the squared distances (128 bits)
     unsigned long long h1;            // max squared distance
     double d2, h2;                    // sum / max of the per-point plane terms
+    __device__ __forceinline__ static Partial zero() { return Partial{0, 0, 0, 0.0, 0.0}; }
+    __device__ __forceinline__ unsigned __int128 d1() const { return (unsigned __int128)d1_hi << 64 | d1_lo; }
+    __device__ __forceinline__ void add_d1(unsigned __int128 v) {
+        v += d1();
+        d1_lo = (unsigned long long)v;
+        d1_hi = (unsigned long long)(v >> 64);
+    }
+    __device__ __forceinline__ void distance(unsigned long long d) { add_d1(d); h1 = d > h1 ? d : h1; }
+    __device__ __forceinline__ void term(double v) { d2 += v; h2 = v > h2 ? v : h2; }
+};
+struct Merge {
+    __device__ __forceinline__ Partial operator()(Partial a, const Partial& b) const {
+        a.add_d1(b.d1());
+        a.h1 = b.h1 > a.h1 ? b.h1 : a.h1;
+        a.d2 += b.d2;
+        a.h2 = b.h2 > a.h2 ? b.h2 : a.h2;
+        return a;
+    }
 };
 
 // ---- query ---------------------------------------------------------------------------------------------------------------------
 
-struct Nearest {                      // the lowest (squared distance, row) so far
-    unsigned long long d2 = ~0ull;
-    unsigned row = ~0u;
-    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
-        if (d < d2 || (d == d2 && r < row)) { d2 = d; row = r; }
-    }
-    __device__ __forceinline__ unsigned long long bound() const { return d2; }
-};
+using Nearest = TieVisitor<>;         // the lowest (squared distance, row): the tie set's lowest row, its count unused
 
 // One lane per query.  RECS: the queries are another index's records (Morton order: a wave's lanes are neighbours in space, and
 // the result goes to the record's row); otherwise row-order points.  Writes nn[row] and sqd[row] (either may be NULL).
@@ -75,91 +85,105 @@ __global__ void __launch_bounds__(256) k_link_keys(const int32_t* __restrict__ t
     if (i < na) { keys[i] = (unsigned)to_b[i]; vals[i] = (unsigned)i; }
 }
 
-// segment [lo[j], hi[j]) of the sorted links holds the original points whose nearest decoded point is j (both zero: none)
-__global__ void __launch_bounds__(256) k_segments(const unsigned* __restrict__ keys, long long na, unsigned* __restrict__ lo,
+// How many sorted (decoded row, original row) pairs there are: all na links of the default rule, or the device's count of tie pairs
+// (then the tail of the arrays is padding with key nb, and past the capacity nothing is done).
+struct AllLinks {
+    static constexpr bool kPadded = false;
+    long long n;
+    __device__ __forceinline__ bool live() const { return true; }
+    __device__ __forceinline__ unsigned long long count() const { return (unsigned long long)n; }
+};
+struct TiePairs {
+    static constexpr bool kPadded = true;
+    const TieCtl* ctl;
+    __device__ __forceinline__ bool live() const { return !ctl->overflow; }
+    __device__ __forceinline__ unsigned long long count() const { return ctl->pairs; }
+};
+
+// segment [lo[j], hi[j]) of the sorted pairs holds the original points that link to (vote for) decoded point j (both zero: none)
+template <class Pairs>
+__global__ void __launch_bounds__(256) k_segments(const unsigned* __restrict__ keys, Pairs pairs, unsigned nb, unsigned* __restrict__ lo,
                                                   unsigned* __restrict__ hi) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= na) return;
+    if (!pairs.live()) return;
+    const unsigned long long n = pairs.count(), t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
     const unsigned k = keys[t];
+    if (Pairs::kPadded && k >= nb) return;
     if (t == 0 || keys[t - 1] != k) lo[k] = (unsigned)t;
-    if (t == na - 1 || keys[t + 1] != k) hi[k] = (unsigned)(t + 1);
+    if (t == n - 1 || keys[t + 1] != k) hi[k] = (unsigned)(t + 1);
 }
 
-// pc_metric.transfer_normals: one sequential float64 sum per segment (increasing i, as bincount), divided by the count
+// The normal of a decoded point nobody links to.  Default rule: that of its nearest original point, through the sum and the division
+// of a one-vote segment ((0.0 + n) / 1.0: -0.0 becomes +0.0).  Tie-averaged: the mean over T_A(b) that k_tie_ba left, copied as is.
+struct OrphanNearest {
+    const double* an;
+    const int32_t* to_a;
+    __device__ __forceinline__ bool live() const { return true; }
+    __device__ __forceinline__ double get(long long j, int c) const { return (0.0 + an[3 * (long long)to_a[j] + c]) / 1.0; }
+};
+struct OrphanMean {
+    const double* orphan;
+    const TieCtl* ctl;
+    __device__ __forceinline__ bool live() const { return !ctl->overflow; }
+    __device__ __forceinline__ double get(long long j, int c) const { return orphan[3 * j + c]; }
+};
+
+// pc_metric.transfer_normals: one sequential float64 sum per segment (increasing original row, as bincount), divided by the count
+template <class Orphan>
 __global__ void __launch_bounds__(256) k_bnormals(const unsigned* __restrict__ lo, const unsigned* __restrict__ hi,
-                                                  const unsigned* __restrict__ vals, const double* __restrict__ an,
-                                                  const int32_t* __restrict__ to_a, long long nb, double* __restrict__ bn) {
+                                                  const unsigned* __restrict__ vals, const double* __restrict__ an, Orphan orphan,
+                                                  long long nb, double* __restrict__ bn) {
+#pragma clang fp contract(off)
+    if (!orphan.live()) return;
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nb) return;
     const unsigned s = lo[j], e = hi[j];
-    double acc[3] = {0.0, 0.0, 0.0}, votes = 1.0;
     if (e > s) {
+        double acc[3] = {0.0, 0.0, 0.0};
         for (unsigned t = s; t < e; ++t) {
             const long long i = vals[t];
 #pragma unroll
             for (int c = 0; c < 3; ++c) acc[c] += an[3 * i + c];
         }
-        votes = (double)(e - s);
+        const double votes = (double)(e - s);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bn[3 * j + c] = acc[c] / votes;
     } else {
-        const long long i = to_a[j];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += an[3 * i + c];
+        for (int c = 0; c < 3; ++c) bn[3 * j + c] = orphan.get(j, c);
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) bn[3 * j + c] = acc[c] / votes;
 }
 
-// ((gx*nx + gy*ny) + gz*nz)^2 rounded after every operation, numpy's order
-__device__ __forceinline__ double plane_term(double gx, double gy, double gz, const double* __restrict__ nrm) {
-#pragma clang fp contract(off)
-    const double p = (gx * nrm[0] + gy * nrm[1]) + gz * nrm[2];
-    return p * p;
-}
+// Where the plane term of point s of one direction comes from.  LinkTerm: src point s links to dst row link[s], nrm is indexed by
+// that row.  StoredTerm: computed already.  Either with a NULL array: no D2.
+struct LinkTerm {
+    const int32_t *src, *dst, *link;
+    const double* nrm;
+    __device__ __forceinline__ bool any() const { return nrm != nullptr; }
+    __device__ __forceinline__ double operator()(long long s) const {
+        const long long j = link[s];
+        const double* n = nrm + 3 * j;
+        return plane_term((double)(src[3 * s] - dst[3 * j]), (double)(src[3 * s + 1] - dst[3 * j + 1]),
+                          (double)(src[3 * s + 2] - dst[3 * j + 2]), n[0], n[1], n[2]);
+    }
+};
+struct StoredTerm {
+    const double* terms;
+    __device__ __forceinline__ bool any() const { return terms != nullptr; }
+    __device__ __forceinline__ double operator()(long long s) const { return terms[s]; }
+};
 
-// One direction: src point s links to dst row link[s]; nrm (NULL: no D2) is indexed by that row.  Grid-stride with a grid fixed by
-// n: every per-thread sum visits the same points in the same order on every call.
-__global__ void __launch_bounds__(256) k_tally(const int32_t* __restrict__ src, long long ns, const int32_t* __restrict__ dst,
-                                               const int32_t* __restrict__ link, const long long* __restrict__ sqd,
-                                               const double* __restrict__ nrm, Partial* __restrict__ out) {
-    __shared__ unsigned __int128 s_d1[256];
-    __shared__ unsigned long long s_h1[256];
-    __shared__ double s_d2[256], s_h2[256];
-    unsigned __int128 d1 = 0;
-    unsigned long long h1 = 0;
-    double d2 = 0.0, h2 = 0.0;
+// One direction over tally_blocks(ns) workgroups: out[block] = its share
+template <class Term>
+__global__ void __launch_bounds__(256) k_tally(long long ns, const long long* __restrict__ sqd, Term term, Partial* __restrict__ out) {
+    __shared__ Partial sh[256];
+    Partial acc = Partial::zero();
     for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < ns; s += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long d = (unsigned long long)sqd[s];
-        d1 += d;
-        h1 = d > h1 ? d : h1;
-        if (nrm) {
-            const long long j = link[s];
-            const double v = plane_term((double)(src[3 * s] - dst[3 * j]), (double)(src[3 * s + 1] - dst[3 * j + 1]),
-                                        (double)(src[3 * s + 2] - dst[3 * j + 2]), nrm + 3 * j);
-            d2 += v;
-            h2 = v > h2 ? v : h2;
-        }
+        acc.distance((unsigned long long)sqd[s]);
+        if (term.any()) acc.term(term(s));
     }
-    const int t = threadIdx.x;
-    s_d1[t] = d1; s_h1[t] = h1; s_d2[t] = d2; s_h2[t] = h2;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (t < w) {
-            s_d1[t] += s_d1[t + w];
-            s_h1[t] = s_h1[t + w] > s_h1[t] ? s_h1[t + w] : s_h1[t];
-            s_d2[t] += s_d2[t + w];
-            s_h2[t] = s_h2[t + w] > s_h2[t] ? s_h2[t + w] : s_h2[t];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        Partial p;
-        p.d1_lo = (unsigned long long)s_d1[0];
-        p.d1_hi = (unsigned long long)(s_d1[0] >> 64);
-        p.h1 = s_h1[0];
-        p.d2 = s_d2[0];
-        p.h2 = s_h2[0];
-        out[blockIdx.x] = p;
-    }
+    const Partial sum = tree256(acc, sh, Merge());
+    if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 
 // correctly rounded double of a 128-bit unsigned integer
@@ -175,82 +199,38 @@ __device__ __forceinline__ double u128_to_double(unsigned __int128 v) {
 // one workgroup: the partials of A->B (ga of them) and B->A (gb), each direction summed in a fixed order
 __global__ void __launch_bounds__(256) k_finish(const Partial* __restrict__ pab, int ga, const Partial* __restrict__ pba, int gb,
                                                 long long nb, double* __restrict__ tally) {
-    __shared__ unsigned __int128 s_d1[2][256];
-    __shared__ unsigned long long s_h1[2][256];
-    __shared__ double s_d2[2][256], s_h2[2][256];
-    const int t = threadIdx.x;
+    __shared__ Slots<Partial, 2> sh[256];
+    Slots<Partial, 2> acc;
+#pragma unroll
     for (int side = 0; side < 2; ++side) {
         const Partial* p = side ? pba : pab;
         const int g = side ? gb : ga;
-        unsigned __int128 d1 = 0;
-        unsigned long long h1 = 0;
-        double d2 = 0.0, h2 = 0.0;
-        for (int b = t; b < g; b += 256) {
-            d1 += (unsigned __int128)p[b].d1_hi << 64 | p[b].d1_lo;
-            h1 = p[b].h1 > h1 ? p[b].h1 : h1;
-            d2 += p[b].d2;
-            h2 = p[b].h2 > h2 ? p[b].h2 : h2;
-        }
-        s_d1[side][t] = d1; s_h1[side][t] = h1; s_d2[side][t] = d2; s_h2[side][t] = h2;
+        acc.v[side] = Partial::zero();
+        for (int b = threadIdx.x; b < g; b += 256) acc.v[side] = Merge()(acc.v[side], p[b]);
     }
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (t < w) {
-#pragma unroll
-            for (int side = 0; side < 2; ++side) {
-                s_d1[side][t] += s_d1[side][t + w];
-                s_h1[side][t] = s_h1[side][t + w] > s_h1[side][t] ? s_h1[side][t + w] : s_h1[side][t];
-                s_d2[side][t] += s_d2[side][t + w];
-                s_h2[side][t] = s_h2[side][t + w] > s_h2[side][t] ? s_h2[side][t + w] : s_h2[side][t];
-            }
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
+    const Slots<Partial, 2> sum = tree256(acc, sh, EachSlot<Merge>());
+    if (threadIdx.x == 0) {
         tally[0] = (double)nb;
-        tally[1] = u128_to_double(s_d1[0][0]);
-        tally[2] = u128_to_double(s_d1[1][0]);
-        tally[3] = s_d2[0][0];
-        tally[4] = s_d2[1][0];
-        tally[5] = (double)s_h1[0][0];
-        tally[6] = (double)s_h1[1][0];
-        tally[7] = s_h2[0][0];
-        tally[8] = s_h2[1][0];
+        tally[1] = u128_to_double(sum.v[0].d1());
+        tally[2] = u128_to_double(sum.v[1].d1());
+        tally[3] = sum.v[0].d2;
+        tally[4] = sum.v[1].d2;
+        tally[5] = (double)sum.v[0].h1;
+        tally[6] = (double)sum.v[1].h1;
+        tally[7] = sum.v[0].h2;
+        tally[8] = sum.v[1].h2;
     }
 }
 
 // ---- tie-averaged D2 (pcc_cloud_distortion_ties, tie_mode mean; DESIGN.md "Tie-averaged D2") --------------------------------------
 // A -> B: k_tie_count counts every original point's tie set T_B(a), an exclusive scan places it, k_tie_emit writes its (b, a) pairs
 // (a second search with the known smallest distance as its bound), the stable sort by b makes every decoded point's votes a segment
-// in increasing a, k_bnormals_ties averages them (or takes the orphan mean of k_tie_ba), k_terms_ab walks each point's own pairs.
+// in increasing a, k_bnormals averages them (or takes the orphan mean of k_tie_ba), k_terms_ab walks each point's own pairs.
 // B -> A: one search, k_tie_ba, whose visitor accumulates the plane terms and the normals of T_A(b) as it meets them.
-// The pair count is only known on the device: k_total compares it with the caller's capacity; past it every later kernel returns
-// early and k_overflow turns the D2 / H2 slots into NaN (status tells the caller the capacity to come back with).
+// The pair list is cloud_tally.h's: past the capacity every later kernel returns early and k_pair_nan turns the D2 / H2 slots into NaN
+// (status tells the caller the capacity to come back with).
 
-struct TieCtl {                       // written by k_total
-    unsigned long long pairs;         // sum of |T_B(a)| over the original points
-    int overflow;                     // pairs > capacity: nothing below k_total touches the pair arrays
-};
-
-// ((gx*nx + gy*ny) + gz*nz)^2 rounded after every operation, as plane_term (kept apart so the kernels of the default rule compile
-// from the same text as before)
-__device__ __forceinline__ double tie_plane_term(double gx, double gy, double gz, const double* __restrict__ nrm) {
-#pragma clang fp contract(off)
-    const double p = (gx * nrm[0] + gy * nrm[1]) + gz * nrm[2];
-    return p * p;
-}
-
-struct TieCount {                     // the size of the tie set so far and its lowest row
-    unsigned long long d2 = ~0ull;
-    unsigned count = 0, row = ~0u;
-    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
-        if (d > d2) return;
-        if (d < d2) { d2 = d; count = 0; row = ~0u; }
-        ++count;
-        row = r < row ? r : row;
-    }
-    __device__ __forceinline__ unsigned long long bound() const { return d2; }
-};
+using TieCount = TieVisitor<>;        // the size of the tie set and its lowest row
 
 struct TieEmit {                      // writes the rows at squared distance `target` (the smallest, known from k_tie_count)
     unsigned* out;
@@ -262,27 +242,22 @@ struct TieEmit {                      // writes the rows at squared distance `ta
     __device__ __forceinline__ unsigned long long bound() const { return target; }
 };
 
-struct TiePlane {                     // over the tie set so far: sum of e(q - p_r, nrm[r]), sum of nrm[r], count, lowest row
+struct PlaneSums {                    // over the tie set: sum of e(q - p_r, nrm[r]) and sum of nrm[r]
     const int32_t* pts;               // the indexed cloud in row order
     const double* nrm;                // its normals
     int q[3];
-    unsigned long long d2 = ~0ull;
-    unsigned count = 0, row = ~0u;
     double e = 0.0, s[3] = {0.0, 0.0, 0.0};
-    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
+    __device__ __forceinline__ void reset() { e = 0.0; s[0] = s[1] = s[2] = 0.0; }
+    __device__ __forceinline__ void add(unsigned r) {
 #pragma clang fp contract(off)
-        if (d > d2) return;
-        if (d < d2) { d2 = d; count = 0; row = ~0u; e = 0.0; s[0] = s[1] = s[2] = 0.0; }
-        ++count;
-        row = r < row ? r : row;
         const long long j = r;
         const double* n = nrm + 3 * j;
-        e += tie_plane_term((double)(q[0] - pts[3 * j]), (double)(q[1] - pts[3 * j + 1]), (double)(q[2] - pts[3 * j + 2]), n);
+        e += plane_term((double)(q[0] - pts[3 * j]), (double)(q[1] - pts[3 * j + 1]), (double)(q[2] - pts[3 * j + 2]), n[0], n[1], n[2]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) s[c] += n[c];
     }
-    __device__ __forceinline__ unsigned long long bound() const { return d2; }
 };
+using TiePlane = TieVisitor<PlaneSums>;
 
 // One lane per original point (A's records, Morton order) against B's index: nn[row] the lowest tied row, sqd[row], cnt[row] = |T_B|.
 __global__ void __launch_bounds__(256) k_tie_count(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
@@ -299,15 +274,6 @@ __global__ void __launch_bounds__(256) k_tie_count(const IndexHdr* __restrict__ 
         sqd[row] = (long long)best.d2;
         cnt[row] = best.count;
     }
-}
-
-__global__ void k_total(const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off, long long na,
-                        unsigned long long cap, TieCtl* __restrict__ ctl, long long* __restrict__ status) {
-    const unsigned long long pairs = off[na - 1] + cnt[na - 1];
-    ctl->pairs = pairs;
-    ctl->overflow = pairs > cap;
-    status[0] = (long long)pairs;
-    status[1] = pairs > cap;
 }
 
 // The pairs of original point `row` at [off[row], off[row] + cnt[row]): keys = the tied decoded rows in visiting order, vals = row.
@@ -332,25 +298,6 @@ __global__ void __launch_bounds__(256) k_tie_emit(const IndexHdr* __restrict__ H
     }
 }
 
-// the unused tail of the pair arrays sorts behind every decoded row (key nb)
-__global__ void __launch_bounds__(256) k_tie_pad(const TieCtl* __restrict__ ctl, unsigned long long cap, unsigned nb,
-                                                 unsigned* __restrict__ keys, unsigned* __restrict__ vals) {
-    if (ctl->overflow) return;
-    const unsigned long long t = ctl->pairs + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < cap) { keys[t] = nb; vals[t] = 0; }
-}
-
-__global__ void __launch_bounds__(256) k_segments_ties(const unsigned* __restrict__ keys, const TieCtl* __restrict__ ctl, unsigned nb,
-                                                       unsigned* __restrict__ lo, unsigned* __restrict__ hi) {
-    if (ctl->overflow) return;
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ctl->pairs) return;
-    const unsigned k = keys[t];
-    if (k >= nb) return;
-    if (t == 0 || keys[t - 1] != k) lo[k] = (unsigned)t;
-    if (t == ctl->pairs - 1 || keys[t + 1] != k) hi[k] = (unsigned)(t + 1);
-}
-
 // One lane per decoded point (B's records) against A's index: nn / sqd as k_tie_count, terms[row] = the mean plane term over T_A(b),
 // orphan[3 * row ..] = the mean original normal over T_A(b) (the decoded point's normal when nobody votes for it).
 __global__ void __launch_bounds__(256) k_tie_ba(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
@@ -364,43 +311,17 @@ __global__ void __launch_bounds__(256) k_tie_ba(const IndexHdr* __restrict__ H, 
         const int4 q = qrecs[t];
         const int qc[3] = {q.x, q.y, q.z};
         TiePlane init;
-        init.pts = pts;
-        init.nrm = nrm;
-        init.q[0] = q.x; init.q[1] = q.y; init.q[2] = q.z;
+        init.over.pts = pts;
+        init.over.nrm = nrm;
+        init.over.q[0] = q.x; init.over.q[1] = q.y; init.over.q[2] = q.z;
         const TiePlane ties = search(g, qc, 0, init);
         const long long row = q.w;
         const double c = (double)ties.count;
         nn[row] = (int32_t)ties.row;
         sqd[row] = (long long)ties.d2;
-        terms[row] = ties.e / c;
+        terms[row] = ties.over.e / c;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) orphan[3 * row + k] = ties.s[k] / c;
-    }
-}
-
-// the normal of decoded point j: the mean of its votes' normals (one sequential float64 sum in increasing a), else its orphan mean
-__global__ void __launch_bounds__(256) k_bnormals_ties(const unsigned* __restrict__ lo, const unsigned* __restrict__ hi,
-                                                       const unsigned* __restrict__ vals, const double* __restrict__ an,
-                                                       const double* __restrict__ orphan, const TieCtl* __restrict__ ctl, long long nb,
-                                                       double* __restrict__ bn) {
-#pragma clang fp contract(off)
-    if (ctl->overflow) return;
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= nb) return;
-    const unsigned s = lo[j], e = hi[j];
-    if (e > s) {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (unsigned t = s; t < e; ++t) {
-            const long long i = vals[t];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += an[3 * i + c];
-        }
-        const double votes = (double)(e - s);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) bn[3 * j + c] = acc[c] / votes;
-    } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) bn[3 * j + c] = orphan[3 * j + c];
+        for (int k = 0; k < 3; ++k) orphan[3 * row + k] = ties.over.s[k] / c;
     }
 }
 
@@ -418,65 +339,11 @@ __global__ void __launch_bounds__(256) k_terms_ab(const int4* __restrict__ qrecs
         double e = 0.0;
         for (unsigned long long k = 0; k < c; ++k) {
             const long long j = keys[o + k];
-            e += tie_plane_term((double)(q.x - bpts[3 * j]), (double)(q.y - bpts[3 * j + 1]), (double)(q.z - bpts[3 * j + 2]), bn + 3 * j);
+            const double* n = bn + 3 * j;
+            e += plane_term((double)(q.x - bpts[3 * j]), (double)(q.y - bpts[3 * j + 1]), (double)(q.z - bpts[3 * j + 2]), n[0], n[1], n[2]);
         }
         terms[row] = e / (double)c;
     }
-}
-
-// k_tally over per-point terms that are already computed (NULL: no D2): the same grid rule, per-thread order and tree
-__global__ void __launch_bounds__(256) k_tally_terms(long long ns, const long long* __restrict__ sqd, const double* __restrict__ terms,
-                                                     Partial* __restrict__ out) {
-#pragma clang fp contract(off)
-    __shared__ unsigned __int128 s_d1[256];
-    __shared__ unsigned long long s_h1[256];
-    __shared__ double s_d2[256], s_h2[256];
-    unsigned __int128 d1 = 0;
-    unsigned long long h1 = 0;
-    double d2 = 0.0, h2 = 0.0;
-    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < ns; s += (long long)gridDim.x * blockDim.x) {
-        const unsigned long long d = (unsigned long long)sqd[s];
-        d1 += d;
-        h1 = d > h1 ? d : h1;
-        if (terms) {
-            const double v = terms[s];
-            d2 += v;
-            h2 = v > h2 ? v : h2;
-        }
-    }
-    const int t = threadIdx.x;
-    s_d1[t] = d1; s_h1[t] = h1; s_d2[t] = d2; s_h2[t] = h2;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if (t < w) {
-            s_d1[t] += s_d1[t + w];
-            s_h1[t] = s_h1[t + w] > s_h1[t] ? s_h1[t + w] : s_h1[t];
-            s_d2[t] += s_d2[t + w];
-            s_h2[t] = s_h2[t + w] > s_h2[t] ? s_h2[t + w] : s_h2[t];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        Partial p;
-        p.d1_lo = (unsigned long long)s_d1[0];
-        p.d1_hi = (unsigned long long)(s_d1[0] >> 64);
-        p.h1 = s_h1[0];
-        p.d2 = s_d2[0];
-        p.h2 = s_h2[0];
-        out[blockIdx.x] = p;
-    }
-}
-
-// past the pair capacity the D2 / H2 slots say so instead of holding numbers made from unwritten pairs
-__global__ void k_overflow(const TieCtl* __restrict__ ctl, double* __restrict__ tally) {
-    if (!ctl->overflow) return;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    tally[3] = nan; tally[4] = nan; tally[7] = nan; tally[8] = nan;
-}
-
-int tally_blocks(long long n) {
-    const long long b = (n + 255) / 256;
-    return (int)(b < kTallyBlocks ? b : kTallyBlocks);
 }
 
 int key_bits(long long nb) {                    // bits of the largest decoded row, nb - 1 (at least 1)
@@ -485,79 +352,99 @@ int key_bits(long long nb) {                    // bits of the largest decoded r
     return bits;
 }
 
+// ---- workspace -----------------------------------------------------------------------------------------------------------------
+// The default rule's buffers, and what the tie-averaged rule puts between them (cap > 0: its pair capacity, which then sizes the
+// key / value arrays instead of na).
 struct DistLayout {
     size_t nn_ab, d_ab, nn_ba, d_ba, keys0, vals0, keys1, vals1, seg_lo, seg_hi, bn, pab, pba, sort_tmp, sort_tmp_bytes, total;
 };
-
-DistLayout dist_layout(long long na, long long nb) {
-    DistLayout l;
-    const size_t A = (size_t)na, B = (size_t)nb;
-    size_t o = 0;
-    l.nn_ab = o; o += al256(A * 4);
-    l.d_ab = o; o += al256(A * 8);
-    l.nn_ba = o; o += al256(B * 4);
-    l.d_ba = o; o += al256(B * 8);
-    l.keys0 = o; o += al256(A * 4);
-    l.vals0 = o; o += al256(A * 4);
-    l.keys1 = o; o += al256(A * 4);
-    l.vals1 = o; o += al256(A * 4);
-    l.seg_lo = o; o += al256(B * 4);
-    l.seg_hi = o; o += al256(B * 4);
-    l.bn = o; o += al256(B * 24);
-    l.pab = o; o += al256(kTallyBlocks * sizeof(Partial));
-    l.pba = o; o += al256(kTallyBlocks * sizeof(Partial));
-    size_t tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                             (unsigned*)nullptr, (int)(na > 0 ? na : 1), 0, key_bits(nb), (hipStream_t)0);
-    l.sort_tmp_bytes = tmp;
-    l.sort_tmp = o; o += al256(tmp + 256);
-    l.total = o;
-    return l;
-}
-
-struct TieLayout {
-    size_t nn_ab, d_ab, nn_ba, d_ba, cnt, off, keys0, vals0, keys1, vals1, seg_lo, seg_hi, bn, orphan, terms_a, terms_b, pab, pba, ctl,
-        scan_tmp, scan_tmp_bytes, sort_tmp, sort_tmp_bytes, total;
+struct TieLayout : DistLayout {
+    size_t cnt, off, orphan, terms_a, terms_b, ctl, scan_tmp, scan_tmp_bytes;
 };
 
-TieLayout tie_layout(long long na, long long nb, long long cap) {
-    TieLayout l;
-    const size_t A = (size_t)na, B = (size_t)nb, P = (size_t)cap;
-    size_t o = 0;
-    l.nn_ab = o; o += al256(A * 4);
-    l.d_ab = o; o += al256(A * 8);
-    l.nn_ba = o; o += al256(B * 4);
-    l.d_ba = o; o += al256(B * 8);
-    l.cnt = o; o += al256(A * 8);
-    l.off = o; o += al256(A * 8);
-    l.keys0 = o; o += al256(P * 4);
-    l.vals0 = o; o += al256(P * 4);
-    l.keys1 = o; o += al256(P * 4);
-    l.vals1 = o; o += al256(P * 4);
-    l.seg_lo = o; o += al256(B * 4);
-    l.seg_hi = o; o += al256(B * 4);
-    l.bn = o; o += al256(B * 24);
-    l.orphan = o; o += al256(B * 24);
-    l.terms_a = o; o += al256(A * 8);
-    l.terms_b = o; o += al256(B * 8);
-    l.pab = o; o += al256(kTallyBlocks * sizeof(Partial));
-    l.pba = o; o += al256(kTallyBlocks * sizeof(Partial));
-    l.ctl = o; o += al256(sizeof(TieCtl));
-    size_t tmp = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)na,
-                                           (hipStream_t)0);
-    l.scan_tmp_bytes = tmp;
-    l.scan_tmp = o; o += al256(tmp + 256);
-    tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                             (unsigned*)nullptr, (int)cap, 0, key_bits(nb + 1), (hipStream_t)0);
-    l.sort_tmp_bytes = tmp;
-    l.sort_tmp = o; o += al256(tmp + 256);
-    l.total = o;
+TieLayout dist_layout(long long na, long long nb, long long cap = 0) {
+    TieLayout l{};
+    const bool mean = cap > 0;
+    const size_t A = (size_t)na, B = (size_t)nb, P = mean ? (size_t)cap : A;
+    Carver w;
+    l.nn_ab = w.take(A * 4);
+    l.d_ab = w.take(A * 8);
+    l.nn_ba = w.take(B * 4);
+    l.d_ba = w.take(B * 8);
+    if (mean) { l.cnt = w.take(A * 8); l.off = w.take(A * 8); }
+    l.keys0 = w.take(P * 4);
+    l.vals0 = w.take(P * 4);
+    l.keys1 = w.take(P * 4);
+    l.vals1 = w.take(P * 4);
+    l.seg_lo = w.take(B * 4);
+    l.seg_hi = w.take(B * 4);
+    l.bn = w.take(B * 24);
+    if (mean) { l.orphan = w.take(B * 24); l.terms_a = w.take(A * 8); l.terms_b = w.take(B * 8); }
+    l.pab = w.take(kTallyBlocks * sizeof(Partial));
+    l.pba = w.take(kTallyBlocks * sizeof(Partial));
+    if (mean) {
+        l.ctl = w.take(sizeof(TieCtl));
+        (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, l.scan_tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                               (int)na, (hipStream_t)0);
+        l.scan_tmp = w.take(l.scan_tmp_bytes + 256);
+    }
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, l.sort_tmp_bytes, (const unsigned*)nullptr, (unsigned*)nullptr,
+                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(mean ? cap : na > 0 ? na : 1), 0,
+                                             key_bits(mean ? nb + 1 : nb), (hipStream_t)0);
+    l.sort_tmp = w.take(l.sort_tmp_bytes + 256);
+    l.total = w.o;
     return l;
 }
 
-bool valid_n(int64_t n) { return n > 0 && n < ((int64_t)1 << 31); }
+// What both rules do around their own middle: the buffers of a call, and the tally of its two directions.
+struct Call {
+    hipStream_t st;
+    IndexView A, B;
+    TieLayout l;
+    unsigned char* w;
+    int32_t *nn_ab, *nn_ba;           // the caller's link arrays where it gave them
+    long long *d_ab, *d_ba;
+    unsigned *keys0, *vals0, *keys1, *vals1, *seg_lo, *seg_hi;
+    double* bn;
+    unsigned ga, gb;                  // workgroups of one lane per point of A / of B
+};
+
+Call open_call(const void* index_a, int64_t na, const void* index_b, int64_t nb, int64_t cap, int32_t* to_b, int32_t* to_a, void* workspace,
+               void* stream) {
+    Call c{(hipStream_t)stream, index_view(index_a, na), index_view(index_b, nb), dist_layout(na, nb, cap), (unsigned char*)workspace};
+    const TieLayout& l = c.l;
+    c.nn_ab = to_b ? to_b : (int32_t*)(c.w + l.nn_ab);
+    c.nn_ba = to_a ? to_a : (int32_t*)(c.w + l.nn_ba);
+    c.d_ab = (long long*)(c.w + l.d_ab); c.d_ba = (long long*)(c.w + l.d_ba);
+    c.keys0 = (unsigned*)(c.w + l.keys0); c.vals0 = (unsigned*)(c.w + l.vals0);
+    c.keys1 = (unsigned*)(c.w + l.keys1); c.vals1 = (unsigned*)(c.w + l.vals1);
+    c.seg_lo = (unsigned*)(c.w + l.seg_lo); c.seg_hi = (unsigned*)(c.w + l.seg_hi);
+    c.bn = (double*)(c.w + l.bn);
+    c.ga = (unsigned)((na + 255) / 256); c.gb = (unsigned)((nb + 255) / 256);
+    return c;
+}
+
+// the stable sort of the n pairs in keys0 / vals0 by decoded row, then every decoded point's segment
+template <class Pairs>
+int group_pairs(const Call& c, long long n, int bits, unsigned blocks, Pairs pairs) {
+    const long long nb = c.B.n;
+    size_t tmp = c.l.sort_tmp_bytes;                       // LSD radix sort: stable, so every segment stays in increasing original row
+    PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(c.w + c.l.sort_tmp), tmp, (const unsigned*)c.keys0, c.keys1,
+                                                     (const unsigned*)c.vals0, c.vals1, (int)n, 0, bits, c.st));
+    PCC_CHECK_HIP(hipMemsetAsync(c.seg_lo, 0, (size_t)nb * 4, c.st));
+    PCC_CHECK_HIP(hipMemsetAsync(c.seg_hi, 0, (size_t)nb * 4, c.st));
+    hipLaunchKernelGGL(k_segments<Pairs>, dim3(blocks), dim3(256), 0, c.st, (const unsigned*)c.keys1, pairs, (unsigned)nb, c.seg_lo, c.seg_hi);
+    return PCC_OK;
+}
+
+template <class Term>
+void tally_call(const Call& c, Term ab, Term ba, double* tally) {
+    Partial *pab = (Partial*)(c.w + c.l.pab), *pba = (Partial*)(c.w + c.l.pba);
+    const int ta = tally_blocks(c.A.n), tb = tally_blocks(c.B.n);
+    hipLaunchKernelGGL(k_tally<Term>, dim3(ta), dim3(256), 0, c.st, c.A.n, (const long long*)c.d_ab, ab, pab);
+    hipLaunchKernelGGL(k_tally<Term>, dim3(tb), dim3(256), 0, c.st, c.B.n, (const long long*)c.d_ba, ba, pba);
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, c.st, (const Partial*)pab, ta, (const Partial*)pba, tb, c.B.n, tally);
+}
 
 }  // namespace
 
@@ -597,41 +484,23 @@ PCC_API int pcc_cloud_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, 
     PCC_REQUIRE(ctx && index_a && index_b && tally && workspace, "pcc_cloud_distortion: NULL argument");
     PCC_REQUIRE(valid_n(na) && valid_n(nb), "pcc_cloud_distortion: na = %lld, nb = %lld outside [1, 2^31)", (long long)na, (long long)nb);
     PCC_CHECK_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    const IndexView A = index_view(index_a, na), B = index_view(index_b, nb);
-    const DistLayout l = dist_layout(na, nb);
-    unsigned char* w = (unsigned char*)workspace;
-    int32_t* nn_ab = to_b ? to_b : (int32_t*)(w + l.nn_ab);
-    int32_t* nn_ba = to_a ? to_a : (int32_t*)(w + l.nn_ba);
-    long long *d_ab = (long long*)(w + l.d_ab), *d_ba = (long long*)(w + l.d_ba);
-    Partial *pab = (Partial*)(w + l.pab), *pba = (Partial*)(w + l.pba);
-    const unsigned ga = (unsigned)((na + 255) / 256), gb = (unsigned)((nb + 255) / 256);
+    const Call c = open_call(index_a, na, index_b, nb, 0, to_b, to_a, workspace, stream);
+    const IndexView &A = c.A, &B = c.B;
     // queries in the other index's Morton order
-    hipLaunchKernelGGL(k_query<true>, dim3(ga), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, (const int32_t*)nullptr, A.n,
-                       nn_ab, d_ab);
-    hipLaunchKernelGGL(k_query<true>, dim3(gb), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, B.recs, (const int32_t*)nullptr, B.n,
-                       nn_ba, d_ba);
+    hipLaunchKernelGGL(k_query<true>, dim3(c.ga), dim3(256), 0, c.st, B.hdr, B.codes, B.recs, B.n, A.recs, (const int32_t*)nullptr, A.n,
+                       c.nn_ab, c.d_ab);
+    hipLaunchKernelGGL(k_query<true>, dim3(c.gb), dim3(256), 0, c.st, A.hdr, A.codes, A.recs, A.n, B.recs, (const int32_t*)nullptr, B.n,
+                       c.nn_ba, c.d_ba);
     const double* bn = nullptr;
     if (a_normals) {
-        unsigned *keys0 = (unsigned*)(w + l.keys0), *vals0 = (unsigned*)(w + l.vals0);
-        unsigned *keys1 = (unsigned*)(w + l.keys1), *vals1 = (unsigned*)(w + l.vals1);
-        unsigned *seg_lo = (unsigned*)(w + l.seg_lo), *seg_hi = (unsigned*)(w + l.seg_hi);
-        hipLaunchKernelGGL(k_link_keys, dim3(ga), dim3(256), 0, st, (const int32_t*)nn_ab, (long long)na, keys0, vals0);
-        size_t tmp = l.sort_tmp_bytes;                     // LSD radix sort: stable, so every segment stays in increasing i
-        PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w + l.sort_tmp), tmp, (const unsigned*)keys0, keys1, (const unsigned*)vals0,
-                                                         vals1, (int)na, 0, key_bits(nb), st));
-        PCC_CHECK_HIP(hipMemsetAsync(seg_lo, 0, (size_t)nb * 4, st));
-        PCC_CHECK_HIP(hipMemsetAsync(seg_hi, 0, (size_t)nb * 4, st));
-        hipLaunchKernelGGL(k_segments, dim3(ga), dim3(256), 0, st, (const unsigned*)keys1, (long long)na, seg_lo, seg_hi);
-        hipLaunchKernelGGL(k_bnormals, dim3(gb), dim3(256), 0, st, (const unsigned*)seg_lo, (const unsigned*)seg_hi, (const unsigned*)vals1,
-                           a_normals, (const int32_t*)nn_ba, (long long)nb, (double*)(w + l.bn));
-        bn = (const double*)(w + l.bn);
+        hipLaunchKernelGGL(k_link_keys, dim3(c.ga), dim3(256), 0, c.st, (const int32_t*)c.nn_ab, (long long)na, c.keys0, c.vals0);
+        { const int rc = group_pairs(c, na, key_bits(nb), c.ga, AllLinks{(long long)na});
+          if (rc != PCC_OK) return rc; }
+        hipLaunchKernelGGL(k_bnormals<OrphanNearest>, dim3(c.gb), dim3(256), 0, c.st, (const unsigned*)c.seg_lo, (const unsigned*)c.seg_hi,
+                           (const unsigned*)c.vals1, a_normals, OrphanNearest{a_normals, c.nn_ba}, (long long)nb, c.bn);
+        bn = c.bn;
     }
-    const int ta = tally_blocks(na), tb = tally_blocks(nb);
-    hipLaunchKernelGGL(k_tally, dim3(ta), dim3(256), 0, st, A.pts, (long long)na, B.pts, (const int32_t*)nn_ab, (const long long*)d_ab, bn, pab);
-    hipLaunchKernelGGL(k_tally, dim3(tb), dim3(256), 0, st, B.pts, (long long)nb, A.pts, (const int32_t*)nn_ba, (const long long*)d_ba,
-                       a_normals, pba);
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, (const Partial*)pab, ta, (const Partial*)pba, tb, (long long)nb, tally);
+    tally_call(c, LinkTerm{A.pts, B.pts, c.nn_ab, bn}, LinkTerm{B.pts, A.pts, c.nn_ba, a_normals}, tally);
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
 }
@@ -640,7 +509,7 @@ PCC_API size_t pcc_cloud_distortion_ties_workspace_bytes(int64_t na, int64_t nb,
     if (!valid_n(na) || !valid_n(nb)) return 0;
     if (tie_mode == PCC_TIES_PICK) return dist_layout(na, nb).total;
     if (tie_mode != PCC_TIES_MEAN || !valid_n(max_pairs)) return 0;
-    const size_t pick = dist_layout(na, nb).total, mean = tie_layout(na, nb, max_pairs).total;      // without normals mean runs pick's pass
+    const size_t pick = dist_layout(na, nb).total, mean = dist_layout(na, nb, max_pairs).total;      // without normals mean runs pick's pass
     return mean > pick ? mean : pick;
 }
 
@@ -653,53 +522,39 @@ PCC_API int pcc_cloud_distortion_ties(pcc_ctx* ctx, const void* index_a, int64_t
     PCC_REQUIRE(tie_mode == PCC_TIES_PICK || tie_mode == PCC_TIES_MEAN, "pcc_cloud_distortion_ties: tie_mode = %d, must be 0 (pick) or 1 (mean)",
                 (int)tie_mode);
     PCC_CHECK_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
     if (tie_mode == PCC_TIES_PICK || !a_normals) {      // the D1 / H1 slots do not depend on the rule: no pairs without normals
-        PCC_CHECK_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int64_t), st));
+        PCC_CHECK_HIP(hipMemsetAsync(status, 0, 2 * sizeof(int64_t), (hipStream_t)stream));
         return pcc_cloud_distortion(ctx, index_a, na, index_b, nb, a_normals, tally, to_b, to_a, workspace, stream);
     }
     PCC_REQUIRE(valid_n(max_pairs), "pcc_cloud_distortion_ties: max_pairs = %lld outside [1, 2^31)", (long long)max_pairs);
-    const IndexView A = index_view(index_a, na), B = index_view(index_b, nb);
-    const TieLayout l = tie_layout(na, nb, max_pairs);
-    unsigned char* w = (unsigned char*)workspace;
-    int32_t* nn_ab = to_b ? to_b : (int32_t*)(w + l.nn_ab);
-    int32_t* nn_ba = to_a ? to_a : (int32_t*)(w + l.nn_ba);
-    long long *d_ab = (long long*)(w + l.d_ab), *d_ba = (long long*)(w + l.d_ba);
+    const Call c = open_call(index_a, na, index_b, nb, max_pairs, to_b, to_a, workspace, stream);
+    const IndexView &A = c.A, &B = c.B;
+    const TieLayout& l = c.l;
+    unsigned char* w = c.w;
+    hipStream_t st = c.st;
     unsigned long long *cnt = (unsigned long long*)(w + l.cnt), *off = (unsigned long long*)(w + l.off);
-    unsigned *keys0 = (unsigned*)(w + l.keys0), *vals0 = (unsigned*)(w + l.vals0);
-    unsigned *keys1 = (unsigned*)(w + l.keys1), *vals1 = (unsigned*)(w + l.vals1);
-    unsigned *seg_lo = (unsigned*)(w + l.seg_lo), *seg_hi = (unsigned*)(w + l.seg_hi);
-    double *bn = (double*)(w + l.bn), *orphan = (double*)(w + l.orphan);
-    double *terms_a = (double*)(w + l.terms_a), *terms_b = (double*)(w + l.terms_b);
-    Partial *pab = (Partial*)(w + l.pab), *pba = (Partial*)(w + l.pba);
+    double *orphan = (double*)(w + l.orphan), *terms_a = (double*)(w + l.terms_a), *terms_b = (double*)(w + l.terms_b);
     TieCtl* ctl = (TieCtl*)(w + l.ctl);
     const unsigned long long cap = (unsigned long long)max_pairs;
-    const unsigned ga = (unsigned)((na + 255) / 256), gb = (unsigned)((nb + 255) / 256), gp = (unsigned)((cap + 255) / 256);
-    hipLaunchKernelGGL(k_tie_count, dim3(ga), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, A.n, nn_ab, d_ab, cnt);
-    hipLaunchKernelGGL(k_tie_ba, dim3(gb), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, A.pts, a_normals, B.recs, B.n, nn_ba, d_ba,
+    const unsigned gp = (unsigned)((cap + 255) / 256);
+    hipLaunchKernelGGL(k_tie_count, dim3(c.ga), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, A.n, c.nn_ab, c.d_ab, cnt);
+    hipLaunchKernelGGL(k_tie_ba, dim3(c.gb), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, A.pts, a_normals, B.recs, B.n, c.nn_ba, c.d_ba,
                        terms_b, orphan);
     size_t tmp = l.scan_tmp_bytes;
     PCC_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum((void*)(w + l.scan_tmp), tmp, (const unsigned long long*)cnt, off, (int)na, st));
-    hipLaunchKernelGGL(k_total, dim3(1), dim3(1), 0, st, (const unsigned long long*)cnt, (const unsigned long long*)off, (long long)na, cap,
-                       ctl, (long long*)status);
-    hipLaunchKernelGGL(k_tie_emit, dim3(ga), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, A.n, (const long long*)d_ab,
-                       (const unsigned long long*)cnt, (const unsigned long long*)off, (const TieCtl*)ctl, keys0, vals0);
-    hipLaunchKernelGGL(k_tie_pad, dim3(gp), dim3(256), 0, st, (const TieCtl*)ctl, cap, (unsigned)nb, keys0, vals0);
-    tmp = l.sort_tmp_bytes;                                // LSD radix sort: stable, so every segment stays in increasing a
-    PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w + l.sort_tmp), tmp, (const unsigned*)keys0, keys1, (const unsigned*)vals0,
-                                                     vals1, (int)cap, 0, key_bits(nb + 1), st));
-    PCC_CHECK_HIP(hipMemsetAsync(seg_lo, 0, (size_t)nb * 4, st));
-    PCC_CHECK_HIP(hipMemsetAsync(seg_hi, 0, (size_t)nb * 4, st));
-    hipLaunchKernelGGL(k_segments_ties, dim3(gp), dim3(256), 0, st, (const unsigned*)keys1, (const TieCtl*)ctl, (unsigned)nb, seg_lo, seg_hi);
-    hipLaunchKernelGGL(k_bnormals_ties, dim3(gb), dim3(256), 0, st, (const unsigned*)seg_lo, (const unsigned*)seg_hi, (const unsigned*)vals1,
-                       a_normals, (const double*)orphan, (const TieCtl*)ctl, (long long)nb, bn);
-    hipLaunchKernelGGL(k_terms_ab, dim3(ga), dim3(256), 0, st, A.recs, A.n, B.pts, (const double*)bn, (const unsigned*)keys0,
+    hipLaunchKernelGGL(k_pair_total<false>, dim3(1), dim3(1), 0, st, (const unsigned long long*)cnt, (const unsigned long long*)off, (size_t)na,
+                       cap, ctl, (long long*)status);
+    hipLaunchKernelGGL(k_tie_emit, dim3(c.ga), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, A.n, (const long long*)c.d_ab,
+                       (const unsigned long long*)cnt, (const unsigned long long*)off, (const TieCtl*)ctl, c.keys0, c.vals0);
+    hipLaunchKernelGGL(k_pair_pad<unsigned>, dim3(gp), dim3(256), 0, st, (const TieCtl*)ctl, cap, (unsigned)nb, c.keys0, c.vals0);
+    { const int rc = group_pairs(c, (long long)cap, key_bits(nb + 1), gp, TiePairs{ctl});
+      if (rc != PCC_OK) return rc; }
+    hipLaunchKernelGGL(k_bnormals<OrphanMean>, dim3(c.gb), dim3(256), 0, st, (const unsigned*)c.seg_lo, (const unsigned*)c.seg_hi,
+                       (const unsigned*)c.vals1, a_normals, OrphanMean{orphan, ctl}, (long long)nb, c.bn);
+    hipLaunchKernelGGL(k_terms_ab, dim3(c.ga), dim3(256), 0, st, A.recs, A.n, B.pts, (const double*)c.bn, (const unsigned*)c.keys0,
                        (const unsigned long long*)cnt, (const unsigned long long*)off, (const TieCtl*)ctl, terms_a);
-    const int ta = tally_blocks(na), tb = tally_blocks(nb);
-    hipLaunchKernelGGL(k_tally_terms, dim3(ta), dim3(256), 0, st, (long long)na, (const long long*)d_ab, (const double*)terms_a, pab);
-    hipLaunchKernelGGL(k_tally_terms, dim3(tb), dim3(256), 0, st, (long long)nb, (const long long*)d_ba, (const double*)terms_b, pba);
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, (const Partial*)pab, ta, (const Partial*)pba, tb, (long long)nb, tally);
-    hipLaunchKernelGGL(k_overflow, dim3(1), dim3(1), 0, st, (const TieCtl*)ctl, tally);
+    tally_call(c, StoredTerm{terms_a}, StoredTerm{terms_b}, tally);
+    hipLaunchKernelGGL(k_pair_nan, dim3(1), dim3(256), 0, st, (const long long*)status, 2, tally + 3, tally + 7);      // D2_AB, D2_BA; H2_AB, H2_BA
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
 }

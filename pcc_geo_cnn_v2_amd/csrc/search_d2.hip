@@ -14,6 +14,7 @@
 // No float atomics anywhere: the results are bit-reproducible.
 #include <hipcub/hipcub.hpp>
 
+#include "cloud_tally.h"
 #include "search_common.h"
 
 namespace {
@@ -138,17 +139,6 @@ __global__ void __launch_bounds__(256) k_plane_err_ba(const unsigned char* __res
     e[(size_t)b * nvox + i] = val;
 }
 
-// fixed-order block reduction of one double per thread (256 threads)
-__device__ __forceinline__ double block_sum_256(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 // D2_BA[b][t] = sum of e over the voxels with level > t.  One workgroup per (t, block); thread k adds voxels k, k + 256, ... in order
 __global__ void __launch_bounds__(256) k_d2_ba(const unsigned char* __restrict__ lev, const double* __restrict__ e,
                                                const int* __restrict__ tcount, size_t nvox, double* __restrict__ d2_ba) {
@@ -158,7 +148,7 @@ __global__ void __launch_bounds__(256) k_d2_ba(const unsigned char* __restrict__
     double s = 0.0;
     for (size_t i = threadIdx.x; i < nvox; i += 256)
         if (lev[(size_t)b * nvox + i] > t) s += e[(size_t)b * nvox + i];
-    s = block_sum_256(s, sh);
+    s = tree256(s, sh, Sum());
     if (threadIdx.x == 0) d2_ba[(size_t)b * kT + t] = s;
 }
 
@@ -230,7 +220,7 @@ __global__ void __launch_bounds__(256) k_d2_ab(const double* __restrict__ err, c
     if (t >= live_thresholds(tcount, b)) return;
     double s = 0.0;
     for (long long i = block_start[b] + threadIdx.x; i < block_start[b + 1]; i += 256) s += err[(size_t)tl * npts + i];
-    s = block_sum_256(s, sh);
+    s = tree256(s, sh, Sum());
     if (threadIdx.x == 0) d2_ab[(size_t)b * kT + t] = s;
 }
 
@@ -243,25 +233,246 @@ D2Layout d2_layout(int32_t B, size_t nvox, int64_t npts) {
     // thresholds resident at a time: 3 bytes per voxel of index grids, 32 bytes per point of sort / error buffers -> ~1 GiB
     size_t tc = ((size_t)1 << 30) / ((size_t)B * nvox * 3 + (size_t)npts * 32 + 1);
     l.TC = (int)(tc < 4 ? 4 : tc > 64 ? 64 : tc);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
-    l.ftz = o; o += al((size_t)B * l.TC * nvox);
-    l.fty = o; o += al((size_t)B * l.TC * nvox * 2);
-    l.fta = o; o += al((size_t)B * nvox * 4);
-    l.idx = o; o += al((size_t)B * nvox * 4);
-    l.e = o; o += al((size_t)B * nvox * 8);
+    Carver w;
+    l.ftz = w.take((size_t)B * l.TC * nvox);
+    l.fty = w.take((size_t)B * l.TC * nvox * 2);
+    l.fta = w.take((size_t)B * nvox * 4);
+    l.idx = w.take((size_t)B * nvox * 4);
+    l.e = w.take((size_t)B * nvox * 8);
     const size_t pairs = (size_t)l.TC * (size_t)npts;
-    l.keys0 = o; o += al(pairs * 8);
-    l.keys1 = o; o += al(pairs * 8);
-    l.vals0 = o; o += al(pairs * 4);
-    l.vals1 = o; o += al(pairs * 4);
-    l.err = o; o += al(pairs * 8);
-    size_t tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr,
-                                       (unsigned*)nullptr, (int)(pairs ? pairs : 1), 0, 48, (hipStream_t)0);
-    l.sort_tmp_bytes = tmp;
-    l.sort_tmp = o; o += al(tmp + 256);
-    l.total = o + 4096;
+    l.keys0 = w.take(pairs * 8);
+    l.keys1 = w.take(pairs * 8);
+    l.vals0 = w.take(pairs * 4);
+    l.vals1 = w.take(pairs * 4);
+    l.err = w.take(pairs * 8);
+    l.sort_tmp_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, l.sort_tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(pairs ? pairs : 1), 0, 48, (hipStream_t)0);
+    l.sort_tmp = w.take(l.sort_tmp_bytes + 256);
+    l.total = w.o + 4096;
+    return l;
+}
+
+// =====================================================================================================================
+// Tie-averaged D2 statistics (pcc_d12_threshold_stats_ties): DESIGN.md 4.8.1 ("Tie-averaged D2") applied per (block, threshold) with
+// A = the block's rows and B = B_t.  Every equidistant nearest point counts: a decoded voxel takes the mean normal of ALL rows that
+// have it in their tie set, a row's term is the mean plane error over its tie set, a voxel's term the mean over ALL rows at its
+// smallest distance.  Nothing depends on which of several equidistant points an engine meets first, so the sums equal the host
+// restatement (model_opt.host_threshold_stats(ties='mean')) up to float64 rounding.  The D1 outputs come from the same
+// pcc_d1_threshold_stats call as pcc_d12_threshold_stats'.
+//   B -> A (once per block): d^2(v) is the EDT of A the D1 call left in its workspace.  Every voxel of level >= 1 walks the block's
+//        rows (staged through LDS, increasing row) and averages e over the rows at exactly that distance; k_d2_ba's per-threshold
+//        sum over the level sets follows.
+//   A -> B (per chunk of thresholds): z/y pass -> in-plane squared distance g[x'][y][z]; the x pass at a row gives d^2_t(a); the tie
+//        set is then enumerated exactly: every plane x' with (x_a - x')^2 + g[x'][y_a][z_a] == d^2 holds the lattice points of the
+//        circle of the remaining radius^2 around (y_a, z_a), of which those of level > t belong.  Count, exclusive scan, emit
+//        (block, t, voxel) -> pair at offsets that increase with (t, row), stable radix sort by key: every group lists its rows in
+//        increasing order; the head of a group sums their normals in that order and writes e of every member; each row averages e
+//        over its own pairs; k_d2_ab's fixed-order sum per (block, t) follows.
+// The pair count of a chunk is only known on the device (the pair list of cloud_tally.h): past the caller's capacity no pair is
+// written, the chunk's later kernels return early, and k_pair_nan turns every D2 slot into NaN.  status = (largest pair count of a
+// chunk, overflowed).  No float atomics, every sum in a fixed order, vector stores only.
+// B -> A: ebar[b][v] = mean of e(v - a, n[a]) over ALL rows a of block b with |v - a|^2 == edt_a[v], for the voxels of level >= 1
+// (0 elsewhere).  thread <-> voxel; the rows pass through LDS in tiles of 256, in increasing row.
+__global__ void __launch_bounds__(256) k_tie_ba(const unsigned char* __restrict__ lev, const unsigned short* __restrict__ edt_a,
+                                                const int* __restrict__ pts, const double* __restrict__ normals,
+                                                const int* __restrict__ block_start, size_t nvox, int H, int W, double* __restrict__ ebar) {
+    __shared__ int sp[256][3];
+    __shared__ double sn[256][3];
+    const int b = blockIdx.y;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < nvox && lev[(size_t)b * nvox + i] != 0;
+    const int any = __syncthreads_or(live ? 1 : 0);
+    if (!any) {
+        if (i < nvox) ebar[(size_t)b * nvox + i] = 0.0;
+        return;
+    }
+    const auto [x, y, z] = voxel_xyz(i, H, W);
+    const int want = live ? (int)edt_a[(size_t)b * nvox + i] : -1;
+    double acc = 0.0, cnt = 0.0;
+    const int lo = block_start[b], hi = block_start[b + 1];
+    for (int r0 = lo; r0 < hi; r0 += 256) {
+        const int r = r0 + (int)threadIdx.x;
+        if (r < hi) {
+            sp[threadIdx.x][0] = pts[(size_t)r * 3]; sp[threadIdx.x][1] = pts[(size_t)r * 3 + 1]; sp[threadIdx.x][2] = pts[(size_t)r * 3 + 2];
+            sn[threadIdx.x][0] = normals[(size_t)r * 3]; sn[threadIdx.x][1] = normals[(size_t)r * 3 + 1]; sn[threadIdx.x][2] = normals[(size_t)r * 3 + 2];
+        }
+        __syncthreads();
+        const int n = hi - r0 < 256 ? hi - r0 : 256;
+        if (live) {
+            for (int k = 0; k < n; ++k) {
+                const int gx = x - sp[k][0], gy = y - sp[k][1], gz = z - sp[k][2];
+                if (gx * gx + gy * gy + gz * gz == want) { acc += plane_term((double)gx, (double)gy, (double)gz, sn[k][0], sn[k][1], sn[k][2]); cnt += 1.0; }
+            }
+        }
+        __syncthreads();
+    }
+    if (i < nvox) ebar[(size_t)b * nvox + i] = cnt > 0.0 ? acc / cnt : 0.0;
+}
+
+__device__ __forceinline__ int tie_isqrt(int v) {
+    int s = (int)sqrtf((float)v);
+    while (s * s > v) --s;
+    while ((s + 1) * (s + 1) <= v) ++s;
+    return s;
+}
+
+// Every voxel of level > t at squared distance exactly d2 from (xa, ya, za), given that d2 is the smallest such distance: f(row-major
+// voxel index), in a fixed order (x' ascending, then |dy| ascending, -dy before +dy, -dz before +dz).  l = the block's levels.
+template <typename F>
+__device__ __forceinline__ void tie_for_each(const unsigned short* __restrict__ c, const unsigned char* __restrict__ l, int t, int D, int H,
+                                             int W, int xa, int ya, int za, unsigned d2, F f) {
+    const size_t hw = (size_t)H * W;
+    const int reach = tie_isqrt((int)d2);
+    const int x_lo = xa - reach > 0 ? xa - reach : 0, x_hi = xa + reach < D - 1 ? xa + reach : D - 1;
+    for (int xs = x_lo; xs <= x_hi; ++xs) {
+        const int dx = xa - xs, r = (int)d2 - dx * dx;
+        if (r < 0 || (int)c[(size_t)xs * hw] != r) continue;       // (kInf = 65535 > any r <= 3 * 127^2: an empty plane never matches)
+        for (int dy = 0; dy * dy <= r; ++dy) {
+            const int rem = r - dy * dy, dz = tie_isqrt(rem);
+            if (dz * dz != rem) continue;
+            for (int sy = (dy ? -1 : 1); sy <= 1; sy += 2) {
+                const int y = ya + sy * dy;
+                if (y < 0 || y >= H) continue;
+                for (int sz = (dz ? -1 : 1); sz <= 1; sz += 2) {
+                    const int z = za + sz * dz;
+                    if (z < 0 || z >= W) continue;
+                    const size_t v = voxel_index(xs, y, z, H, W);
+                    if ((int)l[v] > t) f((unsigned)v);
+                }
+            }
+        }
+    }
+}
+
+// pass 1: |T_B(a)| and d^2_t(a) of every (slot, row); 0 pairs where t >= tcount[block]
+__global__ void __launch_bounds__(256) k_tie_count(const unsigned short* __restrict__ g, const unsigned char* __restrict__ lev,
+                                                   const int* __restrict__ tcount, int tmax, int t0, const int* __restrict__ pts,
+                                                   const int* __restrict__ block_of, long long npts, int D, int H, int W,
+                                                   unsigned long long* __restrict__ cnt, unsigned* __restrict__ dist) {
+    const int tl = blockIdx.y, t = t0 + tl;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    const int b = block_of[i];
+    unsigned long long n = 0;
+    unsigned d2 = 0;
+    const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
+    const bool inside = xa >= 0 && xa < D && ya >= 0 && ya < H && za >= 0 && za < W;      // (k_occupancy's rule: a row outside the grid takes no part)
+    if (inside && t < live_thresholds(tcount, b)) {
+        const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
+        const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
+        d2 = edt_x_pass(c, hw, xa, D);
+        tie_for_each(c, lev + (size_t)b * nvox, t, D, H, W, xa, ya, za, d2, [&](unsigned) { ++n; });
+    }
+    cnt[(size_t)tl * npts + i] = n;
+    dist[(size_t)tl * npts + i] = d2;
+}
+
+// pass 2: the pairs of (slot, row) at [off, off + cnt): key (block, slot, voxel), value = the pair's own position; prow = its row
+__global__ void __launch_bounds__(256) k_tie_emit(const unsigned short* __restrict__ g, const unsigned char* __restrict__ lev,
+                                                  const int* __restrict__ tcount, int tmax, int t0, const int* __restrict__ pts,
+                                                  const int* __restrict__ block_of, long long npts, int D, int H, int W,
+                                                  const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off,
+                                                  const unsigned* __restrict__ dist, const TieCtl* __restrict__ ctl, unsigned long long cap,
+                                                  unsigned long long* __restrict__ keys, unsigned* __restrict__ vals, unsigned* __restrict__ prow) {
+    if (ctl->overflow) return;
+    const int tl = blockIdx.y, t = t0 + tl;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npts) return;
+    const size_t slot = (size_t)tl * npts + i;
+    const unsigned long long n = cnt[slot];
+    if (n == 0) return;
+    const int b = block_of[i];
+    const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
+    const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
+    const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
+    unsigned long long p = off[slot];
+    const unsigned long long end = p + n;
+    const unsigned long long head = search_key(b, tl, 0);      // the voxel field is or-ed in per pair
+    tie_for_each(c, lev + (size_t)b * nvox, t, D, H, W, xa, ya, za, dist[slot], [&](unsigned v) {
+        if (p < end && p < cap) { keys[p] = head | v; vals[p] = (unsigned)p; prow[p] = (unsigned)i; }
+        ++p;
+    });
+}
+
+// sorted groups (block, slot, voxel): the head sums the normals of the group's rows in increasing row (the stable sort kept the
+// emit order) and writes e(a - voxel, mean normal) of every member at the pair's own position
+__global__ void __launch_bounds__(256) k_tie_groups(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                    const unsigned* __restrict__ prow, const TieCtl* __restrict__ ctl, unsigned long long cap,
+                                                    const int* __restrict__ pts, const double* __restrict__ normals, int H, int W,
+                                                    double* __restrict__ perr) {
+    if (ctl->overflow) return;
+    const unsigned long long n = ctl->pairs < cap ? ctl->pairs : cap;
+    const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const unsigned long long key = keys[j];
+    if (j > 0 && keys[j - 1] == key) return;            // not a group head
+    double sx = 0.0, sy = 0.0, sz = 0.0, votes = 0.0;
+    unsigned long long end = j;
+    for (; end < n && keys[end] == key; ++end) {
+        const size_t r = prow[vals[end]];
+        sx += normals[r * 3]; sy += normals[r * 3 + 1]; sz += normals[r * 3 + 2]; votes += 1.0;
+    }
+    sx /= votes; sy /= votes; sz /= votes;
+    const auto [xs, ys, zs] = voxel_xyz(search_key_decode(key).voxel, H, W);
+    for (unsigned long long m = j; m < end; ++m) {
+        const unsigned p = vals[m];
+        const size_t r = prow[p];
+        perr[p] = plane_term((double)(pts[r * 3] - xs), (double)(pts[r * 3 + 1] - ys), (double)(pts[r * 3 + 2] - zs), sx, sy, sz);
+    }
+}
+
+// err[slot][row] = mean of perr over the row's own pairs (emit order)
+__global__ void __launch_bounds__(256) k_tie_row_mean(const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off,
+                                                      const double* __restrict__ perr, const TieCtl* __restrict__ ctl, size_t n,
+                                                      double* __restrict__ err) {
+    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    double v = 0.0;
+    if (!ctl->overflow && cnt[s]) {
+        const unsigned long long o = off[s], c = cnt[s];
+        double acc = 0.0;
+        for (unsigned long long k = 0; k < c; ++k) acc += perr[o + k];
+        v = acc / (double)c;
+    }
+    err[s] = v;
+}
+
+struct TieLayout {
+    size_t g0, g1, ebar, cnt, off, dist, err, ctl, keys0, keys1, vals0, vals1, prow, perr, scan_tmp, scan_tmp_bytes, sort_tmp, sort_tmp_bytes, total;
+    int TC;
+};
+int tie_chunk(int32_t B, size_t nvox) {
+    const int tc = chunk_thresholds(B, nvox);
+    return tc > 64 ? 64 : tc;
+}
+TieLayout tie_layout(int32_t B, size_t nvox, int64_t npts, int64_t max_pairs) {
+    TieLayout l;
+    l.TC = tie_chunk(B, nvox);
+    const size_t slots = (size_t)l.TC * (size_t)npts, cap = (size_t)max_pairs;
+    Carver w;
+    l.g0 = w.take((size_t)B * l.TC * nvox * 2);
+    l.g1 = w.take((size_t)B * l.TC * nvox * 2);
+    l.ebar = w.take((size_t)B * nvox * 8);
+    l.cnt = w.take(slots * 8);
+    l.off = w.take(slots * 8);
+    l.dist = w.take(slots * 4);
+    l.err = w.take(slots * 8);
+    l.ctl = w.take(sizeof(TieCtl));
+    l.keys0 = w.take(cap * 8);
+    l.keys1 = w.take(cap * 8);
+    l.vals0 = w.take(cap * 4);
+    l.vals1 = w.take(cap * 4);
+    l.prow = w.take(cap * 4);
+    l.perr = w.take(cap * 8);
+    l.scan_tmp_bytes = l.sort_tmp_bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, l.scan_tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                           (int)(slots ? slots : 1), (hipStream_t)0);
+    l.scan_tmp = w.take(l.scan_tmp_bytes + 256);
+    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, l.sort_tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(cap ? cap : 1), 0, 48, (hipStream_t)0);
+    l.sort_tmp = w.take(l.sort_tmp_bytes + 256);
+    l.total = w.o + 4096;
     return l;
 }
 
@@ -332,277 +543,6 @@ PCC_API int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B,
     return PCC_OK;
 }
 
-
-// =====================================================================================================================
-// Tie-averaged D2 statistics (pcc_d12_threshold_stats_ties): DESIGN.md 4.8.1 ("Tie-averaged D2") applied per (block, threshold) with
-// A = the block's rows and B = B_t.  Every equidistant nearest point counts: a decoded voxel takes the mean normal of ALL rows that
-// have it in their tie set, a row's term is the mean plane error over its tie set, a voxel's term the mean over ALL rows at its
-// smallest distance.  Nothing depends on which of several equidistant points an engine meets first, so the sums equal the host
-// restatement (model_opt.host_threshold_stats(ties='mean')) up to float64 rounding.  pcc_d12_threshold_stats and its kernels above
-// are untouched; the D1 outputs come from the same pcc_d1_threshold_stats call.
-//   B -> A (once per block): d^2(v) is the EDT of A the D1 call left in its workspace.  Every voxel of level >= 1 walks the block's
-//        rows (staged through LDS, increasing row) and averages e over the rows at exactly that distance; k_d2_ba's per-threshold
-//        sum over the level sets follows.
-//   A -> B (per chunk of thresholds): z/y pass -> in-plane squared distance g[x'][y][z]; the x pass at a row gives d^2_t(a); the tie
-//        set is then enumerated exactly: every plane x' with (x_a - x')^2 + g[x'][y_a][z_a] == d^2 holds the lattice points of the
-//        circle of the remaining radius^2 around (y_a, z_a), of which those of level > t belong.  Count, exclusive scan, emit
-//        (block, t, voxel) -> pair at offsets that increase with (t, row), stable radix sort by key: every group lists its rows in
-//        increasing order; the head of a group sums their normals in that order and writes e of every member; each row averages e
-//        over its own pairs; k_d2_ab's fixed-order sum per (block, t) follows.
-// The pair count of a chunk is only known on the device: k_tie_total compares it with the caller's capacity, past it no pair is
-// written, the chunk's later kernels return early, and k_tie_finish turns every D2 slot into NaN.  status = (largest pair count of a
-// chunk, overflowed).  No float atomics, every sum in a fixed order, vector stores only.
-namespace {
-
-struct TieCtl {                       // written by k_tie_total, once per chunk
-    unsigned long long pairs;         // pairs of this chunk
-    int overflow;                     // pairs > capacity: nothing below k_tie_total touches the pair arrays in this chunk
-};
-
-// ((gx*nx + gy*ny) + gz*nz)^2, every operation rounded: pc_metric.plane_terms
-__device__ __forceinline__ double tie_plane_term(int gx, int gy, int gz, double nx, double ny, double nz) {
-#pragma clang fp contract(off)
-    const double p = ((double)gx * nx + (double)gy * ny) + (double)gz * nz;
-    return p * p;
-}
-
-// B -> A: ebar[b][v] = mean of e(v - a, n[a]) over ALL rows a of block b with |v - a|^2 == edt_a[v], for the voxels of level >= 1
-// (0 elsewhere).  thread <-> voxel; the rows pass through LDS in tiles of 256, in increasing row.
-__global__ void __launch_bounds__(256) k_tie_ba(const unsigned char* __restrict__ lev, const unsigned short* __restrict__ edt_a,
-                                                const int* __restrict__ pts, const double* __restrict__ normals,
-                                                const int* __restrict__ block_start, size_t nvox, int H, int W, double* __restrict__ ebar) {
-    __shared__ int sp[256][3];
-    __shared__ double sn[256][3];
-    const int b = blockIdx.y;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = i < nvox && lev[(size_t)b * nvox + i] != 0;
-    const int any = __syncthreads_or(live ? 1 : 0);
-    if (!any) {
-        if (i < nvox) ebar[(size_t)b * nvox + i] = 0.0;
-        return;
-    }
-    const auto [x, y, z] = voxel_xyz(i, H, W);
-    const int want = live ? (int)edt_a[(size_t)b * nvox + i] : -1;
-    double acc = 0.0, cnt = 0.0;
-    const int lo = block_start[b], hi = block_start[b + 1];
-    for (int r0 = lo; r0 < hi; r0 += 256) {
-        const int r = r0 + (int)threadIdx.x;
-        if (r < hi) {
-            sp[threadIdx.x][0] = pts[(size_t)r * 3]; sp[threadIdx.x][1] = pts[(size_t)r * 3 + 1]; sp[threadIdx.x][2] = pts[(size_t)r * 3 + 2];
-            sn[threadIdx.x][0] = normals[(size_t)r * 3]; sn[threadIdx.x][1] = normals[(size_t)r * 3 + 1]; sn[threadIdx.x][2] = normals[(size_t)r * 3 + 2];
-        }
-        __syncthreads();
-        const int n = hi - r0 < 256 ? hi - r0 : 256;
-        if (live) {
-            for (int k = 0; k < n; ++k) {
-                const int gx = x - sp[k][0], gy = y - sp[k][1], gz = z - sp[k][2];
-                if (gx * gx + gy * gy + gz * gz == want) { acc += tie_plane_term(gx, gy, gz, sn[k][0], sn[k][1], sn[k][2]); cnt += 1.0; }
-            }
-        }
-        __syncthreads();
-    }
-    if (i < nvox) ebar[(size_t)b * nvox + i] = cnt > 0.0 ? acc / cnt : 0.0;
-}
-
-__device__ __forceinline__ int tie_isqrt(int v) {
-    int s = (int)sqrtf((float)v);
-    while (s * s > v) --s;
-    while ((s + 1) * (s + 1) <= v) ++s;
-    return s;
-}
-
-// Every voxel of level > t at squared distance exactly d2 from (xa, ya, za), given that d2 is the smallest such distance: f(row-major
-// voxel index), in a fixed order (x' ascending, then |dy| ascending, -dy before +dy, -dz before +dz).  l = the block's levels.
-template <typename F>
-__device__ __forceinline__ void tie_for_each(const unsigned short* __restrict__ c, const unsigned char* __restrict__ l, int t, int D, int H,
-                                             int W, int xa, int ya, int za, unsigned d2, F f) {
-    const size_t hw = (size_t)H * W;
-    const int reach = tie_isqrt((int)d2);
-    const int x_lo = xa - reach > 0 ? xa - reach : 0, x_hi = xa + reach < D - 1 ? xa + reach : D - 1;
-    for (int xs = x_lo; xs <= x_hi; ++xs) {
-        const int dx = xa - xs, r = (int)d2 - dx * dx;
-        if (r < 0 || (int)c[(size_t)xs * hw] != r) continue;       // (kInf = 65535 > any r <= 3 * 127^2: an empty plane never matches)
-        for (int dy = 0; dy * dy <= r; ++dy) {
-            const int rem = r - dy * dy, dz = tie_isqrt(rem);
-            if (dz * dz != rem) continue;
-            for (int sy = (dy ? -1 : 1); sy <= 1; sy += 2) {
-                const int y = ya + sy * dy;
-                if (y < 0 || y >= H) continue;
-                for (int sz = (dz ? -1 : 1); sz <= 1; sz += 2) {
-                    const int z = za + sz * dz;
-                    if (z < 0 || z >= W) continue;
-                    const size_t v = voxel_index(xs, y, z, H, W);
-                    if ((int)l[v] > t) f((unsigned)v);
-                }
-            }
-        }
-    }
-}
-
-// pass 1: |T_B(a)| and d^2_t(a) of every (slot, row); 0 pairs where t >= tcount[block]
-__global__ void __launch_bounds__(256) k_tie_count(const unsigned short* __restrict__ g, const unsigned char* __restrict__ lev,
-                                                   const int* __restrict__ tcount, int tmax, int t0, const int* __restrict__ pts,
-                                                   const int* __restrict__ block_of, long long npts, int D, int H, int W,
-                                                   unsigned long long* __restrict__ cnt, unsigned* __restrict__ dist) {
-    const int tl = blockIdx.y, t = t0 + tl;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npts) return;
-    const int b = block_of[i];
-    unsigned long long n = 0;
-    unsigned d2 = 0;
-    const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
-    const bool inside = xa >= 0 && xa < D && ya >= 0 && ya < H && za >= 0 && za < W;      // (k_occupancy's rule: a row outside the grid takes no part)
-    if (inside && t < live_thresholds(tcount, b)) {
-        const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
-        const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
-        d2 = edt_x_pass(c, hw, xa, D);
-        tie_for_each(c, lev + (size_t)b * nvox, t, D, H, W, xa, ya, za, d2, [&](unsigned) { ++n; });
-    }
-    cnt[(size_t)tl * npts + i] = n;
-    dist[(size_t)tl * npts + i] = d2;
-}
-
-__global__ void k_tie_total(const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off, size_t n,
-                            unsigned long long cap, TieCtl* __restrict__ ctl, long long* __restrict__ status) {
-    const unsigned long long pairs = off[n - 1] + cnt[n - 1];
-    ctl->pairs = pairs;
-    ctl->overflow = pairs > cap;
-    if ((long long)pairs > status[0]) status[0] = (long long)pairs;
-    if (pairs > cap) status[1] = 1;
-}
-
-// pass 2: the pairs of (slot, row) at [off, off + cnt): key (block, slot, voxel), value = the pair's own position; prow = its row
-__global__ void __launch_bounds__(256) k_tie_emit(const unsigned short* __restrict__ g, const unsigned char* __restrict__ lev,
-                                                  const int* __restrict__ tcount, int tmax, int t0, const int* __restrict__ pts,
-                                                  const int* __restrict__ block_of, long long npts, int D, int H, int W,
-                                                  const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off,
-                                                  const unsigned* __restrict__ dist, const TieCtl* __restrict__ ctl, unsigned long long cap,
-                                                  unsigned long long* __restrict__ keys, unsigned* __restrict__ vals, unsigned* __restrict__ prow) {
-    if (ctl->overflow) return;
-    const int tl = blockIdx.y, t = t0 + tl;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npts) return;
-    const size_t slot = (size_t)tl * npts + i;
-    const unsigned long long n = cnt[slot];
-    if (n == 0) return;
-    const int b = block_of[i];
-    const int xa = pts[i * 3], ya = pts[i * 3 + 1], za = pts[i * 3 + 2];
-    const size_t hw = (size_t)H * W, nvox = (size_t)D * hw;
-    const unsigned short* c = g + ((size_t)b * tmax + tl) * nvox + (size_t)ya * W + za;
-    unsigned long long p = off[slot];
-    const unsigned long long end = p + n;
-    const unsigned long long head = search_key(b, tl, 0);      // the voxel field is or-ed in per pair
-    tie_for_each(c, lev + (size_t)b * nvox, t, D, H, W, xa, ya, za, dist[slot], [&](unsigned v) {
-        if (p < end && p < cap) { keys[p] = head | v; vals[p] = (unsigned)p; prow[p] = (unsigned)i; }
-        ++p;
-    });
-}
-
-// the tail of the capacity sorts behind every pair
-__global__ void __launch_bounds__(256) k_tie_pad(const TieCtl* __restrict__ ctl, unsigned long long cap, unsigned long long* __restrict__ keys,
-                                                 unsigned* __restrict__ vals) {
-    if (ctl->overflow) return;
-    for (unsigned long long p = ctl->pairs + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; p < cap;
-         p += (unsigned long long)gridDim.x * blockDim.x) {
-        keys[p] = kPadKey;
-        vals[p] = (unsigned)p;
-    }
-}
-
-// sorted groups (block, slot, voxel): the head sums the normals of the group's rows in increasing row (the stable sort kept the
-// emit order) and writes e(a - voxel, mean normal) of every member at the pair's own position
-__global__ void __launch_bounds__(256) k_tie_groups(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
-                                                    const unsigned* __restrict__ prow, const TieCtl* __restrict__ ctl, unsigned long long cap,
-                                                    const int* __restrict__ pts, const double* __restrict__ normals, int H, int W,
-                                                    double* __restrict__ perr) {
-    if (ctl->overflow) return;
-    const unsigned long long n = ctl->pairs < cap ? ctl->pairs : cap;
-    const unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const unsigned long long key = keys[j];
-    if (j > 0 && keys[j - 1] == key) return;            // not a group head
-    double sx = 0.0, sy = 0.0, sz = 0.0, votes = 0.0;
-    unsigned long long end = j;
-    for (; end < n && keys[end] == key; ++end) {
-        const size_t r = prow[vals[end]];
-        sx += normals[r * 3]; sy += normals[r * 3 + 1]; sz += normals[r * 3 + 2]; votes += 1.0;
-    }
-    sx /= votes; sy /= votes; sz /= votes;
-    const auto [xs, ys, zs] = voxel_xyz(search_key_decode(key).voxel, H, W);
-    for (unsigned long long m = j; m < end; ++m) {
-        const unsigned p = vals[m];
-        const size_t r = prow[p];
-        perr[p] = tie_plane_term(pts[r * 3] - xs, pts[r * 3 + 1] - ys, pts[r * 3 + 2] - zs, sx, sy, sz);
-    }
-}
-
-// err[slot][row] = mean of perr over the row's own pairs (emit order)
-__global__ void __launch_bounds__(256) k_tie_row_mean(const unsigned long long* __restrict__ cnt, const unsigned long long* __restrict__ off,
-                                                      const double* __restrict__ perr, const TieCtl* __restrict__ ctl, size_t n,
-                                                      double* __restrict__ err) {
-    const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    double v = 0.0;
-    if (!ctl->overflow && cnt[s]) {
-        const unsigned long long o = off[s], c = cnt[s];
-        double acc = 0.0;
-        for (unsigned long long k = 0; k < c; ++k) acc += perr[o + k];
-        v = acc / (double)c;
-    }
-    err[s] = v;
-}
-
-// a chunk met more pairs than the capacity: every D2 slot becomes NaN (the D1 outputs stay valid)
-__global__ void __launch_bounds__(256) k_tie_finish(const long long* __restrict__ status, int n, double* __restrict__ d2_ab, double* __restrict__ d2_ba) {
-    if (!status[1]) return;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { d2_ab[i] = __longlong_as_double(0x7FF8000000000000ll); d2_ba[i] = __longlong_as_double(0x7FF8000000000000ll); }
-}
-
-struct TieLayout {
-    size_t g0, g1, ebar, cnt, off, dist, err, ctl, keys0, keys1, vals0, vals1, prow, perr, scan_tmp, scan_tmp_bytes, sort_tmp, sort_tmp_bytes, total;
-    int TC;
-};
-int tie_chunk(int32_t B, size_t nvox) {
-    const int tc = chunk_thresholds(B, nvox);
-    return tc > 64 ? 64 : tc;
-}
-TieLayout tie_layout(int32_t B, size_t nvox, int64_t npts, int64_t max_pairs) {
-    TieLayout l;
-    l.TC = tie_chunk(B, nvox);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t slots = (size_t)l.TC * (size_t)npts, cap = (size_t)max_pairs;
-    size_t o = 0;
-    l.g0 = o; o += al((size_t)B * l.TC * nvox * 2);
-    l.g1 = o; o += al((size_t)B * l.TC * nvox * 2);
-    l.ebar = o; o += al((size_t)B * nvox * 8);
-    l.cnt = o; o += al(slots * 8);
-    l.off = o; o += al(slots * 8);
-    l.dist = o; o += al(slots * 4);
-    l.err = o; o += al(slots * 8);
-    l.ctl = o; o += al(sizeof(TieCtl));
-    l.keys0 = o; o += al(cap * 8);
-    l.keys1 = o; o += al(cap * 8);
-    l.vals0 = o; o += al(cap * 4);
-    l.vals1 = o; o += al(cap * 4);
-    l.prow = o; o += al(cap * 4);
-    l.perr = o; o += al(cap * 8);
-    size_t tmp = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                           (int)(slots ? slots : 1), (hipStream_t)0);
-    l.scan_tmp_bytes = tmp;
-    l.scan_tmp = o; o += al(tmp + 256);
-    tmp = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs((void*)nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                             (const unsigned*)nullptr, (unsigned*)nullptr, (int)(cap ? cap : 1), 0, 48, (hipStream_t)0);
-    l.sort_tmp_bytes = tmp;
-    l.sort_tmp = o; o += al(tmp + 256);
-    l.total = o + 4096;
-    return l;
-}
-
-}  // namespace
-
 PCC_API int32_t pcc_d12_search_ties_chunk(int32_t B, int32_t D, int32_t H, int32_t W) {
     return tie_chunk(B, (size_t)D * H * W);
 }
@@ -658,10 +598,11 @@ PCC_API int pcc_d12_threshold_stats_ties(pcc_ctx* ctx, const float* x_hat, int32
                            cnt, dist);
         size_t tmp = l.scan_tmp_bytes;
         PCC_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum((void*)(w2 + l.scan_tmp), tmp, (const unsigned long long*)cnt, off, (int)slots, st));
-        hipLaunchKernelGGL(k_tie_total, dim3(1), dim3(1), 0, st, cnt, off, slots, cap, ctl, (long long*)status);
+        hipLaunchKernelGGL(k_pair_total<true>, dim3(1), dim3(1), 0, st, (const unsigned long long*)cnt, (const unsigned long long*)off, slots, cap, ctl,
+                           (long long*)status);
         hipLaunchKernelGGL(k_tie_emit, dim3(pblocks, nt), dim3(256), 0, st, g1, lev, tcount, l.TC, t0, pts, block_of, (long long)npts, D, H, W,
                            cnt, off, dist, ctl, cap, keys0, vals0, prow);
-        hipLaunchKernelGGL(k_tie_pad, dim3(256), dim3(256), 0, st, ctl, cap, keys0, vals0);
+        hipLaunchKernelGGL(k_pair_pad<unsigned long long>, dim3(256), dim3(256), 0, st, (const TieCtl*)ctl, cap, kPadKey, keys0, vals0);
         tmp = l.sort_tmp_bytes;
         PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w2 + l.sort_tmp), tmp, keys0, keys1, vals0, vals1, (int)cap, 0, 48, st));
         hipLaunchKernelGGL(k_tie_groups, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, keys1, vals1, prow, ctl, cap, pts, normals, H, W,
@@ -669,7 +610,7 @@ PCC_API int pcc_d12_threshold_stats_ties(pcc_ctx* ctx, const float* x_hat, int32
         hipLaunchKernelGGL(k_tie_row_mean, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, cnt, off, perr, ctl, slots, err);
         hipLaunchKernelGGL(k_d2_ab, dim3(nt, B), dim3(256), 0, st, err, block_start, tcount, t0, (long long)npts, d2_ab);
     }
-    hipLaunchKernelGGL(k_tie_finish, dim3((B * kT + 255) / 256), dim3(256), 0, st, (const long long*)status, B * kT, d2_ab, d2_ba);
+    hipLaunchKernelGGL(k_pair_nan, dim3((B * kT + 255) / 256), dim3(256), 0, st, (const long long*)status, B * kT, d2_ab, d2_ba);
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
 }
