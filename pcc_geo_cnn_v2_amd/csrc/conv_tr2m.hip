@@ -17,6 +17,8 @@
 //     odd set is read out (AccVGPR -> ReLU -> store) under taps 0..7 and the old even_cur under taps 0..15, before taps 9 /
 //     18 re-open those registers (first tap of a class starts from the bias: srcC = bias, no init pass);
 //   * everything that selects code is a compile-time constant (plane parity, first micro-step): no branches in the stream.
+// The grid, the launch, the epilogue schedule and the drain are shared with the other three variants: tr2m_common.h, which also says
+// which parts of the march must stay written out here.
 // Fixed summation order per output (cin group -> tap -> k-slice, one fp32 chain): bit-deterministic, batch invariant.
 #include <cstdlib>
 
@@ -27,8 +29,7 @@ namespace pcctr2m {
 using namespace pcck;
 using namespace pcctr2;
 
-constexpr int ITEMS = 5;                                // 1 KB chunks per wave (4 x 5 = 20 >= 1156 / 64)
-constexpr int TILE_BYTES = 4 * ITEMS * 1024;            // 20480
+constexpr int TILE_BYTES = 4 * ITEMS * 1024;            // 20480: ITEMS 1 KB chunks per wave (4 x 5 = 20 >= 1156 / 64)
 constexpr int W_BASE = 2 * TILE_BYTES;                  // ring of two tiles, then the weights
 constexpr int ROWB = LXY * 64;                          // bytes per tile row
 
@@ -37,9 +38,7 @@ struct Tr2mArgs {
     const float* w;      // conv_tr2g order: [cin group][27 taps, class-major][cout tile][64 lanes][4]
     const float* bias;
     float* out;
-    int N, D, H, W;      // input dims (output = 2x)
-    int nty, ntx, zsplit, zlen, nct;
-    int flags, ocs, oco;
+    Tr2mGrid g;
 };
 
 template <int NG, bool RELU>
@@ -50,19 +49,19 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
     auto ldsr = [&](unsigned off) -> f32x4 { return *reinterpret_cast<const f32x4*>(smem + off); };
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
-    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const Tr2mTile tile = tr2m_tile(a.g, nwg);
     const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
-    const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
+    const int nsteps = a.g.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 16;
-    const size_t HW = (size_t)a.H * a.W;
+    const size_t HW = (size_t)a.g.H * a.g.W;
     const unsigned HWI = (unsigned)(HW * CIN * 4);
-    const float* in_n = a.in + (size_t)n * a.D * HW * CIN;
+    const float* in_n = a.in + (size_t)n * a.g.D * HW * CIN;
 
     // ---- weights of this cout tile -> LDS (resident): NG x 27 fragments of 1 KB, fragment (g, sq) at W_BASE + (g * 27 + sq) KB
     {
-        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, (unsigned)(NG * 27 * a.nct) * 1024u);
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, (unsigned)(NG * 27 * a.g.nct) * 1024u);
         for (int p = wave; p < NG * 27; p += 4)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + W_BASE + p * 1024), 16, lane * 16, (p * a.nct + ct) * 1024, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + W_BASE + p * 1024), 16, lane * 16, (p * a.g.nct + ct) * 1024, 0, 0);
     }
     // ---- tile staging: global -> LDS directly.  LDS slot s = 4 * voxel + (channel quad ^ 2 * bit 2 of lx): the swizzle is
     //      applied on the global side (lane L of chunk c fetches what belongs into slot 64 c + L); OOB lanes write zeros.
@@ -73,12 +72,12 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
         const int u = slot >> 2, ly = u / LXY, lx = u - ly * LXY;
         const int q = (slot & 3) ^ (((lx >> 2) & 1) << 1);
         const int y = Y0 - 1 + ly, x = X0 - 1 + lx;
-        const bool ok = slot < TILE_SLOTS && y >= 0 && y < a.H && x >= 0 && x < a.W;
-        rel[it] = ok ? (unsigned)(((y * a.W + x) * CIN + q * 4) * 4) : kOOB;
+        const bool ok = slot < TILE_SLOTS && y >= 0 && y < a.g.H && x >= 0 && x < a.g.W;
+        rel[it] = ok ? (unsigned)(((y * a.g.W + x) * CIN + q * 4) * 4) : kOOB;
     }
     // tile of (step sp, cin group cg): `addr` = address of channel 16 cg of input plane zb - 1 + sp (kept incrementally)
     auto stage_tile = [&](unsigned ring_off, int sp, int cg, unsigned long long addr) __attribute__((always_inline)) {
-        const bool ok = (unsigned)(zb - 1 + sp) < (unsigned)a.D && sp < nsteps;
+        const bool ok = (unsigned)(zb - 1 + sp) < (unsigned)a.g.D && sp < nsteps;
         const __amdgpu_buffer_rsrc_t rp = make_rsrc((const void*)(ok ? addr : (unsigned long long)in_n), ok ? HWI - (unsigned)(64 * cg) : 0u);
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it)
@@ -96,12 +95,12 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
     unsigned wa = (unsigned)(W_BASE + lane * 16);      // + cin group * 27 KB (per micro-step), + tap * 1 KB (immediate)
 
     // ---- epilogue addressing: lane writes couts 4 cq .. 4 cq + 3 (of this cout tile) of output voxel (2 z + pz, 2 y + py, 2 x + px)
-    const int OH = 2 * a.H, OW = 2 * a.W;
-    const unsigned ob = (unsigned)((((2 * (Y0 + 4 * wave)) * OW + 2 * (X0 + v)) * a.ocs + a.oco + 16 * ct + 4 * cq) * 4);
-    const unsigned PLANE_O = (unsigned)((size_t)OH * OW * a.ocs * 4);          // bytes per output plane (launcher: two planes < 2^31)
-    float* out_n = a.out + (size_t)n * (2 * a.D) * OH * OW * a.ocs;
+    const int OH = 2 * a.g.H, OW = 2 * a.g.W;
+    const unsigned ob = (unsigned)((((2 * (Y0 + 4 * wave)) * OW + 2 * (X0 + v)) * a.g.ocs + a.g.oco + 16 * ct + 4 * cq) * 4);
+    const unsigned PLANE_O = (unsigned)((size_t)OH * OW * a.g.ocs * 4);          // bytes per output plane (launcher: two planes < 2^31)
+    float* out_n = a.out + (size_t)n * (2 * a.g.D) * OH * OW * a.g.ocs;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 bias_l = (a.flags & PCC_CONV_BIAS) ? *reinterpret_cast<const f32x4*>(a.bias + 16 * ct + 4 * cq) : zero4;
+    const f32x4 bias_l = (a.g.flags & PCC_CONV_BIAS) ? *reinterpret_cast<const f32x4*>(a.bias + 16 * ct + 4 * cq) : zero4;
 
     // ---- prologue
     unsigned long long tile_pl = (unsigned long long)in_n + (unsigned long long)(long long)(zb - 1) * HWI;     // tile of micro-step 0
@@ -137,7 +136,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
         f32x4 o = acc_read(pz ? O[cls][i] : E[PH ^ 1][cls][i]);
         if (RELU) o = __builtin_elementwise_maximum(o, zero4);
         keep = o;
-        const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.ocs * 4);
+        const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.g.ocs * 4);
         buf_store4(rout, keep, ob, soff);
     };
 
@@ -167,17 +166,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
                     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[t & 1][j], b[T.dyi][T.dxi][i][j], (open && j == 0) ? bias_l : acc, 0, 0, 0);
                 }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (FIRST && !HALO) {
-                if constexpr (t < 8) {
-                    finish(ph_tag, std::integral_constant<int, 2 * t>{}, rout, ost[t & 1][0]);
-                    finish(ph_tag, std::integral_constant<int, 2 * t + 1>{}, rout, ost[t & 1][1]);
-                }
-                if constexpr (t < 16) finish(ph_tag, std::integral_constant<int, 16 + t>{}, rout, ost[t & 1][2]);
-                if constexpr (t >= 1 && t < 17) {     // store data registers stay untouched for one more tap (late read, see conv_wino.hip)
-                    asm volatile("" ::"v"(ost[(t - 1) & 1][2]));
-                    if constexpr (t < 9) { asm volatile("" ::"v"(ost[(t - 1) & 1][0])); asm volatile("" ::"v"(ost[(t - 1) & 1][1])); }
-                }
-            }
+            if constexpr (FIRST && !HALO) tr2m_finish_under_tap<t>(finish, ph_tag, rout, ost);
             __builtin_amdgcn_sched_barrier(0);
         });
         // the next tile must have landed before the barrier publishes it; the only younger memory operations are the 32 stores
@@ -204,23 +193,19 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_kernel(Tr2mArgs a, int nwg) {
 #pragma unroll
         for (int k = 1; k < NG; ++k) micro(ph_tag, std::false_type{}, halo_tag);
     };
+    // the plane loop is written out in every variant: as a shared function template it compiles to other code (note in tr2m_common.h)
     plane(std::integral_constant<int, 0>{}, std::true_type{});          // step 0: the halo plane
 #pragma nounroll
     for (int sp = 1; sp < nsteps; sp += 2) {
         plane(std::integral_constant<int, 1>{}, std::false_type{});
         if (sp + 1 < nsteps) plane(std::integral_constant<int, 0>{}, std::false_type{});
     }
-    // ---- drain: the planes finished by the last input plane (s == nsteps here; its parity decides which even set is complete)
+    // ---- drain: the planes finished by the last input plane (s == nsteps here; tr2m_common.h on the parity, the branch and keep[])
     {
         const __amdgpu_buffer_rsrc_t rout = make_rsrc((const void*)out_pl, nsteps >= 2 ? 2u * PLANE_O : 0u);
         f32x4 keep[32];
-        if (nsteps & 1) {      // last plane had PH = 0: its even_cur is E[0] = "E[PH ^ 1]" of a PH = 1 epilogue
-            static_for(std::make_integer_sequence<int, 32>{}, [&](auto e_tag) __attribute__((always_inline)) {
-                finish(std::integral_constant<int, 1>{}, e_tag, rout, keep[decltype(e_tag)::value]); });
-        } else {
-            static_for(std::make_integer_sequence<int, 32>{}, [&](auto e_tag) __attribute__((always_inline)) {
-                finish(std::integral_constant<int, 0>{}, e_tag, rout, keep[decltype(e_tag)::value]); });
-        }
+        if (nsteps & 1) tr2m_drain<1>(finish, rout, keep);
+        else tr2m_drain<0>(finish, rout, keep);
 #pragma unroll
         for (int e = 0; e < 32; ++e) asm volatile("" ::"v"(keep[e]));
     }
@@ -242,21 +227,10 @@ int pcc_conv_tr2m(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const f
     PCC_REQUIRE(pcc_tr2m_eligible(d), "pcc_conv_tr2m: shape not covered");
     Tr2mArgs a;
     a.in = in; a.w = w_tr2g; a.bias = bias; a.out = out;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.nty = d->H / 16; a.ntx = d->W / 16; a.nct = d->Cout / 16;
-    a.flags = d->flags;
-    a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    a.oco = d->out_coffset;
-    const int zs = tr2m_zsplit(ctx, d);
-    a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = d->N * a.nty * a.ntx * a.nct * zs;
+    const int nwg = tr2m_grid(ctx, d, a.g);
     const int NG = d->Cin / 16;
     const int lds = W_BASE + NG * 27 * 1024;
     typedef void (*kern_t)(Tr2mArgs, int);
     static const kern_t kerns[4] = {conv_tr2m_kernel<2, false>, conv_tr2m_kernel<2, true>, conv_tr2m_kernel<4, false>, conv_tr2m_kernel<4, true>};
-    const kern_t kern = kerns[(NG == 4 ? 2 : 0) + ((d->flags & PCC_CONV_RELU) ? 1 : 0)];
-    { const int rc = pcc_enable_big_lds((const void*)kern, lds); if (rc != PCC_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), lds, st, a, nwg);
-    PCC_CHECK_HIP(hipGetLastError());
-    return PCC_OK;
+    return tr2m_launch(kerns[(NG == 4 ? 2 : 0) + ((d->flags & PCC_CONV_RELU) ? 1 : 0)], lds, nwg, a, st);
 }

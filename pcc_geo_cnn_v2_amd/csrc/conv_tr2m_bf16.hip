@@ -13,7 +13,8 @@
 //     acc += [Wh | Wm] . [dh | dm];   acc += [Wh | Wm] . [dl | dh];   acc += [Wl | Wh] . [dh | dm]
 // The split weights of the cout tile (2 x 27 fragments of 2 KB = 108 KB) stay LDS-resident beside the two-tile ring (40 KB); NG = 4
 // (64 -> 32: 216 KB) does not fit and keeps the fp32 kernel / conv_tr2g_kernel.  Everything else -- parity decomposition, three
-// accumulator sets, epilogue under the first taps of the next plane, compile-time plane parity -- is conv_tr2m_kernel's.
+// accumulator sets, epilogue under the first taps of the next plane, compile-time plane parity -- is conv_tr2m_kernel's (conv_tr2m.hip);
+// the code the variants share -- grid, launch, next tile, epilogue schedule, drain -- is in tr2m_common.h.
 #include <cstdlib>
 
 #include "tr2m_common.h"
@@ -23,7 +24,6 @@ namespace pcctr2mb {
 using namespace pcck;
 using namespace pcctr2;
 
-constexpr int ITEMS = 5;                                // (voxel, channel quad) items per thread: 5 x 256 = 1280 >= 1156
 constexpr int VSB = 160;                                // bytes per voxel of the operand-form tile: B1 x 4 quads, B2 x 4 quads, 32 pad (10 bank quads:
                                                         // the 8 voxels x 2 quads of a ds_read_b128 lane group fall on 16 different ones)
 constexpr int TILE_BYTES = ITEMS * 64 * VSB;            // 51200: 320 voxel slots (289 used; the items past the tile write zeros into the rest)
@@ -35,9 +35,7 @@ struct Tr2mArgs {
     const float* w;      // split image in conv_tr2g order: [cin group][27 taps, class-major][cout tile][operand][64 lanes][8 bf16]
     const float* bias;
     float* out;
-    int N, D, H, W;      // input dims (output = 2x)
-    int nty, ntx, zsplit, zlen, nct;
-    int flags, ocs, oco;
+    Tr2mGrid g;
     unsigned* amax_out = nullptr;      // per-block max |out| for the fp16-split layer behind this one (common.h, pcc_conv_ext)
 };
 
@@ -49,20 +47,20 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
     auto ldsu = [&](unsigned off) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + off); };
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
-    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const Tr2mTile tile = tr2m_tile(a.g, nwg);
     const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
-    const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
+    const int nsteps = a.g.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 16;
-    const size_t HW = (size_t)a.H * a.W;
+    const size_t HW = (size_t)a.g.H * a.g.W;
     const unsigned HWI = (unsigned)(HW * CIN * 4);
-    const float* in_n = a.in + (size_t)n * a.D * HW * CIN;
+    const float* in_n = a.in + (size_t)n * a.g.D * HW * CIN;
 
     // ---- split weights of this cout tile -> LDS (resident): NG x 27 fragments of 2 KB ([Wh | Wm] then [Wl | Wh]), fragment (g, sq) at
     //      W_BASE + (g * 27 + sq) * 2 KB
     {
-        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, (unsigned)(NG * 27 * a.nct) * 2048u);
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.w, (unsigned)(NG * 27 * a.g.nct) * 2048u);
         for (int p = wave; p < NG * 27 * 2; p += 4)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + W_BASE + p * 1024), 16, lane * 16, ((p >> 1) * a.nct + ct) * 2048 + (p & 1) * 1024, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(smem + W_BASE + p * 1024), 16, lane * 16, ((p >> 1) * a.g.nct + ct) * 2048 + (p & 1) * 1024, 0, 0);
     }
     // ---- tile staging: global -> registers (one micro-step ahead) -> split -> LDS.  Item it of thread tid = (voxel u, channel quad q) =
     //      ((it * 256 + tid) >> 2, tid & 3); its operands go to u * 160 + q * 16 (B1) and + 64 (B2).  OOB items read zeros.
@@ -76,14 +74,14 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
         const int item = it * NT + tid;
         const int u = it * 64 + gperm, q = item & 3, ly = u / LXY, lx = u - ly * LXY;
         const int y = Y0 - 1 + ly, x = X0 - 1 + lx;
-        const bool ok = item < TILE_SLOTS && y >= 0 && y < a.H && x >= 0 && x < a.W;
-        rel[it] = ok ? (unsigned)(((y * a.W + x) * CIN + q * 4) * 4) : kOOB;
+        const bool ok = item < TILE_SLOTS && y >= 0 && y < a.g.H && x >= 0 && x < a.g.W;
+        rel[it] = ok ? (unsigned)(((y * a.g.W + x) * CIN + q * 4) * 4) : kOOB;
     }
     const unsigned cw = (unsigned)(gperm * VSB + (tid & 3) * 16);       // item it: cw + it * 64 * VSB
     f32x4 stg[ITEMS];
     // tile of (step sp, cin group cg): `addr` = address of channel 16 cg of input plane zb - 1 + sp (kept incrementally)
     auto fetch_tile = [&](int sp, int cg, unsigned long long addr) __attribute__((always_inline)) {
-        const bool ok = (unsigned)(zb - 1 + sp) < (unsigned)a.D && sp < nsteps;
+        const bool ok = (unsigned)(zb - 1 + sp) < (unsigned)a.g.D && sp < nsteps;
         const __amdgpu_buffer_rsrc_t rp = make_rsrc((const void*)(ok ? addr : (unsigned long long)in_n), ok ? HWI - (unsigned)(64 * cg) : 0u);
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) stg[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rp, (int)rel[it], 0, 0));
@@ -109,12 +107,12 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
     unsigned wa = (unsigned)(W_BASE + lane * 16);      // + cin group * 54 KB (per micro-step), + tap * 2 KB (immediate)
 
     // ---- epilogue addressing: lane writes couts 4 cq .. 4 cq + 3 (of this cout tile) of output voxel (2 z + pz, 2 y + py, 2 x + px)
-    const int OH = 2 * a.H, OW = 2 * a.W;
-    const unsigned ob = (unsigned)((((2 * (Y0 + 4 * wave)) * OW + 2 * (X0 + v)) * a.ocs + a.oco + 16 * ct + 4 * cq) * 4);
-    const unsigned PLANE_O = (unsigned)((size_t)OH * OW * a.ocs * 4);          // bytes per output plane (launcher: two planes < 2^31)
-    float* out_n = a.out + (size_t)n * (2 * a.D) * OH * OW * a.ocs;
+    const int OH = 2 * a.g.H, OW = 2 * a.g.W;
+    const unsigned ob = (unsigned)((((2 * (Y0 + 4 * wave)) * OW + 2 * (X0 + v)) * a.g.ocs + a.g.oco + 16 * ct + 4 * cq) * 4);
+    const unsigned PLANE_O = (unsigned)((size_t)OH * OW * a.g.ocs * 4);          // bytes per output plane (launcher: two planes < 2^31)
+    float* out_n = a.out + (size_t)n * (2 * a.g.D) * OH * OW * a.g.ocs;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 bias_l = (a.flags & PCC_CONV_BIAS) ? *reinterpret_cast<const f32x4*>(a.bias + 16 * ct + 4 * cq) : zero4;
+    const f32x4 bias_l = (a.g.flags & PCC_CONV_BIAS) ? *reinterpret_cast<const f32x4*>(a.bias + 16 * ct + 4 * cq) : zero4;
 
     // ---- prologue
     // (s2, c2, tile_pl): input plane step / cin group / address of the next tile to fetch (wave-uniform)
@@ -122,7 +120,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
     unsigned long long tile_pl = (unsigned long long)in_n + (unsigned long long)(long long)(zb - 1) * HWI;     // tile of micro-step 0
     auto fetch_next = [&]() __attribute__((always_inline)) {
         fetch_tile(s2, c2, tile_pl);
-        if (++c2 == NG) { c2 = 0; ++s2; tile_pl += HWI - 64 * (NG - 1); } else tile_pl += 64;
+        tr2m_next_tile<NG, 64>(s2, c2, tile_pl, HWI);
     };
     fetch_next();
     commit2(std::integral_constant<int, 0>{}); commit2(std::integral_constant<int, 2>{}); commit2(std::integral_constant<int, 4>{});
@@ -166,7 +164,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
         keep = o;
         asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(mxt) : "v"(o[0]), "v"(o[1]));
         asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(mxt) : "v"(o[2]), "v"(o[3]));
-        const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.ocs * 4);
+        const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.g.ocs * 4);
         buf_store4(rout, keep, ob, soff);
     };
 
@@ -207,17 +205,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
                 commit2(std::integral_constant<int, 0>{}); commit2(std::integral_constant<int, 2>{}); commit2(std::integral_constant<int, 4>{});
                 fetch_next();
             }
-            if constexpr (FIRST && !HALO) {
-                if constexpr (t < 8) {
-                    finish(ph_tag, std::integral_constant<int, 2 * t>{}, rout, ost[t & 1][0]);
-                    finish(ph_tag, std::integral_constant<int, 2 * t + 1>{}, rout, ost[t & 1][1]);
-                }
-                if constexpr (t < 16) finish(ph_tag, std::integral_constant<int, 16 + t>{}, rout, ost[t & 1][2]);
-                if constexpr (t >= 1 && t < 17) {     // store data registers stay untouched for one more tap (late read, see conv_wino.hip)
-                    asm volatile("" ::"v"(ost[(t - 1) & 1][2]));
-                    if constexpr (t < 9) { asm volatile("" ::"v"(ost[(t - 1) & 1][0])); asm volatile("" ::"v"(ost[(t - 1) & 1][1])); }
-                }
-            }
+            if constexpr (FIRST && !HALO) tr2m_finish_under_tap<t>(finish, ph_tag, rout, ost);
             __builtin_amdgcn_sched_barrier(0);
         });
         if constexpr (FIRST && !HALO) { mx = fmaxf(mx, prev_ok ? mxt : 0.f); mxt = 0.f; }
@@ -238,23 +226,19 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_bf16_kernel(Tr2mArgs a, int n
 #pragma unroll
         for (int k = 1; k < NG; ++k) micro(ph_tag, std::false_type{}, halo_tag);
     };
+    // the plane loop is written out in every variant: as a shared function template it compiles to other code (note in tr2m_common.h)
     plane(std::integral_constant<int, 0>{}, std::true_type{});          // step 0: the halo plane
 #pragma nounroll
     for (int sp = 1; sp < nsteps; sp += 2) {
         plane(std::integral_constant<int, 1>{}, std::false_type{});
         if (sp + 1 < nsteps) plane(std::integral_constant<int, 0>{}, std::false_type{});
     }
-    // ---- drain: the planes finished by the last input plane (s == nsteps here; its parity decides which even set is complete)
+    // ---- drain: the planes finished by the last input plane (s == nsteps here; tr2m_common.h on the parity, the branch and keep[])
     {
         const __amdgpu_buffer_rsrc_t rout = make_rsrc((const void*)out_pl, nsteps >= 2 ? 2u * PLANE_O : 0u);
         f32x4 keep[32];
-        if (nsteps & 1) {      // last plane had PH = 0: its even_cur is E[0] = "E[PH ^ 1]" of a PH = 1 epilogue
-            static_for(std::make_integer_sequence<int, 32>{}, [&](auto e_tag) __attribute__((always_inline)) {
-                finish(std::integral_constant<int, 1>{}, e_tag, rout, keep[decltype(e_tag)::value]); });
-        } else {
-            static_for(std::make_integer_sequence<int, 32>{}, [&](auto e_tag) __attribute__((always_inline)) {
-                finish(std::integral_constant<int, 0>{}, e_tag, rout, keep[decltype(e_tag)::value]); });
-        }
+        if (nsteps & 1) tr2m_drain<1>(finish, rout, keep);
+        else tr2m_drain<0>(finish, rout, keep);
 #pragma unroll
         for (int e = 0; e < 32; ++e) asm volatile("" ::"v"(keep[e]));
         mx = fmaxf(mx, nsteps >= 2 ? mxt : 0.f);
@@ -294,20 +278,10 @@ int pcc_conv_tr2m_bf16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
     PCC_REQUIRE(pcc_tr2m_bf16_covers(d), "pcc_conv_tr2m_bf16: shape not covered");
     Tr2mArgs a;
     a.in = in; a.w = w_split; a.bias = bias; a.out = out;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.nty = d->H / 16; a.ntx = d->W / 16; a.nct = d->Cout / 16;
-    a.flags = d->flags;
-    a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    a.oco = d->out_coffset;
     if (ext && ext->out_amax) { a.amax_out = ext->out_amax; ext->out_recorded = true; }
-    const int zs = tr2m_zsplit(ctx, d);
-    a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = d->N * a.nty * a.ntx * a.nct * zs;
+    const int nwg = tr2m_grid(ctx, d, a.g);
     const int lds = W_BASE + 2 * 27 * 2048;
     typedef void (*kern_t)(Tr2mArgs, int);
     const kern_t kern = (d->flags & PCC_CONV_RELU) ? (kern_t)conv_tr2m_bf16_kernel<2, true> : (kern_t)conv_tr2m_bf16_kernel<2, false>;
-    { const int rc = pcc_enable_big_lds((const void*)kern, lds); if (rc != PCC_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), lds, st, a, nwg);
-    PCC_CHECK_HIP(hipGetLastError());
-    return PCC_OK;
+    return tr2m_launch(kern, lds, nwg, a, st);
 }

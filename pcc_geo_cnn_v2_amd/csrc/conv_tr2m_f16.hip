@@ -16,6 +16,7 @@
 //     the prologue and stay LDS-resident; a 4-deep fragment ring (a tap is 4 MFMAs = 64 cycles) covers the LDS latency;
 //   * parity decomposition, three accumulator sets (192 AccVGPRs), the finished planes leaving under the first taps of the next plane,
 //     compile-time plane parity: conv_tr2m_kernel's (DESIGN_HISTORY.md 3.3b).  The epilogue rounds to fp16 and stores 8 bytes per lane.
+//     The code the variants share -- grid, launch, next tile, epilogue schedule, drain -- is in tr2m_common.h.
 // Summation order per output element: cin group of 32 -> tap -> the K = 32 chain of the instruction, fp32 accumulation, fixed:
 // bit-deterministic, independent of batch and z split; NOT the order of conv_tr2g_kernel<F16>, so the dispatch is a function of the layer
 // shape only (encoder and decoder must produce the same bits).
@@ -34,7 +35,6 @@ __device__ __forceinline__ u32x4 to_h8(const f32x4& lo, const f32x4& hi) {
     return __builtin_bit_cast(u32x4, __builtin_convertvector(v, f16x8));
 }
 
-constexpr int ITEMS = 5;                                // items per thread: 5 x 256 = 1280 >= 1156
 constexpr int VSB = 96;                                 // bytes per voxel of the fp16 tile: 4 quads x 16 B + 32 pad
 constexpr int TILE_BYTES = ITEMS * 64 * VSB;            // 30720: 320 voxel slots (289 used; the items past the tile write zeros into the rest)
 constexpr int W_BASE = 2 * TILE_BYTES;                  // two tile buffers, then the weights
@@ -45,9 +45,7 @@ struct Args {
     const float* w;      // conv_tr2g order, fp32: [cin group of 16][27 taps, class-major][cout tile][64 lanes][4]
     const float* bias;
     void* out;           // fp16 NDHWC
-    int N, D, H, W;      // input dims (output = 2x)
-    int nty, ntx, zsplit, zlen, nct;
-    int flags, ocs, oco;
+    Tr2mGrid g;
 };
 
 // NG = 32-channel cin groups (1: 32 -> 16, 2: 64 -> 32)
@@ -58,13 +56,13 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
     const int v = lane & 15, cq = lane >> 4;
     auto ldsu = [&](unsigned off) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + off); };
 
-    const Tr2mTile tile = tr2m_tile(a, nwg);
+    const Tr2mTile tile = tr2m_tile(a.g, nwg);
     const int ct = tile.ct, n = tile.n, X0 = tile.X0, Y0 = tile.Y0, zb = tile.zb;
-    const int nsteps = a.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
+    const int nsteps = a.g.zlen + 1;                   // input planes zb-1 .. zb+zlen-1 (the first one only opens output plane 2 zb)
     constexpr int CIN = NG * 32;
-    const size_t HW = (size_t)a.H * a.W;
+    const size_t HW = (size_t)a.g.H * a.g.W;
     const unsigned HWI = (unsigned)(HW * CIN * 4);
-    const float* in_n = a.in + (size_t)n * a.D * HW * CIN;
+    const float* in_n = a.in + (size_t)n * a.g.D * HW * CIN;
 
     // ---- fp16 weights of this cout tile -> LDS (resident): fragment (G, sq) at W_BASE + (G * 27 + sq) KB; lane (cout = lane & 15, kq = lane >> 4)
     //      holds input channels 32 G + 8 kq .. + 7 = two float4 of the tr2g-order image (group 2 G + (kq >> 1), channel quads 2 (kq & 1), + 1)
@@ -72,7 +70,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
         const f32x4* w4 = reinterpret_cast<const f32x4*>(a.w);
         for (int p = wave; p < NG * 27; p += 4) {
             const int G = p / 27, sq = p - G * 27;
-            const size_t frag = ((size_t)((2 * G + (cq >> 1)) * 27 + sq) * a.nct + ct) * 64;
+            const size_t frag = ((size_t)((2 * G + (cq >> 1)) * 27 + sq) * a.g.nct + ct) * 64;
             const f32x4 lo = w4[frag + v + 16 * (2 * (cq & 1))], hi = w4[frag + v + 16 * (2 * (cq & 1) + 1)];
             *reinterpret_cast<u32x4*>(smem + W_BASE + p * 1024 + lane * 16) = to_h8(lo, hi);
         }
@@ -88,14 +86,14 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
         const int item = it * NT + tid;
         const int u = it * 64 + gperm, q = item & 3, ly = u / LXY, lx = u - ly * LXY;
         const int y = Y0 - 1 + ly, x = X0 - 1 + lx;
-        const bool ok = item < TILE_SLOTS && y >= 0 && y < a.H && x >= 0 && x < a.W;
-        rel[it] = ok ? (unsigned)(((y * a.W + x) * CIN + q * 8) * 4) : kOOB;
+        const bool ok = item < TILE_SLOTS && y >= 0 && y < a.g.H && x >= 0 && x < a.g.W;
+        rel[it] = ok ? (unsigned)(((y * a.g.W + x) * CIN + q * 8) * 4) : kOOB;
     }
     const unsigned cw = (unsigned)(gperm * VSB + (tid & 3) * 16);       // item it: cw + it * 64 * VSB (+ the tile buffer)
     f32x4 stg[ITEMS][2];
     // tile of (step sp, cin group cg): `addr` = address of channel 32 cg of input plane zb - 1 + sp (kept incrementally)
     auto fetch_tile = [&](int sp, int cg, unsigned long long addr) __attribute__((always_inline)) {
-        const bool ok = (unsigned)(zb - 1 + sp) < (unsigned)a.D && sp < nsteps;
+        const bool ok = (unsigned)(zb - 1 + sp) < (unsigned)a.g.D && sp < nsteps;
         const __amdgpu_buffer_rsrc_t rp = make_rsrc((const void*)(ok ? addr : (unsigned long long)in_n), ok ? HWI - (unsigned)(128 * cg) : 0u);
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
@@ -117,19 +115,19 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
     unsigned wa = (unsigned)(W_BASE + lane * 16);      // + cin group * 27 KB (per micro-step), + tap * 1 KB (immediate)
 
     // ---- epilogue addressing (bytes, fp16 output): lane writes couts 4 cq .. 4 cq + 3 (of this cout tile) of output voxel (2 z + pz, 2 y + py, 2 x + px)
-    const int OH = 2 * a.H, OW = 2 * a.W;
-    const unsigned ob = (unsigned)((((2 * (Y0 + 4 * wave)) * OW + 2 * (X0 + v)) * a.ocs + a.oco + 16 * ct + 4 * cq) * 2);
-    const unsigned PLANE_O = (unsigned)((size_t)OH * OW * a.ocs * 2);          // bytes per output plane
-    unsigned char* out_n = (unsigned char*)a.out + (size_t)n * (2 * a.D) * OH * OW * a.ocs * 2;
+    const int OH = 2 * a.g.H, OW = 2 * a.g.W;
+    const unsigned ob = (unsigned)((((2 * (Y0 + 4 * wave)) * OW + 2 * (X0 + v)) * a.g.ocs + a.g.oco + 16 * ct + 4 * cq) * 2);
+    const unsigned PLANE_O = (unsigned)((size_t)OH * OW * a.g.ocs * 2);          // bytes per output plane
+    unsigned char* out_n = (unsigned char*)a.out + (size_t)n * (2 * a.g.D) * OH * OW * a.g.ocs * 2;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 bias_l = (a.flags & PCC_CONV_BIAS) ? *reinterpret_cast<const f32x4*>(a.bias + 16 * ct + 4 * cq) : zero4;
+    const f32x4 bias_l = (a.g.flags & PCC_CONV_BIAS) ? *reinterpret_cast<const f32x4*>(a.bias + 16 * ct + 4 * cq) : zero4;
 
     // ---- prologue
     int s2 = 0, c2 = 0;                               // input plane step / cin group of the next tile to fetch (wave-uniform)
     unsigned long long tile_pl = (unsigned long long)in_n + (unsigned long long)(long long)(zb - 1) * HWI;     // tile of micro-step 0
     auto fetch_next = [&]() __attribute__((always_inline)) {
         fetch_tile(s2, c2, tile_pl);
-        if (++c2 == NG) { c2 = 0; ++s2; tile_pl += HWI - 128 * (NG - 1); } else tile_pl += 128;
+        tr2m_next_tile<NG, 128>(s2, c2, tile_pl, HWI);
     };
     fetch_next();
     commit(0u);
@@ -161,7 +159,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
         f32x4 o = acc_read(pz ? O[cls][i] : E[PH ^ 1][cls][i]);
         if (RELU) o = __builtin_elementwise_maximum(o, zero4);
         keep = __builtin_bit_cast(u32x2, __builtin_convertvector(o, f16x4));
-        const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.ocs * 2);
+        const unsigned soff = (unsigned)pz * PLANE_O + (unsigned)(((2 * i + py) * OW + px) * a.g.ocs * 2);
         __builtin_amdgcn_raw_buffer_store_b64(keep, rout, (int)ob, (int)soff, 0);
     };
 
@@ -191,17 +189,7 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
                 commit((unsigned)((BUF ^ 1) * TILE_BYTES));
                 fetch_next();
             }
-            if constexpr (FIRST && !HALO) {
-                if constexpr (t < 8) {
-                    finish(ph_tag, std::integral_constant<int, 2 * t>{}, rout, ost[t & 1][0]);
-                    finish(ph_tag, std::integral_constant<int, 2 * t + 1>{}, rout, ost[t & 1][1]);
-                }
-                if constexpr (t < 16) finish(ph_tag, std::integral_constant<int, 16 + t>{}, rout, ost[t & 1][2]);
-                if constexpr (t >= 1 && t < 17) {     // store data registers stay untouched for one more tap (late read, see conv_wino.hip)
-                    asm volatile("" ::"v"(ost[(t - 1) & 1][2]));
-                    if constexpr (t < 9) { asm volatile("" ::"v"(ost[(t - 1) & 1][0])); asm volatile("" ::"v"(ost[(t - 1) & 1][1])); }
-                }
-            }
+            if constexpr (FIRST && !HALO) tr2m_finish_under_tap<t>(finish, ph_tag, rout, ost);
             __builtin_amdgcn_sched_barrier(0);
         });
         __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): this wave's tile writes; the others': the barrier
@@ -223,23 +211,19 @@ __global__ void __launch_bounds__(NT, 1) conv_tr2m_f16_kernel(Args a, int nwg) {
             micro(ph_tag, std::false_type{}, halo_tag, B1{});
         }
     };
+    // the plane loop is written out in every variant: as a shared function template it compiles to other code (note in tr2m_common.h)
     plane(std::integral_constant<int, 0>{}, std::true_type{});          // step 0: the halo plane
 #pragma nounroll
     for (int sp = 1; sp < nsteps; sp += 2) {
         plane(std::integral_constant<int, 1>{}, std::false_type{});
         if (sp + 1 < nsteps) plane(std::integral_constant<int, 0>{}, std::false_type{});
     }
-    // ---- drain: the planes finished by the last input plane (s == nsteps here; its parity decides which even set is complete)
+    // ---- drain: the planes finished by the last input plane (s == nsteps here; tr2m_common.h on the parity, the branch and keep[])
     {
         const __amdgpu_buffer_rsrc_t rout = make_rsrc((const void*)out_pl, nsteps >= 2 ? 2u * PLANE_O : 0u);
         u32x2 keep[32];
-        if (nsteps & 1) {      // last plane had PH = 0: its even_cur is E[0] = "E[PH ^ 1]" of a PH = 1 epilogue
-            static_for(std::make_integer_sequence<int, 32>{}, [&](auto e_tag) __attribute__((always_inline)) {
-                finish(std::integral_constant<int, 1>{}, e_tag, rout, keep[decltype(e_tag)::value]); });
-        } else {
-            static_for(std::make_integer_sequence<int, 32>{}, [&](auto e_tag) __attribute__((always_inline)) {
-                finish(std::integral_constant<int, 0>{}, e_tag, rout, keep[decltype(e_tag)::value]); });
-        }
+        if (nsteps & 1) tr2m_drain<1>(finish, rout, keep);
+        else tr2m_drain<0>(finish, rout, keep);
 #pragma unroll
         for (int e = 0; e < 32; ++e) asm volatile("" ::"v"(keep[e]));
     }
@@ -261,22 +245,12 @@ int pcc_conv_tr2m_f16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, con
     PCC_REQUIRE(pcc_tr2m_f16_covers(d), "pcc_conv_tr2m_f16: shape not covered");
     Args a;
     a.in = in; a.w = w_tr2g; a.bias = bias; a.out = out;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.nty = d->H / 16; a.ntx = d->W / 16; a.nct = d->Cout / 16;
-    a.flags = d->flags;
-    a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    a.oco = d->out_coffset;
-    const int zs = tr2m_zsplit(ctx, d);
-    a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = d->N * a.nty * a.ntx * a.nct * zs;
+    const int nwg = tr2m_grid(ctx, d, a.g);
     const int NG = d->Cin / 32;
     const int lds = W_BASE + NG * 27 * 1024;
     typedef void (*kern_t)(Args, int);
     const bool relu = (d->flags & PCC_CONV_RELU) != 0;
     const kern_t kern = NG == 1 ? (relu ? (kern_t)conv_tr2m_f16_kernel<1, true> : (kern_t)conv_tr2m_f16_kernel<1, false>)
                                 : (relu ? (kern_t)conv_tr2m_f16_kernel<2, true> : (kern_t)conv_tr2m_f16_kernel<2, false>);
-    { const int rc = pcc_enable_big_lds((const void*)kern, lds); if (rc != PCC_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), lds, st, a, nwg);
-    PCC_CHECK_HIP(hipGetLastError());
-    return PCC_OK;
+    return tr2m_launch(kern, lds, nwg, a, st);
 }
