@@ -378,6 +378,38 @@ int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t
                             int64_t npts, const float* normals, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum,
                             uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream);
 
+/* ---- rank levels: the same search over candidate point COUNTS (count-matched thresholding) ------------------------
+ * The top-k sets of a block are a nested family like its threshold level sets; here the family is indexed by a row of candidate counts
+ * instead of score thresholds.  A block has n = D*H*W float32 scores and a row c[0] >= c[1] >= ... >= c[J-1] of int32, 1 <= J <= 255,
+ * a negative entry counts as 0.  Rule (normative):
+ *   key(i) and P are those of pcc_topk_compact: the 32 raw bits of x[i] where x[i] > 0, else 0 (NaN, -0, +0, negatives); nothing is
+ *   clipped;  rank(i) = the 0-based position of voxel i among the P voxels with key > 0 in the order (key descending, i ascending);
+ *   lev(i) = 0 where key(i) = 0, else #{j : rank(i) < c[j]};   tcount = max_i lev(i) = #{j : c[j] >= 1} when P >= 1, else 0.
+ * Then {i : lev(i) > j} is exactly the voxel set pcc_topk_compact emits for k = c[j], also for c[j] > P; equal entries give equal sets.
+ * For a row that is not non-increasing the formula still is the output (the row is walked whole) and no access leaves the buffers; it
+ * just is no nested top-k family.  x: block b at x + b * x_stride (elements, >= n); counts: (B,J) int32 (device); lev: B*n uint8, block b
+ * at lev + b*n; tcount: (B,) int32; both written whole by the call.  The result of a block is a function of its scores and its row alone
+ * (no dependence on B, the stride, the position in the batch or the launch geometry); no score-valued atomics; every store into lev is
+ * under the test index < n.  workspace: pcc_rank_levels_workspace_bytes(B, n) bytes of device memory, 0 for a shape outside the contract.
+ * B = 0: nothing is done; n = 0: tcount = 0.  PCC_ERR_ARG: a NULL pointer, n > 2^28, B > 65535, B*n >= 2^31 (one sort of all voxels of
+ * the call), J outside [1, 255], a workspace that is too small.                                                                         */
+size_t pcc_rank_levels_workspace_bytes(int32_t B, int64_t n);
+int pcc_rank_levels(pcc_ctx* ctx, const float* x, int64_t x_stride, int32_t B, int64_t n, const int32_t* counts, int32_t J, uint8_t* lev,
+                    int32_t* tcount, void* workspace, size_t workspace_bytes, void* stream);
+
+/* pcc_d1_threshold_stats / pcc_d12_threshold_stats with the level grid of pcc_rank_levels in place of the threshold levels: entry [b][j]
+ * of every output is the statistic of the top-counts[b][j] set of block b (sum_{k>j} hcnt[b][k] = min(counts[b][j], P_b)), valid for
+ * j < tcount[b].  `thr, nthr, clip` are replaced by `counts` ((B,J) int32, device) and J in [1, 255]; rank_workspace:
+ * pcc_rank_levels_workspace_bytes(B, D*H*W) bytes beside the other workspaces.  Everything behind the level grid is the code of the
+ * threshold entries, so equal level grids give equal bits.  A level of 256 cannot occur.                                                */
+int pcc_d1_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts, int32_t J,
+                       const int32_t* pts, const int32_t* block_of, int64_t npts, void* workspace, void* rank_workspace,
+                       size_t rank_workspace_bytes, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, void* stream);
+int pcc_d12_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts, int32_t J,
+                        const int32_t* pts, const int32_t* block_of, const int32_t* block_start, int64_t npts, const float* normals,
+                        void* workspace, void* workspace2, void* rank_workspace, size_t rank_workspace_bytes, uint64_t* s_ab,
+                        uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream);
+
 /* The same search under the tie-averaged D2 definition (DESIGN.md "Tie-averaged D2", applied per block and threshold with A = the
  * block's rows and B = B_t): T_B(a) = ALL voxels of B_t at the smallest squared distance from row a, T_A(v) = ALL rows at the
  * smallest squared distance from voxel v (rows that share a voxel are separate members).  A voxel b takes the unweighted float64 mean

@@ -4,7 +4,7 @@
          --checkpoint_dir models/c3p/1.00e-04 --model_config c3p --resolution 1024 --octree_level 4 \\
          [--dec_files a.dec.ply] [--fixed_threshold] [--opt_metrics d1_mse] [--max_deltas inf] [--debug]
          [--estimate_normals [--normals_k 16]] [--metrics_device host|gpu] [--d2_ties pick|mean] [--search_ties pick|mean]
-         [--entropy_coder range|rans] [--lossless] [--count_threshold [RHO]]
+         [--entropy_coder range|rans] [--lossless] [--count_threshold [RHO]] [--count_search [LO HI STEPS]]
 
 Differences: `--checkpoint_dir` holds `model.npz` (this framework's weight container) instead of a TF1
 checkpoint; `--batch_size` (blocks resident per GPU pass) is new.  Under
@@ -149,6 +149,53 @@ def check_count_threshold(args, world):
                              'strings, drop the flag or run on one GPU')
 
 
+COUNT_SEARCH_DEFAULT = (0.5, 2.0, 33)      # a design choice (half to twice the input count, 33 geometric steps), not a tuned value
+
+
+def count_search_of(args):
+    """--count_search [LO HI STEPS] as (lo, hi, steps), None without the flag; the bare flag is COUNT_SEARCH_DEFAULT."""
+    v = getattr(args, 'count_search', None)
+    if v is None:
+        return None
+    if len(v) == 0:
+        return COUNT_SEARCH_DEFAULT
+    try:
+        lo, hi, steps = (float(x) for x in v)
+    except ValueError:
+        lo = hi = steps = None
+    if steps is None or not steps.is_integer():
+        raise AssertionError(f'--count_search takes no value or LO HI STEPS (two scales and an integer), got {list(v)}')
+    return lo, hi, int(steps)
+
+
+def check_count_search(args, world):
+    """--count_search replaces the threshold search by the search over point counts: one process, the GPU engines with
+    their 'pick' tie rule, block grids up to 128^3.  From the parsed arguments, before the process group and the GPU are touched."""
+    ladder = count_search_of(args)
+    if ladder is None:
+        return
+    from .model_opt import count_ladder
+    try:
+        count_ladder(*ladder)
+    except AssertionError as e:
+        raise AssertionError(f'--count_search: {e}') from None
+    if getattr(args, 'count_threshold', None) is not None:
+        raise AssertionError('--count_search and --count_threshold are two policies for the same decision, drop one of the two flags')
+    if getattr(args, 'fixed_threshold', False):
+        raise AssertionError('--count_search and --fixed_threshold are two policies for the same decision, drop one of the two flags')
+    if getattr(args, 'lossless', False):
+        raise AssertionError('--count_search and --lossless: a stream carries the point counts or the occupancy layer, drop one of the two flags')
+    if getattr(args, 'search_ties', 'pick') == 'mean':
+        raise AssertionError('--count_search: the tie-averaged D2 engine has no count source, drop --search_ties mean')
+    if any(str(m).startswith('d2_') for m in (getattr(args, 'opt_metrics', None) or ())) and getattr(args, 'd2_search', None) != 'gpu':
+        raise AssertionError('--count_search with a d2_* metric needs --d2_search gpu: the host KD-tree path has no count source')
+    if (int(args.resolution) >> int(args.octree_level)) > 128:
+        raise AssertionError(f'--count_search covers block grids up to 128^3, not {int(args.resolution) >> int(args.octree_level)}^3: raise --octree_level')
+    if world > 1:
+        raise AssertionError(f'--count_search is single-process only (world size {world}): the sharded path does not carry the count '
+                             'strings, drop the flag or run on one GPU')
+
+
 def check_d2_ties(d2_ties, world):
     """--d2_ties mean averages the whole-cloud D2 over all equidistant nearest points in one process; tie sets are not sharded."""
     from .utils.pc_metric import check_ties
@@ -203,6 +250,10 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
             record['threshold_policy'] = 'count'
             record['count_scale'] = float(args.count_threshold)
             record['count_bytes'] = sum(len(strings[-1]) for strings, _ in streams)      # (4 per block)
+        if count_search_of(args) is not None:
+            record['threshold_policy'] = 'count_search'
+            record['count_ladder'] = list(count_search_of(args))
+            record['count_bytes'] = sum(len(strings[-1]) for strings, _ in streams)      # (4 per block)
         if getattr(args, 'lossless', False):
             # the last string of every block is the occupancy layer; the rate of the exact cloud counts the whole file as written
             n_points = sum(len(b) for b in blocks)
@@ -233,9 +284,11 @@ def compress(args):
     T.mark('imports')
 
     check_count_threshold(args, int(os.environ.get('WORLD_SIZE', '1')))     # (first: its message names the flag, not what _plan meets)
+    check_count_search(args, int(os.environ.get('WORLD_SIZE', '1')))
     clouds, with_normals = _plan(args)
     lossless = getattr(args, 'lossless', False)
     count_scale = getattr(args, 'count_threshold', None)
+    count_search = count_search_of(args)
     check_lossless(lossless, int(os.environ.get('WORLD_SIZE', '1')))      # (before the process group and the GPU are touched)
     rank, world, local = _join_process_group()
     check_metrics_device(getattr(args, 'metrics_device', 'host'), world)
@@ -278,13 +331,14 @@ def compress(args):
             sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
             max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
             metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'),
-            **({} if count_scale is None else {'count_scale': count_scale}))
+            **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}))
         T.mark('compress_blocks', sess.device)
         if rank == 0:       # the other ranks only took part in the collectives
             if len(streams) != len(cloud.targets):
                 raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
             for n, target in enumerate(cloud.targets):
-                infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless, count_scale is not None)
+                infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless,
+                                                        count_scale is not None or count_search is not None)
                 _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
             logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
         T.mark('container_gzip_write')
@@ -362,6 +416,14 @@ def build_parser():
                              'highest-scoring voxels.  The stream names the layer (numerics tag suffix /cnt1); .enc.metric.json gains '
                              'threshold_policy, count_scale and count_bytes.  Not with --fixed_threshold, --lossless, --search_ties mean or '
                              '--d2_search gpu; single process only.')
+    parser.add_argument('--count_search', nargs='*', default=None, metavar='LO HI STEPS',
+                        help='Count search (new) instead of the threshold search: every block tries the point counts k = floor(RHO x input '
+                             'points + 0.5) over STEPS scales RHO spaced geometrically from HI down to LO, scores each top-k set exactly '
+                             '(D1, and D2 with --d2_search gpu) on the GPU and keeps, per output file, the count its metric prefers; the '
+                             'stream is the one of --count_threshold (tag suffix /cnt1, one 4-byte count per block).  The bare flag means '
+                             f'{" ".join(map(str, COUNT_SEARCH_DEFAULT))}: a design choice, not a tuned value.  .enc.metric.json gains threshold_policy, '
+                             'count_ladder and count_bytes.  Not with --count_threshold, --fixed_threshold, --lossless or --search_ties mean; '
+                             'd2_* metrics need --d2_search gpu; blocks up to 128^3; single process only.')
     return parser
 
 

@@ -43,6 +43,20 @@ inline D1Layout d1_layout(int32_t B, size_t nvox) {
     return l;
 }
 
+// Where the level grid of a search call comes from.  Thresholds (counts == nullptr): level(v) = #{t : x_hat[v] > thr[t]}, k_levels of
+// search_d1.hip.  Candidate counts: level(v) = #{j : rank(v) < counts[b][j]}, pcc_rank_levels (rank_levels.hip) with its own workspace.
+// Everything behind the grid reads `lev` and `tcount` alone, so both sources share it unchanged.
+struct LevelSource {
+    const char* who;                       // the public entry, for its messages
+    const float* thr; int nthr, clip;
+    const int32_t* counts; int J; void* rank_ws; size_t rank_ws_bytes;
+    int levels() const { return counts ? J : nthr; }
+};
+// pcc_d1_threshold_stats / pcc_d1_count_stats (search_d1.hip), and what the D2 entries run first
+int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* pts,
+                        const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount,
+                        void* stream);
+
 // Row-major voxel index <-> (x, y, z) on a grid of planes H x W; the divisions are done in the width of the caller's index type
 struct Voxel { int x, y, z; };
 __device__ __forceinline__ size_t voxel_index(int x, int y, int z, int H, int W) { return ((size_t)x * H + y) * W + z; }

@@ -260,15 +260,18 @@ PCC_API size_t pcc_d1_search_workspace_bytes(int32_t B, int32_t D, int32_t H, in
 // block, block_of: (npts,) int32.  Outputs (device, zero-filled by this call): s_ab, hsum, hcnt: (B,256) uint64;
 // tcount: (B,) int32 = number of thresholds with a non-empty decoded set.  hsum/hcnt are per-level histograms:
 // S_BA(t) = sum_{k>t} hsum[k], n_B(t) = sum_{k>t} hcnt[k].
-PCC_API int pcc_d1_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W,
-                                   const float* thr, int32_t nthr, int32_t clip, const int32_t* pts,
-                                   const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab,
-                                   uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, void* stream) {
-    PCC_REQUIRE(ctx && x_hat && thr && workspace && s_ab && hsum && hcnt && tcount, "pcc_d1_threshold_stats: NULL argument");
-    PCC_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && npts >= 0 && (pts || npts == 0), "pcc_d1_threshold_stats: bad dimension");
-    PCC_REQUIRE(nthr >= 1 && nthr <= kT, "pcc_d1_threshold_stats: at most 256 thresholds");
-    PCC_REQUIRE(D <= 128 && H <= 128 && W <= 128, "pcc_d1_threshold_stats: blocks up to 128^3 (uint16 squared distances)");
-    PCC_REQUIRE(B <= 65535, "pcc_d1_threshold_stats: at most 65535 blocks per call");
+// The level grid comes from `src` (search_common.h): thresholds or candidate counts; everything after it is the same code for both.
+int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* pts,
+                        const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount,
+                        void* stream) {
+    const int nthr = src.levels();
+    PCC_REQUIRE(ctx && x_hat && (src.counts ? src.rank_ws != nullptr : src.thr != nullptr) && workspace && s_ab && hsum && hcnt && tcount,
+                "%s: NULL argument", src.who);
+    PCC_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && npts >= 0 && (pts || npts == 0), "%s: bad dimension", src.who);
+    if (src.counts) PCC_REQUIRE(nthr >= 1 && nthr < kT, "%s: 1 to 255 candidate counts per block", src.who);
+    else PCC_REQUIRE(nthr >= 1 && nthr <= kT, "%s: at most 256 thresholds", src.who);
+    PCC_REQUIRE(D <= 128 && H <= 128 && W <= 128, "%s: blocks up to 128^3 (uint16 squared distances)", src.who);
+    PCC_REQUIRE(B <= 65535, "%s: at most 65535 blocks per call", src.who);
     PCC_CHECK_HIP(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t nvox = (size_t)D * H * W;
@@ -285,7 +288,12 @@ PCC_API int pcc_d1_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, 
     PCC_CHECK_HIP(hipMemsetAsync(hsum, 0, (size_t)B * kT * 8, st));
     PCC_CHECK_HIP(hipMemsetAsync(hcnt, 0, (size_t)B * kT * 8, st));
     const unsigned vox_blocks = (unsigned)((nvox + 255) / 256);
-    hipLaunchKernelGGL(k_levels, dim3(256, B), dim3(256), 0, st, x_hat, thr, nthr, clip, nvox, lev, tcount);
+    if (src.counts) {       // (tcount and lev are written whole by the call; it runs behind the fills above on the same stream)
+        const int rc = pcc_rank_levels(ctx, x_hat, (int64_t)nvox, B, (int64_t)nvox, src.counts, src.J, lev, tcount, src.rank_ws, src.rank_ws_bytes, stream);
+        if (rc != PCC_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(k_levels, dim3(256, B), dim3(256), 0, st, x_hat, src.thr, nthr, src.clip, nvox, lev, tcount);
+    }
     // ---- EDT of the original points A (one "threshold": occupancy > 0)
     if (npts > 0) {
         unsigned pblocks = (unsigned)((npts + 255) / 256);
@@ -310,4 +318,21 @@ PCC_API int pcc_d1_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, 
     }
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
+}
+
+PCC_API int pcc_d1_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W,
+                                   const float* thr, int32_t nthr, int32_t clip, const int32_t* pts,
+                                   const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab,
+                                   uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, void* stream) {
+    const LevelSource src = {"pcc_d1_threshold_stats", thr, nthr, clip, nullptr, 0, nullptr, 0};
+    return pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
+}
+
+// The same statistics for the top-counts[b][j] sets of every block (include/pcc_geo.h): only the source of the level grid differs
+PCC_API int pcc_d1_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts, int32_t J,
+                               const int32_t* pts, const int32_t* block_of, int64_t npts, void* workspace, void* rank_workspace,
+                               size_t rank_workspace_bytes, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, void* stream) {
+    PCC_REQUIRE(counts, "pcc_d1_count_stats: NULL argument");
+    const LevelSource src = {"pcc_d1_count_stats", nullptr, 0, 0, counts, J, rank_workspace, rank_workspace_bytes};
+    return pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
 }

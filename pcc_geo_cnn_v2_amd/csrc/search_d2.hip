@@ -486,15 +486,16 @@ PCC_API size_t pcc_d12_search_workspace_bytes(int32_t B, int32_t D, int32_t H, i
 //   normals: (npts, 3) float32 (device), block_start: (B + 1,) int32 offsets of the blocks' points in pts (device),
 //   workspace: pcc_d1_search_workspace_bytes, workspace2: pcc_d12_search_workspace_bytes,
 //   d2_ab, d2_ba: (B, 256) float64 (device), entry [b][t] valid for t < tcount[b].
-PCC_API int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const float* thr,
-                                    int32_t nthr, int32_t clip, const int32_t* pts, const int32_t* block_of, const int32_t* block_start,
-                                    int64_t npts, const float* normals, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum,
-                                    uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream) {
-    PCC_REQUIRE(normals && block_start && workspace2 && d2_ab && d2_ba && pts && npts > 0, "pcc_d12_threshold_stats: NULL argument");
-    PCC_REQUIRE((size_t)npts * 64 < ((size_t)1 << 31), "pcc_d12_threshold_stats: too many points for one call");
+// The level grid comes from `src` (search_common.h): the D1 call builds it, everything here reads `lev` and `tcount` alone.
+static int d12_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* pts,
+                     const int32_t* block_of, const int32_t* block_start, int64_t npts, const float* normals, void* workspace, void* workspace2,
+                     uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream) {
+    PCC_REQUIRE(normals && block_start && workspace2 && d2_ab && d2_ba && pts && npts > 0, "%s: NULL argument", src.who);
+    PCC_REQUIRE((size_t)npts * 64 < ((size_t)1 << 31), "%s: too many points for one call", src.who);
     // D1 part (and the levels / tcount the D2 part builds on): unchanged kernels
-    { const int rc = pcc_d1_threshold_stats(ctx, x_hat, B, D, H, W, thr, nthr, clip, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
+    { const int rc = pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
       if (rc != PCC_OK) return rc; }
+    const int nthr = src.levels();
     hipStream_t st = (hipStream_t)stream;
     const size_t nvox = (size_t)D * H * W;
     const D2Layout l = d2_layout(B, nvox, npts);
@@ -541,6 +542,26 @@ PCC_API int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B,
     }
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
+}
+
+PCC_API int pcc_d12_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const float* thr,
+                                    int32_t nthr, int32_t clip, const int32_t* pts, const int32_t* block_of, const int32_t* block_start,
+                                    int64_t npts, const float* normals, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum,
+                                    uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream) {
+    const LevelSource src = {"pcc_d12_threshold_stats", thr, nthr, clip, nullptr, 0, nullptr, 0};
+    return d12_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, block_start, npts, normals, workspace, workspace2, s_ab, hsum, hcnt, tcount, d2_ab,
+                     d2_ba, stream);
+}
+
+// pcc_d12_threshold_stats for the top-counts[b][j] sets of every block (include/pcc_geo.h): only the source of the level grid differs
+PCC_API int pcc_d12_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts, int32_t J,
+                                const int32_t* pts, const int32_t* block_of, const int32_t* block_start, int64_t npts, const float* normals,
+                                void* workspace, void* workspace2, void* rank_workspace, size_t rank_workspace_bytes, uint64_t* s_ab,
+                                uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream) {
+    PCC_REQUIRE(counts, "pcc_d12_count_stats: NULL argument");
+    const LevelSource src = {"pcc_d12_count_stats", nullptr, 0, 0, counts, J, rank_workspace, rank_workspace_bytes};
+    return d12_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, block_start, npts, normals, workspace, workspace2, s_ab, hsum, hcnt, tcount, d2_ab,
+                     d2_ba, stream);
 }
 
 PCC_API int32_t pcc_d12_search_ties_chunk(int32_t B, int32_t D, int32_t H, int32_t W) {

@@ -556,3 +556,71 @@ def compute_optimal_thresholds_gpu(ctx, blocks, x_hat, thresholds, resolution, o
     if callable(d2_stats):
         d2_stats = d2_stats()
     return decide_from_tallies(blocks, d1, len(thresholds), resolution, opt_metrics, max_deltas, d2_stats, ties=ties)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Count search: the adaptive search over a ladder of count scales rho_j instead of score thresholds.  Candidate j of a
+# block with N_b input rows is the top-k set for k = block_count(N_b, rho_j, voxels); the decisions are select_thresholds_from_stats',
+# unchanged, with J candidates and the 'emit nothing' index J.
+
+def count_ladder(lo, hi, steps):
+    """The count scales of the count search, float64, highest first: rho_j = hi (lo / hi)^(j / (steps - 1)), geometric from rho_0 = hi
+    to rho_last = lo (both set exactly), [hi] for steps = 1.  Requires 0 < lo <= hi finite and 1 <= steps <= 255 (the level grid of
+    the search engines is uint8)."""
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 255:
+        raise AssertionError(f'count_search: steps must be an integer in [1, 255], got {steps!r}')
+    for name, v in (('lo', lo), ('hi', hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+            raise AssertionError(f'count_search: {name} must be a finite number above 0, got {v!r}')
+    lo, hi = np.float64(lo), np.float64(hi)
+    if lo > hi:
+        raise AssertionError(f'count_search: lo = {lo!r} above hi = {hi!r}')
+    if steps == 1:
+        return np.array([hi], np.float64)
+    rho = hi * (lo / hi) ** (np.arange(steps, dtype=np.float64) / np.float64(steps - 1))
+    rho = np.minimum(np.maximum(rho, lo), hi)       # (rounding may leave the bracket by an ulp; monotone either way after the clamp)
+    rho = np.minimum.accumulate(rho)
+    rho[0], rho[-1] = hi, lo
+    return rho
+
+
+def count_rows(blocks, ladder, n_voxels):
+    """(B, J) int32: row b holds c[j] = block_count(rows of block b, ladder[j], n_voxels).  Non-increasing along j for a non-increasing
+    ladder, because block_count is monotone in the scale."""
+    from .model_types import block_count
+    return np.array([[block_count(len(b), rho, n_voxels) for rho in ladder] for b in blocks], np.int32).reshape(len(blocks), len(ladder))
+
+
+def count_tallies_gpu(ctx, blocks, x_hat, rows, d2=False):
+    """The twin of d1_tallies_gpu / d12_tallies_gpu(ties='pick') for candidate counts: per block float64[T_b, 5] tallies of the top-rows[b][j]
+    sets of x_hat (ops.d1_count_stats; with d2 ops.d12_count_stats, blocks then carry normals in their last three columns), j < T_b =
+    the candidates with a non-empty set.  x_hat is NOT clipped: the decoder's top-k selection ranks the raw scores."""
+    import torch
+    from . import ops
+    rows = torch.from_numpy(np.ascontiguousarray(rows, np.int32))
+    if d2:
+        _, xyz, bof, start, nrm = _upload_blocks(ctx, blocks, [], np.float32)
+        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_count_stats(ctx, x_hat, rows, xyz, bof, start, nrm)
+        return _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab, d2_ba)
+    _, xyz, bof = _upload_blocks(ctx, blocks, [])
+    s_ab, s_ba, n_b, tcount = ops.d1_count_stats(ctx, x_hat, rows, xyz, bof)
+    return _tally_tables(tcount, n_b, s_ab, s_ba)
+
+
+def decide_counts_from_tallies(blocks, tallies, rows, resolution, opt_metrics, max_deltas, with_normals=False):
+    """The decisions of the count search for a chunk: select_thresholds_from_stats, unchanged, over the J candidates of every block
+    (n_thresholds = J + 1: the max_delta eligibility, the first minimum and the mean-point guard are the threshold search's).  A returned
+    index j < J means k = rows[b][j], the 'emit nothing' index J means k = 0; a block without a positive score has no candidate and gets
+    k = 0 for every metric.  with_normals: the tallies hold D2 slots (count_tallies_gpu(d2=True)), the guard follows their tie rule.
+    Returns (names, [k per name] per block, [index per name] per block)."""
+    validate_opt_metrics(opt_metrics, with_normals=with_normals)
+    rows = np.asarray(rows)
+    J = rows.shape[1]
+    names, ks, idx = metric_names(list(opt_metrics), list(max_deltas)), [], []
+    for b, blk in enumerate(blocks):
+        names, best = select_thresholds_from_stats(len(blk), tallies[b], mean_point_tally(blk, with_normals), J + 1, resolution,
+                                                   list(opt_metrics), list(max_deltas))
+        best = list(best) + [best[-1]] * (len(names) - len(best))      # (an empty table answers once per metric: SearchSchedule._finalize)
+        idx.append([int(j) for j in best])
+        ks.append([int(rows[b][j]) if j < J else 0 for j in best])
+    return names, ks, idx

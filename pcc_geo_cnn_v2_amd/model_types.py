@@ -32,6 +32,7 @@ from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
 from ._stream_io import _Immediate, _Pinned, _host_dtypes, gather_points, indexes_to_host, on_side_stream, ship, side_stream, symbols_to_device, to_host
 from .block_search import SearchSchedule
+from .model_opt import count_rows, count_tallies_gpu, d2_on_gpu, decide_counts_from_tallies
 from .model_syntax import count_from_bytes, count_to_bytes
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
@@ -130,6 +131,35 @@ def check_count_scale(count_scale, fixed_threshold, lossless, world=1):
         raise AssertionError('count_scale and lossless: a stream carries the point counts or the occupancy layer, not both')
     if world > 1:
         raise AssertionError('count_scale is single-process only: the sharded path moves the y/z strings alone')
+
+
+def check_count_search(count_search, count_scale=None, fixed_threshold=False, lossless=False, world=1, search_ties='pick', opt_metrics=(),
+                       d2_gpu=None, dhw=None):
+    """What the count search (count_search = (lo, hi, steps)) excludes; None (off) passes.  Returns the ladder of count
+    scales (model_opt.count_ladder).  d2_gpu: whether the D2 statistics of the search come from the GPU -- a callable is asked only when a
+    d2_* metric is requested; dhw: the block grid, when known."""
+    if count_search is None:
+        return None
+    from .model_opt import count_ladder, gpu_search_supported
+    if not (isinstance(count_search, (tuple, list)) and len(count_search) == 3):
+        raise AssertionError(f'count_search must be (lo, hi, steps), got {count_search!r}')
+    ladder = count_ladder(*count_search)
+    if count_scale is not None:
+        raise AssertionError('count_search and count_scale are two policies for the same decision: pick one')
+    if fixed_threshold:
+        raise AssertionError('count_search and fixed_threshold are two policies for the same decision: pick one')
+    if lossless:
+        raise AssertionError('count_search and lossless: a stream carries the point counts or the occupancy layer, not both')
+    if world > 1:
+        raise AssertionError('count_search is single-process only: the sharded path moves the y/z strings alone')
+    if search_ties == 'mean':
+        raise AssertionError("count_search with search_ties 'mean': the tie-averaged D2 engine has no count source")
+    if any(m.startswith('d2_') for m in opt_metrics) and not (d2_gpu() if callable(d2_gpu) else d2_gpu):
+        raise AssertionError("count_search with a d2_* metric needs the D2 statistics from the GPU (d2_search 'gpu'): the host KD-tree "
+                             'path has no count source')
+    if dhw is not None and not gpu_search_supported(opt_metrics, dhw):
+        raise AssertionError(f'count_search covers block grids up to 128^3 (the GPU search engines), not {tuple(dhw)}')
+    return ladder
 
 
 def _np(t):
@@ -458,17 +488,26 @@ class CompressionModel:
 
     # ------------------------------------------------------------------ block loops
     def encode_block_range(self, sess, blocks, resolution, with_normals=False, opt_metrics=('d1_mse',),
-                           max_deltas=(np.inf,), fixed_threshold=False, debug=False, count_scale=None):
+                           max_deltas=(np.inf,), fixed_threshold=False, debug=False, count_scale=None, count_search=None):
         """The per-block part of compress_blocks (model_types.py:192-212) for a list of blocks: returns
         (strings per block, best-threshold list per block, candidate point lists per block, metric names,
         debug).  This is the unit that shards across GPUs (sharded_blocks.py).
         count_scale = rho: count-matched thresholding instead of the search: every block carries one more string, LAST,
         with k = block_count(its input rows, rho, voxels); its candidate is the k highest-scoring voxels of x_hat (ops.topk_compact) and
-        its threshold byte the fixed one."""
-        ctx = self._ctx(sess)
+        its threshold byte the fixed one.
+        count_search = (lo, hi, steps): the count search.  The chunk is encoded as under count_scale; the candidates of a
+        block are the top-k sets for k = block_count(its input rows, rho_j, voxels) over the ladder model_opt.count_ladder(lo, hi, steps),
+        scored exactly on the GPU (ops.d1_count_stats / d12_count_stats) and chosen per metric name by the threshold search's own
+        decision rule (model_opt.decide_counts_from_tallies).  The candidate of a name is ops.topk_compact(x_hat, its k).  A block's
+        strings are then the y/z strings followed by ONE COUNT STRING PER METRIC NAME, in the order of the returned names
+        (compress_blocks keeps the one of each output), and the threshold byte is the fixed one."""
         dhw = self._spatial(self.x_shape)
+        ladder = check_count_search(count_search, count_scale, fixed_threshold, self.lossless, 1, self.search_ties, opt_metrics,
+                                    lambda: d2_on_gpu(self.d2_search, 'pick'), dhw)
+        ctx = self._ctx(sess)
         check_count_scale(count_scale, fixed_threshold, self.lossless)
         counted = count_scale is not None
+        want_d2 = any(m.startswith('d2_') for m in opt_metrics)
         if not fixed_threshold:
             # once per call what the reference asserts per block (model_opt.py:22-24): unknown metric names, d2_* without normals
             from .utils.pc_metric import validate_opt_metrics
@@ -488,7 +527,19 @@ class CompressionModel:
                 ks = [block_count(len(b), count_scale, int(np.prod(dhw))) for b in chunk]
                 enc['xyz'], enc['counts'] = ops.topk_compact(ctx, enc['x_hat'], torch.tensor(ks, dtype=torch.int32).to(ctx.device, non_blocking=True))
             strings = enc['finish']()
-            if fixed_threshold or counted:
+            if ladder is not None:
+                rows = count_rows(chunk, ladder, int(np.prod(dhw)))
+                tallies = count_tallies_gpu(ctx, chunk, enc['x_hat'], rows, d2=want_d2)
+                search.names, ks_m, _ = decide_counts_from_tallies(chunk, tallies, rows, resolution, opt_metrics, max_deltas, with_normals=want_d2)
+                per_name = []
+                for m in range(len(search.names)):
+                    xyz, cnt = ops.topk_compact(ctx, enc['x_hat'], torch.tensor([k[m] for k in ks_m], dtype=torch.int32).to(ctx.device, non_blocking=True))
+                    per_name.append(self._gather_points(xyz, cnt))
+                for j in range(len(chunk)):
+                    search.thresholds.append([half] * len(search.names))
+                    search.points.append([pts_m[j] for pts_m in per_name])
+                strings = [tuple(ss) + tuple(count_to_bytes(k) for k in ks) for ss, ks in zip(strings, ks_m)]
+            elif fixed_threshold or counted:
                 # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 for every metric; under count_scale the
                 # byte is the same and the candidate is the top-k one
                 n_m = len(max_deltas) * len(opt_metrics)
@@ -509,14 +560,15 @@ class CompressionModel:
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
-                        need_points=True, metrics_device='host', d2_ties='pick', count_scale=None):
+                        need_points=True, metrics_device='host', d2_ties='pick', count_scale=None, count_search=None):
         """Uses the compression model to compress a point cloud (model_types.py:184-218).  Under torch.distributed (one
         process per GPU) the block list is sharded (sharded_blocks.py): rank 0 returns the complete result, the other ranks
         return (None, metadata without point lists, local debug list).  `need_points=False` skips the gather of the
         decoded candidate point lists to rank 0 (they are only needed for --dec_files / --debug).  metrics_device='gpu'
         (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree.  d2_ties='mean' (single process
         only): the whole-cloud D2 averages over all equidistant nearest points; the per-block threshold search is not affected.
-        count_scale (single process only): see encode_block_range."""
+        count_scale, count_search (single process only): see encode_block_range; under count_search the data of output m carries, as every
+        block's last string, the count chosen for that output's metric name."""
         from . import sharding
         from .utils.pc_metric import check_ties
         rank, world = sharding.world_info()
@@ -524,6 +576,8 @@ class CompressionModel:
         if self.lossless and world > 1:
             raise AssertionError('lossless is single-process only: the sharded path moves the y/z strings alone')
         check_count_scale(count_scale, fixed_threshold, self.lossless, world)
+        check_count_search(count_search, count_scale, fixed_threshold, self.lossless, world, self.search_ties, opt_metrics,
+                           lambda: d2_on_gpu(self.d2_search, 'pick'), None if count_search is None else self._spatial(self.x_shape))
         if metrics_device not in METRICS_DEVICES:
             raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
         if metrics_device == 'gpu' and world > 1:
@@ -540,7 +594,7 @@ class CompressionModel:
         try:
             strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
                 sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug,
-                **({} if count_scale is None else {'count_scale': count_scale}))
+                **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}))
         finally:
             tree = tree_future.result() if tree_future is not None else None
         # block -> opt metric to opt metric -> block
@@ -549,7 +603,11 @@ class CompressionModel:
         metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
                                               metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess),
                                               d2_ties=d2_ties)
-        data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
+        if count_search is not None:      # y/z strings + one count string per metric name: output m keeps its own
+            n = self.n_strings
+            data_list = [[(tuple(ss[:n]) + (ss[n + x['idx']],), t) for ss, t in zip(strings_list, threshold_list[x['idx']])] for x in metadata]
+        else:
+            data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
         return data_list, metadata, debug_t_list
 
     def roundtrip_stream(self, sess, dense_chunks, thr_idx=None, gather=True):

@@ -17,7 +17,8 @@ from .training import (  # noqa: F401
     occupancy_scores)
 from .search import (  # noqa: F401
     d1_threshold_stats, d12_threshold_stats, SearchTiePairOverflow,
-    search_tie_pair_capacity, d12_threshold_stats_ties_launch, d12_threshold_stats_ties)
+    search_tie_pair_capacity, d12_threshold_stats_ties_launch, d12_threshold_stats_ties, check_count_rows, rank_levels, d1_count_stats,
+    d12_count_stats)
 from .cloud import (  # noqa: F401
     NORMALS_COORD_LIMIT, _voxel_points, estimate_normals, CLOUD_TALLY_SLOTS, _device_u8, _device_points, CloudIndex, cloud_nearest,
     _normals64, TIE_MODES, _PAIR_LIMIT, tie_pair_capacity, _tie_mode, cloud_distortion_launch, TiePairOverflow, cloud_distortion,

@@ -1,4 +1,5 @@
-"""The per-block threshold search (include/pcc_geo.h: pcc_d1_threshold_stats, pcc_d12_threshold_stats, pcc_d12_threshold_stats_ties)."""
+"""The per-block search statistics (include/pcc_geo.h: pcc_d1_threshold_stats, pcc_d12_threshold_stats, pcc_d12_threshold_stats_ties) and their
+count-indexed twins (pcc_rank_levels, pcc_d1_count_stats, pcc_d12_count_stats)."""
 import numpy as np
 import torch
 
@@ -122,3 +123,86 @@ def d12_threshold_stats_ties(ctx, x_hat, thr, pts, block_of, block_start, normal
         assert not over, 'd12_threshold_stats_ties: the reported pair capacity did not suffice'
     res = _search_results('d12_threshold_stats_ties', *out[:-1])
     return res + ((pairs, bool(over)),) if return_status else res
+
+
+def check_count_rows(counts, B):
+    """The candidate rows of the count search: a (B,J) int32 tensor, 1 <= J <= 255, every row non-increasing (block_count is monotone in
+    the scale, so the rows of a ladder are).  Anything else is refused here, before the upload: the kernels would still stay inside
+    their buffers, but the sets they score would not be the nested top-k family.  `counts` may live on the host or the device."""
+    if not (counts.dtype == torch.int32 and counts.dim() == 2 and counts.shape[0] == B and 1 <= counts.shape[1] <= 255):
+        raise L.PccError(f'count rows: a ({B}, J) int32 tensor with 1 <= J <= 255, got {tuple(counts.shape)} {counts.dtype}')
+    if counts.shape[1] > 1 and bool((counts[:, 1:] > counts[:, :-1]).any()):
+        raise L.PccError('count rows: every row must be non-increasing (c[0] >= c[1] >= ...)')
+    return int(counts.shape[1])
+
+
+def _count_rows_device(ctx, counts, B):
+    J = check_count_rows(counts, B)
+    return counts.to(ctx.device).contiguous(), J
+
+
+def _rank_workspace(ctx, B, n):
+    return _workspace(ctx, lambda: L.lib().pcc_rank_levels_workspace_bytes(B, n),
+                      f'rank levels: {B} blocks of {n} voxels are outside the contract (n <= 2^28, B <= 65535, B n < 2^31)')
+
+
+def rank_levels(ctx, x, counts):
+    """The level grid of the count search (include/pcc_geo.h "rank levels"): lev[b][v] = #{j : rank(v) < counts[b][j]} for
+    the voxels with a positive score, rank by (score bits descending, voxel index ascending), 0 elsewhere; {lev > j} is the voxel set
+    topk_compact emits for k = counts[b][j].  x: (B,D,H,W) float32 on the context's device, each block contiguous, blocks at least D*H*W
+    elements apart; counts: (B,J) int32, rows non-increasing (check_count_rows).  Returns (lev (B,D,H,W) uint8, tcount (B,) int32) on the
+    device."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.device == ctx.device, 'rank_levels: x is a (B,D,H,W) float32 tensor on the context\'s device'
+    B, D, H, W = x.shape
+    n = D * H * W
+    assert B == 0 or n == 0 or x[0].is_contiguous(), 'rank_levels: the voxels of a block must be contiguous'
+    stride = x.stride(0) if B > 1 and n > 0 else n
+    assert stride >= n, 'rank_levels: blocks overlap'
+    counts, J = _count_rows_device(ctx, counts, B)
+    lev = torch.zeros((B, D, H, W), dtype=torch.uint8, device=x.device)
+    tcount = torch.zeros((B,), dtype=torch.int32, device=x.device)
+    if B == 0 or n == 0:
+        return lev, tcount
+    ws = _rank_workspace(ctx, B, n)
+    L.check(L.lib().pcc_rank_levels(ctx.handle, _ptr(x), stride, B, n, _ptr(counts), J, _ptr(lev), _ptr(tcount), _ptr(ws), ws.numel(), ctx.stream),
+            'pcc_rank_levels')
+    return lev, tcount
+
+
+def _count_search_args(ctx, x_hat, counts, pts, block_of, block_start=None):
+    assert x_hat.dtype == torch.float32 and x_hat.is_contiguous() and x_hat.dim() == 4
+    assert pts.dtype == torch.int32 and pts.is_contiguous() and block_of.dtype == torch.int32 and block_of.is_contiguous()
+    if block_start is not None:
+        assert block_start.dtype == torch.int32 and block_start.is_contiguous() and block_start.numel() == x_hat.shape[0] + 1
+    B, D, H, W = x_hat.shape
+    counts, J = _count_rows_device(ctx, counts, B)
+    return B, D, H, W, counts, J
+
+
+def d1_count_stats(ctx, x_hat, counts, pts, block_of):
+    """d1_threshold_stats with candidate point counts in place of thresholds (include/pcc_geo.h: pcc_d1_count_stats): entry [b][j] of
+    s_ab, s_ba, n_b is the exact D1 sum / size of the top-counts[b][j] set of block b -- the voxels topk_compact decodes for that k --
+    valid for j < tcount[b]; n_b[b][j] = min(counts[b][j], positive voxels of b).  counts: (B,J) int32, J <= 255, rows non-increasing.
+    Nothing is clipped.  Returns the tuple of d1_threshold_stats, (B,256) arrays of which the first J columns are used."""
+    B, D, H, W, counts, J = _count_search_args(ctx, x_hat, counts, pts, block_of)
+    ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
+    rws = _rank_workspace(ctx, B, D * H * W)
+    s_ab, hsum, hcnt, tcount = out = _search_outputs(x_hat, d2=False)
+    L.check(L.lib().pcc_d1_count_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(counts), J, _ptr(pts), _ptr(block_of), pts.shape[0], _ptr(ws),
+                                       _ptr(rws), rws.numel(), _ptr(s_ab), _ptr(hsum), _ptr(hcnt), _ptr(tcount), ctx.stream), 'pcc_d1_count_stats')
+    return _search_results('d1_count_stats', *out)
+
+
+def d12_count_stats(ctx, x_hat, counts, pts, block_of, block_start, normals):
+    """d1_count_stats plus the D2 sums of every candidate count (include/pcc_geo.h: pcc_d12_count_stats), the tie rule of
+    d12_threshold_stats.  Returns (s_ab, s_ba, n_b, tcount, d2_ab, d2_ba)."""
+    B, D, H, W, counts, J = _count_search_args(ctx, x_hat, counts, pts, block_of, block_start)
+    assert normals.dtype == torch.float32 and normals.is_contiguous() and normals.shape == pts.shape
+    ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
+    ws2 = _workspace(ctx, L.lib().pcc_d12_search_workspace_bytes(B, D, H, W, pts.shape[0]))
+    rws = _rank_workspace(ctx, B, D * H * W)
+    s_ab, hsum, hcnt, tcount, d2_ab, d2_ba = out = _search_outputs(x_hat, d2=True)
+    L.check(L.lib().pcc_d12_count_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(counts), J, _ptr(pts), _ptr(block_of), _ptr(block_start),
+                                        pts.shape[0], _ptr(normals), _ptr(ws), _ptr(ws2), _ptr(rws), rws.numel(), _ptr(s_ab), _ptr(hsum),
+                                        _ptr(hcnt), _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba), ctx.stream), 'pcc_d12_count_stats')
+    return _search_results('d12_count_stats', *out)
