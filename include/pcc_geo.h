@@ -522,6 +522,18 @@ int pcc_cloud_map_colors(pcc_ctx* ctx, const void* index, int64_t npts, const ui
 size_t pcc_cloud_color_workspace_bytes(int64_t na, int64_t nb);
 int pcc_cloud_color_distortion(pcc_ctx* ctx, const void* index_a, int64_t na, const uint8_t* a_colours, const void* index_b, int64_t nb,
                                const uint8_t* b_colours, double* tally, void* workspace, void* stream);
+/* Colour transfer (new; a simplified MPEG-style recolouring, NOT TMC13-conformant): colours for B that make the A->B sums above
+ * small (the least-squares ones where every row of A has a single nearest row of B, up to the final rounding).  Every row a of A votes for ALL rows of B at the smallest squared distance from a; row b gathers the exact
+ * integer sums S_b[R,G,B] of its voters' colours and their number V_b.  A row with V_b = 0 takes S_b and n from its own tie set in
+ * A (all rows of A at the smallest squared distance from b) instead.  out_colours[b][c] = (2 S_b[c] + n) / (2 n) in integer
+ * division, n = V_b or the size of that tie set: the mean rounded half up, no floating point.  votes (int32[nb], may be NULL) =
+ * V_b, 0 for a row that fell back.  The sums are 64-bit and the counts 32-bit integer atomics: exact for every na < 2^31 and the
+ * same bits whatever the order of the votes, the row order of A, or (row for row) of B; duplicate rows of B get the same colour.
+ * B is given as its own index (pcc_cloud_index_build over its nb points).  workspace: pcc_cloud_transfer_workspace_bytes(na, nb)
+ * bytes (0 for a size outside [1, 2^31)), zeroed by the call on the stream.  No host synchronisation.                          */
+size_t pcc_cloud_transfer_workspace_bytes(int64_t na, int64_t nb);
+int pcc_cloud_transfer_colors(pcc_ctx* ctx, const void* index_a, int64_t na, const uint8_t* a_colours, const void* index_b, int64_t nb,
+                              uint8_t* out_colours, int32_t* votes, void* workspace, void* stream);
 
 /* ---- mesh sampling (new: the reference's dataset step src/ds_mesh_to_pc.py, pyntcloud's mesh_random sampler + voxelisation) -----
  * A triangle mesh to a voxelised point cloud, reproducible from a seed.  Inputs (device): verts (nverts,3) float64, tris (ntris,3)

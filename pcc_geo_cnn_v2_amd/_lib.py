@@ -35,6 +35,7 @@ EXPORTS = [
     'pcc_cloud_index_bytes', 'pcc_cloud_index_build', 'pcc_cloud_nearest', 'pcc_cloud_distortion_workspace_bytes', 'pcc_cloud_distortion',
     'pcc_cloud_distortion_ties_workspace_bytes', 'pcc_cloud_distortion_ties',
     'pcc_cloud_map_colors', 'pcc_cloud_color_workspace_bytes', 'pcc_cloud_color_distortion',
+    'pcc_cloud_transfer_workspace_bytes', 'pcc_cloud_transfer_colors',
     'pcc_mesh_sample_workspace_bytes', 'pcc_mesh_to_points', 'pcc_render_workspace_bytes', 'pcc_render_points',
     'pcc_conv_wgrad_workspace_bytes', 'pcc_conv_wgrad_slices', 'pcc_conv3d_wgrad', 'pcc_relu_backward', 'pcc_focal_loss_grad', 'pcc_conv_repack_map',
     'pcc_conv_repack_weights_device',
@@ -175,6 +176,9 @@ def lib():
     L.pcc_cloud_color_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.pcc_cloud_color_workspace_bytes.restype = sz
     L.pcc_cloud_color_distortion.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp]
+    L.pcc_cloud_transfer_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    L.pcc_cloud_transfer_workspace_bytes.restype = sz
+    L.pcc_cloud_transfer_colors.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp]
     L.pcc_mesh_sample_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
     L.pcc_mesh_sample_workspace_bytes.restype = sz
     L.pcc_mesh_to_points.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int64, C.c_uint64, i32, vp, vp, vp, vp, vp]

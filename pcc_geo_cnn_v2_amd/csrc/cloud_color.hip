@@ -7,7 +7,9 @@
 //   - distortion: over ALL indexed points at the smallest squared distance, the exact integer sums S of R, G, B and their count;
 //     m = S / count and d = c_q - m in float64, then the BT.709 terms eY = (0.2126 dR + 0.7152 dG) + 0.0722 dB,
 //     eU = (-0.1146 dR - 0.3854 dG) + 0.5 dB, eV = (0.5 dR - 0.4542 dG) - 0.0458 dB, every operation rounded (no contraction);
-//     tally float64[6] = the sums of eY^2, eU^2, eV^2 for A -> B (each A point against B), then for B -> A.
+//     tally float64[6] = the sums of eY^2, eU^2, eV^2 for A -> B (each A point against B), then for B -> A;
+//   - transfer (pinned by tests/test_transfer_gpu.py against utils/pc_metric.transfer_colors_host): the colour of a row of B that
+//     minimises the A -> B sums above, the mean of the rows of A that have it in their tie set, rounded half up in integers.
 //
 // Search: the cell index of cell_index.h (built by pcc_cloud_index_build), one lane per query, queries in the query cloud's
 // Morton order (its index records), as k_query<true> of cloud_metrics.hip.  Tally: the per-point terms are written by row and
@@ -144,7 +146,120 @@ ColorLayout color_layout(long long na, long long nb) {
     return l;
 }
 
+// ---- transfer ------------------------------------------------------------------------------------------------------------------
+// Least-squares recolouring (DESIGN.md §4.9 "Colour transfer"): every row of A votes for ALL rows of B at its smallest squared
+// distance; a row of B takes the mean of its voters' colours, or, with no voter, of its own equidistant nearest rows of A; the mean
+// is rounded half up in integers, (2 S + n) / (2 n).  The accumulators are integers and only ever added to, so the bits do not
+// depend on the order in which the votes arrive: 64-bit sums (255 * N_A < 2^39) and a 32-bit vote count (<= N_A < 2^31), exact for
+// every size the entry point accepts.
+
+struct TransferLayout {
+    size_t sums, votes, total;          // unsigned long long[3 * nb], unsigned[nb]
+};
+
+TransferLayout transfer_layout(long long nb) {
+    TransferLayout l;
+    Carver w;
+    l.sums = w.take((size_t)nb * 24);
+    l.votes = w.take((size_t)nb * 4);
+    l.total = w.o;
+    return l;
+}
+
+// Second visit of a query whose smallest squared distance is known: the bound is that distance from the start, so the search covers
+// every row at it (each once) and stops as the first one did or earlier; every such row receives the query's colour and one vote.
+struct VoteScatter {
+    unsigned long long d2;
+    unsigned c[3];
+    unsigned long long* sums;
+    unsigned* votes;
+    __device__ __forceinline__ void consider(unsigned long long d, unsigned r) {
+        if (d != d2) return;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) atomicAdd(&sums[3 * (long long)r + k], (unsigned long long)c[k]);
+        atomicAdd(&votes[r], 1u);
+    }
+    __device__ __forceinline__ unsigned long long bound() const { return d2; }
+};
+
+// One lane per record of A (Morton order) against B's index: two searches, the first for the distance, the second scatters.
+__global__ void __launch_bounds__(256) k_vote(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
+                                              const int4* __restrict__ recs, long long n, const int4* __restrict__ qrecs,
+                                              const uint8_t* __restrict__ qcolours, long long nq, unsigned long long* __restrict__ sums,
+                                              unsigned* __restrict__ votes) {
+    const Cells g = cells(H, codes, recs, n);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += (long long)gridDim.x * blockDim.x) {
+        const int4 q = qrecs[t];
+        const int qc[3] = {q.x, q.y, q.z};
+        const TieVisitor<> best = search(g, qc, 0, TieVisitor<>());
+        const long long row = q.w;
+        VoteScatter sc;
+        sc.d2 = best.d2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sc.c[k] = qcolours[3 * row + k];
+        sc.sums = sums;
+        sc.votes = votes;
+        search(g, qc, 0, sc);
+    }
+}
+
+// One lane per record of B: the rounded mean of its votes, or of its own tie set in A's index when nobody voted for it.
+__global__ void __launch_bounds__(256) k_transfer(const IndexHdr* __restrict__ H, const unsigned long long* __restrict__ codes,
+                                                  const int4* __restrict__ recs, long long n, const uint8_t* __restrict__ colours,
+                                                  const int4* __restrict__ qrecs, long long nq,
+                                                  const unsigned long long* __restrict__ sums, const unsigned* __restrict__ votes,
+                                                  uint8_t* __restrict__ out, int32_t* __restrict__ out_votes) {
+    const Cells g = cells(H, codes, recs, n);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nq; t += (long long)gridDim.x * blockDim.x) {
+        const int4 q = qrecs[t];
+        const long long row = q.w;
+        const unsigned v = votes[row];
+        unsigned long long s[3], cnt = v;
+        if (v) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s[k] = sums[3 * row + k];
+        } else {
+            const int qc[3] = {q.x, q.y, q.z};
+            TieSet init;
+            init.over.colours = colours;
+            const TieSet ties = search(g, qc, 0, init);
+            cnt = ties.count;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s[k] = ties.over.s[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[3 * row + k] = (uint8_t)((2 * s[k] + cnt) / (2 * cnt));
+        if (out_votes) out_votes[row] = (int32_t)v;
+    }
+}
+
 }  // namespace
+
+PCC_API size_t pcc_cloud_transfer_workspace_bytes(int64_t na, int64_t nb) {
+    if (!valid_n(na) || !valid_n(nb)) return 0;
+    return transfer_layout(nb).total;
+}
+
+PCC_API int pcc_cloud_transfer_colors(pcc_ctx* ctx, const void* index_a, int64_t na, const uint8_t* a_colours, const void* index_b,
+                                      int64_t nb, uint8_t* out_colours, int32_t* votes, void* workspace, void* stream) {
+    PCC_REQUIRE(ctx && index_a && a_colours && index_b && out_colours && workspace, "pcc_cloud_transfer_colors: NULL argument");
+    PCC_REQUIRE(valid_n(na) && valid_n(nb), "pcc_cloud_transfer_colors: na = %lld, nb = %lld outside [1, 2^31)", (long long)na,
+                (long long)nb);
+    PCC_CHECK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const IndexView A = index_view(index_a, na), B = index_view(index_b, nb);
+    const TransferLayout l = transfer_layout(nb);
+    unsigned char* w = (unsigned char*)workspace;
+    unsigned long long* sums = (unsigned long long*)(w + l.sums);
+    unsigned* cnt = (unsigned*)(w + l.votes);
+    PCC_CHECK_HIP(hipMemsetAsync(w, 0, l.total, st));
+    hipLaunchKernelGGL(k_vote, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, B.hdr, B.codes, B.recs, B.n, A.recs, a_colours, A.n,
+                       sums, cnt);
+    hipLaunchKernelGGL(k_transfer, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A.hdr, A.codes, A.recs, A.n, a_colours, B.recs,
+                       B.n, (const unsigned long long*)sums, (const unsigned*)cnt, out_colours, votes);
+    PCC_CHECK_HIP(hipGetLastError());
+    return PCC_OK;
+}
 
 PCC_API int pcc_cloud_map_colors(pcc_ctx* ctx, const void* index, int64_t npts, const uint8_t* colours, const void* query_index, int64_t nq,
                                  int32_t rank, uint8_t* out_colours, int32_t* rows, void* stream) {

@@ -3,7 +3,7 @@
   python -m pcc_geo_cnn_v2_amd.ev_experiment --output_dir OUT --model_dir models/c3p/1.00e-04 --model_config c3p --pc_name loot
       --input_pc loot.ply [--input_norm loot_n.ply | --estimate_normals] --resolution 1024 [--octree_level 4]
       --opt_metrics d1_mse d2_mse --max_deltas inf [--fixed_threshold | --count_threshold [RHO] | --count_search [LO HI STEPS]] [--no_merge_coding] [--metrics_device host|gpu]
-      [--d2_ties pick|mean] [--consistency assert|warn]
+      [--d2_ties pick|mean] [--consistency assert|warn] [--recolor rank2|transfer]
 
 Files in OUT, per optimisation group g (d1 always; d2 only when a d2_* metric is asked for, which needs normals):
 
@@ -12,6 +12,10 @@ Files in OUT, per optimisation group g (d1 always; d2 only when a d2_* metric is
                                                no_merge_coding, by the decoder
   <pc_name>_<g>.ply.bin.ply.color.ply          the decoded cloud with the original's colours (map_color), when the input has colours
   report_<g>.json                              ev_report.build_report's dictionary of those files + enc_dec_d1_psnr_diff
+
+--recolor picks the colour step: rank2 (default; the reference's map_color, ops.map_colors rank 2) or transfer (ops.transfer_colors,
+DESIGN.md 4.9 "Colour transfer": the mean of the original points nearest to each decoded point; not TMC13-conformant).  With
+transfer, and only then, the reports written gain "recolor": "transfer".
 
 The reference starts one Python process per step and one pc_error per report.  Here every step runs in the calling process on
 a `Resident`: the GPU context, the original cloud with its normals, octree partition, KD-tree and GPU cell index, and the
@@ -44,6 +48,7 @@ logger = logging.getLogger(__name__)
 DIFF_KEY = 'enc_dec_d1_psnr_diff'
 DIFF_BOUND = 0.01
 CONSISTENCY = ('assert', 'warn')
+RECOLOR = ('rank2', 'transfer')
 
 
 class Original:
@@ -237,13 +242,17 @@ def _decode(res, enc_pcs, dec_pcs, model_dir, model_config, batch_size, precisio
         pc_io.write_df(dec, pc_io.pa_to_df(pa))
 
 
-def _recolor(res, original, dec, out):
-    """map_color.map_color with the original's resident colours and index."""
+def _recolor(res, original, dec, out, recolor='rank2'):
+    """map_color.map_color (rank 2, or mode 'transfer') with the original's resident colours and index."""
     import pandas as pd
     from . import ops
     from .utils import pc_io
+    assert recolor in RECOLOR, f'recolor must be one of {RECOLOR}, got {recolor!r}'
     target = pc_io.read_ply(dec)[['x', 'y', 'z']]
-    mapped = ops.map_colors(res.ctx, original.index, original.colors, target.values, rank=2)
+    if recolor == 'transfer':
+        mapped = ops.transfer_colors(res.ctx, original.index, original.colors, target.values)
+    else:
+        mapped = ops.map_colors(res.ctx, original.index, original.colors, target.values, rank=2)
     pc_io.write_ply(out, pd.concat([target.reset_index(drop=True),
                                     pd.DataFrame({c: mapped[:, k] for k, c in enumerate(pc_io.COLOR_COLUMNS)})], axis=1))
 
@@ -293,11 +302,12 @@ def enc_dec_diff(enc_pc, report):
 def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input_norm=None, estimate_normals=False,
                    opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, no_merge_coding=False, metrics_device='host',
                    d2_ties='pick', consistency='assert', resolution=None, octree_level=4, batch_size=32, normals_k=16, resident=None,
-                   count_threshold=None, count_search=None):
+                   count_threshold=None, count_search=None, recolor='rank2'):
     """See the module docstring.  Returns {group: report dictionary} of the reports that exist afterwards."""
     from .utils.experiment import opt_groups
     from .utils.pc_metric import validate_opt_metrics
     assert consistency in CONSISTENCY, f'consistency must be one of {CONSISTENCY}, got {consistency!r}'
+    assert recolor in RECOLOR, f'recolor must be one of {RECOLOR}, got {recolor!r}'
     assert resolution is not None and int(resolution) > 0, 'resolution (the size of the voxel grid) is needed'
     assert not (input_norm and estimate_normals), 'estimate_normals and input_norm are mutually exclusive'
     assert os.path.isdir(model_dir), f'{model_dir} not found'
@@ -336,7 +346,7 @@ def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input
             _progress(dec, col, '(exists)')
         elif original.colors is not None:
             _progress(dec, col)
-            _recolor(res, original, dec, col)
+            _recolor(res, original, dec, col, recolor)
 
     # reports: every missing one in one pass over the original
     todo = [k for k, r in enumerate(report_paths) if not os.path.exists(r)]
@@ -346,6 +356,8 @@ def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input
         new = measure(res, original, [dec_pcs[k] for k in todo], [enc_pcs[k] for k in todo], resolution, metrics_device, d2_ties)
         for k, data in zip(todo, new):
             data[DIFF_KEY] = diff = enc_dec_diff(enc_pcs[k], data)
+            if recolor != 'rank2':
+                data['recolor'] = recolor
             tmp = report_paths[k] + '.tmp'
             with open(tmp, 'w') as f:
                 json.dump(data, f, sort_keys=True, indent=4)
@@ -398,6 +410,9 @@ def build_parser():
     p.add_argument('--consistency', choices=CONSISTENCY, default='assert',
                    help='Encoder / decoder D1 PSNR difference of 0.01 dB or more: assert = fail (the reference), warn = log (new)')
     p.add_argument('--batch_size', type=int, default=32, help='Blocks resident on the GPU per pass (new)')
+    p.add_argument('--recolor', choices=RECOLOR, default='rank2',
+                   help='Colour step of the decoded clouds: rank2 = the reference map_color, transfer = the mean of the nearest original '
+                        'points (ops.transfer_colors; not TMC13-conformant; new)')
     return p
 
 
@@ -419,7 +434,7 @@ def main(argv=None):
     run_experiment(a.output_dir, a.model_dir, a.model_config, a.pc_name, a.input_pc, a.input_norm, a.estimate_normals, a.opt_metrics,
                    a.max_deltas, a.fixed_threshold, a.no_merge_coding, a.metrics_device, a.d2_ties, a.consistency, resolution,
                    a.octree_level, a.batch_size, count_threshold=a.count_threshold,
-                   count_search=count_search_of(a))
+                   count_search=count_search_of(a), recolor=a.recolor)
     return 0
 
 

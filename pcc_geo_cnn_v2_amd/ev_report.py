@@ -15,7 +15,8 @@ row); `--hausdorff` adds pc_error's Hausdorff terms (utils/pc_metric.hausdorff_t
 y/u/v_mse and y/u/v_psnr (utils/pc_metric.color_table; both clouds must carry colours: recolour a decoded cloud with map_color).
 `--d2_ties mean` evaluates D2 (and its Hausdorff terms) over ALL equidistant nearest points instead of one of them (DESIGN.md
 "Tie-averaged D2"): the same numbers on either device up to float64 rounding, whatever the row order of the files; the report then
-carries "d2_ties".  Without them the report is unchanged.
+carries "d2_ties".  `--color --recolor transfer` records that map_color --mode transfer coloured the decoded cloud: the report then
+carries "recolor": "transfer" (a label, not checked).  Without them the report is unchanged.
 """
 import argparse
 import json
@@ -32,8 +33,12 @@ logger = logging.getLogger(__name__)
 
 
 def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, estimate_normals=False, normals_k=16,
-                 metrics_device='host', hausdorff=False, color=False, d2_ties='pick'):
+                 metrics_device='host', hausdorff=False, color=False, d2_ties='pick', recolor='rank2'):
     check_ties(d2_ties)
+    if recolor not in ('rank2', 'transfer'):
+        raise AssertionError(f"recolor must be rank2 or transfer, got {recolor!r}")
+    if recolor != 'rank2' and not color:
+        raise AssertionError('--recolor names the rule that coloured the decoded cloud: it goes with --color')
     if input_norm and estimate_normals:
         raise AssertionError('--estimate_normals and --input_norm are mutually exclusive')
     p1 = pc_io.load_pc(input_pc)
@@ -75,6 +80,8 @@ def build_report(input_pc, decoded_pc, enc_pc, resolution, input_norm=None, esti
         data.update({k: float(v) for k, v in color_table(color_tally, len(a), len(b)).items()})
     if d2_ties != 'pick':      # the default writes exactly the keys it always wrote
         data['d2_ties'] = d2_ties
+    if recolor != 'rank2':
+        data['recolor'] = recolor
     return data
 
 
@@ -111,13 +118,18 @@ def main():
                    help="Add pc_error's Hausdorff terms: d1_hausdorff[_AB|_BA|_psnr] (+ d2_* with normals; new)")
     p.add_argument('--color', default=False, action='store_true',
                    help="Add pc_error's colour keys y/u/v_mse and y/u/v_psnr (both clouds need red green blue; see map_color; new)")
+    p.add_argument('--recolor', choices=('rank2', 'transfer'), default='rank2',
+                   help='With --color: the rule that coloured the decoded cloud (map_color --mode); recorded in the report as '
+                        '"recolor" when it is transfer, not checked (new)')
     p.add_argument('--resolution', type=int, required=True, help='Voxel grid resolution of the input (peak = resolution - 1)')
     p.add_argument('--output', required=True, help='Report JSON path')
     args = p.parse_args()
     if args.input_norm and args.estimate_normals:
         p.error('--estimate_normals and --input_norm are mutually exclusive')
+    if args.recolor != 'rank2' and not args.color:
+        p.error('--recolor goes with --color')
     data = build_report(args.input_pc, args.decoded_pc, args.enc_pc, args.resolution, args.input_norm, args.estimate_normals, args.normals_k,
-                        args.metrics_device, args.hausdorff, args.color, args.d2_ties)
+                        args.metrics_device, args.hausdorff, args.color, args.d2_ties, args.recolor)
     with open(args.output, 'w') as f:
         json.dump(data, f, sort_keys=True, indent=4)
     enc_metric = args.enc_pc + '.enc.metric.json'

@@ -36,7 +36,9 @@ A rate directory that has a .color.ply and an entry in color_rates gains
                                                                                                        colour bits per input point, ev_report --color's
                                                                                                        y/u/v mse and psnr of the coded-colour cloud
 
-and the decoded colours are checked against anchor_color.reconstruct.  report.json is untouched.
+and the decoded colours are checked against anchor_color.reconstruct.  report.json is untouched.  The optional top-level YAML key
+recolor (rank2 | transfer, as ev_experiment --recolor) picks the rule that colours the decoded clouds; with transfer, and only then,
+report_color.json gains "recolor": "transfer".
 
 A step whose outputs exist is skipped, so the command resumes.  The GPU context, each cloud (points, normals, KD-tree / GPU index)
 and its quantisation input stay resident across the rates (ev_experiment.Resident); the reports of all rates of a cloud are measured
@@ -147,8 +149,9 @@ def run(exp, resident=None, codec='octree', color=False):
     return done
 
 
-def _code_colors(res, original, device, enc, dec, col, report, qstep):
-    """The --color step of one rate directory: the colour stream, the coded-colour cloud and report_color.json."""
+def _code_colors(res, original, device, enc, dec, col, report, qstep, recolor='rank2'):
+    """The --color step of one rate directory: the colour stream, the coded-colour cloud and report_color.json (which names the
+    recolouring rule when it is not the default)."""
     from . import anchor_color as AC
     from . import ops
     from .utils import pc_io
@@ -166,6 +169,8 @@ def _code_colors(res, original, device, enc, dec, col, report, qstep):
     out = {'color_qstep': qstep, 'color_total_size_in_bytes': len(data), 'color_bits_per_input_point': len(data) * 8 / n,
            'total_bits_per_input_point': (geometry + len(data)) * 8 / n, 'input_point_count': n}
     out.update({k: float(v) for k, v in color_table(tally, n, len(pts)).items()})
+    if recolor != 'rank2':
+        out['recolor'] = recolor
     pc_io.write_df(dec + '.coded.color.ply', pc_io.pa_to_df(np.concatenate([np.asarray(pts, np.float64), coded], axis=1)))
     with open(enc + '.color.bin.tmp', 'wb') as f:
         f.write(data)
@@ -180,6 +185,7 @@ def _run_one(exp, res, anchor, color_rates=None):
     from .utils import pc_io
     A, anchor_id, rates, device = anchor.codec, anchor.anchor_id, anchor.rates, anchor.device
     metrics_device, d2_ties = exp.get('metrics_device', 'host'), exp.get('d2_ties', 'pick')
+    recolor = exp.get('recolor', 'rank2')
     done = {'coded': 0, 'reports': 0, **({'colors': 0} if color_rates is not None else {})}
     t0 = time.perf_counter()
     for entry in exp['data']:
@@ -212,14 +218,14 @@ def _run_one(exp, res, anchor, color_rates=None):
                 logger.info(f'[{dec}] -> [{col}] (exists)')
             elif original.colors is not None:
                 logger.info(f'[{dec}] -> [{col}]')
-                _recolor(res, original, dec, col)
+                _recolor(res, original, dec, col, recolor)
             if color_rates is not None and rate in color_rates and os.path.exists(col):
                 creport = os.path.join(out, 'report_color.json')
                 if os.path.exists(creport):
                     logger.info(f'[{col}] -> [{creport}] (exists)')
                 else:
                     logger.info(f'[{col}] -> [{enc}.color.bin, {dec}.coded.color.ply, {creport}] qstep {color_rates[rate]}')
-                    _code_colors(res, original, device, enc, dec, col, creport, color_rates[rate])
+                    _code_colors(res, original, device, enc, dec, col, creport, color_rates[rate], recolor)
                     done['colors'] += 1
             if not os.path.exists(report):
                 todo.append((dec, enc, report))

@@ -9,6 +9,7 @@ without its `done` file is skipped with a warning, as in the reference.  The ref
 one per step; here all jobs share one ev_experiment.Resident: one GPU context, each original cloud (points, normals, octree
 partition, KD-tree, GPU index) loaded once, and the jobs ordered by checkpoint so that each checkpoint's weights are uploaded
 once, for all the clouds and model ids that use it.  Finished steps are skipped (ev_experiment), so the command resumes.
+The optional top-level key `recolor` (rank2 | transfer, ev_experiment --recolor) picks the colour step of every job.
 --num_parallel and --no_stream_redirection are accepted and ignored.  More than one rank (torch.distributed.run) is refused.
 """
 import argparse
@@ -21,7 +22,7 @@ from .utils import experiment as E
 
 logger = logging.getLogger(__name__)
 
-RUN_KEYS = ('estimate_normals', 'metrics_device', 'd2_ties', 'consistency', 'no_merge_coding')
+RUN_KEYS = ('estimate_normals', 'metrics_device', 'd2_ties', 'consistency', 'no_merge_coding', 'recolor')
 
 
 def build_jobs(exp):

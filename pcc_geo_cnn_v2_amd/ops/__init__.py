@@ -22,7 +22,7 @@ from .search import (  # noqa: F401
 from .cloud import (  # noqa: F401
     NORMALS_COORD_LIMIT, _voxel_points, estimate_normals, CLOUD_TALLY_SLOTS, _device_u8, _device_points, CloudIndex, cloud_nearest,
     _normals64, TIE_MODES, _PAIR_LIMIT, tie_pair_capacity, _tie_mode, cloud_distortion_launch, TiePairOverflow, cloud_distortion,
-    COLOR_TALLY_SLOTS, _colors_u8, _index_or_points, map_colors, cloud_color_distortion, mesh_to_points, render_points, error_map)
+    COLOR_TALLY_SLOTS, _colors_u8, _index_or_points, map_colors, transfer_colors, cloud_color_distortion, mesh_to_points, render_points, error_map)
 from .anchors import (  # noqa: F401
     _u8, anchor_code_bits, anchor_decode_bits, anchor_encode_nodes, AnchorDecoder, anchor_tree_launch, anchor_tree,
     anchor_expand, anchor_points, surface_encode_vertices, surface_decode_vertices, _surface_ws, _surface_hdr, surface_leaves,

@@ -250,8 +250,8 @@ def map_colors(ctx, index_a, a_colors, queries, rank=2, return_rows=False):
     its rank-th nearest point of the original cloud, points ordered by (squared distance, row).  rank=2 (the default) is the
     reference's map_color.py (the second of a k = 2 KD-tree query), rank=1 the nearest point (cloud_nearest's row).
     index_a: a CloudIndex of the original cloud or its (N,3) points; a_colors: (N,3) integer colours in 0..255; queries: (nq,3)
-    integer coordinates in [0, 2^21).  Returns (nq,3) uint8 numpy colours (and the int32 rows with return_rows=True); nq = 0 gives
-    empty arrays.  Every input is checked before the first GPU call."""
+    integer coordinates in [0, 2^21), or a CloudIndex of them.  Returns (nq,3) uint8 numpy colours (and the int32 rows with
+    return_rows=True); nq = 0 gives empty arrays.  Every input is checked before the first GPU call."""
     if rank not in (1, 2):
         raise L.PccError(f'map_colors: rank = {rank!r}, must be 1 or 2')
     index_a, n = _index_or_points(index_a, 'map_colors')
@@ -261,10 +261,10 @@ def map_colors(ctx, index_a, a_colors, queries, rank=2, return_rows=False):
     if len(queries) == 0:
         out = np.zeros((0, 3), np.uint8)
         return (out, np.zeros(0, np.int32)) if return_rows else out
-    q = _voxel_points(queries, 'map_colors')
+    q = _index_or_points(queries, 'map_colors')[0]
     if not isinstance(index_a, CloudIndex):
         index_a = CloudIndex(ctx, index_a)
-    index_q = CloudIndex(ctx, q)
+    index_q = q if isinstance(q, CloudIndex) else CloudIndex(ctx, q)
     nq = index_q.n
     colors_d = _to_device(ctx, colors)          # held in a local: a temporary's block could be handed out again before the launch
     out = torch.empty((nq, 3), dtype=torch.uint8, device=ctx.device)
@@ -273,6 +273,36 @@ def map_colors(ctx, index_a, a_colors, queries, rank=2, return_rows=False):
                                          _ptr(rows), ctx.stream), 'pcc_cloud_map_colors')
     if return_rows:
         return out.cpu().numpy(), rows.cpu().numpy()
+    return out.cpu().numpy()
+
+
+def transfer_colors(ctx, index_a, a_colors, queries, return_votes=False):
+    """Least-squares colours of the query (decoded) points from the original cloud (include/pcc_geo.h "cloud colours", DESIGN.md
+    §4.9 "Colour transfer"; a simplified MPEG-style recolouring, not TMC13-conformant): every original point votes for all query
+    points at its smallest squared distance, a query point takes the mean colour of its voters, or of its own equidistant nearest
+    original points when it has none, rounded half up in integers.  Where every original point has one nearest query point these are,
+    before rounding, the colours under which the A->B sums of cloud_color_distortion are smallest.  Inputs as map_colors: index_a a CloudIndex of the original cloud or its (N,3) points;
+    a_colors (N,3) integers in 0..255; queries (nq,3) integer coordinates in [0, 2^21) (duplicates allowed) or a CloudIndex of
+    them.  Returns (nq,3) uint8 numpy colours (and the int32 votes, 0 for a point that fell back, with return_votes=True); nq = 0
+    gives empty arrays.  Independent of the row order of either cloud; every input is checked before the first GPU call."""
+    index_a, n = _index_or_points(index_a, 'transfer_colors')
+    colors = _colors_u8(a_colors, n, 'transfer_colors')
+    if len(queries) == 0:
+        out = np.zeros((0, 3), np.uint8)
+        return (out, np.zeros(0, np.int32)) if return_votes else out
+    q = _index_or_points(queries, 'transfer_colors')[0]
+    if not isinstance(index_a, CloudIndex):
+        index_a = CloudIndex(ctx, index_a)
+    index_q = q if isinstance(q, CloudIndex) else CloudIndex(ctx, q)
+    nq = index_q.n
+    colors_d = _to_device(ctx, colors)          # alive until the launch (see map_colors)
+    out = torch.empty((nq, 3), dtype=torch.uint8, device=ctx.device)
+    votes = torch.empty((nq,), dtype=torch.int32, device=ctx.device) if return_votes else None
+    ws = _workspace(ctx, L.lib().pcc_cloud_transfer_workspace_bytes(index_a.n, nq))
+    L.check(L.lib().pcc_cloud_transfer_colors(ctx.handle, _ptr(index_a.buffer), index_a.n, _ptr(colors_d), _ptr(index_q.buffer), nq,
+                                              _ptr(out), _ptr(votes), _ptr(ws), ctx.stream), 'pcc_cloud_transfer_colors')
+    if return_votes:
+        return out.cpu().numpy(), votes.cpu().numpy()
     return out.cpu().numpy()
 
 

@@ -20,7 +20,8 @@ Keys read (everything else in the file is ignored, PCERROR and MPEG_TMC13_DIR am
     bd_ignore, mpeg_modes[] (id, label)
     TRAIN_DATASET_PATH, TRAIN_RESOLUTION, alpha, gamma, batch_size, train_mode          (tr_train_all)
 New, all optional: octree_level (top level or per cloud; default 4, the encoder's), estimate_normals, metrics_device, d2_ties,
-consistency, no_merge_coding, codec_batch_size (top level): passed to ev_experiment.run_experiment.  anchor_id, anchor_rates,
+consistency, no_merge_coding, recolor, codec_batch_size (top level): passed to ev_experiment.run_experiment (recolor, rank2 |
+transfer, also picks the colour step of ev_run_anchor).  anchor_id, anchor_rates,
 anchor_device: ev_run_anchor, which writes EXPERIMENT_DIR/gpcc/<anchor id>/ with this project's octree anchor codec (not G-PCC).
 surface_anchor_id, surface_rates: ev_run_anchor --codec surface|both, the same tree from the surface anchor codec (not G-PCC, not
 trisoup-conformant).

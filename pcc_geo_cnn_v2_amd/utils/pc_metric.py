@@ -393,6 +393,30 @@ def tie_mean_colors(points, colors, queries, k=16):
     return sums.astype(np.float64) / count[:, None].astype(np.float64)
 
 
+def transfer_colors_host(points, colors, queries):
+    """Host restatement of ops.transfer_colors (include/pcc_geo.h "cloud colours", DESIGN.md §4.9 "Colour transfer"): (colours
+    uint8[nq,3], votes int64[nq]).  Every row of `points` votes for all rows of `queries` in its tie set (tie_pairs: the exact
+    equidistant nearest set, ball query included); a query row takes the exact integer sums of its voters' colours, or, with no
+    voter, of its own tie set in `points`; colour = (2 S + n) // (2 n), the mean rounded half up.  votes is 0 where a row fell back."""
+    p, q = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(queries, np.float64).reshape(-1, 3)
+    col = np.asarray(colors, np.int64).reshape(-1, 3)
+    assert len(p) and len(q) and len(col) == len(p), 'transfer_colors_host: empty cloud or colours that do not match the points'
+    nq = len(q)
+    qa, jb, _ = tie_pairs(q, p)                                   # original row qa votes for query row jb
+    # bincount adds in float64: exact, every sum is an integer below 255 * 2^31 < 2^53
+    gather = lambda to, frm, n: np.stack([np.bincount(to, weights=col[frm, c], minlength=n) for c in range(3)], axis=1).astype(np.int64)
+    votes = np.bincount(jb, minlength=nq).astype(np.int64)
+    sums = gather(jb, qa, nq)
+    count = votes.copy()
+    rows = np.nonzero(votes == 0)[0]
+    if len(rows):
+        qb, ja, _ = tie_pairs(p, q[rows])                         # query row rows[qb] against its own tie set ja
+        sums[rows] = gather(qb, ja, len(rows))
+        count[rows] = np.bincount(qb, minlength=len(rows))
+    out = (2 * sums + count[:, None]) // (2 * count[:, None])
+    return out.astype(np.uint8), votes
+
+
 def color_tally_host(p1, c1, p2, c2):
     """Host restatement of the colour tally of ops.cloud_color_distortion (scipy KD-trees): float64[6] = the sums of eY^2, eU^2,
     eV^2 of every original point against the mean colour of its equidistant nearest decoded points, then the same for the decoded
