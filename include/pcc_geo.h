@@ -172,6 +172,21 @@ int pcc_weights_upload(pcc_ctx* ctx, int32_t transform, int32_t filters, const f
 size_t pcc_network_workspace_bytes(int32_t transform, int32_t filters, int32_t N, int32_t D, int32_t H, int32_t W);
 int pcc_network_out_dims(int32_t transform, int32_t filters, int32_t D, int32_t H, int32_t W, int32_t* OD, int32_t* OH,
                          int32_t* OW, int32_t* OC);
+/* The plan of a stack of conv layers on an N x D x H x W input: host arithmetic, no context, no device.  It is the one place
+ * that decides which tensors the fp16 mode stores as fp16 and which layer records the block maxima of its output;
+ * pcc_network_forward runs it, and a caller that chains the layers itself through pcc_conv3d asks for it to get the same bits. */
+typedef struct {
+    pcc_conv_desc desc;    /* what the layer runs with: its input dims; flags = its own | layer_flags | PCC_CONV_IN16 / OUT16 /
+                              RES16 as planned | final_flags (last layer); everything else as given                        */
+    int32_t record_amax;   /* 1: the next layer runs a two-piece fp16 kernel ("fp16 x 2" in pcc_conv_kernel_family), which scales
+                              each block by the max |x| this layer is asked to record with its output                      */
+} pcc_layer_plan;
+/* layers[i]: geometry (Cin, Cout, k, stride, transposed), own flags (BIAS / RELU / ADD) and impl of layer i as pcc_network_layer
+ * gives them (N, D, H, W ignored); roles[i]: its residual role (ibid.).  numerics: the PCC_NUM_* switches (pcc_ctx_get_numerics).
+ * fp16 storage needs layer_flags & PCC_CONV_F16, roles 1, 0, 2 and PCC_IMPL_AUTO on a block's three layers.  plan: n entries;
+ * *any_amax (may be NULL): whether any record_amax is set.                                                                  */
+int pcc_network_plan(const pcc_conv_desc* layers, const int32_t* roles, int32_t n, int32_t N, int32_t D, int32_t H, int32_t W,
+                     int32_t layer_flags, int32_t final_flags, uint32_t numerics, pcc_layer_plan* plan, int32_t* any_amax);
 /* y = transform(x).  x: (N,D,H,W,Cin) with Cin = 1 for the analysis transforms, `filters` otherwise; y: NDHWC of
  * pcc_network_out_dims.  layer_flags: 0 or PCC_CONV_F16 (every layer); final_flags: 0 or PCC_CONV_CLIP01 (last layer).
  * Results are bit-identical to the same layers issued one by one through pcc_conv3d (with layer_flags = PCC_CONV_F16 the

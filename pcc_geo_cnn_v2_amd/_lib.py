@@ -28,7 +28,7 @@ EXPORTS = [
     'pcc_d1_search_workspace_bytes', 'pcc_d1_threshold_stats', 'pcc_d12_search_workspace_bytes', 'pcc_d12_threshold_stats', 'pcc_octree_bucket',
     'pcc_d12_search_ties_chunk', 'pcc_d12_search_ties_workspace_bytes', 'pcc_d12_threshold_stats_ties',
     'pcc_network_num_layers', 'pcc_network_layer', 'pcc_weights_blob_floats', 'pcc_weights_pack', 'pcc_weights_upload',
-    'pcc_network_workspace_bytes', 'pcc_network_out_dims', 'pcc_network_forward', 'pcc_network_forward_analysis',
+    'pcc_network_workspace_bytes', 'pcc_network_out_dims', 'pcc_network_plan', 'pcc_network_forward', 'pcc_network_forward_analysis',
     'pcc_network_forward_synthesis', 'pcc_network_forward_hyper_a', 'pcc_network_forward_hyper_s',
     'pcc_codec_workspace_bytes', 'pcc_codec_encode', 'pcc_codec_decode_hyper', 'pcc_codec_decode_main',
     'pcc_profile_select', 'pcc_profile_read', 'pcc_normals_workspace_bytes', 'pcc_estimate_normals',
@@ -66,6 +66,10 @@ PCC_ERR_ARG, PCC_ERR_HIP, PCC_ERR_NOGPU, PCC_ERR_SPACE, PCC_ERR_CORRUPT = -1, -2
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('N', 'D', 'H', 'W', 'Cin', 'Cout', 'k', 'stride', 'transposed',
                                          'flags', 'impl', 'out_cstride', 'out_coffset')]
+
+
+class LayerPlan(C.Structure):            # pcc_layer_plan
+    _fields_ = [('desc', ConvDesc), ('record_amax', C.c_int32)]
 
 
 class CdfTable(C.Structure):
@@ -263,6 +267,8 @@ def lib():
     L.pcc_network_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
     L.pcc_network_workspace_bytes.restype = sz
     L.pcc_network_out_dims.argtypes = [i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.pcc_network_plan.argtypes = [C.POINTER(ConvDesc), C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, C.c_uint32, C.POINTER(LayerPlan),
+                                   C.POINTER(i32)]
     for fn in (L.pcc_network_forward, L.pcc_network_forward_analysis, L.pcc_network_forward_synthesis,
                L.pcc_network_forward_hyper_a, L.pcc_network_forward_hyper_s):
         fn.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, sz, i32, i32, vp]

@@ -108,8 +108,8 @@ enum pcc_conv_family {
 };
 pcc_conv_family pcc_conv_route(const pcc_conv_desc* d, uint32_t numerics);
 // the two fp16-pair families scale each block by the max |x| of their input: the layer that produces it records it
-inline bool pcc_conv_wants_amax(const pcc_ctx* ctx, const pcc_conv_desc* d) {
-    const pcc_conv_family f = pcc_conv_route(d, ctx->numerics);
+inline bool pcc_conv_wants_amax(const pcc_conv_desc* d, uint32_t numerics) {
+    const pcc_conv_family f = pcc_conv_route(d, numerics);
     return f == PCC_FAM_WINO_F16S || f == PCC_FAM_TR2M_F16S;
 }
 int pcc_conv3d_ext(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* w, const float* w_packed, const float* bias,

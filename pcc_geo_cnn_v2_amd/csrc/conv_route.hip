@@ -242,7 +242,7 @@ PCC_API int pcc_conv_pack_weights(const pcc_conv_desc* d, const float* w, float*
 // The kernel family that computes a layer: a function of the layer (shape, flags, impl) and the context's numerics word only, never
 // of the batch -- encoder and decoder run with different batch sizes, and the family is part of the stream's identity (DESIGN.md
 // section 5).  Everything that depends on the choice reads it here: the dispatch below, pcc_conv_kernel_family, the block-maximum rows
-// of pcc_network_forward (pcc_conv_wants_amax) and the generic / MFMA decision of pcc_conv3d.
+// of pcc_network_plan (pcc_conv_wants_amax) and the generic / MFMA decision of pcc_conv3d.
 pcc_conv_family pcc_conv_route(const pcc_conv_desc* d, uint32_t numerics) {
     auto num = [numerics](uint32_t bits) { return (numerics & bits) != 0; };
     const Plan p = make_plan(d);

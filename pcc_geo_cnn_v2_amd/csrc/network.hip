@@ -106,17 +106,25 @@ size_t blob_layout(const std::vector<LayerSpec>& v, int cin0, std::vector<LayerI
     return off;
 }
 
-void out_dims(const LayerSpec& L, int& D, int& H, int& W) {
-    if (L.transposed) { D *= L.stride; H *= L.stride; W *= L.stride; }
-    else { D = pcc_same_out(D, L.stride); H = pcc_same_out(H, L.stride); W = pcc_same_out(W, L.stride); }
+// pcc_network_plan of a transform's own stack: every layer with the dims, flags and block-maxima request it runs with
+int plan_transform(const std::vector<LayerSpec>& v, int cin0, int N, int D, int H, int W, int layer_flags, int final_flags,
+                   uint32_t numerics, std::vector<pcc_layer_plan>& plan, int32_t* any_amax) {
+    std::vector<pcc_conv_desc> geo;
+    std::vector<int32_t> roles;
+    for (const LayerSpec& L : v) {
+        geo.push_back(layer_desc(L, geo.empty() ? cin0 : geo.back().Cout, 0, 0, 0, 0, 0));
+        roles.push_back(L.res);
+    }
+    plan.resize(v.size());
+    return pcc_network_plan(geo.data(), roles.data(), (int32_t)v.size(), N, D, H, W, layer_flags, final_flags, numerics, plan.data(), any_amax);
 }
 
 // activations: three rotating buffers (x -> t1 -> t -> t1 + t reuses x's buffer), each as large as the largest intermediate
-size_t act_floats(const std::vector<LayerSpec>& v, int N, int D, int H, int W) {
+size_t act_floats(const std::vector<pcc_layer_plan>& plan) {
     size_t mx = 0;
-    for (size_t i = 0; i + 1 < v.size(); ++i) {
-        out_dims(v[i], D, H, W);
-        const size_t n = (size_t)N * D * H * W * v[i].cout;
+    for (size_t i = 1; i < plan.size(); ++i) {
+        const pcc_conv_desc& d = plan[i].desc;       // (its input is the output of layer i - 1)
+        const size_t n = (size_t)d.N * d.D * d.H * d.W * d.Cin;
         if (n > mx) mx = n;
     }
     return align64(mx);
@@ -220,17 +228,77 @@ PCC_API int pcc_weights_upload(pcc_ctx* ctx, int32_t transform, int32_t filters,
 PCC_API size_t pcc_network_workspace_bytes(int32_t transform, int32_t filters, int32_t N, int32_t D, int32_t H, int32_t W) {
     std::vector<LayerSpec> v;
     int c0;
-    if (!build_layers(transform, filters, v, &c0) || N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    return 3 * act_floats(v, N, D, H, W) * sizeof(float) + 256 + amax_bytes(v.size(), N);
+    std::vector<pcc_layer_plan> plan;
+    if (!build_layers(transform, filters, v, &c0) || plan_transform(v, c0, N, D, H, W, 0, 0, 0, plan, nullptr) != PCC_OK) return 0;
+    return 3 * act_floats(plan) * sizeof(float) + 256 + amax_bytes(v.size(), N);
 }
 
 PCC_API int pcc_network_out_dims(int32_t transform, int32_t filters, int32_t D, int32_t H, int32_t W, int32_t* OD, int32_t* OH,
                                  int32_t* OW, int32_t* OC) {
     std::vector<LayerSpec> v;
     int c0;
+    std::vector<pcc_layer_plan> plan;
     PCC_REQUIRE(OD && OH && OW && OC && build_layers(transform, filters, v, &c0), "pcc_network_out_dims: bad argument");
-    for (const LayerSpec& L : v) out_dims(L, D, H, W);
-    *OD = D; *OH = H; *OW = W; *OC = v.back().cout;
+    const int rc = plan_transform(v, c0, 1, D, H, W, 0, 0, 0, plan, nullptr);
+    if (rc != PCC_OK) return rc;
+    *OC = v.back().cout;
+    return pcc_conv_out_dims(&plan.back().desc, OD, OH, OW);
+}
+
+// the three layers at p (roles at r) are a residual block whose two mid-block tensors the fp16 mode stores as fp16
+static bool block_stores_fp16(const pcc_layer_plan* p, const int32_t* r) {
+    const pcc_conv_desc& d0 = p[0].desc;
+    if (!(r[0] == 1 && r[1] == 0 && r[2] == 2 && d0.k == 3 && d0.stride == 2 && (d0.Cout == 16 || d0.Cout == 32 || d0.Cout == 64))) return false;
+    if (d0.H % 2 || d0.W % 2 || p[1].desc.H % 16 || p[1].desc.W % 16) return false;
+    // every layer of the block must be able to take its fp16 role: pcc_conv3d has no fallback for IN16 / RES16, a layer on the
+    // generic path cannot hand over in fp16, and a caller's impl override chooses a kernel that knows no fp16 tensors
+    if (d0.impl != PCC_IMPL_AUTO || pcc_conv_mfma_supported(&d0) != 1) return false;
+    for (int q = 1; q <= 2; ++q) {          // (k3 stride 1: pcc_f16_eligible)
+        const pcc_conv_desc& dq = p[q].desc;
+        if (dq.impl != PCC_IMPL_AUTO || pcc_conv_mfma_supported(&dq) != 1 || !pcc_f16_eligible(&dq)) return false;
+    }
+    return true;
+}
+
+PCC_API int pcc_network_plan(const pcc_conv_desc* layers, const int32_t* roles, int32_t n, int32_t N, int32_t D, int32_t H, int32_t W,
+                             int32_t layer_flags, int32_t final_flags, uint32_t numerics, pcc_layer_plan* plan, int32_t* any_amax) {
+    PCC_REQUIRE(layers && roles && plan, "pcc_network_plan: NULL argument");
+    PCC_REQUIRE(n > 0, "pcc_network_plan: %d layers", n);
+    PCC_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "pcc_network_plan: non-positive dimension");
+    for (int i = 0; i < n; ++i) {
+        pcc_conv_desc& d = plan[i].desc;
+        d = layers[i];
+        d.N = N; d.D = D; d.H = H; d.W = W;
+        d.flags |= layer_flags | (i + 1 == n ? final_flags : 0);
+        plan[i].record_amax = 0;
+        const int rc = pcc_conv_out_dims(&d, &D, &H, &W);
+        if (rc != PCC_OK) return rc;
+    }
+    // fp16 mode: inside an AnalysisBlock / SynthesisBlock (width 16, 32 or 64) the two intermediate tensors (tensor1 and the
+    // output of the middle conv) live in HBM as fp16: the stride-2 (transposed) conv hands over in fp16 (PCC_CONV_OUT16), the two k3
+    // stride-1 convs run on conv_f16.hip (PCC_CONV_IN16), the last one adds the fp16 residual and writes fp32 for the next block.
+    for (int i = 0; (layer_flags & PCC_CONV_F16) && i + 2 < n; ++i) {
+        if (!block_stores_fp16(plan + i, roles + i)) continue;
+        plan[i].desc.flags |= PCC_CONV_OUT16;
+        plan[i + 1].desc.flags |= PCC_CONV_IN16 | PCC_CONV_OUT16;
+        plan[i + 2].desc.flags |= PCC_CONV_IN16 | PCC_CONV_RES16;
+        // the block's output stays fp16 when its only consumer is the final 16 -> 1 transposed conv (which then reads 8 B
+        // per lane and contracts with one fp16 MFMA)
+        if (i + 4 == n) {
+            pcc_conv_desc& df = plan[i + 3].desc;
+            if (df.transposed && df.Cout == 1 && df.k == 3 && df.stride == 1 && plan[i + 2].desc.Cout == 16 && df.impl == PCC_IMPL_AUTO &&
+                pcc_conv_mfma_supported(&df) == 1) {
+                plan[i + 2].desc.flags |= PCC_CONV_OUT16;
+                df.flags |= PCC_CONV_IN16;
+            }
+        }
+        i += 2;
+    }
+    // pre-scale side channel: a layer records the max |x| of its output blocks when the next one takes an fp16-split kernel
+    bool any = false;
+    for (int i = 0; !(layer_flags & PCC_CONV_F16) && i + 1 < n; ++i)
+        if (pcc_conv_wants_amax(&plan[i + 1].desc, numerics)) { plan[i].record_amax = 1; any = true; }
+    if (any_amax) *any_amax = any;
     return PCC_OK;
 }
 
@@ -260,7 +328,11 @@ static int network_forward(pcc_ctx* ctx, int32_t transform, int32_t filters, con
     PCC_REQUIRE((layer_flags & ~PCC_CONV_F16) == 0 && (final_flags & ~PCC_CONV_CLIP01) == 0,
                 "pcc_network_forward: layer_flags may hold PCC_CONV_F16, final_flags PCC_CONV_CLIP01");
     blob_layout(v, c0, im);
-    const size_t af = act_floats(v, N, D, H, W);
+    std::vector<pcc_layer_plan> plan;
+    int32_t any_amax = 0;
+    int rc = plan_transform(v, c0, N, D, H, W, layer_flags, final_flags, ctx->numerics, plan, &any_amax);
+    if (rc != PCC_OK) return rc;
+    const size_t af = act_floats(plan);
     PCC_REQUIRE(v.size() == 1 || (workspace && workspace_bytes >= 3 * af * sizeof(float) + amax_bytes(v.size(), N)),
                 "pcc_network_forward: workspace too small (need pcc_network_workspace_bytes)");
     float* buf[3];
@@ -278,63 +350,14 @@ static int network_forward(pcc_ctx* ctx, int32_t transform, int32_t filters, con
     const float* t1 = nullptr;
     int cur = 0;                 // rotating buffer that receives the next output
     int in_buf = -1, t1_buf = -1;
-    // fp16 mode: inside an AnalysisBlock / SynthesisBlock (width 16, 32 or 64) the two intermediate tensors (tensor1 and the
-    // output of the middle conv) live in HBM as fp16: the stride-2 (transposed) conv hands over in fp16 (PCC_CONV_OUT16), the two k3
-    // stride-1 convs run on conv_f16.hip (PCC_CONV_IN16), the last one adds the fp16 residual and writes fp32 for the next block.
-    int f16_block_left = 0;      // layers of the current fp16-storage block still to come
-    bool final_in16 = false;
-    // pre-scale side channel: does some layer take an fp16-split kernel at all (then the rows are zeroed once, here)?
+    // pre-scale side channel: the rows are zeroed once, here, when some layer is asked to record into its row at all
     bool amax_prev = false;      // the previous layer's kernel recorded the max |x| of its output blocks into its row
-    if (amax && !(layer_flags & PCC_CONV_F16)) {
-        bool any = false;
-        int aD = D, aH = H, aW = W;
-        for (size_t i = 0; i < v.size(); ++i) {
-            const pcc_conv_desc da = layer_desc(v[i], im[i].cin, N, aD, aH, aW, 0);
-            if (i > 0 && pcc_conv_wants_amax(ctx, &da)) any = true;
-            out_dims(v[i], aD, aH, aW);
-        }
-        if (any) { PCC_CHECK_HIP(hipSetDevice(ctx->device)); PCC_CHECK_HIP(hipMemsetAsync(amax, 0, amax_bytes(v.size(), N), (hipStream_t)stream)); }
-        else amax = nullptr;
-    } else amax = nullptr;
+    if (amax && any_amax) { PCC_CHECK_HIP(hipSetDevice(ctx->device)); PCC_CHECK_HIP(hipMemsetAsync(amax, 0, amax_bytes(v.size(), N), (hipStream_t)stream)); }
+    else amax = nullptr;
     for (size_t i = 0; i < v.size(); ++i) {
         const LayerSpec& L = v[i];
         const bool last = i + 1 == v.size();
-        int storage = 0;
-        const int oH = L.transposed ? 2 * H : H / 2, oW = L.transposed ? 2 * W : W / 2;      // (stride-2 layers)
-        if ((layer_flags & PCC_CONV_F16) && L.res == 1 && L.stride == 2 && L.k == 3 && (L.cout == 16 || L.cout == 32 || L.cout == 64) &&
-            oH % 16 == 0 && oW % 16 == 0 && H % 2 == 0 && W % 2 == 0 && i + 2 < v.size() && v[i + 1].res == 0 && v[i + 2].res == 2 &&
-            v[i + 1].k == 3 && v[i + 1].stride == 1 && v[i + 2].k == 3 && v[i + 2].stride == 1 &&
-            [&] {   // every layer of the block must be able to take its fp16 role: pcc_conv3d has no fallback for IN16 / RES16
-                const pcc_conv_desc d0 = layer_desc(L, im[i].cin, N, D, H, W, layer_flags);
-                if (pcc_conv_mfma_supported(&d0) != 1) return false;     // (a layer on the generic path cannot hand over in fp16)
-                int bD = D, bH = H, bW = W;
-                out_dims(L, bD, bH, bW);
-                for (size_t q = i + 1; q <= i + 2; ++q) {
-                    const pcc_conv_desc dq = layer_desc(v[q], im[q].cin, N, bD, bH, bW, layer_flags | PCC_CONV_IN16);
-                    if (pcc_conv_mfma_supported(&dq) != 1 || !pcc_f16_eligible(&dq)) return false;
-                }
-                return true;
-            }()) {
-            storage = PCC_CONV_OUT16;
-            f16_block_left = 2;
-        } else if (f16_block_left == 2) {
-            storage = PCC_CONV_IN16 | PCC_CONV_OUT16;
-            f16_block_left = 1;
-        } else if (f16_block_left == 1) {
-            storage = PCC_CONV_IN16 | PCC_CONV_RES16;
-            f16_block_left = 0;
-            // the block's output stays fp16 when its only consumer is the final 16 -> 1 transposed conv (which then reads 8 B
-            // per lane and contracts with one fp16 MFMA)
-            if (i + 2 == v.size() && v[i + 1].transposed && v[i + 1].cout == 1 && v[i + 1].k == 3 && v[i + 1].stride == 1 && L.cout == 16 &&
-                [&] { const pcc_conv_desc df = layer_desc(v[i + 1], im[i + 1].cin, N, D, H, W, layer_flags | PCC_CONV_IN16);
-                      return pcc_conv_mfma_supported(&df) == 1; }()) {
-                storage |= PCC_CONV_OUT16;
-                final_in16 = true;
-            }
-        } else if (last && final_in16) {
-            storage = PCC_CONV_IN16;
-        }
-        pcc_conv_desc d = layer_desc(L, im[i].cin, N, D, H, W, layer_flags | storage | (last ? final_flags : 0));
+        const pcc_conv_desc& d = plan[i].desc;
         float* out;
         if (last) out = y;
         else {
@@ -350,17 +373,11 @@ static int network_forward(pcc_ctx* ctx, int32_t transform, int32_t filters, con
             }
             PCC_CHECK_HIP(hipEventRecord(prof->ev[prof->used], st));
         }
-        int rc;
         // the layer's input maxima (if its producer recorded them) and where its own go (if the next layer will ask for them)
         pcc_conv_ext ext = {nullptr, nullptr, false};
         if (amax) {
             if (i > 0 && amax_prev) ext.in_amax = amax + (i - 1) * amax_row(N);
-            if (!last) {
-                int nD = D, nH = H, nW = W;
-                out_dims(L, nD, nH, nW);
-                const pcc_conv_desc dn = layer_desc(v[i + 1], im[i + 1].cin, N, nD, nH, nW, 0);
-                if (pcc_conv_wants_amax(ctx, &dn)) ext.out_amax = amax + i * amax_row(N);
-            }
+            if (plan[i].record_amax) ext.out_amax = amax + i * amax_row(N);
         }
         if (last && fuse && im[i].pk_floats && d.impl == PCC_IMPL_AUTO && pcc_conv_mfma_supported(&d) == 1) {
             PCC_CHECK_HIP(hipSetDevice(ctx->device));
@@ -373,7 +390,6 @@ static int network_forward(pcc_ctx* ctx, int32_t transform, int32_t filters, con
         if (rc != PCC_OK) return rc;
         amax_prev = ext.out_recorded;
         if (timed) { PCC_CHECK_HIP(hipEventRecord(prof->ev[prof->used + 1], st)); prof->used += 2; }
-        out_dims(L, D, H, W);
         if (L.res == 1) { t1 = out; t1_buf = last ? -1 : cur; }
         if (L.res == 2) { t1 = nullptr; t1_buf = -1; }
         in = out;

@@ -59,6 +59,30 @@ class Layer:
     def conv_layers(self):
         return []
 
+    def residual_roles(self):
+        """Role of every conv of conv_layers() in a residual block, as pcc_network_layer numbers them (include/pcc_geo.h)."""
+        return [0] * len(self.conv_layers())
+
+
+_STORAGE = L.PCC_CONV_IN16 | L.PCC_CONV_OUT16 | L.PCC_CONV_RES16
+
+
+def _planned_flags(ctx, stack, x, final_flags=0):
+    """What every conv of `stack` runs with beyond its own and the context's flags, as an iterator its convs draw from in
+    conv_layers() order: `final_flags` on the last one and, in the fp16 mode, the fp16 storage bits of pcc_network_plan
+    (csrc/network.hip) -- the plan pcc_network_forward itself runs, so both paths give the same bits."""
+    convs = stack.conv_layers()
+    flags = [0] * (len(convs) - 1) + [final_flags]
+    if ctx.conv_flags & L.PCC_CONV_F16:
+        for c, cin in zip(convs, input_channels(stack, x.shape[-1])):
+            if c.layer is None:
+                c.build(cin)
+        roles = stack.residual_roles()
+        descs = [c.layer.desc(0, 0, 0, 0, L.PCC_CONV_ADD if r == 2 else 0, c.impl) for c, r in zip(convs, roles)]
+        plan = ops.network_plan(descs, roles, x.shape, ctx.conv_flags, final_flags, ctx.numerics()[1])
+        flags = [f | (p.desc.flags & _STORAGE) for f, p in zip(flags, plan)]
+    return iter(flags)
+
 
 class _ConvBase(Layer):
     transposed = False
@@ -89,9 +113,10 @@ class _ConvBase(Layer):
         self.layer = ops.ConvLayer(kernel, bias, self.stride, self.transposed, self.relu)
         assert self.layer.cout == self.filters and self.layer.k == self.k
 
-    def forward_ndhwc(self, ctx, x, residual=None, flags=0, out=None, out_coffset=0):
+    def forward_ndhwc(self, ctx, x, plan=None, residual=None, out=None, out_coffset=0):
         if self.layer is None:
             self.build(x.shape[-1])
+        flags = next(plan) if plan is not None else 0
         return ops.conv3d(ctx, x, self.layer, residual=residual, flags=flags, impl=self.impl, out=out,
                           out_coffset=out_coffset)
 
@@ -139,34 +164,18 @@ class SequentialLayer(Layer):
             self._net = (key, ops.NetworkWeights(self.NET_ID, self.net_filters, [c.layer for c in convs]))
         return self._net[1]
 
-    def forward_ndhwc(self, ctx, x, final_flags=0):
-        net = self.network() if not (final_flags & ~L.PCC_CONV_CLIP01) else None
+    def forward_ndhwc(self, ctx, x, final_flags=0, plan=None):
+        net = self.network() if plan is None and not (final_flags & ~L.PCC_CONV_CLIP01) else None
         if net is not None:
             return ops.network_forward(ctx, net, x, final_flags)       # the whole transform in one ABI call
-        for i, layer in enumerate(self._layers):
-            if i == len(self._layers) - 2 and self._final_in16(ctx, layer, x):
-                # fp16 mode: the last block hands over in fp16 to the final 16 -> 1 transposed conv, as csrc/network.hip plans it
-                t = layer.forward_ndhwc(ctx, x, out16=True)
-                return ops.conv3d_fp16_storage(ctx, t, self._layers[-1].layer, None, in16=True, out16=False, flags=final_flags)
-            if final_flags and i == len(self._layers) - 1:
-                x = layer.forward_ndhwc(ctx, x, flags=final_flags)
-            else:
-                x = layer.forward_ndhwc(ctx, x)
+        if plan is None:
+            plan = _planned_flags(ctx, self, x, final_flags)
+        for layer in self._layers:
+            x = layer.forward_ndhwc(ctx, x, plan=plan)
         return x
 
-    def _final_in16(self, ctx, block, x):
-        """csrc/network.hip (pcc_network_forward, `final_in16`): in the fp16 mode the output of the last block stays fp16 when its only
-        consumer is the final 16 -> 1 k3 stride-1 transposed conv."""
-        import ctypes as C
-        fin = self._layers[-1]
-        if not (isinstance(block, ResidualLayer) and isinstance(fin, _ConvBase) and block.fp16_storage(ctx, x)):
-            return False
-        if not (fin.transposed and fin.filters == 1 and fin.k == 3 and fin.stride == 1 and fin.layer is not None and fin.impl == L.PCC_IMPL_AUTO
-                and block._layers[-1].filters == 16):
-            return False
-        N, D, H, W, _ = ops.conv_out_shape(block._layers[0].layer, x.shape)
-        d = fin.layer.desc(N, D, H, W, L.PCC_CONV_F16 | L.PCC_CONV_IN16)
-        return L.lib().pcc_conv_mfma_supported(C.byref(d)) == 1
+    def residual_roles(self):
+        return [r for layer in self._layers for r in layer.residual_roles()]
 
     def conv_layers(self):
         return [c for layer in self._layers for c in layer.conv_layers()]
@@ -179,54 +188,26 @@ class ResidualLayer(Layer):
         self.residual_mode = residual_mode
         self.data_format = normalize_data_format(data_format)
 
-    def fp16_storage(self, ctx, x):
-        """csrc/network.hip's plan of the fp16 mode (pcc_network_forward, `storage`), restated for the layer-by-layer path so that both
-        give the same bits: inside an AnalysisBlock / SynthesisBlock of width 16, 32 or 64 whose grid is a multiple of 16 the two
-        intermediate tensors live in HBM as fp16 -- the stride-2 conv hands over in fp16 (PCC_CONV_OUT16), the two k3 stride-1 convs
-        run on conv_f16.hip (PCC_CONV_IN16), the last one adds the fp16 residual and writes fp32."""
-        import ctypes as C
-        if not (getattr(ctx, 'conv_flags', 0) & L.PCC_CONV_F16) or self.residual_mode != 'add' or len(self._layers) != 3:
-            return False
-        if any(not isinstance(c, _ConvBase) or c.layer is None or c.impl != L.PCC_IMPL_AUTO for c in self._layers):
-            return False
-        first, mid, last = self._layers
-        N, D, H, W, _ = x.shape
-        if not (first.k == 3 and first.stride == 2 and first.filters in (16, 32, 64) and H % 2 == 0 and W % 2 == 0):
-            return False
-        _, oD, oH, oW, _ = ops.conv_out_shape(first.layer, x.shape)
-        if oH % 16 or oW % 16:
-            return False
-        d0 = first.layer.desc(N, D, H, W, L.PCC_CONV_F16)
-        if L.lib().pcc_conv_mfma_supported(C.byref(d0)) != 1:          # (a layer on the generic path cannot hand over in fp16)
-            return False
-        for c in (mid, last):      # pcc_f16_eligible (csrc/conv_f16.hip)
-            l = c.layer
-            if not (l.k == 3 and l.stride == 1 and l.cin == l.cout and l.cin in (16, 32, 64) and oH * oW * l.cin * 4 < 2 ** 31):
-                return False
-            d = l.desc(N, oD, oH, oW, L.PCC_CONV_F16 | L.PCC_CONV_IN16)
-            if L.lib().pcc_conv_mfma_supported(C.byref(d)) != 1:
-                return False
-        return True
+    def residual_roles(self):
+        if self.residual_mode == 'add' and len(self._layers) == 3 and all(isinstance(c, _ConvBase) for c in self._layers):
+            return [1, 0, 2]
+        return super().residual_roles()
 
-    def forward_ndhwc(self, ctx, x, flags=0, out16=False):
-        if self.fp16_storage(ctx, x):
-            first, mid, last = self._layers
-            t1 = ops.conv3d_fp16_storage(ctx, x, first.layer, None, in16=False, out16=True)
-            t = ops.conv3d_fp16_storage(ctx, t1, mid.layer, None, out16=True)
-            return ops.conv3d_fp16_storage(ctx, t, last.layer, t1, out16=out16, flags=flags)
-        assert not out16
-        t1 = self._layers[0].forward_ndhwc(ctx, x)
+    def forward_ndhwc(self, ctx, x, plan=None):
+        if plan is None:
+            plan = _planned_flags(ctx, self, x)
+        t1 = self._layers[0].forward_ndhwc(ctx, x, plan=plan)
         t = t1
         for layer in self._layers[1:-1]:
-            t = layer.forward_ndhwc(ctx, t)
+            t = layer.forward_ndhwc(ctx, t, plan=plan)
         last = self._layers[-1]
         if self.residual_mode == 'add':
             # tensor1 + tensor, fused into the epilogue of the last conv (ReLU is applied before the add)
-            return last.forward_ndhwc(ctx, t, residual=t1, flags=flags)
+            return last.forward_ndhwc(ctx, t, plan=plan, residual=t1)
         # tf.concat((tensor, tensor1), channel_axis): the last conv writes channels [0,F), tensor1 follows
         F = last.filters
         out = torch.empty(tuple(t1.shape[:4]) + (F + t1.shape[4],), dtype=torch.float32, device=x.device)
-        last.forward_ndhwc(ctx, t, out=out, out_coffset=0)
+        last.forward_ndhwc(ctx, t, plan=plan, out=out, out_coffset=0)
         out[..., F:] = t1
         return out
 

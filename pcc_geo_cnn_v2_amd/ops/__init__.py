@@ -6,7 +6,7 @@ a hand-written HIP kernel (or the host range coder) inside libpcc_geo_hip.so.
 from ._context import (  # noqa: F401
     _ptr, Context, _ContextView, _CONTEXTS, get_context, usable_cores)
 from .conv import (  # noqa: F401
-    ConvLayer, conv_out_shape, conv3d, NetworkWeights, _FAMILY, network_forward, profile_select, profile_read, conv3d_fp16_storage,
+    ConvLayer, conv_out_shape, conv3d, NetworkWeights, _FAMILY, network_forward, network_plan, profile_select, profile_read, conv3d_fp16_storage,
     mfma_supported)
 from .codec import (  # noqa: F401
     codec_desc, _ITEM, SymbolStaging, symbols_pack, symbols_unpack, _out, quantize_pack, index_pack, unpack_dequantize,

@@ -57,7 +57,11 @@ def conv_out_shape(layer, x_shape):
 
 
 def conv3d(ctx, x, layer, residual=None, flags=0, impl=L.PCC_IMPL_AUTO, out=None, out_coffset=0):
-    """x: (N,D,H,W,Cin) float32 contiguous on ctx.device.  Returns (N,OD,OH,OW,Cout)."""
+    """x: (N,D,H,W,Cin) float32 contiguous on ctx.device.  Returns (N,OD,OH,OW,Cout).  flags with PCC_CONV_IN16 / OUT16 / RES16 (a
+    layer of the fp16 mode as network_plan plans it): x, residual and the result are fp16 where the bits say so."""
+    if flags & (L.PCC_CONV_IN16 | L.PCC_CONV_OUT16 | L.PCC_CONV_RES16):
+        assert impl == L.PCC_IMPL_AUTO and out is None
+        return conv3d_fp16_storage(ctx, x, layer, residual, bool(flags & L.PCC_CONV_IN16), bool(flags & L.PCC_CONV_OUT16), flags)
     assert x.dtype == torch.float32 and x.is_contiguous() and x.device == ctx.device and x.dim() == 5
     N, D, H, W, Cin = x.shape
     assert Cin == layer.cin, f'expected {layer.cin} input channels, got {Cin}'
@@ -127,6 +131,19 @@ def network_forward(ctx, net, x, final_flags=0):
     L.check(fn(ctx.handle, net.transform, net.filters, _ptr(net.blob(ctx)), _ptr(x), N, D, H, W, _ptr(y), _ptr(ws), ws.numel(),
                ctx.conv_flags, final_flags, ctx.stream), 'pcc_network_forward')
     return y
+
+
+def network_plan(descs, roles, x_shape, layer_flags=0, final_flags=0, numerics=0):
+    """pcc_network_plan: what every layer of a stack runs with on an input of x_shape (N,D,H,W,C) -- one L.LayerPlan per layer,
+    `.desc` with its input dims and flags (the fp16 storage bits of the fp16 mode included), `.record_amax` whether it is asked for
+    the block maxima of its output.  descs: L.ConvDesc per layer (geometry, own flags, impl), roles: 0 | 1 | 2 as
+    pcc_network_layer gives them.  Host arithmetic: needs no context and no GPU."""
+    n = len(descs)
+    plan = (L.LayerPlan * n)()
+    N, D, H, W = x_shape[:4]
+    L.check(L.lib().pcc_network_plan((L.ConvDesc * n)(*descs), (C.c_int32 * n)(*roles), n, N, D, H, W, layer_flags, final_flags,
+                                     numerics, plan, None), 'pcc_network_plan')
+    return list(plan)
 
 
 def profile_select(ctx, transform, layer, stride=1):

@@ -212,7 +212,7 @@ def test_ctypes_structs_match_the_header_as_compiled_by_a_c_compiler(tmp_path):
     cc = shutil.which('gcc') or shutil.which('cc')
     if cc is None:
         pytest.skip('no C compiler')
-    structs = {'pcc_conv_desc': L.ConvDesc, 'pcc_cdf_table': L.CdfTable, 'pcc_codec_desc': L.CodecDesc, 'pcc_symbol_io': L.SymbolSink}
+    structs = {'pcc_conv_desc': L.ConvDesc, 'pcc_layer_plan': L.LayerPlan, 'pcc_cdf_table': L.CdfTable, 'pcc_codec_desc': L.CodecDesc, 'pcc_symbol_io': L.SymbolSink}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "pcc_geo.h")}"', 'int main(void) {']
     for name, cls in structs.items():
         lines.append(f'  printf("{name} %zu", sizeof({name}));')

@@ -68,6 +68,82 @@ def test_fp16_mode_network_matches_the_fp16_restatement(ctx, name, F, cin, res):
     assert err <= 2e-3 * (1 + np.abs(ref16).max()), err
 
 
+@pytest.mark.parametrize('name,F,shape,final_flags', [
+    ('SynthesisTransformProgressiveV2', 64, (2, 4, 4, 4, 64), 0),       # a block without storage, two with, fp16 hand-over to the 16 -> 1 layer
+    ('SynthesisTransformProgressiveV2', 64, (2, 4, 4, 4, 64), L.PCC_CONV_CLIP01),
+    ('SynthesisTransformProgressiveV2', 64, (2, 2, 2, 2, 64), 0),       # only the last block has storage
+    ('SynthesisTransformV2', 32, (2, 4, 4, 4, 32), 0),
+    ('AnalysisTransformProgressiveV2', 64, (2, 32, 32, 32, 1), 0)])
+def test_fp16_mode_network_is_bit_identical_to_the_layerwise_path(ctx, monkeypatch, name, F, shape, final_flags):
+    """fp16 mode: which tensors are stored as fp16 reaches every bit of the result, and both paths read it from pcc_network_plan
+    (csrc/network.hip): the one-call transform equals the layer-by-layer one, and each repeats itself."""
+    tr = MT.TransformType[name].value(F, data_format='channels_last')
+    MT.init_transform(tr, shape[-1], np.random.default_rng(7))
+    g = torch.Generator().manual_seed(4)
+    x = ((torch.rand(shape, generator=g) < 0.1).float() if shape[-1] == 1 else torch.randn(shape, generator=g)).to(ctx.device)
+    v = ctx.view(L.PCC_CONV_F16)
+    assert tr.network() is not None
+    a = tr.forward_ndhwc(v, x, final_flags=final_flags)
+    a2 = tr.forward_ndhwc(v, x, final_flags=final_flags)
+    monkeypatch.setenv('PCC_LAYERWISE', '1')
+    assert tr.network() is None
+    b = tr.forward_ndhwc(v, x, final_flags=final_flags)
+    b2 = tr.forward_ndhwc(v, x, final_flags=final_flags)
+    torch.cuda.synchronize()
+    assert a.dtype == b.dtype == torch.float32 and a.shape == b.shape
+    assert torch.equal(a, b) and torch.equal(a, a2) and torch.equal(b, b2)
+
+
+def test_free_form_stack_takes_the_planned_fp16_storage(ctx):
+    """No NET_ID: a SequentialLayer of one 'add' ResidualLayer in the fp16 mode runs its three convs with the planned storage bits;
+    the same convs as a 'concat' block keep every tensor in fp32."""
+    convs = [MT.Conv3DTranspose(32, 3, strides=s, padding='same', activation=MT.relu) for s in (2, 1, 1)]
+    stack = MT.SequentialLayer([MT.ResidualLayer(convs, 'add')])
+    MT.init_transform(stack, 32, np.random.default_rng(8))
+    l0, l1, l2 = (c.layer for c in convs)
+    x = torch.randn((1, 8, 8, 8, 32), generator=torch.Generator().manual_seed(5)).to(ctx.device)
+    v = ctx.view(L.PCC_CONV_F16)
+    assert stack.network() is None
+    got = stack.forward_ndhwc(v, x)
+    t1 = ops.conv3d_fp16_storage(v, x, l0, None, in16=False, out16=True)            # OUT16
+    t = ops.conv3d_fp16_storage(v, t1, l1, None, in16=True, out16=True)             # IN16 | OUT16
+    want = ops.conv3d_fp16_storage(v, t, l2, t1, in16=True, out16=False)            # IN16 | RES16 (+ ADD)
+    assert got.dtype == torch.float32 and torch.equal(got, want)
+    cat = MT.SequentialLayer([MT.ResidualLayer(convs, 'concat')]).forward_ndhwc(v, x)
+    t1 = ops.conv3d(v, x, l0)
+    want = torch.cat((ops.conv3d(v, ops.conv3d(v, t1, l1), l2), t1), -1)
+    torch.cuda.synchronize()
+    assert cat.dtype == torch.float32 and torch.equal(cat, want)
+
+
+def test_planned_block_maxima_follow_the_router(ctx):
+    """pcc_network_plan asks layer i for the block maxima of its output exactly when layer i + 1, as planned, takes a two-piece fp16
+    kernel under the context's numerics word."""
+    import ctypes as C
+    lib, tid = L.lib(), L.PCC_NET_SYNTHESIS_PROGRESSIVE_V2
+    descs, roles = [], []
+    for i in range(lib.pcc_network_num_layers(tid, 64)):
+        d, role = L.ConvDesc(), C.c_int32()
+        L.check(lib.pcc_network_layer(tid, 64, i, C.byref(d), C.byref(role)), 'pcc_network_layer')
+        descs.append(d)
+        roles.append(role.value)
+
+    def asked_and_wanted():
+        plan = ops.network_plan(descs, roles, (2, 8, 8, 8, 64), 0, 0, ctx.numerics()[1])
+        buf = C.create_string_buffer(256)
+        fams = []
+        for p in plan:
+            L.check(lib.pcc_conv_kernel_family(ctx.handle, C.byref(p.desc), buf, 256), 'pcc_conv_kernel_family')
+            fams.append(buf.value.decode())
+        return [bool(p.record_amax) for p in plan], ['fp16 x 2' in f for f in fams[1:]] + [False]
+
+    asked, wanted = asked_and_wanted()
+    assert asked == wanted
+    with ctx.numerics_override(no_f16s=True):
+        asked, wanted = asked_and_wanted()
+        assert asked == wanted and not any(asked)
+
+
 def test_family_entry_points_reject_other_families(ctx):
     tr = MT.TransformType['HyperAnalysisTransform'].value(64, data_format='channels_last')
     MT.init_transform(tr, 64, np.random.default_rng(0))
