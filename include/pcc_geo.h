@@ -425,6 +425,40 @@ int pcc_d12_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, 
                         void* workspace, void* workspace2, void* rank_workspace, size_t rank_workspace_bytes, uint64_t* s_ab,
                         uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream);
 
+/* ---- Hausdorff terms of the search -------------------------------------------------------------------------------
+ * The four entries above with the per-point MAXIMA beside their sums, through the same kernels: every output they share with the plain
+ * entry is the same bits, and the plain entries do no work for the maxima.  With A the original points of block b and B_t the decoded set
+ * of candidate t (threshold t, or the top-counts[b][t] set):
+ *   h1_ab[b][t]  (uint32)  = max_{a in A} min_{v in B_t} |a - v|^2                       (d1_hausdorff_AB; <= 3 * 127^2)
+ *   h1_max[b][k] (uint32)  = max over the voxels v of level k of min_{a in A} |v - a|^2;  d1_hausdorff_BA(t) = max_{k>t} h1_max[b][k]
+ *   h2_ab[b][t]  (float64) = the largest of the per-point plane terms whose sum is d2_ab[b][t]            (d2_hausdorff_AB)
+ *   h2_max[b][k] (float64) = the largest of the per-voxel plane terms of d2_ba over the voxels of level k;
+ *                            d2_hausdorff_BA(t) = max_{k>t} h2_max[b][k]
+ * under the tie rule of pcc_d12_threshold_stats (lowest (x, y, z)).  All four are (B,256), device, caller-provided beside the workspaces
+ * (whose sizes do not change) and zero-filled by the call on its stream.  Live levels as above: only t < min(tcount[b], 255) are
+ * computed, h1_ab / h2_ab[b][t] stay zero elsewhere, a voxel of level 256 is held at level 255.  D1 values are integers and a maximum has
+ * no order: h1_* are exact; h2_* are maxima over finite non-negative doubles (integer atomic maxima on their bit patterns, or a tree),
+ * hence bit-reproducible like the sums.  There is no tie-averaged (_ties) form.                                                      */
+int pcc_d1_threshold_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W,
+                                     const float* thr, int32_t nthr, int32_t clip, const int32_t* pts,
+                                     const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab,
+                                     uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, uint32_t* h1_ab, uint32_t* h1_max, void* stream);
+int pcc_d12_threshold_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const float* thr,
+                                      int32_t nthr, int32_t clip, const int32_t* pts, const int32_t* block_of, const int32_t* block_start,
+                                      int64_t npts, const float* normals, void* workspace, void* workspace2, uint64_t* s_ab, uint64_t* hsum,
+                                      uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, uint32_t* h1_ab, uint32_t* h1_max,
+                                      double* h2_ab, double* h2_max, void* stream);
+int pcc_d1_count_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts,
+                                 int32_t J, const int32_t* pts, const int32_t* block_of, int64_t npts, void* workspace,
+                                 void* rank_workspace, size_t rank_workspace_bytes, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt,
+                                 int32_t* tcount, uint32_t* h1_ab, uint32_t* h1_max, void* stream);
+int pcc_d12_count_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts,
+                                  int32_t J, const int32_t* pts, const int32_t* block_of, const int32_t* block_start, int64_t npts,
+                                  const float* normals, void* workspace, void* workspace2, void* rank_workspace,
+                                  size_t rank_workspace_bytes, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount,
+                                  double* d2_ab, double* d2_ba, uint32_t* h1_ab, uint32_t* h1_max, double* h2_ab, double* h2_max,
+                                  void* stream);
+
 /* The same search under the tie-averaged D2 definition (DESIGN.md "Tie-averaged D2", applied per block and threshold with A = the
  * block's rows and B = B_t): T_B(a) = ALL voxels of B_t at the smallest squared distance from row a, T_A(v) = ALL rows at the
  * smallest squared distance from voxel v (rows that share a voxel are separate members).  A voxel b takes the unweighted float64 mean

@@ -52,6 +52,7 @@ EXPORTS = [
     'pcc_occ_stream_cap', 'pcc_occ_workspace_bytes', 'pcc_occ_check_strings', 'pcc_occ_encode_batch', 'pcc_occ_decode_batch',
     'pcc_topk_workspace_bytes', 'pcc_topk_compact',
     'pcc_rank_levels_workspace_bytes', 'pcc_rank_levels', 'pcc_d1_count_stats', 'pcc_d12_count_stats',
+    'pcc_d1_threshold_stats_hausdorff', 'pcc_d12_threshold_stats_hausdorff', 'pcc_d1_count_stats_hausdorff', 'pcc_d12_count_stats_hausdorff',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -256,6 +257,11 @@ def lib():
     L.pcc_rank_levels.argtypes = [vp, vp, i64, i32, i64, vp, i32, vp, vp, vp, sz, vp]
     L.pcc_d1_count_stats.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, i64, vp, vp, sz, vp, vp, vp, vp, vp]
     L.pcc_d12_count_stats.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    # the Hausdorff forms: the plain entry's arguments with (h1_ab, h1_max) -- and, with D2, (h2_ab, h2_max) -- in front of the stream
+    L.pcc_d1_threshold_stats_hausdorff.argtypes = L.pcc_d1_threshold_stats.argtypes[:-1] + [vp, vp, vp]
+    L.pcc_d12_threshold_stats_hausdorff.argtypes = L.pcc_d12_threshold_stats.argtypes[:-1] + [vp, vp, vp, vp, vp]
+    L.pcc_d1_count_stats_hausdorff.argtypes = L.pcc_d1_count_stats.argtypes[:-1] + [vp, vp, vp]
+    L.pcc_d12_count_stats_hausdorff.argtypes = L.pcc_d12_count_stats.argtypes[:-1] + [vp, vp, vp, vp, vp]
     L.pcc_octree_bucket.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
     L.pcc_octree_bucket.restype = C.c_int64
     L.pcc_network_num_layers.argtypes = [i32, i32]

@@ -6,6 +6,7 @@ from collections import namedtuple
 import numpy as np
 
 from .model_opt import d1_tallies_gpu, d12_tallies_gpu, d2_on_gpu, decide_from_tallies, gpu_search_supported, metric_names
+from .utils.pc_metric import wants_hausdorff
 
 # gpu_tallies: None | 'd1' (d1_tallies_gpu) | 'd12' (d12_tallies_gpu);  host_job: None or the HostSearchPool job kind of every block;
 # ties: the rule of the D2 statistics ('pick' when no d2_* metric is asked for)
@@ -67,7 +68,7 @@ class SearchSchedule:
         thr, wn, ties = self.model.thresholds, self.with_normals, self.plan.ties
         blocks = [np.ascontiguousarray(b) for b in chunk]
         if kind == 'tally_pruned':
-            return [(kind, b, xh[j], thr, wn, d1[j], self.resolution, list(self.opt_metrics), list(self.max_deltas)) for j, b in enumerate(blocks)]
+            return [(kind, b, xh[j], thr, wn, d1[j][:, :5], self.resolution, list(self.opt_metrics), list(self.max_deltas)) for j, b in enumerate(blocks)]
         if kind == 'tally':
             return [(kind, b, xh[j], thr, wn, ties) for j, b in enumerate(blocks)]
         return [(kind, b, xh[j], thr, self.resolution, wn, list(self.opt_metrics), list(self.max_deltas), ties) for j, b in enumerate(blocks)]
@@ -78,8 +79,9 @@ class SearchSchedule:
             self.plan = self._make_plan()      # (with the first chunk: d2_on_gpu logs what it chose)
         plan = self.plan
         item = dict(chunk=chunk, x_hat=x_hat, futures=None, d1=None)
-        if plan.host_job == 'tally_pruned':
-            item['d1'] = d1_tallies_gpu(ctx, chunk, x_hat, m.thresholds)
+        hd = wants_hausdorff(self.opt_metrics)      # 9-slot tallies: the Hausdorff forms of the GPU calls, made only then
+        if plan.host_job == 'tally_pruned':         # (the pruned jobs bound sums: they get the five sum slots)
+            item['d1'] = d1_tallies_gpu(ctx, chunk, x_hat, m.thresholds, hausdorff=hd)
         if plan.host_job is not None:
             jobs = self._jobs(plan.host_job, chunk, np.clip(x_hat.cpu().numpy(), 0.0, 1.0), item['d1'])
             m.host_search_jobs += len(jobs)
@@ -87,8 +89,8 @@ class SearchSchedule:
             pool = m._search_pool(self.n_blocks)
             item['futures'] = [pool.submit(job) for job in jobs]
         if plan.gpu_tallies is not None and item['d1'] is None:
-            item['d1'] = d12_tallies_gpu(ctx, chunk, x_hat, m.thresholds, ties=plan.ties) if plan.gpu_tallies == 'd12' \
-                else d1_tallies_gpu(ctx, chunk, x_hat, m.thresholds)
+            item['d1'] = d12_tallies_gpu(ctx, chunk, x_hat, m.thresholds, ties=plan.ties, hausdorff=hd) if plan.gpu_tallies == 'd12' \
+                else d1_tallies_gpu(ctx, chunk, x_hat, m.thresholds, hausdorff=hd)
         self.pending.append(item)
         if len(self.pending) > self.SEARCH_LAG:
             self._finalize(self.pending.pop(0))

@@ -196,6 +196,20 @@ def check_count_search(args, world):
                              'strings, drop the flag or run on one GPU')
 
 
+def check_hausdorff_metrics(args, world):
+    """--opt_metrics with a Hausdorff name (pc_metric.hausdorff_opt_metrics): what the maxima cannot be combined with,
+    refused at argument time with the flag to change (model_opt.check_hausdorff_search).  d2_hausdorff* reads the GPU's D2 statistics:
+    it needs --d2_search gpu on the command line.  --fixed_threshold runs no search: nothing to refuse."""
+    from .model_opt import check_hausdorff_search
+    if getattr(args, 'fixed_threshold', False):
+        return
+    try:
+        check_hausdorff_search(getattr(args, 'opt_metrics', None) or (), getattr(args, 'search_ties', 'pick'),
+                               getattr(args, 'd2_search', None) == 'gpu', world)
+    except AssertionError as e:
+        raise AssertionError(f'--opt_metrics: {e}') from None
+
+
 def check_d2_ties(d2_ties, world):
     """--d2_ties mean averages the whole-cloud D2 over all equidistant nearest points in one process; tie sets are not sharded."""
     from .utils.pc_metric import check_ties
@@ -285,6 +299,7 @@ def compress(args):
 
     check_count_threshold(args, int(os.environ.get('WORLD_SIZE', '1')))     # (first: its message names the flag, not what _plan meets)
     check_count_search(args, int(os.environ.get('WORLD_SIZE', '1')))
+    check_hausdorff_metrics(args, int(os.environ.get('WORLD_SIZE', '1')))
     clouds, with_normals = _plan(args)
     lossless = getattr(args, 'lossless', False)
     count_scale = getattr(args, 'count_threshold', None)
@@ -350,7 +365,7 @@ def compress(args):
 
 
 def build_parser():
-    from .utils.pc_metric import avail_opt_metrics
+    from .utils.pc_metric import avail_opt_metrics, hausdorff_opt_metrics
     parser = argparse.ArgumentParser(prog='compress_octree.py', description='Compress a file.',
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument('--input_files', nargs='+', help='Input files.', required=True)
@@ -384,7 +399,10 @@ def build_parser():
     parser.add_argument('--model_config', help='Model used: c1, c2, c3, c3p.', required=True)
     # the reference's default (compress_octree.py:156); translated to d1_mse in compress(), see there
     parser.add_argument('--opt_metrics', nargs='+', default=['d1_psnr'],
-                        help=f'Optimization metrics used. Available: {avail_opt_metrics}')
+                        help=f'Optimization metrics used. Available: {avail_opt_metrics}; worst-point objectives (new): '
+                             f'{hausdorff_opt_metrics} -- the largest per-point error instead of the sum (GPU search, one process, '
+                             '--search_ties pick; d2_hausdorff* needs --d2_search gpu); .enc.metric.json then also carries the '
+                             'whole-cloud Hausdorff keys.')
     parser.add_argument('--max_deltas', nargs='+', default=[np.inf], type=float, help='Max deltas tested during optimization.')
     parser.add_argument('--fixed_threshold', default=False, action='store_true', help='Enable fixed thresholding.')
     parser.add_argument('--read_batch_size', type=int, default=1, help='Batch size for parallel reading.')

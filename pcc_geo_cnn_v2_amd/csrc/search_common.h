@@ -52,10 +52,16 @@ struct LevelSource {
     const int32_t* counts; int J; void* rank_ws; size_t rank_ws_bytes;
     int levels() const { return counts ? J : nthr; }
 };
-// pcc_d1_threshold_stats / pcc_d1_count_stats (search_d1.hip), and what the D2 entries run first
+// The D1 Hausdorff outputs of a search call, (B,256) uint32 each, caller-provided (no part of D1Layout); both NULL = the plain entries,
+// which launch the kernels without the maxima.  h1_ab[b][t] per candidate, h1_max[b][k] per level (the host forms max_{k>t}).
+struct SearchHausdorff {
+    uint32_t* h1_ab = nullptr;
+    uint32_t* h1_max = nullptr;
+};
+// pcc_d1_threshold_stats / pcc_d1_count_stats and their _hausdorff forms (search_d1.hip), and what the D2 entries run first
 int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* pts,
                         const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount,
-                        void* stream);
+                        void* stream, const SearchHausdorff& hd = {});
 
 // Row-major voxel index <-> (x, y, z) on a grid of planes H x W; the divisions are done in the width of the caller's index type
 struct Voxel { int x, y, z; };

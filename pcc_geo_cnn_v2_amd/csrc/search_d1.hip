@@ -185,10 +185,13 @@ __global__ void __launch_bounds__(64) k_edt_zy(const unsigned char* __restrict__
 bool edt_zy_takes(int D, int H, int W) { return W % 16 == 0 && W <= 128 && H <= 128 && D >= 1; }
 
 // last pass (along x = the slowest axis) evaluated only at the points of A: S_AB[b][t] += min_x' (x_a-x')^2 + g[x'][y_a][z_a]
+// HD (the Hausdorff entries): the same value also goes through a maximum, H1_AB[b][t] = max_a of it -- integers, so the order of the
+// atomics does not matter.  HD = false is the kernel of the plain entries, instruction for instruction (h_ab unused).
+template <bool HD>
 __global__ void __launch_bounds__(256) k_edt_points(const unsigned short* __restrict__ g, const int* __restrict__ tcount,
                                                     int tmax, int t0, const int* __restrict__ pts, const int* __restrict__ block_of,
                                                     long long npts, int D, int H, int W,
-                                                    unsigned long long* __restrict__ s_ab) {
+                                                    unsigned long long* __restrict__ s_ab, unsigned* __restrict__ h_ab) {
     const int tl = blockIdx.y, t = t0 + tl;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long val = 0;
@@ -205,33 +208,50 @@ __global__ void __launch_bounds__(256) k_edt_points(const unsigned short* __rest
     // points are grouped by block: reduce within the wave when the whole wave belongs to one block, else use atomics
     const int b0 = __shfl(b, 0, 64);
     const bool uniform = __all(b == b0 || b == -1) && b0 >= 0;
+    [[maybe_unused]] unsigned far = (unsigned)val;      // (<= 3 * 127^2; 0 for the lanes that take no part)
     if (uniform) {
         for (int o = 32; o > 0; o >>= 1) val += __shfl_xor(val, o, 64);
         if ((threadIdx.x & 63) == 0 && val) atomicAdd(&s_ab[(size_t)b0 * kT + t], val);
+        if constexpr (HD) {
+            for (int o = 32; o > 0; o >>= 1) far = max(far, (unsigned)__shfl_xor((int)far, o, 64));
+            if ((threadIdx.x & 63) == 0 && far) atomicMax(&h_ab[(size_t)b0 * kT + t], far);
+        }
     } else if (b >= 0 && val) {
         atomicAdd(&s_ab[(size_t)b * kT + t], val);
+        if constexpr (HD) atomicMax(&h_ab[(size_t)b * kT + t], far);
     }
 }
 
 // S_BA / n_B histograms by level: hist[b][k] += edt_A[v] for every voxel of level k >= 1
+// HD (the Hausdorff entries): hmax[b][k] = the largest edt_A[v] of level k beside them (a table of 256 maxima per workgroup in LDS, then
+// one global atomic maximum per level met); H1_BA(t) = max_{k>t} hmax[b][k] is formed where the suffix sums are.  HD = false: as before.
+template <bool HD>
 __global__ void __launch_bounds__(256) k_level_hist(const unsigned char* __restrict__ lev, const unsigned short* __restrict__ edt_a,
                                                     size_t nvox, unsigned long long* __restrict__ hsum,
-                                                    unsigned long long* __restrict__ hcnt) {
+                                                    unsigned long long* __restrict__ hcnt, unsigned* __restrict__ hmax) {
     __shared__ unsigned long long ssum[kT];
     __shared__ unsigned int scnt[kT];
+    __shared__ unsigned int smax[HD ? kT : 1];
     const int b = blockIdx.y;
-    for (int j = threadIdx.x; j < kT; j += blockDim.x) { ssum[j] = 0; scnt[j] = 0; }
+    for (int j = threadIdx.x; j < kT; j += blockDim.x) {
+        ssum[j] = 0; scnt[j] = 0;
+        if constexpr (HD) smax[j] = 0;
+    }
     __syncthreads();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (size_t)gridDim.x * blockDim.x) {
         const int k = lev[(size_t)b * nvox + i];
         if (k) {
             atomicAdd(&ssum[k], (unsigned long long)edt_a[(size_t)b * nvox + i]);
             atomicAdd(&scnt[k], 1u);
+            if constexpr (HD) atomicMax(&smax[k], (unsigned)edt_a[(size_t)b * nvox + i]);
         }
     }
     __syncthreads();
     for (int j = threadIdx.x; j < kT; j += blockDim.x) {
-        if (scnt[j]) { atomicAdd(&hsum[(size_t)b * kT + j], ssum[j]); atomicAdd(&hcnt[(size_t)b * kT + j], (unsigned long long)scnt[j]); }
+        if (scnt[j]) {
+            atomicAdd(&hsum[(size_t)b * kT + j], ssum[j]); atomicAdd(&hcnt[(size_t)b * kT + j], (unsigned long long)scnt[j]);
+            if constexpr (HD) { if (smax[j]) atomicMax(&hmax[(size_t)b * kT + j], smax[j]); }
+        }
     }
 }
 
@@ -261,10 +281,14 @@ PCC_API size_t pcc_d1_search_workspace_bytes(int32_t B, int32_t D, int32_t H, in
 // tcount: (B,) int32 = number of thresholds with a non-empty decoded set.  hsum/hcnt are per-level histograms:
 // S_BA(t) = sum_{k>t} hsum[k], n_B(t) = sum_{k>t} hcnt[k].
 // The level grid comes from `src` (search_common.h): thresholds or candidate counts; everything after it is the same code for both.
+// hd (the Hausdorff entries; all NULL in the plain ones, which then launch the kernels they always did): h1_ab, h1_max (B,256) uint32,
+// zero-filled by the call: h1_ab[b][t] = max_a min_{v in B_t} |a - v|^2, h1_max[b][k] = max over the voxels of level k of min_a |v - a|^2.
 int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* pts,
                         const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount,
-                        void* stream) {
+                        void* stream, const SearchHausdorff& hd) {
     const int nthr = src.levels();
+    const bool HD = hd.h1_ab != nullptr;
+    PCC_REQUIRE((hd.h1_ab != nullptr) == (hd.h1_max != nullptr), "%s: NULL argument", src.who);
     PCC_REQUIRE(ctx && x_hat && (src.counts ? src.rank_ws != nullptr : src.thr != nullptr) && workspace && s_ab && hsum && hcnt && tcount,
                 "%s: NULL argument", src.who);
     PCC_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0 && npts >= 0 && (pts || npts == 0), "%s: bad dimension", src.who);
@@ -287,6 +311,10 @@ int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat
     PCC_CHECK_HIP(hipMemsetAsync(s_ab, 0, (size_t)B * kT * 8, st));
     PCC_CHECK_HIP(hipMemsetAsync(hsum, 0, (size_t)B * kT * 8, st));
     PCC_CHECK_HIP(hipMemsetAsync(hcnt, 0, (size_t)B * kT * 8, st));
+    if (HD) {
+        PCC_CHECK_HIP(hipMemsetAsync(hd.h1_ab, 0, (size_t)B * kT * 4, st));
+        PCC_CHECK_HIP(hipMemsetAsync(hd.h1_max, 0, (size_t)B * kT * 4, st));
+    }
     const unsigned vox_blocks = (unsigned)((nvox + 255) / 256);
     if (src.counts) {       // (tcount and lev are written whole by the call; it runs behind the fills above on the same stream)
         const int rc = pcc_rank_levels(ctx, x_hat, (int64_t)nvox, B, (int64_t)nvox, src.counts, src.J, lev, tcount, src.rank_ws, src.rank_ws_bytes, stream);
@@ -303,8 +331,8 @@ int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat
     hipLaunchKernelGGL(k_fill_int, dim3((B + 255) / 256), dim3(256), 0, st, one, 1, B);
     pcc_search_edt_zy(st, occ, one, 1, 0, 1, B, D, H, W, ea0, ea1);
     hipLaunchKernelGGL(k_edt_axis, dim3(vox_blocks, 1, B), dim3(256), 0, st, ea1, one, 1, 0, nvox, D, H * W, ea0);
-    hipLaunchKernelGGL(k_level_hist, dim3(64, B), dim3(256), 0, st, lev, ea0, nvox, (unsigned long long*)hsum,
-                       (unsigned long long*)hcnt);
+    hipLaunchKernelGGL(HD ? k_level_hist<true> : k_level_hist<false>, dim3(64, B), dim3(256), 0, st, lev, ea0, nvox, (unsigned long long*)hsum,
+                       (unsigned long long*)hcnt, hd.h1_max);
     // ---- EDT of every level set, evaluated at the points of A
     //      in chunks of TC thresholds (workspace bound); chunks beyond every block's tcount exit at once
     for (int t0 = 0; t0 < nthr; t0 += TC) {
@@ -312,8 +340,8 @@ int pcc_search_d1_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat
         pcc_search_edt_zy(st, lev, tcount, TC, t0, nt, B, D, H, W, g0, g1);
         if (npts > 0) {
             const unsigned pblocks = (unsigned)((npts + 255) / 256);
-            hipLaunchKernelGGL(k_edt_points, dim3(pblocks, nt), dim3(256), 0, st, g1, tcount, TC, t0, pts, block_of,
-                               (long long)npts, D, H, W, (unsigned long long*)s_ab);
+            hipLaunchKernelGGL(HD ? k_edt_points<true> : k_edt_points<false>, dim3(pblocks, nt), dim3(256), 0, st, g1, tcount, TC, t0, pts,
+                               block_of, (long long)npts, D, H, W, (unsigned long long*)s_ab, hd.h1_ab);
         }
     }
     PCC_CHECK_HIP(hipGetLastError());
@@ -328,6 +356,16 @@ PCC_API int pcc_d1_threshold_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, 
     return pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
 }
 
+// pcc_d1_threshold_stats with the D1 Hausdorff terms beside the sums (include/pcc_geo.h "Hausdorff terms of the search")
+PCC_API int pcc_d1_threshold_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W,
+                                             const float* thr, int32_t nthr, int32_t clip, const int32_t* pts,
+                                             const int32_t* block_of, int64_t npts, void* workspace, uint64_t* s_ab,
+                                             uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, uint32_t* h1_ab, uint32_t* h1_max, void* stream) {
+    PCC_REQUIRE(h1_ab && h1_max, "pcc_d1_threshold_stats_hausdorff: NULL argument");
+    const LevelSource src = {"pcc_d1_threshold_stats_hausdorff", thr, nthr, clip, nullptr, 0, nullptr, 0};
+    return pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream, {h1_ab, h1_max});
+}
+
 // The same statistics for the top-counts[b][j] sets of every block (include/pcc_geo.h): only the source of the level grid differs
 PCC_API int pcc_d1_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts, int32_t J,
                                const int32_t* pts, const int32_t* block_of, int64_t npts, void* workspace, void* rank_workspace,
@@ -335,4 +373,13 @@ PCC_API int pcc_d1_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int3
     PCC_REQUIRE(counts, "pcc_d1_count_stats: NULL argument");
     const LevelSource src = {"pcc_d1_count_stats", nullptr, 0, 0, counts, J, rank_workspace, rank_workspace_bytes};
     return pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
+}
+
+PCC_API int pcc_d1_count_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts,
+                                         int32_t J, const int32_t* pts, const int32_t* block_of, int64_t npts, void* workspace,
+                                         void* rank_workspace, size_t rank_workspace_bytes, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt,
+                                         int32_t* tcount, uint32_t* h1_ab, uint32_t* h1_max, void* stream) {
+    PCC_REQUIRE(counts && h1_ab && h1_max, "pcc_d1_count_stats_hausdorff: NULL argument");
+    const LevelSource src = {"pcc_d1_count_stats_hausdorff", nullptr, 0, 0, counts, J, rank_workspace, rank_workspace_bytes};
+    return pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream, {h1_ab, h1_max});
 }

@@ -212,16 +212,55 @@ __global__ void __launch_bounds__(256) k_group_plane_err(const unsigned long lon
     }
 }
 
+struct Larger {
+    __device__ __forceinline__ double operator()(double a, double b) const { return a > b ? a : b; }
+};
+
 // D2_AB[b][t0 + tl] = sum over the points of block b of err[tl][.], fixed order
+// HD (the Hausdorff entries): H2_AB[b][t0 + tl] = the largest of the same doubles beside it (a maximum has no order to fix; the terms are
+// squares: finite, >= 0).  HD = false: the kernel of the plain entries.
+template <bool HD>
 __global__ void __launch_bounds__(256) k_d2_ab(const double* __restrict__ err, const int* __restrict__ block_start, const int* __restrict__ tcount,
-                                               int t0, long long npts, double* __restrict__ d2_ab) {
+                                               int t0, long long npts, double* __restrict__ d2_ab, double* __restrict__ h2_ab) {
     __shared__ double sh[256];
+    __shared__ double shm[HD ? 256 : 1];
     const int tl = blockIdx.x, b = blockIdx.y, t = t0 + tl;
     if (t >= live_thresholds(tcount, b)) return;
     double s = 0.0;
-    for (long long i = block_start[b] + threadIdx.x; i < block_start[b + 1]; i += 256) s += err[(size_t)tl * npts + i];
+    [[maybe_unused]] double m = 0.0;
+    for (long long i = block_start[b] + threadIdx.x; i < block_start[b + 1]; i += 256) {
+        const double e = err[(size_t)tl * npts + i];
+        s += e;
+        if constexpr (HD) m = Larger()(m, e);
+    }
     s = tree256(s, sh, Sum());
     if (threadIdx.x == 0) d2_ab[(size_t)b * kT + t] = s;
+    if constexpr (HD) {
+        m = tree256(m, shm, Larger());
+        if (threadIdx.x == 0) h2_ab[(size_t)b * kT + t] = m;
+    }
+}
+
+// H2_BA by level: hmax[b][k] = the largest e(v) over the voxels of level k, the doubles k_d2_ba adds.  They are squares (finite, >= 0), so
+// the order of their bit patterns as unsigned 64-bit integers is their order as numbers and an integer atomic maximum is exact, whatever
+// order the voxels arrive in: a table of 256 maxima per workgroup in LDS, then one global atomic maximum per level met.  hmax is
+// zero-filled by the caller (the bits of 0.0); H2_BA(t) = max_{k>t} hmax[b][k] is formed on the host like the suffix sums.
+__global__ void __launch_bounds__(256) k_level_max(const unsigned char* __restrict__ lev, const double* __restrict__ e, size_t nvox,
+                                                   unsigned long long* __restrict__ hmax) {
+    __shared__ unsigned long long smax[kT];
+    const int b = blockIdx.y;
+    for (int j = threadIdx.x; j < kT; j += blockDim.x) smax[j] = 0;
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (size_t)gridDim.x * blockDim.x) {
+        const int k = lev[(size_t)b * nvox + i];
+        if (k) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(e[(size_t)b * nvox + i]);
+            if (bits) atomicMax(&smax[k], bits);
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < kT; j += blockDim.x)
+        if (smax[j]) atomicMax(&hmax[(size_t)b * kT + j], smax[j]);
 }
 
 struct D2Layout {
@@ -487,13 +526,19 @@ PCC_API size_t pcc_d12_search_workspace_bytes(int32_t B, int32_t D, int32_t H, i
 //   workspace: pcc_d1_search_workspace_bytes, workspace2: pcc_d12_search_workspace_bytes,
 //   d2_ab, d2_ba: (B, 256) float64 (device), entry [b][t] valid for t < tcount[b].
 // The level grid comes from `src` (search_common.h): the D1 call builds it, everything here reads `lev` and `tcount` alone.
+// hd1 / h2_ab / h2_max (the Hausdorff entries; NULL in the plain ones, which launch the kernels they always did): the D1 maxima of
+// search_common.h's SearchHausdorff and, (B,256) float64, zero-filled here, h2_ab[b][t] = the largest term of d2_ab[b][t], h2_max[b][k] =
+// the largest term of d2_ba among the voxels of level k.
 static int d12_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* pts,
                      const int32_t* block_of, const int32_t* block_start, int64_t npts, const float* normals, void* workspace, void* workspace2,
-                     uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream) {
+                     uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba, void* stream,
+                     const SearchHausdorff& hd1 = {}, double* h2_ab = nullptr, double* h2_max = nullptr) {
     PCC_REQUIRE(normals && block_start && workspace2 && d2_ab && d2_ba && pts && npts > 0, "%s: NULL argument", src.who);
     PCC_REQUIRE((size_t)npts * 64 < ((size_t)1 << 31), "%s: too many points for one call", src.who);
+    const bool HD = h2_ab != nullptr;
+    PCC_REQUIRE(HD == (h2_max != nullptr) && HD == (hd1.h1_ab != nullptr), "%s: NULL argument", src.who);
     // D1 part (and the levels / tcount the D2 part builds on): unchanged kernels
-    { const int rc = pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream);
+    { const int rc = pcc_search_d1_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, npts, workspace, s_ab, hsum, hcnt, tcount, stream, hd1);
       if (rc != PCC_OK) return rc; }
     const int nthr = src.levels();
     hipStream_t st = (hipStream_t)stream;
@@ -518,6 +563,10 @@ static int d12_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, i
     const unsigned pblocks = (unsigned)((npts + 255) / 256);
     PCC_CHECK_HIP(hipMemsetAsync(d2_ab, 0, (size_t)B * kT * 8, st));
     PCC_CHECK_HIP(hipMemsetAsync(d2_ba, 0, (size_t)B * kT * 8, st));
+    if (HD) {
+        PCC_CHECK_HIP(hipMemsetAsync(h2_ab, 0, (size_t)B * kT * 8, st));
+        PCC_CHECK_HIP(hipMemsetAsync(h2_max, 0, (size_t)B * kT * 8, st));
+    }
     // ---- B -> A: index transform of the original points (occupancy as a one-threshold level set), plane error per voxel
     PCC_CHECK_HIP(hipMemsetAsync(idx, 0x7F, (size_t)B * nvox * 4, st));
     hipLaunchKernelGGL(k_index_grid, dim3(pblocks), dim3(256), 0, st, pts, block_of, (long long)npts, D, H, W, idx);
@@ -526,6 +575,7 @@ static int d12_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, i
     hipLaunchKernelGGL(k_ft_x_full, dim3(vox_blocks, 1, B), dim3(256), 0, st, fty, nvox, D, H, W, fta);
     hipLaunchKernelGGL(k_plane_err_ba, dim3(vox_blocks, B), dim3(256), 0, st, lev, fta, idx, normals, nvox, D, H, W, e);
     hipLaunchKernelGGL(k_d2_ba, dim3(nthr, B), dim3(256), 0, st, lev, e, tcount, nvox, d2_ba);
+    if (HD) hipLaunchKernelGGL(k_level_max, dim3(64, B), dim3(256), 0, st, lev, e, nvox, (unsigned long long*)h2_max);
     // ---- A -> B per chunk of thresholds (the D1 sums of this direction came from the D1 call above)
     for (int t0 = 0; t0 < nthr; t0 += l.TC) {
         const int nt = nthr - t0 < l.TC ? nthr - t0 : l.TC;
@@ -538,7 +588,8 @@ static int d12_stats(pcc_ctx* ctx, const LevelSource& src, const float* x_hat, i
         PCC_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs((void*)(w2 + l.sort_tmp), tmp, keys0, keys1, vals0, vals1, (int)pairs, 0, 48, st));
         hipLaunchKernelGGL(k_group_plane_err, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, keys1, vals1, pairs, pts, normals,
                            (long long)npts, H, W, err);
-        hipLaunchKernelGGL(k_d2_ab, dim3(nt, B), dim3(256), 0, st, err, block_start, tcount, t0, (long long)npts, d2_ab);
+        hipLaunchKernelGGL(HD ? k_d2_ab<true> : k_d2_ab<false>, dim3(nt, B), dim3(256), 0, st, err, block_start, tcount, t0, (long long)npts, d2_ab,
+                           h2_ab);
     }
     PCC_CHECK_HIP(hipGetLastError());
     return PCC_OK;
@@ -562,6 +613,31 @@ PCC_API int pcc_d12_count_stats(pcc_ctx* ctx, const float* x_hat, int32_t B, int
     const LevelSource src = {"pcc_d12_count_stats", nullptr, 0, 0, counts, J, rank_workspace, rank_workspace_bytes};
     return d12_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, block_start, npts, normals, workspace, workspace2, s_ab, hsum, hcnt, tcount, d2_ab,
                      d2_ba, stream);
+}
+
+// pcc_d12_threshold_stats / pcc_d12_count_stats with the D1 and D2 Hausdorff terms beside the sums (include/pcc_geo.h "Hausdorff terms of
+// the search"): the same kernels with their maxima switched on, so the shared outputs are the same bits
+PCC_API int pcc_d12_threshold_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const float* thr,
+                                              int32_t nthr, int32_t clip, const int32_t* pts, const int32_t* block_of,
+                                              const int32_t* block_start, int64_t npts, const float* normals, void* workspace, void* workspace2,
+                                              uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount, double* d2_ab, double* d2_ba,
+                                              uint32_t* h1_ab, uint32_t* h1_max, double* h2_ab, double* h2_max, void* stream) {
+    PCC_REQUIRE(h1_ab && h1_max && h2_ab && h2_max, "pcc_d12_threshold_stats_hausdorff: NULL argument");
+    const LevelSource src = {"pcc_d12_threshold_stats_hausdorff", thr, nthr, clip, nullptr, 0, nullptr, 0};
+    return d12_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, block_start, npts, normals, workspace, workspace2, s_ab, hsum, hcnt, tcount, d2_ab,
+                     d2_ba, stream, {h1_ab, h1_max}, h2_ab, h2_max);
+}
+
+PCC_API int pcc_d12_count_stats_hausdorff(pcc_ctx* ctx, const float* x_hat, int32_t B, int32_t D, int32_t H, int32_t W, const int32_t* counts,
+                                          int32_t J, const int32_t* pts, const int32_t* block_of, const int32_t* block_start, int64_t npts,
+                                          const float* normals, void* workspace, void* workspace2, void* rank_workspace,
+                                          size_t rank_workspace_bytes, uint64_t* s_ab, uint64_t* hsum, uint64_t* hcnt, int32_t* tcount,
+                                          double* d2_ab, double* d2_ba, uint32_t* h1_ab, uint32_t* h1_max, double* h2_ab, double* h2_max,
+                                          void* stream) {
+    PCC_REQUIRE(counts && h1_ab && h1_max && h2_ab && h2_max, "pcc_d12_count_stats_hausdorff: NULL argument");
+    const LevelSource src = {"pcc_d12_count_stats_hausdorff", nullptr, 0, 0, counts, J, rank_workspace, rank_workspace_bytes};
+    return d12_stats(ctx, src, x_hat, B, D, H, W, pts, block_of, block_start, npts, normals, workspace, workspace2, s_ab, hsum, hcnt, tcount, d2_ab,
+                     d2_ba, stream, {h1_ab, h1_max}, h2_ab, h2_max);
 }
 
 PCC_API int32_t pcc_d12_search_ties_chunk(int32_t B, int32_t D, int32_t H, int32_t W) {
@@ -629,7 +705,7 @@ PCC_API int pcc_d12_threshold_stats_ties(pcc_ctx* ctx, const float* x_hat, int32
         hipLaunchKernelGGL(k_tie_groups, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, keys1, vals1, prow, ctl, cap, pts, normals, H, W,
                            perr);
         hipLaunchKernelGGL(k_tie_row_mean, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, cnt, off, perr, ctl, slots, err);
-        hipLaunchKernelGGL(k_d2_ab, dim3(nt, B), dim3(256), 0, st, err, block_start, tcount, t0, (long long)npts, d2_ab);
+        hipLaunchKernelGGL(k_d2_ab<false>, dim3(nt, B), dim3(256), 0, st, err, block_start, tcount, t0, (long long)npts, d2_ab, (double*)nullptr);
     }
     hipLaunchKernelGGL(k_pair_nan, dim3((B * kT + 255) / 256), dim3(256), 0, st, (const long long*)status, B * kT, d2_ab, d2_ba);
     PCC_CHECK_HIP(hipGetLastError());

@@ -179,6 +179,7 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
     """compress_octree.compress for one cloud on the resident state: the same arguments, the same plan, the same writer."""
     from . import compress_octree as CO
     from .model_syntax import stream_tag
+    from .utils.pc_metric import hausdorff_opt_metrics
     argv = ['--input_files', original.input_pc, '--output_files', *enc_pcs, '--checkpoint_dir', model_dir, '--model_config', model_config,
             '--opt_metrics', *opt_metrics, '--max_deltas', *[str(d) for d in max_deltas], '--resolution', str(resolution),
             '--octree_level', str(octree_level), '--metrics_device', metrics_device, '--d2_ties', d2_ties, '--batch_size', str(batch_size)]
@@ -196,9 +197,12 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
         # the count search scores d2_* metrics with the GPU engine alone: ask for it where one is requested
         argv += ['--count_search', *[repr(v) for v in count_search]]
         argv += ['--d2_search', 'gpu'] if any(m.startswith('d2_') for m in opt_metrics) else []
+    elif any(m.startswith('d2_') and m in hausdorff_opt_metrics for m in opt_metrics):
+        argv += ['--d2_search', 'gpu']      # likewise: the d2 Hausdorff terms exist in the GPU engine alone
     args = CO.build_parser().parse_args(argv)
     CO.check_count_threshold(args, 1)
     CO.check_count_search(args, 1)
+    CO.check_hausdorff_metrics(args, 1)
     clouds, with_normals = CO._plan(args)
     CO.check_metrics_device(args.metrics_device, 1)
     CO.check_d2_ties(args.d2_ties, 1)
@@ -380,7 +384,7 @@ def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input
 
 
 def build_parser():
-    from .utils.pc_metric import avail_opt_metrics
+    from .utils.pc_metric import avail_opt_metrics, hausdorff_opt_metrics
     p = argparse.ArgumentParser(prog='ev_experiment.py', description='Run experiment for a point cloud.',
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('--output_dir', help='Output directory', required=True)
@@ -394,7 +398,9 @@ def build_parser():
     p.add_argument('--octree_level', type=int, default=4, help='Octree level of the encoder (new)')
     p.add_argument('--pcerror_path', help='Accepted and ignored: no external pc_error is run')
     p.add_argument('--pcerror_cfg_path', help='pc_error configuration: its resolution (a peak value) + 1 is the grid size')
-    p.add_argument('--opt_metrics', nargs='+', help=f'Optimization metrics used. Available: {avail_opt_metrics}', required=True)
+    p.add_argument('--opt_metrics', nargs='+', required=True,
+                   help=f'Optimization metrics used. Available: {avail_opt_metrics}; worst-point objectives (new): {hausdorff_opt_metrics} '
+                        '(one process, --search_ties pick; the d2 ones read the GPU search engine)')
     p.add_argument('--max_deltas', nargs='+', type=float, help='Max deltas tested during optimization.', required=True)
     p.add_argument('--fixed_threshold', help='Enable fixed thresholding.', default=False, action='store_true')
     p.add_argument('--count_threshold', nargs='?', type=float, const=1.0, default=None, metavar='RHO',

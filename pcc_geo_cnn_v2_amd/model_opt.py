@@ -24,7 +24,7 @@ import numpy as np
 from scipy.spatial import cKDTree
 
 from .utils import pc_metric as PM
-from .utils.pc_metric import validate_opt_metrics
+from .utils.pc_metric import validate_opt_metrics, wants_hausdorff
 
 logger = logging.getLogger(__name__)
 
@@ -94,12 +94,35 @@ def check_search_ties(ties, opt_metrics=None, with_normals=True):
             raise AssertionError("search_ties 'mean' needs normals (--input_normals or --estimate_normals): d2_* metrics read them")
 
 
-def host_threshold_stats(block, x_hat, thresholds, normals=None, ties='pick'):
+def check_hausdorff_search(opt_metrics, ties='pick', d2_gpu=True, world=1):
+    """What the Hausdorff opt metrics (PM.hausdorff_opt_metrics) cannot be combined with, refused before any work with
+    the flag to change: the tie-averaged search (no _ties form of the maxima), the pruned host KD-tree D2 search (its bounds hold for
+    sums, not for a maximum; d1_hausdorff* never needs it) and sharded runs (the ranks' tallies are reduced by sums).  d2_gpu may be a
+    callable, evaluated only when a d2 Hausdorff metric is named."""
+    named = [m for m in (opt_metrics or ()) if m in PM.hausdorff_opt_metrics]
+    if not named:
+        return
+    if ties == 'mean':
+        raise AssertionError(f"opt metric {named[0]}: Hausdorff terms are not computed by the tie-averaged search, drop --search_ties mean "
+                             '(the default --search_ties pick has them)')
+    if world > 1:
+        raise AssertionError(f'opt metric {named[0]}: Hausdorff terms need a single process (world size {world}): the sharded search '
+                             'reduces its tallies by sums, run on one GPU (--gpus 1) or drop the metric')
+    d2_named = [m for m in named if m.startswith('d2_')]
+    if d2_named and not (d2_gpu() if callable(d2_gpu) else d2_gpu):
+        raise AssertionError(f'opt metric {d2_named[0]}: the host KD-tree D2 search prunes with bounds that hold for sums only, '
+                             'pass --d2_search gpu')
+
+
+def host_threshold_stats(block, x_hat, thresholds, normals=None, ties='pick', hausdorff=False):
     """Tallies of every non-empty leading level set of one block against the original points, with KD-trees.
     Returns (tallies float64[T, 5], mean_tally float64[5]); T = number of leading non-empty level sets.
     ties='mean': the plain restatement of the tie-averaged definition, PM.tie_mean_tally per level set and
-    for the mean point -- every level set evaluated, nothing pruned; the D1 slots are the same integers either way."""
+    for the mean point -- every level set evaluated, nothing pruned; the D1 slots are the same integers either way.
+    hausdorff=True (ties='pick' only): 9-slot tallies and a 9-slot mean-point tally, PM.pair_tally_hausdorff -- np.max over the
+    per-point terms pair_tally sums, the plain restatement the GPU's maxima are checked against."""
     check_search_ties(ties)
+    assert not (hausdorff and ties == 'mean'), "host_threshold_stats: hausdorff=True needs ties='pick'"
     if ties == 'mean':
         a = np.asarray(block)[:, :3]
         tree_a = cKDTree(np.asarray(a, np.float64), balanced_tree=False)
@@ -111,14 +134,15 @@ def host_threshold_stats(block, x_hat, thresholds, normals=None, ties='pick'):
     a = block[:, :3]
     tree_a = cKDTree(a, balanced_tree=False)
     cand, subsets = _level_subsets(x_hat, thresholds)
-    tallies = np.zeros((len(subsets), 5), np.float64)
+    pair = PM.pair_tally_hausdorff if hausdorff else PM.pair_tally
+    tallies = np.zeros((len(subsets), 9 if hausdorff else 5), np.float64)
     cand_to_a = PM.nearest(tree_a, cand) if subsets else None       # B->A: one query serves every threshold
     for t, sel in enumerate(subsets):
         b = cand[sel]
         to_b = PM.nearest(cKDTree(b, balanced_tree=False), a)       # A->B: the reference's tree over B_t
-        tallies[t] = PM.pair_tally(a, b, to_b, cand_to_a[sel], normals)
+        tallies[t] = pair(a, b, to_b, cand_to_a[sel], normals)
     mean_point = np.round(np.mean(a, axis=0))[np.newaxis, :]
-    mean_tally = PM.pair_tally(a, mean_point, np.zeros(len(a), np.int64), PM.nearest(tree_a, mean_point), normals)
+    mean_tally = pair(a, mean_point, np.zeros(len(a), np.int64), PM.nearest(tree_a, mean_point), normals)
     return tallies, mean_tally
 
 
@@ -257,22 +281,34 @@ def host_threshold_stats_pruned(block, x_hat, thresholds, normals, d1_gpu, resol
     return hi, mean_tally, int(exact.sum())
 
 
-def mean_point_d1_tally(block):
-    """D1 tally of the rounded mean point without a KD-tree (which nearest original point is taken does not matter for D1)."""
+def mean_point_d1_tally(block, hausdorff=False):
+    """D1 tally of the rounded mean point without a KD-tree (which nearest original point is taken does not matter for D1).
+    hausdorff=True: nine slots; H1_AB = the largest squared distance of an original point to the mean point, H1_BA = the smallest (the
+    one decoded point's distance to its nearest original point)."""
     a = np.asarray(block)[:, :3].astype(np.float64)
     sq = PM.squared_norms(a - np.round(np.mean(a, axis=0)))
-    tally = np.zeros(5, np.float64)
+    tally = np.zeros(9 if hausdorff else 5, np.float64)
     tally[PM.N_B], tally[PM.D1_AB], tally[PM.D1_BA] = 1, sq.sum(), sq.min()
+    if hausdorff:
+        tally[PM.H1_AB], tally[PM.H1_BA] = sq.max(), sq.min()
     return tally
 
 
 def select_thresholds_from_stats(n_a, tallies, mean_tally, n_thresholds, resolution, opt_metrics, max_deltas):
     """Every decision of the reference's search (model_opt.py:33-73) from the per-threshold tallies of one block: for each
     max_delta the eligible thresholds (all of them when none is eligible or max_delta is None), for each metric the first
-    minimum over those, replaced by the 'emit nothing' index n_thresholds - 1 when the single mean point scores better."""
+    minimum over those, replaced by the 'emit nothing' index n_thresholds - 1 when the single mean point scores better.
+    With a Hausdorff metric (PM.hausdorff_opt_metrics) among opt_metrics the tallies and the guard carry nine slots, five otherwise; the
+    rule is the same.  Plateaus: a maximum changes only when the worst point does, so neighbouring candidates often score EQUAL -- the
+    first minimum then is the lowest candidate index of the plateau (the lowest threshold, hence the largest decoded set; the highest
+    count of a count ladder), and the guard replaces it only when strictly better, never on a tie."""
     names = metric_names(opt_metrics, max_deltas)
     nothing = n_thresholds - 1
-    tallies = np.asarray(tallies, np.float64).reshape(-1, 5)
+    width = 9 if wants_hausdorff(opt_metrics) else 5
+    tallies = np.asarray(tallies, np.float64)
+    assert tallies.size == 0 or tallies.shape[-1] == width, \
+        f'select_thresholds_from_stats: {width}-slot tallies expected for {list(opt_metrics)}, got {tallies.shape}'
+    tallies = tallies.reshape(-1, width)
     if len(tallies) == 0:
         return names, [nothing] * len(opt_metrics)          # (sic) not x len(max_deltas): model_opt.py:35-36
     groups = sorted({m.split('_', 1)[0] for m in opt_metrics})
@@ -297,10 +333,11 @@ def compute_optimal_thresholds(block, x_hat, thresholds, resolution, normals=Non
     """The reference's entry point (model_opt.py:21): (names '{metric}_{max_delta}', threshold index per name).  ties='mean' (new):
     the d2 statistics average over all equidistant nearest points (host_threshold_stats)."""
     validate_opt_metrics(opt_metrics, with_normals=normals is not None)
+    check_hausdorff_search(opt_metrics, ties)
     assert len(max_deltas) > 0
     if fixed_threshold:
         return metric_names(opt_metrics, max_deltas), [len(thresholds) // 2] * (len(max_deltas) * len(opt_metrics))
-    tallies, mean_tally = host_threshold_stats(block, x_hat, thresholds, normals, ties)
+    tallies, mean_tally = host_threshold_stats(block, x_hat, thresholds, normals, ties, hausdorff=wants_hausdorff(opt_metrics))
     return select_thresholds_from_stats(len(block), tallies, mean_tally, len(thresholds), resolution, opt_metrics, max_deltas)
 
 
@@ -456,27 +493,37 @@ def _upload_blocks(ctx, blocks, thresholds, normals=None):
     return [torch.from_numpy(a).to(ctx.device) for a in arrays]
 
 
-def _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab=None, d2_ba=None):
-    """[float64[T_i, 5]] per block from the kernels' (B, n_thresholds) outputs; the d2 slots stay zero without d2 sums."""
+def _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab=None, d2_ba=None, hd=None):
+    """[float64[T_i, 5]] per block from the kernels' (B, n_thresholds) outputs; the d2 slots stay zero without d2 sums.  hd: the Hausdorff
+    arrays of an ops call with hausdorff=True, (h1_ab, h1_ba) or (h1_ab, h1_ba, h2_ab, h2_ba) -> [float64[T_i, 9]]."""
     out = []
     for i in range(len(tcount)):
         T = int(tcount[i])
-        t = np.zeros((T, 5), np.float64)
+        t = np.zeros((T, 9 if hd is not None else 5), np.float64)
         t[:, PM.N_B], t[:, PM.D1_AB], t[:, PM.D1_BA] = n_b[i][:T], s_ab[i][:T], s_ba[i][:T]
         if d2_ab is not None:
             t[:, PM.D2_AB], t[:, PM.D2_BA] = d2_ab[i][:T], d2_ba[i][:T]
+        for slot, h in zip((PM.H1_AB, PM.H1_BA, PM.H2_AB, PM.H2_BA), hd or ()):
+            t[:, slot] = h[i][:T]
         out.append(t)
     return out
 
 
-def d1_tallies_gpu(ctx, blocks, x_hat, thresholds):
+def _split_stats(res, d2):
+    """An ops search result as _tally_tables' arguments: the plain tuple, and whatever follows it (hausdorff=True) as `hd`."""
+    s_ab, s_ba, n_b, tcount = res[:4]
+    d2_ab, d2_ba = res[4:6] if d2 else (None, None)
+    return tcount, n_b, s_ab, s_ba, d2_ab, d2_ba, (res[6 if d2 else 4:] or None)
+
+
+def d1_tallies_gpu(ctx, blocks, x_hat, thresholds, hausdorff=False):
     """Per-block D1 tallies from exact distance transforms on the GPU (csrc/search_d1.hip).  blocks: list of
     (n_i, >=3) arrays; x_hat: (B,D,H,W) float32 device tensor (clipped inside, like model_types.py:202).
-    Returns [float64[T_i, 5]] -- the d2 slots are zero."""
+    Returns [float64[T_i, 5]] -- the d2 slots are zero.  hausdorff=True: [float64[T_i, 9]] with the H1 slots filled (the Hausdorff form
+    of the call is only made then)."""
     from . import ops
     thr, xyz, bof = _upload_blocks(ctx, blocks, thresholds)
-    s_ab, s_ba, n_b, tcount = ops.d1_threshold_stats(ctx, x_hat, thr, xyz, bof, clip=True)
-    return _tally_tables(tcount, n_b, s_ab, s_ba)
+    return _tally_tables(*_split_stats(ops.d1_threshold_stats(ctx, x_hat, thr, xyz, bof, clip=True, hausdorff=hausdorff), d2=False))
 
 
 def _canonical_rows(block):
@@ -487,31 +534,35 @@ def _canonical_rows(block):
     return blk[np.lexsort((nrm[:, 2], nrm[:, 1], nrm[:, 0], blk[:, 2], blk[:, 1], blk[:, 0]))]
 
 
-def d12_tallies_gpu(ctx, blocks, x_hat, thresholds, ties='pick', max_pairs=None):
+def d12_tallies_gpu(ctx, blocks, x_hat, thresholds, ties='pick', max_pairs=None, hausdorff=False):
     """Per-block D1 AND D2 tallies on the GPU.  blocks: list of (n_i, 6) arrays, xyz + normals (the last three columns, as
     model_types.get_normals_if takes them).  Returns [float64[T_i, 5]].  ties='pick': ties between equidistant nearest neighbours go
     to the lowest (x, y, z) -- the reference takes scipy's pick (pc_metric.py:114); D1 does not depend on the pick.  ties='mean': D2
     averages over ALL equidistant nearest points (ops.d12_threshold_stats_ties, float64 normals): the sums of
-    host_threshold_stats(ties='mean') up to float64 rounding, whatever the row order of the blocks."""
+    host_threshold_stats(ties='mean') up to float64 rounding, whatever the row order of the blocks.
+    hausdorff=True (ties='pick' only): [float64[T_i, 9]], all four Hausdorff slots filled by the Hausdorff form of the call."""
     from . import ops
     check_search_ties(ties)
+    assert not (hausdorff and ties == 'mean'), "d12_tallies_gpu: hausdorff=True needs ties='pick'"
     if ties == 'mean':
         thr, xyz, bof, start, nrm = _upload_blocks(ctx, [_canonical_rows(b) for b in blocks], thresholds, np.float64)
         s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats_ties(ctx, x_hat, thr, xyz, bof, start, nrm, clip=True, max_pairs=max_pairs)
     else:
         thr, xyz, bof, start, nrm = _upload_blocks(ctx, blocks, thresholds, np.float32)
-        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_threshold_stats(ctx, x_hat, thr, xyz, bof, start, nrm, clip=True)
+        return _tally_tables(*_split_stats(ops.d12_threshold_stats(ctx, x_hat, thr, xyz, bof, start, nrm, clip=True, hausdorff=hausdorff), d2=True))
     return _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab, d2_ba)
 
 
-def mean_point_tally(block, with_normals, ties='pick'):
+def mean_point_tally(block, with_normals, ties='pick', hausdorff=False):
     """Tally of the rounded mean point (the guard of model_opt.py:59-68) without a KD-tree: its nearest original point; among
     equidistant ones the lowest (x, y, z) in lexicographic order -- the tie rule of the GPU path (csrc/search_d2.hip), whatever
     order the block's points are stored in (a plain argmin is that rule only for sorted blocks).  ties='mean': the
-    tie-averaged rule, PM.tie_mean_tally(a, mean_point, normals)."""
+    tie-averaged rule, PM.tie_mean_tally(a, mean_point, normals).  hausdorff=True (ties='pick'): nine slots, the maxima of the same
+    per-point terms (mean_point_d1_tally for the D1 pair)."""
     blk = np.asarray(block)
+    assert not (hausdorff and ties == 'mean'), "mean_point_tally: hausdorff=True needs ties='pick'"
     if not with_normals:
-        return mean_point_d1_tally(blk)
+        return mean_point_d1_tally(blk, hausdorff)
     a = blk[:, :3]
     mean_point = np.round(np.mean(a, axis=0))[np.newaxis, :]
     if ties == 'mean':      # rows in canonical order, like the tallies: the guard's bits do not depend on the input's row order either
@@ -520,19 +571,22 @@ def mean_point_tally(block, with_normals, ties='pick'):
     d = PM.squared_norms(a - mean_point)
     near = np.flatnonzero(d == d.min())
     to_a = np.array([int(near[np.lexsort((a[near, 2], a[near, 1], a[near, 0]))[0]])], np.int64)
-    return PM.pair_tally(a, mean_point, np.zeros(len(a), np.int64), to_a, blk[:, blk.shape[1] - 3:])
+    pair = PM.pair_tally_hausdorff if hausdorff else PM.pair_tally
+    return pair(a, mean_point, np.zeros(len(a), np.int64), to_a, blk[:, blk.shape[1] - 3:])
 
 
 def decide_from_tallies(blocks, d1, n_thresholds, resolution, opt_metrics, max_deltas, d2_stats=None, gpu_d2=False, ties='pick'):
     """Decisions of a chunk from the GPU's D1 tallies (d1_tallies_gpu), merged with the host pool's (tallies, mean_tally) per
     block when d2_* metrics are requested: their D2 slots go into the GPU's table; the D1 slots of both sources are the same
     integers, which is asserted.  `ties`: the rule the D2 slots were computed by (d12_tallies_gpu(ties=) with gpu_d2, or the host
-    pool's 'tally' jobs).  Returns (names, [best thresholds per block])."""
+    pool's 'tally' jobs).  With a Hausdorff metric among opt_metrics `d1` holds 9-slot tallies (d1_tallies_gpu / d12_tallies_gpu with
+    hausdorff=True) and the guard carries nine slots too.  Returns (names, [best thresholds per block])."""
     validate_opt_metrics(opt_metrics, with_normals=d2_stats is not None or gpu_d2)
+    check_hausdorff_search(opt_metrics, ties, d2_gpu=gpu_d2)
     names, best = metric_names(list(opt_metrics), list(max_deltas)), []
     for i, blk in enumerate(blocks):
         # gpu_d2: the tallies of d12_tallies_gpu already hold their D2 slots; the guard point follows the same tie rule
-        tallies, mean_tally = d1[i], mean_point_tally(blk, gpu_d2, ties)      # (ties: the guard follows the rule of the tallies)
+        tallies, mean_tally = d1[i], mean_point_tally(blk, gpu_d2, ties, wants_hausdorff(opt_metrics))      # (ties: the guard follows the rule of the tallies)
         if d2_stats is not None:
             host_t, host_mean = d2_stats[i]
             assert len(host_t) == len(tallies), 'host and GPU disagree on the number of non-empty level sets'
@@ -552,7 +606,7 @@ def compute_optimal_thresholds_gpu(ctx, blocks, x_hat, thresholds, resolution, o
     transforms on the GPU.  `d2_stats`: per block (tallies, mean_tally) from the host pool when d2_* metrics are requested -- or
     a callable returning that list, evaluated after the GPU work has been issued; `ties`: the rule they were computed by.  Returns
     (names, [best thresholds per block])."""
-    d1 = d1_tallies_gpu(ctx, blocks, x_hat, thresholds)
+    d1 = d1_tallies_gpu(ctx, blocks, x_hat, thresholds, hausdorff=wants_hausdorff(opt_metrics))
     if callable(d2_stats):
         d2_stats = d2_stats()
     return decide_from_tallies(blocks, d1, len(thresholds), resolution, opt_metrics, max_deltas, d2_stats, ties=ties)
@@ -591,20 +645,19 @@ def count_rows(blocks, ladder, n_voxels):
     return np.array([[block_count(len(b), rho, n_voxels) for rho in ladder] for b in blocks], np.int32).reshape(len(blocks), len(ladder))
 
 
-def count_tallies_gpu(ctx, blocks, x_hat, rows, d2=False):
+def count_tallies_gpu(ctx, blocks, x_hat, rows, d2=False, hausdorff=False):
     """The twin of d1_tallies_gpu / d12_tallies_gpu(ties='pick') for candidate counts: per block float64[T_b, 5] tallies of the top-rows[b][j]
     sets of x_hat (ops.d1_count_stats; with d2 ops.d12_count_stats, blocks then carry normals in their last three columns), j < T_b =
-    the candidates with a non-empty set.  x_hat is NOT clipped: the decoder's top-k selection ranks the raw scores."""
+    the candidates with a non-empty set.  x_hat is NOT clipped: the decoder's top-k selection ranks the raw scores.  hausdorff=True:
+    float64[T_b, 9] from the Hausdorff forms of the two calls."""
     import torch
     from . import ops
     rows = torch.from_numpy(np.ascontiguousarray(rows, np.int32))
     if d2:
         _, xyz, bof, start, nrm = _upload_blocks(ctx, blocks, [], np.float32)
-        s_ab, s_ba, n_b, tcount, d2_ab, d2_ba = ops.d12_count_stats(ctx, x_hat, rows, xyz, bof, start, nrm)
-        return _tally_tables(tcount, n_b, s_ab, s_ba, d2_ab, d2_ba)
+        return _tally_tables(*_split_stats(ops.d12_count_stats(ctx, x_hat, rows, xyz, bof, start, nrm, hausdorff=hausdorff), d2=True))
     _, xyz, bof = _upload_blocks(ctx, blocks, [])
-    s_ab, s_ba, n_b, tcount = ops.d1_count_stats(ctx, x_hat, rows, xyz, bof)
-    return _tally_tables(tcount, n_b, s_ab, s_ba)
+    return _tally_tables(*_split_stats(ops.d1_count_stats(ctx, x_hat, rows, xyz, bof, hausdorff=hausdorff), d2=False))
 
 
 def decide_counts_from_tallies(blocks, tallies, rows, resolution, opt_metrics, max_deltas, with_normals=False):
@@ -614,11 +667,12 @@ def decide_counts_from_tallies(blocks, tallies, rows, resolution, opt_metrics, m
     k = 0 for every metric.  with_normals: the tallies hold D2 slots (count_tallies_gpu(d2=True)), the guard follows their tie rule.
     Returns (names, [k per name] per block, [index per name] per block)."""
     validate_opt_metrics(opt_metrics, with_normals=with_normals)
+    hd = wants_hausdorff(opt_metrics)       # (the tallies then are count_tallies_gpu(hausdorff=True)'s)
     rows = np.asarray(rows)
     J = rows.shape[1]
     names, ks, idx = metric_names(list(opt_metrics), list(max_deltas)), [], []
     for b, blk in enumerate(blocks):
-        names, best = select_thresholds_from_stats(len(blk), tallies[b], mean_point_tally(blk, with_normals), J + 1, resolution,
+        names, best = select_thresholds_from_stats(len(blk), tallies[b], mean_point_tally(blk, with_normals, hausdorff=hd), J + 1, resolution,
                                                    list(opt_metrics), list(max_deltas))
         best = list(best) + [best[-1]] * (len(names) - len(best))      # (an empty table answers once per metric: SearchSchedule._finalize)
         idx.append([int(j) for j in best])

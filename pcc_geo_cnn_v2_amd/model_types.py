@@ -32,11 +32,11 @@ from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
 from ._stream_io import _Immediate, _Pinned, _host_dtypes, gather_points, indexes_to_host, on_side_stream, ship, side_stream, symbols_to_device, to_host
 from .block_search import SearchSchedule
-from .model_opt import count_rows, count_tallies_gpu, d2_on_gpu, decide_counts_from_tallies
+from .model_opt import check_hausdorff_search, count_rows, count_tallies_gpu, d2_on_gpu, decide_counts_from_tallies
 from .model_syntax import count_from_bytes, count_to_bytes
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
-from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu
+from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu, wants_hausdorff
 
 logger = logging.getLogger(__name__)
 
@@ -80,13 +80,16 @@ METRICS_DEVICES = ('host', 'gpu')      # where the encoder's whole-cloud metrics
 
 
 def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, resolution, with_normals,
-                               opt_groups=('d1', 'd2'), tree=None, metrics_device='host', ctx=None, d2_ties='pick'):
+                               opt_groups=('d1', 'd2'), tree=None, metrics_device='host', ctx=None, d2_ties='pick', hausdorff=False):
     """Per optimisation group, which candidate reconstruction of the whole cloud to keep (the reference's function of the same
     name, model_types.py:128-176; results pinned by tests/golden/select_best.npz).  x_hat_list[m] = the decoded blocks of
     candidate m (block-local coordinates).  Returns one dict per non-empty group: 'idx', 'metrics', 'x_hat_list',
     'blocks_depart' (blocks in cloud coordinates), 'blocks_full' (one array).  metrics_device='gpu': the whole-cloud metrics come
     from pc_metric.cloud_metrics_batch_gpu on context `ctx` (neighbour ties to the lowest row) instead of the KD-trees.
-    d2_ties='mean': either engine averages D2 over all equidistant nearest points (pc_metric.tie_mean_tally)."""
+    d2_ties='mean': either engine averages D2 over all equidistant nearest points (pc_metric.tie_mean_tally).
+    hausdorff=True (a Hausdorff opt metric was named; single process): every 'metrics' also carries pc_metric.hausdorff_table's keys, from
+    the 9-slot whole-cloud tally of the same engine (cloud_tallies_gpu / cloud_tally_host: the same neighbour links, so the other keys
+    keep their values); the ranking is unchanged."""
     if metrics_device not in METRICS_DEVICES:
         raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
     assert len(opt_metrics) == len(x_hat_list), f'lengths of opt_metrics {len(opt_metrics)} and x_hat_list' + \
@@ -96,7 +99,18 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
     clouds = {m: np.vstack(placed[m]) for m in grouped}
     original = points[:, :3]
     # `tree`: the KD-tree over the original points when the caller built it meanwhile (compress_blocks: beside the block loop)
-    if metrics_device == 'gpu':
+    if hausdorff:
+        from .utils import pc_metric as PM
+        normals, peak = get_normals_if(points, with_normals), resolution - 1
+        if metrics_device == 'gpu':
+            from . import ops
+            tallies = PM.cloud_tallies_gpu(ctx if ctx is not None else ops.get_context(), original, [clouds[m] for m in grouped], normals, ties=d2_ties)
+        else:
+            tree = tree if tree is not None else cKDTree(original)
+            tallies = [PM.cloud_tally_host(original, clouds[m], normals, t1=tree, ties=d2_ties) if len(clouds[m]) else None for m in grouped]
+        scored = [None if t is None else dict(PM.metrics_table(len(original), t[:5], peak, PM.GROUPS if with_normals else PM.GROUPS[:1]),
+                                              **PM.hausdorff_table(t, peak, with_normals)) for t in tallies]
+    elif metrics_device == 'gpu':
         from . import ops
         scored = cloud_metrics_batch_gpu(ctx if ctx is not None else ops.get_context(), original, [clouds[m] for m in grouped],
                                          resolution - 1, get_normals_if(points, with_normals), ties=d2_ties)
@@ -529,7 +543,7 @@ class CompressionModel:
             strings = enc['finish']()
             if ladder is not None:
                 rows = count_rows(chunk, ladder, int(np.prod(dhw)))
-                tallies = count_tallies_gpu(ctx, chunk, enc['x_hat'], rows, d2=want_d2)
+                tallies = count_tallies_gpu(ctx, chunk, enc['x_hat'], rows, d2=want_d2, hausdorff=wants_hausdorff(opt_metrics))
                 search.names, ks_m, _ = decide_counts_from_tallies(chunk, tallies, rows, resolution, opt_metrics, max_deltas, with_normals=want_d2)
                 per_name = []
                 for m in range(len(search.names)):
@@ -578,6 +592,8 @@ class CompressionModel:
         check_count_scale(count_scale, fixed_threshold, self.lossless, world)
         check_count_search(count_search, count_scale, fixed_threshold, self.lossless, world, self.search_ties, opt_metrics,
                            lambda: d2_on_gpu(self.d2_search, 'pick'), None if count_search is None else self._spatial(self.x_shape))
+        if not fixed_threshold:
+            check_hausdorff_search(opt_metrics, self.search_ties, lambda: d2_on_gpu(self.d2_search, 'pick'), world)
         if metrics_device not in METRICS_DEVICES:
             raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
         if metrics_device == 'gpu' and world > 1:
@@ -602,7 +618,7 @@ class CompressionModel:
         x_hat_list = list(zip(*x_hat_list))
         metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
                                               metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess),
-                                              d2_ties=d2_ties)
+                                              d2_ties=d2_ties, **({'hausdorff': True} if wants_hausdorff(opt_metrics) and not fixed_threshold else {}))
         if count_search is not None:      # y/z strings + one count string per metric name: output m keeps its own
             n = self.n_strings
             data_list = [[(tuple(ss[:n]) + (ss[n + x['idx']],), t) for ss, t in zip(strings_list, threshold_list[x['idx']])] for x in metadata]

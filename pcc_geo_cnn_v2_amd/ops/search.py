@@ -1,5 +1,6 @@
 """The per-block search statistics (include/pcc_geo.h: pcc_d1_threshold_stats, pcc_d12_threshold_stats, pcc_d12_threshold_stats_ties) and their
-count-indexed twins (pcc_rank_levels, pcc_d1_count_stats, pcc_d12_count_stats)."""
+count-indexed twins (pcc_rank_levels, pcc_d1_count_stats, pcc_d12_count_stats); with hausdorff=True the four pick entries call their
+_hausdorff forms, which return the per-point maxima beside the sums."""
 import numpy as np
 import torch
 
@@ -24,6 +25,40 @@ def _search_outputs(x_hat, d2):
     return out + [torch.empty((B, 256), dtype=torch.float64, device=dev) for _ in range(2 if d2 else 0)]
 
 
+def _hausdorff_outputs(x_hat, d2):
+    """(h1_ab, h1_max uint32 (B,256)) and, with d2, (h2_ab, h2_max float64 (B,256)): the extra outputs of the _hausdorff entries, which
+    zero-fill them.  uint32 travels as int32 storage (every value is at most 3 * 127^2)."""
+    B, dev = x_hat.shape[0], x_hat.device
+    return [torch.empty((B, 256), dtype=torch.int32, device=dev) for _ in range(2)] + \
+        [torch.empty((B, 256), dtype=torch.float64, device=dev) for _ in range(2 if d2 else 0)]
+
+
+def _suffix_max(h):
+    """max over the levels k > t of a per-level table (B,256): where _search_results forms the suffix sums; 0 where no level is above t."""
+    return np.concatenate([np.maximum.accumulate(h[:, ::-1], 1)[:, ::-1][:, 1:], np.zeros((h.shape[0], 1), h.dtype)], 1)
+
+
+def _hausdorff_results(res, h1_ab, h1_max, h2_ab=None, h2_max=None):
+    """`res` (the tuple of _search_results) with (h1_ab, h1_ba) int64 and, with D2, (h2_ab, h2_ba) float64 appended: AB per candidate as
+    the engine wrote it, BA after the suffix maximum over the levels k > t."""
+    out = res + (h1_ab.cpu().numpy().astype(np.int64), _suffix_max(h1_max.cpu().numpy().astype(np.int64)))
+    if h2_ab is not None:
+        out += (h2_ab.cpu().numpy(), _suffix_max(h2_max.cpu().numpy()))
+    return out
+
+
+def _finish(who, out, hd):
+    """_search_results, with the Hausdorff arrays `hd` (None: a plain call) appended -- also to the `.results` of its PccError."""
+    if hd is None:
+        return _search_results(who, *out)
+    try:
+        return _hausdorff_results(_search_results(who, *out), *hd)
+    except L.PccError as err:
+        if hasattr(err, 'results'):
+            err.results = _hausdorff_results(err.results, *hd)
+        raise
+
+
 def _search_results(who, s_ab, hsum, hcnt, tcount, *d2):
     """The device outputs of a search as numpy: (s_ab, s_ba, n_b, tcount, *d2) with s_ba, n_b the suffix sums of the level
     histograms over the levels k > t.  tcount[b] == 256 (256 thresholds and a voxel above the last one: a level the engine's uint8
@@ -41,28 +76,45 @@ def _search_results(who, s_ab, hsum, hcnt, tcount, *d2):
     return res
 
 
-def d1_threshold_stats(ctx, x_hat, thr, pts, block_of, clip=True):
+def d1_threshold_stats(ctx, x_hat, thr, pts, block_of, clip=True, hausdorff=False):
     """Exact D1 sums for every threshold of every block (see include/pcc_geo.h).  x_hat (B,D,H,W) float32,
     thr (T<=256,) float32, pts (n,3) int32 grouped by block, block_of (n,) int32 -- all on the device.
     Returns int64 numpy arrays s_ab (B,256), s_ba (B,256), n_b (B,256) indexed by threshold, and tcount (B,).  Like the two D2
-    searches below it raises PccError when a block holds a voxel above all of 256 thresholds (_search_results)."""
+    searches below it raises PccError when a block holds a voxel above all of 256 thresholds (_search_results).
+    hausdorff=True (pcc_d1_threshold_stats_hausdorff): (h1_ab, h1_ba) int64 (B,256) appended -- the largest per-point squared distance
+    in each direction, h1_ba after the suffix maximum over the levels; the first four arrays are the plain call's bits."""
     B, D, H, W = _search_args(x_hat, thr, pts, block_of)
     ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
     s_ab, hsum, hcnt, tcount = out = _search_outputs(x_hat, d2=False)
+    if hausdorff:
+        hd = _hausdorff_outputs(x_hat, d2=False)
+        L.check(L.lib().pcc_d1_threshold_stats_hausdorff(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip), _ptr(pts),
+                                                         _ptr(block_of), pts.shape[0], _ptr(ws), _ptr(s_ab), _ptr(hsum), _ptr(hcnt), _ptr(tcount),
+                                                         _ptr(hd[0]), _ptr(hd[1]), ctx.stream), 'pcc_d1_threshold_stats_hausdorff')
+        return _finish('d1_threshold_stats', out, hd)
     L.check(L.lib().pcc_d1_threshold_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip),
                                            _ptr(pts), _ptr(block_of), pts.shape[0], _ptr(ws), _ptr(s_ab), _ptr(hsum),
                                            _ptr(hcnt), _ptr(tcount), ctx.stream), 'pcc_d1_threshold_stats')
     return _search_results('d1_threshold_stats', *out)
 
 
-def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, clip=True):
+def d12_threshold_stats(ctx, x_hat, thr, pts, block_of, block_start, normals, clip=True, hausdorff=False):
     """d1_threshold_stats plus the D2 sums of every threshold (include/pcc_geo.h: pcc_d12_threshold_stats).  normals (n,3) float32,
-    block_start (B+1,) int32 -- on the device.  Returns (s_ab, s_ba, n_b, tcount, d2_ab, d2_ba); d2_* float64 (B,256)."""
+    block_start (B+1,) int32 -- on the device.  Returns (s_ab, s_ba, n_b, tcount, d2_ab, d2_ba); d2_* float64 (B,256).
+    hausdorff=True (pcc_d12_threshold_stats_hausdorff): (h1_ab, h1_ba int64, h2_ab, h2_ba float64) appended, the largest of the
+    per-point terms whose sums the first six arrays hold (those are the plain call's bits)."""
     B, D, H, W = _search_args(x_hat, thr, pts, block_of, block_start)
     assert normals.dtype == torch.float32 and normals.is_contiguous() and normals.shape == pts.shape
     ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
     ws2 = _workspace(ctx, L.lib().pcc_d12_search_workspace_bytes(B, D, H, W, pts.shape[0]))
     s_ab, hsum, hcnt, tcount, d2_ab, d2_ba = out = _search_outputs(x_hat, d2=True)
+    if hausdorff:
+        hd = _hausdorff_outputs(x_hat, d2=True)
+        L.check(L.lib().pcc_d12_threshold_stats_hausdorff(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip), _ptr(pts),
+                                                          _ptr(block_of), _ptr(block_start), pts.shape[0], _ptr(normals), _ptr(ws), _ptr(ws2),
+                                                          _ptr(s_ab), _ptr(hsum), _ptr(hcnt), _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba),
+                                                          *(_ptr(h) for h in hd), ctx.stream), 'pcc_d12_threshold_stats_hausdorff')
+        return _finish('d12_threshold_stats', out, hd)
     L.check(L.lib().pcc_d12_threshold_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(thr), thr.numel(), int(clip), _ptr(pts), _ptr(block_of),
                                             _ptr(block_start), pts.shape[0], _ptr(normals), _ptr(ws), _ptr(ws2), _ptr(s_ab), _ptr(hsum), _ptr(hcnt),
                                             _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba), ctx.stream), 'pcc_d12_threshold_stats')
@@ -179,29 +231,44 @@ def _count_search_args(ctx, x_hat, counts, pts, block_of, block_start=None):
     return B, D, H, W, counts, J
 
 
-def d1_count_stats(ctx, x_hat, counts, pts, block_of):
+def d1_count_stats(ctx, x_hat, counts, pts, block_of, hausdorff=False):
     """d1_threshold_stats with candidate point counts in place of thresholds (include/pcc_geo.h: pcc_d1_count_stats): entry [b][j] of
     s_ab, s_ba, n_b is the exact D1 sum / size of the top-counts[b][j] set of block b -- the voxels topk_compact decodes for that k --
     valid for j < tcount[b]; n_b[b][j] = min(counts[b][j], positive voxels of b).  counts: (B,J) int32, J <= 255, rows non-increasing.
-    Nothing is clipped.  Returns the tuple of d1_threshold_stats, (B,256) arrays of which the first J columns are used."""
+    Nothing is clipped.  Returns the tuple of d1_threshold_stats, (B,256) arrays of which the first J columns are used.
+    hausdorff=True (pcc_d1_count_stats_hausdorff): (h1_ab, h1_ba) appended, as d1_threshold_stats does."""
     B, D, H, W, counts, J = _count_search_args(ctx, x_hat, counts, pts, block_of)
     ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
     rws = _rank_workspace(ctx, B, D * H * W)
     s_ab, hsum, hcnt, tcount = out = _search_outputs(x_hat, d2=False)
+    if hausdorff:
+        hd = _hausdorff_outputs(x_hat, d2=False)
+        L.check(L.lib().pcc_d1_count_stats_hausdorff(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(counts), J, _ptr(pts), _ptr(block_of), pts.shape[0],
+                                                     _ptr(ws), _ptr(rws), rws.numel(), _ptr(s_ab), _ptr(hsum), _ptr(hcnt), _ptr(tcount),
+                                                     _ptr(hd[0]), _ptr(hd[1]), ctx.stream), 'pcc_d1_count_stats_hausdorff')
+        return _finish('d1_count_stats', out, hd)
     L.check(L.lib().pcc_d1_count_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(counts), J, _ptr(pts), _ptr(block_of), pts.shape[0], _ptr(ws),
                                        _ptr(rws), rws.numel(), _ptr(s_ab), _ptr(hsum), _ptr(hcnt), _ptr(tcount), ctx.stream), 'pcc_d1_count_stats')
     return _search_results('d1_count_stats', *out)
 
 
-def d12_count_stats(ctx, x_hat, counts, pts, block_of, block_start, normals):
+def d12_count_stats(ctx, x_hat, counts, pts, block_of, block_start, normals, hausdorff=False):
     """d1_count_stats plus the D2 sums of every candidate count (include/pcc_geo.h: pcc_d12_count_stats), the tie rule of
-    d12_threshold_stats.  Returns (s_ab, s_ba, n_b, tcount, d2_ab, d2_ba)."""
+    d12_threshold_stats.  Returns (s_ab, s_ba, n_b, tcount, d2_ab, d2_ba); hausdorff=True (pcc_d12_count_stats_hausdorff): (h1_ab, h1_ba,
+    h2_ab, h2_ba) appended, as d12_threshold_stats does."""
     B, D, H, W, counts, J = _count_search_args(ctx, x_hat, counts, pts, block_of, block_start)
     assert normals.dtype == torch.float32 and normals.is_contiguous() and normals.shape == pts.shape
     ws = _workspace(ctx, L.lib().pcc_d1_search_workspace_bytes(B, D, H, W))
     ws2 = _workspace(ctx, L.lib().pcc_d12_search_workspace_bytes(B, D, H, W, pts.shape[0]))
     rws = _rank_workspace(ctx, B, D * H * W)
     s_ab, hsum, hcnt, tcount, d2_ab, d2_ba = out = _search_outputs(x_hat, d2=True)
+    if hausdorff:
+        hd = _hausdorff_outputs(x_hat, d2=True)
+        L.check(L.lib().pcc_d12_count_stats_hausdorff(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(counts), J, _ptr(pts), _ptr(block_of),
+                                                      _ptr(block_start), pts.shape[0], _ptr(normals), _ptr(ws), _ptr(ws2), _ptr(rws), rws.numel(),
+                                                      _ptr(s_ab), _ptr(hsum), _ptr(hcnt), _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba),
+                                                      *(_ptr(h) for h in hd), ctx.stream), 'pcc_d12_count_stats_hausdorff')
+        return _finish('d12_count_stats', out, hd)
     L.check(L.lib().pcc_d12_count_stats(ctx.handle, _ptr(x_hat), B, D, H, W, _ptr(counts), J, _ptr(pts), _ptr(block_of), _ptr(block_start),
                                         pts.shape[0], _ptr(normals), _ptr(ws), _ptr(ws2), _ptr(rws), rws.numel(), _ptr(s_ab), _ptr(hsum),
                                         _ptr(hcnt), _ptr(tcount), _ptr(d2_ab), _ptr(d2_ba), ctx.stream), 'pcc_d12_count_stats')

@@ -28,8 +28,18 @@ H1_AB, H1_BA, H2_AB, H2_BA = range(5, 9)
 _HAUSDORFF_SLOTS = {'d1': (H1_AB, H1_BA), 'd2': (H2_AB, H2_BA)}
 
 
+# new: the worst-point objectives of the per-block search, kept apart so that the reference's list above stays as it is
+_HAUSDORFF_STEMS = ('hausdorff_AB', 'hausdorff_BA', 'hausdorff')
+hausdorff_opt_metrics = [f'{g}_{stem}' for g in GROUPS for stem in _HAUSDORFF_STEMS]
+
+
+def wants_hausdorff(opt_metrics):
+    """Whether one of the opt metrics is a Hausdorff one: the search then carries 9-slot tallies (the maxima beside the sums)."""
+    return any(m in hausdorff_opt_metrics for m in (opt_metrics or ()))
+
+
 def validate_opt_metrics(opt_metrics, with_normals=False):
-    unknown = [m for m in opt_metrics if m not in avail_opt_metrics]
+    unknown = [m for m in opt_metrics if m not in avail_opt_metrics and m not in hausdorff_opt_metrics]
     assert not unknown, f'{unknown[0] if unknown else None} not found in {avail_opt_metrics}'
     needs_normals = [m for m in opt_metrics if m.split('_', 1)[0] == 'd2']
     assert with_normals or not needs_normals, f'{needs_normals[0] if needs_normals else None} not available without normals'
@@ -103,9 +113,24 @@ def pair_tally(a, b, to_b, to_a, a_normals=None, a_mask=None):
     return tally
 
 
+def pair_tally_hausdorff(a, b, to_b, to_a, a_normals=None):
+    """float64[9]: pair_tally's five slots plus the Hausdorff maxima, np.max over the per-point terms pair_tally sums (H1_AB, H1_BA and,
+    with normals, H2_AB, H2_BA).  B must not be empty."""
+    tally = np.zeros(9, np.float64)
+    tally[:5] = pair_tally(a, b, to_b, to_a, a_normals)
+    gap_ab, gap_ba = point_gap(a, b, to_b), point_gap(b, a, to_a)
+    tally[H1_AB], tally[H1_BA] = squared_norms(gap_ab).max(), squared_norms(gap_ba).max()
+    if a_normals is not None:
+        b_normals = transfer_normals(a_normals, to_a, to_b)
+        tally[H2_AB] = (((gap_ab * b_normals[to_b]).sum(axis=1)) ** 2).max()
+        tally[H2_BA] = (((gap_ba * a_normals[to_a]).sum(axis=1)) ** 2).max()
+    return tally
+
+
 def metrics_table(n_a, tally, peak, groups=GROUPS):
     """The reference's metric dictionary (pc_metric.py:83-137) from tallies.  `tally` is float64[5] (-> scalars) or
-    float64[T, 5] (-> arrays over T candidate clouds).  An empty B gives mse_BA = nan / psnr nan -- callers guard that."""
+    float64[T, 5] (-> arrays over T candidate clouds).  An empty B gives mse_BA = nan / psnr nan -- callers guard that.
+    A 9-slot tally (float64[9] / float64[T, 9]) also gives the three Hausdorff columns of every group, hausdorff_table's values."""
     tally = np.asarray(tally, np.float64)
     n_b = tally[..., N_B]
     energy = 3 * peak * peak
@@ -123,6 +148,9 @@ def metrics_table(n_a, tally, peak, groups=GROUPS):
             for d, (_, mse) in per_dir.items():
                 out[f'{g}_psnr_{d}'] = psnr(mse, energy)
             out[f'{g}_psnr'] = np.minimum(out[f'{g}_psnr_AB'], out[f'{g}_psnr_BA'])
+            if tally.shape[-1] == 9:
+                h_ab, h_ba = (tally[..., k] for k in _HAUSDORFF_SLOTS[g])
+                out[f'{g}_hausdorff_AB'], out[f'{g}_hausdorff_BA'], out[f'{g}_hausdorff'] = h_ab, h_ba, np.maximum(h_ab, h_ba)
     return out
 
 
@@ -206,15 +234,7 @@ def cloud_tally_host(p1, p2, p1_n=None, t1=None, ties='pick'):
     if ties == 'mean':
         return tie_mean_tally(p1, p2, p1_n, tree_a)
     to_b, to_a = nearest(cKDTree(p2, balanced_tree=False), p1), nearest(tree_a, p2)
-    tally = np.zeros(9, np.float64)
-    tally[:5] = pair_tally(p1, p2, to_b, to_a, p1_n)
-    gap_ab, gap_ba = point_gap(p1, p2, to_b), point_gap(p2, p1, to_a)
-    tally[H1_AB], tally[H1_BA] = squared_norms(gap_ab).max(), squared_norms(gap_ba).max()
-    if p1_n is not None:
-        b_normals = transfer_normals(p1_n, to_a, to_b)
-        tally[H2_AB] = (((gap_ab * b_normals[to_b]).sum(axis=1)) ** 2).max()
-        tally[H2_BA] = (((gap_ba * p1_n[to_a]).sum(axis=1)) ** 2).max()
-    return tally
+    return pair_tally_hausdorff(p1, p2, to_b, to_a, p1_n)
 
 
 def cloud_tallies_gpu(ctx, p1, p2_list, p1_n=None, index_a=None, ties='pick'):
