@@ -19,8 +19,10 @@
 //     what else is in the batch and break the encoder-chunk / decoder-chunk / shard bit-equality the codec needs).  The producer of
 //     the input tensor records max |x| of each block (atomicMax on the fp32 bit pattern: order-independent; this kernel does it for
 //     its own output), or pcc_block_amax computes it; s = 2^(12 - floor(log2 max)), so that |V| = |B^T d B| <= 4 max lands below 2^15.
-//     The low piece's denormal step is then 2^-37 of the block's max -- below fp32 accumulation noise.  NaNs are left out of the max
-//     (a NaN stays local), an all-zero block takes s = 1.
+//     The low piece's denormal step is then 2^-37 of the block's max -- below fp32 accumulation noise RELATIVE TO THE BLOCK'S MAX, not
+//     relative to a small output: outputs whose operands are all small in a block that holds a value 2^20 times larger keep about 7e-6 of
+//     the sum of their terms' magnitudes, 2^12 and below is fp32-like (per-output error contract; tests/_f16s_model.py is
+//     this arithmetic in numpy).  NaNs are left out of the max (a NaN stays local), an all-zero block takes s = 1.
 // The scale is applied inside the x transform (packed fma: s d0 - s d2 ...: exact, +16 packed ops per plane) and undone in the
 // epilogue (the residual add becomes a packed fma).  Scaling the operands of a launch by powers of two therefore scales the result
 // bit for bit, as with the bf16 pieces.
