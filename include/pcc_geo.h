@@ -320,6 +320,38 @@ int pcc_index_pack(pcc_ctx* ctx, const float* sigma, const float* table, int32_t
 int pcc_unpack_dequantize(pcc_ctx* ctx, const void* src, int32_t src_bytes, int32_t N, int64_t vox, int32_t C,
                           int32_t channels_first, int32_t* sym, const float* medians, float* deq, void* stream);
 
+/* ---- latent step: variable rate from one checkpoint ---------------------------------------------------
+ * The ladder: step(q) = (8 + (q & 7)) * 2^((q >> 3) - 5) for q in [0, 63] -- 0.25 ... 60, step(16) = 1, every value exact in
+ * fp32.  `q` below is a DEVICE array with one ladder index per block (N entries, each <= 63).
+ * The three stepped kernels are, bit for bit, their un-stepped twins above applied to a pre-divided input, respectively followed
+ * by one multiply; the quotient is the correctly rounded fp32 division (never a reciprocal multiply), and multiply and add are
+ * rounded separately (never fused).  Subnormal quotients are outside the contract.
+ * pcc_quantize_step_pack: t = v / step(q[n]); sym from t under `mode` and the medians rule of pcc_quantize;
+ *   deq = float(sym) * step(q[n]) + medians[c] (medians NULL: + 0); packed copy and tile_max as pcc_quantize_pack.
+ * pcc_index_pack_step: s = sigma / step(q[n]), then the formula of pcc_scale_to_index on s (its lower bound at table[0] included).
+ * pcc_unpack_dequantize_step: unpack, then deq = float(sym) * step(q[n]) + medians[c].
+ * dst of the two pack kernels may be NULL: then no packed copy is written (a coder that reads the int32 tensors on the device).
+ * pcc_rate_ladder: bits16[n * J + j] = the exact size of block n's y string under step(steps[j]) in units of 2^-16 bit:
+ *   every element adds cost16[row * cost_stride + bin], its symbol as pcc_quantize_step_pack (no medians) and its row as
+ *   pcc_index_pack_step compute them; v = sym - offset[row], m = cdf_size[row] - 2; 0 <= v < m: bin v; otherwise bin m plus
+ *   65536 * overflow_width * (widths / omax + 1 + widths) for the escape digits of the host range coder (overflow = -2v - 1
+ *   for v < 0, else 2 (v - m); widths = its overflow_width-bit digits; omax = 2^overflow_width - 1).  y, sigma: N blocks of
+ *   (vox, C) fp32 on the device; table: L scale entries (device); steps: J in [1, 64] ladder indexes on the HOST; cost16
+ *   (L rows of cost_stride uint32), offset, cdf_size (L each): device.  groups_per_block: workgroups per block (0: one per
+ *   2048 elements); the integer sums do not depend on it.  bits16 is zeroed and filled on `stream`.                        */
+int pcc_quantize_step_pack(pcc_ctx* ctx, const float* v, const float* medians, int32_t* sym, float* deq, int32_t N, int64_t vox,
+                           int32_t C, int32_t mode, int32_t channels_first, void* dst, int32_t dst_bytes, int32_t* tile_max,
+                           const uint8_t* q, void* stream);
+int pcc_index_pack_step(pcc_ctx* ctx, const float* sigma, const float* table, int32_t L, int32_t* idx, int32_t N, int64_t vox,
+                        int32_t C, int32_t channels_first, void* dst, int32_t dst_bytes, const uint8_t* q, void* stream);
+int pcc_unpack_dequantize_step(pcc_ctx* ctx, const void* src, int32_t src_bytes, int32_t N, int64_t vox, int32_t C,
+                               int32_t channels_first, int32_t* sym, const float* medians, float* deq, const uint8_t* q,
+                               void* stream);
+int pcc_rate_ladder(pcc_ctx* ctx, const float* y, const float* sigma, int32_t N, int64_t vox, int32_t C, const float* table,
+                    int32_t L, int32_t mode, const uint8_t* steps, int32_t J, const uint32_t* cost16, int32_t cost_stride,
+                    const int32_t* offset, const int32_t* cdf_size, int32_t overflow_width, int32_t groups_per_block,
+                    int64_t* bits16, void* stream);
+
 /* ---- occupancy thresholding + order-preserving compaction ------------------------------
  * Replaces `np.argwhere(x_hat > thresholds[t]).astype(float32)` (src/model_types.py:209,233-234,
  * src/model_opt.py:12,29).  x: B blocks of D*H*W float32; thr[b] is the float32 threshold of

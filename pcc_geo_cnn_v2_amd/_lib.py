@@ -53,6 +53,7 @@ EXPORTS = [
     'pcc_topk_workspace_bytes', 'pcc_topk_compact',
     'pcc_rank_levels_workspace_bytes', 'pcc_rank_levels', 'pcc_d1_count_stats', 'pcc_d12_count_stats',
     'pcc_d1_threshold_stats_hausdorff', 'pcc_d12_threshold_stats_hausdorff', 'pcc_d1_count_stats_hausdorff', 'pcc_d12_count_stats_hausdorff',
+    'pcc_quantize_step_pack', 'pcc_index_pack_step', 'pcc_unpack_dequantize_step', 'pcc_rate_ladder',
 ]
 ABI_VERSION = 4
 # include/pcc_geo.h "codec numerics": switches that select the kernel family of a layer (state of the context, recorded beside every stream)
@@ -289,6 +290,11 @@ def lib():
     L.pcc_quantize_pack.argtypes = [vp, vp, vp, vp, vp, i32, C.c_int64, i32, i32, i32, vp, i32, vp, vp]
     L.pcc_index_pack.argtypes = [vp, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, i32, vp]
     L.pcc_unpack_dequantize.argtypes = [vp, vp, i32, i32, C.c_int64, i32, i32, vp, vp, vp, vp]
+    # the stepped twins: the twin's arguments with the per-block ladder indexes in front of the stream
+    L.pcc_quantize_step_pack.argtypes = L.pcc_quantize_pack.argtypes[:-1] + [vp, vp]
+    L.pcc_index_pack_step.argtypes = L.pcc_index_pack.argtypes[:-1] + [vp, vp]
+    L.pcc_unpack_dequantize_step.argtypes = L.pcc_unpack_dequantize.argtypes[:-1] + [vp, vp]
+    L.pcc_rate_ladder.argtypes = [vp, vp, vp, i32, C.c_int64, i32, vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp]
     L.pcc_codec_decode_hyper.argtypes = [vp, C.POINTER(CodecDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, i32, C.POINTER(SymbolSink), vp]
     L.pcc_codec_decode_main.argtypes = [vp, C.POINTER(CodecDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, C.c_int64, vp,
                                         vp, sz, i32, C.POINTER(SymbolSink), vp]

@@ -196,6 +196,25 @@ def check_count_search(args, world):
                              'strings, drop the flag or run on one GPU')
 
 
+def check_latent_step(args, world):
+    """--latent_step Q / --target_bpp R: a hyperprior model in fp32, one process, no other layer in the stream; the rate
+    target also needs the range coder.  From the parsed arguments, before the process group and the GPU are touched."""
+    q, target = getattr(args, 'latent_step', None), getattr(args, 'target_bpp', None)
+    if q is None and target is None:
+        return
+    from .model_configs import ModelConfigType
+    from .model_types import CompressionModelV2, check_latent_step as check
+    version = 2
+    if args.model_config in ModelConfigType.keys():
+        version = 2 if issubclass(ModelConfigType[args.model_config].value.model_type.value, CompressionModelV2) else 1
+    flag = '--latent_step' if q is not None else '--target_bpp'
+    try:
+        check(q, target, version, getattr(args, 'precision', 'fp32'), world, getattr(args, 'lossless', False), getattr(args, 'count_threshold', None),
+              count_search_of(args), getattr(args, 'entropy_coder', 'range'))
+    except AssertionError as e:
+        raise AssertionError(f'{flag}: {e}') from None
+
+
 def check_hausdorff_metrics(args, world):
     """--opt_metrics with a Hausdorff name (pc_metric.hausdorff_opt_metrics): what the maxima cannot be combined with,
     refused at argument time with the flag to change (model_opt.check_hausdorff_search).  d2_hausdorff* reads the GPU's D2 statistics:
@@ -268,6 +287,15 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
             record['threshold_policy'] = 'count_search'
             record['count_ladder'] = list(count_search_of(args))
             record['count_bytes'] = sum(len(strings[-1]) for strings, _ in streams)      # (4 per block)
+        if 'latent_step' in info:
+            from .model_syntax import latent_step as step_size
+            q = info['latent_step']
+            record['latent_step'] = q
+            record['latent_step_size'] = step_size(q) if isinstance(q, int) else [step_size(v) for v in q]
+            if 'rate_target' in info:      # the size is the container's before gzip
+                record['target_bpp'] = info['rate_target']['target_bpp']
+                record['predicted_bytes'] = info['rate_target']['predicted_bytes']
+                record['container_bytes'] = len(payload)
         if getattr(args, 'lossless', False):
             # the last string of every block is the occupancy layer; the rate of the exact cloud counts the whole file as written
             n_points = sum(len(b) for b in blocks)
@@ -300,6 +328,8 @@ def compress(args):
     check_count_threshold(args, int(os.environ.get('WORLD_SIZE', '1')))     # (first: its message names the flag, not what _plan meets)
     check_count_search(args, int(os.environ.get('WORLD_SIZE', '1')))
     check_hausdorff_metrics(args, int(os.environ.get('WORLD_SIZE', '1')))
+    check_latent_step(args, int(os.environ.get('WORLD_SIZE', '1')))
+    latent_step, target_bpp = getattr(args, 'latent_step', None), getattr(args, 'target_bpp', None)
     clouds, with_normals = _plan(args)
     lossless = getattr(args, 'lossless', False)
     count_scale = getattr(args, 'count_threshold', None)
@@ -346,14 +376,16 @@ def compress(args):
             sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
             max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
             metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'),
-            **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}))
+            **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}),
+            **({} if latent_step is None else {'latent_step': latent_step}), **({} if target_bpp is None else {'target_bpp': target_bpp}))
         T.mark('compress_blocks', sess.device)
         if rank == 0:       # the other ranks only took part in the collectives
             if len(streams) != len(cloud.targets):
                 raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
             for n, target in enumerate(cloud.targets):
                 infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless,
-                                                        count_scale is not None or count_search is not None)
+                                                        count_scale is not None or count_search is not None,
+                                                        **({'step': True} if 'latent_step' in infos[n] else {}))
                 _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
             logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
         T.mark('container_gzip_write')
@@ -442,6 +474,17 @@ def build_parser():
                              f'{" ".join(map(str, COUNT_SEARCH_DEFAULT))}: a design choice, not a tuned value.  .enc.metric.json gains threshold_policy, '
                              'count_ladder and count_bytes.  Not with --count_threshold, --fixed_threshold, --lossless or --search_ties mean; '
                              'd2_* metrics need --d2_search gpu; blocks up to 128^3; single process only.')
+    parser.add_argument('--latent_step', type=int, default=None, metavar='Q',
+                        help='Quality knob on the checkpoint at hand (new): quantise the latents y with the step (8 + (Q & 7)) x 2^((Q >> 3) - 5), '
+                             'Q in 0..63 (0.25 ... 60; Q = 16 is the step 1 of the plain stream) and code them under the scales divided by '
+                             'it.  Every block carries one more string, the byte Q, and the stream names it (numerics tag suffix /qs1), so '
+                             'decompress_octree needs no flag; .enc.metric.json gains latent_step and latent_step_size.  Hyperprior models '
+                             '(c2, c3, c3p) in fp32 only; not with --lossless, --count_threshold or --count_search; single process only.')
+    parser.add_argument('--target_bpp', type=float, default=None, metavar='R',
+                        help='Rate target (new): the finest --latent_step whose PREDICTED container (before gzip) holds at most R bits per '
+                             'input point; the prediction is the cost model plus a measured margin, not a proven bound, so the written '
+                             'container can exceed the target by the coder\'s excess on unusual streams; analysis runs twice.  Out of reach: the coarsest step, with a warning.  .enc.metric.json also '
+                             'gains target_bpp, predicted_bytes and container_bytes.  As --latent_step, and not with it or --entropy_coder rans.')
     return parser
 
 

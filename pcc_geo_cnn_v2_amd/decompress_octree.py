@@ -63,7 +63,7 @@ def decompress(args):
     T.mark('context', sess.device)
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
-    compressed_data, coders, counted = [], [], []
+    compressed_data, coders, counted, stepped = [], [], [], []
     base_only = getattr(args, 'base_only', False)
     for file in args.input_files:
         # the stream names its entropy coder and its layers (tag suffixes); the rest of the tag is compared as before
@@ -71,7 +71,8 @@ def decompress(args):
                                       ignore=args.ignore_numerics_tag)
         coders.append(coder)
         counted.append('cnt1' in layers)
-        if base_only and not layers:
+        stepped.append('qs1' in layers)      # the latent steps (compress_octree --latent_step / --target_bpp): part of the base decode itself
+        if base_only and (not layers or stepped[-1]):
             logger.warning('--base_only has no effect on %s: the stream carries no occupancy layer', file)
         if args.debug and 'occ1' in layers and not base_only:
             raise AssertionError(f'--debug compares the decoded blocks with the encoder dumps, which hold the lossy candidate: pass --base_only '
@@ -91,7 +92,8 @@ def decompress(args):
         logger.info(f'{i}/{len(args.input_files)} - Writing {ori_file} to {output_file} with {len(blocks)} blocks')
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
         model.entropy_coder = coders[i]
-        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug, layers='base' if base_only else 'count' if counted[i] else 'all')
+        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug,
+                                                          layers='step' if stepped[i] else 'base' if base_only else 'count' if counted[i] else 'all')
         T.mark('decompress_blocks', sess.device)
         if args.debug and rank == 0:
             dec_blocks_enc = read_pcs(len(blocks), ori_file + '.enc.blocks')

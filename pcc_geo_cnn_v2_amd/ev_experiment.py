@@ -2,7 +2,7 @@
 
   python -m pcc_geo_cnn_v2_amd.ev_experiment --output_dir OUT --model_dir models/c3p/1.00e-04 --model_config c3p --pc_name loot
       --input_pc loot.ply [--input_norm loot_n.ply | --estimate_normals] --resolution 1024 [--octree_level 4]
-      --opt_metrics d1_mse d2_mse --max_deltas inf [--fixed_threshold | --count_threshold [RHO] | --count_search [LO HI STEPS]] [--no_merge_coding] [--metrics_device host|gpu]
+      --opt_metrics d1_mse d2_mse --max_deltas inf [--fixed_threshold | --count_threshold [RHO] | --count_search [LO HI STEPS]] [--latent_step Q | --target_bpp R] [--no_merge_coding] [--metrics_device host|gpu]
       [--d2_ties pick|mean] [--consistency assert|warn] [--recolor rank2|transfer]
 
 Files in OUT, per optimisation group g (d1 always; d2 only when a d2_* metric is asked for, which needs normals):
@@ -175,7 +175,7 @@ def _progress(src, dst, comment=''):
 
 
 def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution, octree_level, opt_metrics, max_deltas,
-            fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold=None, count_search=None):
+            fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold=None, count_search=None, latent_step=None, target_bpp=None):
     """compress_octree.compress for one cloud on the resident state: the same arguments, the same plan, the same writer."""
     from . import compress_octree as CO
     from .model_syntax import stream_tag
@@ -199,10 +199,15 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
         argv += ['--d2_search', 'gpu'] if any(m.startswith('d2_') for m in opt_metrics) else []
     elif any(m.startswith('d2_') and m in hausdorff_opt_metrics for m in opt_metrics):
         argv += ['--d2_search', 'gpu']      # likewise: the d2 Hausdorff terms exist in the GPU engine alone
+    if latent_step is not None:
+        argv += ['--latent_step', str(int(latent_step))]
+    if target_bpp is not None:
+        argv += ['--target_bpp', repr(float(target_bpp))]
     args = CO.build_parser().parse_args(argv)
     CO.check_count_threshold(args, 1)
     CO.check_count_search(args, 1)
     CO.check_hausdorff_metrics(args, 1)
+    CO.check_latent_step(args, 1)
     clouds, with_normals = CO._plan(args)
     CO.check_metrics_device(args.metrics_device, 1)
     CO.check_d2_ties(args.d2_ties, 1)
@@ -219,11 +224,13 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
         opt_metrics=args.opt_metrics, max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=False,
         need_points=cloud.decoded is not None, metrics_device=args.metrics_device, d2_ties=args.d2_ties,
         **({} if args.count_threshold is None else {'count_scale': args.count_threshold}),
-        **({} if CO.count_search_of(args) is None else {'count_search': CO.count_search_of(args)}))
+        **({} if CO.count_search_of(args) is None else {'count_search': CO.count_search_of(args)}),
+        **({} if args.latent_step is None else {'latent_step': args.latent_step}), **({} if args.target_bpp is None else {'target_bpp': args.target_bpp}))
     if len(streams) != len(cloud.targets):
         raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
     for n, target in enumerate(cloud.targets):
-        infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, count=args.count_threshold is not None or CO.count_search_of(args) is not None)
+        infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, count=args.count_threshold is not None or CO.count_search_of(args) is not None,
+                                              **({'step': True} if 'latent_step' in infos[n] else {}))
         CO._write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks,
                              debug_t_list)
 
@@ -240,7 +247,7 @@ def _decode(res, enc_pcs, dec_pcs, model_dir, model_config, batch_size, precisio
         with gzip.open(enc, 'rb') as f:
             resolution, level, binstr, blocks = load_compressed_file(f)
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
-        dec_blocks, _ = model.decompress_blocks(sess, blocks, x_shape, debug=False, layers='count' if 'cnt1' in layers else 'all')
+        dec_blocks, _ = model.decompress_blocks(sess, blocks, x_shape, debug=False, layers='step' if 'qs1' in layers else 'count' if 'cnt1' in layers else 'all')
         dec_blocks = departition_octree(dec_blocks, binstr, [0, 0, 0], x_shape * (2 ** level), level)
         pa = np.vstack(dec_blocks) if len(dec_blocks) else np.zeros((0, 3))
         pc_io.write_df(dec, pc_io.pa_to_df(pa))
@@ -306,7 +313,7 @@ def enc_dec_diff(enc_pc, report):
 def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input_norm=None, estimate_normals=False,
                    opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, no_merge_coding=False, metrics_device='host',
                    d2_ties='pick', consistency='assert', resolution=None, octree_level=4, batch_size=32, normals_k=16, resident=None,
-                   count_threshold=None, count_search=None, recolor='rank2'):
+                   count_threshold=None, count_search=None, recolor='rank2', latent_step=None, target_bpp=None):
     """See the module docstring.  Returns {group: report dictionary} of the reports that exist afterwards."""
     from .utils.experiment import opt_groups
     from .utils.pc_metric import validate_opt_metrics
@@ -334,7 +341,7 @@ def run_experiment(output_dir, model_dir, model_config, pc_name, input_pc, input
     else:
         _progress(input_pc, enc_pcs)
         _encode(res, original, enc_pcs, None if no_merge_coding else dec_pcs, model_dir, model_config, resolution, octree_level,
-                opt_metrics, max_deltas, fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold, count_search)
+                opt_metrics, max_deltas, fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold, count_search, latent_step, target_bpp)
 
     # decoding: whatever the encoder did not leave behind
     todo = [(e, d) for e, d in zip(enc_pcs, dec_pcs) if not os.path.exists(d)]
@@ -408,6 +415,10 @@ def build_parser():
     p.add_argument('--count_search', nargs='*', default=None, metavar='LO HI STEPS',
                    help='Count search instead of the threshold search, passed to the compress step (new; the bare flag is its default '
                         'ladder; d2_* metrics then take their search statistics from the GPU engine)')
+    p.add_argument('--latent_step', type=int, default=None, metavar='Q',
+                   help='Latent step of the hyperprior models (ladder index 0..63, 16 = the plain stream), passed to the compress step (new)')
+    p.add_argument('--target_bpp', type=float, default=None, metavar='R',
+                   help='Rate target in bits per input point of the container before gzip, passed to the compress step (new)')
     p.add_argument('--num_parallel', type=int, default=1, help='Accepted and ignored: the steps run in this process')
     p.add_argument('--no_stream_redirection', default=False, action='store_true', help='Accepted and ignored')
     p.add_argument('--no_merge_coding', help='Do not merge encoding and decoding.', default=False, action='store_true')
@@ -440,7 +451,7 @@ def main(argv=None):
     run_experiment(a.output_dir, a.model_dir, a.model_config, a.pc_name, a.input_pc, a.input_norm, a.estimate_normals, a.opt_metrics,
                    a.max_deltas, a.fixed_threshold, a.no_merge_coding, a.metrics_device, a.d2_ties, a.consistency, resolution,
                    a.octree_level, a.batch_size, count_threshold=a.count_threshold,
-                   count_search=count_search_of(a), recolor=a.recolor)
+                   count_search=count_search_of(a), recolor=a.recolor, latent_step=a.latent_step, target_bpp=a.target_bpp)
     return 0
 
 

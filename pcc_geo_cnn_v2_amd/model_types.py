@@ -33,7 +33,7 @@ from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
 from ._stream_io import _Immediate, _Pinned, _host_dtypes, gather_points, indexes_to_host, on_side_stream, ship, side_stream, symbols_to_device, to_host
 from .block_search import SearchSchedule
 from .model_opt import check_hausdorff_search, count_rows, count_tallies_gpu, d2_on_gpu, decide_counts_from_tallies
-from .model_syntax import count_from_bytes, count_to_bytes
+from .model_syntax import count_from_bytes, count_to_bytes, latent_step as latent_step_size, step_from_bytes, step_to_bytes
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
 from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu, wants_hausdorff
@@ -174,6 +174,62 @@ def check_count_search(count_search, count_scale=None, fixed_threshold=False, lo
     if dhw is not None and not gpu_search_supported(opt_metrics, dhw):
         raise AssertionError(f'count_search covers block grids up to 128^3 (the GPU search engines), not {tuple(dhw)}')
     return ladder
+
+
+# The margin of the rate target's prediction, in units of 2^-16 bit.  The host range coder's string is longer than the
+# cost model's sum: it never writes fewer than two bytes and its termination depends on the final range state (16.000 bits measured on a
+# one-symbol stream, plus 8), and its interval arithmetic truncates, which costs in proportion to the bits coded (largest ratio measured:
+# 938.2 parts per million, 32768 symbols that mostly sit on frequency-1 bins of the four narrowest rows; rounded up here).  Both figures
+# are MEASURED on seeded streams (tests/test_latent_step_cpu.py holds them against the real coder), not proven bounds.
+RATE_MARGIN_FIXED_BITS = 24
+RATE_MARGIN_PPM = 939
+
+
+def rate_margin_bits16(bits16):
+    """What choose_latent_step adds to a block's predicted y bits before it rounds them up to bytes (int64 array or int, units of 2^-16 bit)."""
+    return (RATE_MARGIN_FIXED_BITS << 16) + (bits16 * RATE_MARGIN_PPM + 999999) // 1000000
+
+
+def check_latent_step(latent_step=None, target_bpp=None, version=2, precision='fp32', world=1, lossless=False, count_scale=None,
+                      count_search=None, entropy_coder='range', n_blocks=None):
+    """What the latent step and the rate target on top of it exclude; both None (off) passes.  latent_step: a ladder index
+    (model_syntax.latent_step) or one per block; target_bpp: bits per input point of the container.  Returns the steps as a uint8 array
+    (n_blocks entries when n_blocks is known and a step was given), None otherwise.  Every message names the flag to drop."""
+    if latent_step is None and target_bpp is None:
+        return None
+    what = 'latent_step' if latent_step is not None else 'target_bpp'
+    if latent_step is not None and target_bpp is not None:
+        raise AssertionError('latent_step and target_bpp: the rate target chooses the step itself, drop --latent_step or --target_bpp')
+    if version != 2:
+        raise AssertionError(f'{what} needs a hyperprior model (c3p and its siblings): the factorized prior of a V1 model has no parametric '
+                             f'rescale, drop --{what}')
+    if precision == 'fp16':
+        raise AssertionError(f'{what} is built on the fp32 layer-wise path, drop --precision fp16 (or --{what})')
+    if world > 1:
+        raise AssertionError(f'{what} is single-process only (world size {world}): the sharded path moves the y/z strings alone, drop --{what} '
+                             'or run on one GPU')
+    if lossless:
+        raise AssertionError(f'{what} and lossless: a stepped stream carries no occupancy layer yet, drop --lossless (or --{what})')
+    if count_scale is not None:
+        raise AssertionError(f'{what} and count_scale: a stepped stream carries no point counts yet, drop --count_threshold (or --{what})')
+    if count_search is not None:
+        raise AssertionError(f'{what} and count_search: a stepped stream carries no point counts yet, drop --count_search (or --{what})')
+    if target_bpp is not None:
+        if not (isinstance(target_bpp, (int, float, np.floating, np.integer)) and not isinstance(target_bpp, bool) and np.isfinite(target_bpp) and target_bpp > 0):
+            raise AssertionError(f'target_bpp must be a finite number above 0, got {target_bpp!r}')
+        if entropy_coder == 'rans':
+            raise AssertionError('target_bpp predicts the size of range-coded strings, the escapes of the rANS coder cost otherwise: drop '
+                                 '--entropy_coder rans (or --target_bpp)')
+        return None
+    from .model_syntax import LATENT_STEPS
+    q = np.asarray(latent_step)
+    if not (np.issubdtype(q.dtype, np.integer) and q.ndim <= 1 and q.size and q.min() >= 0 and q.max() < LATENT_STEPS):
+        raise AssertionError(f'latent_step is a ladder index in [0, {LATENT_STEPS - 1}] or one per block, got {latent_step!r}')
+    if q.ndim == 1 and n_blocks is not None and q.size != n_blocks:
+        raise AssertionError(f'latent_step: {q.size} ladder indexes for {n_blocks} blocks')
+    if q.ndim == 0 and n_blocks is not None:
+        q = np.full(n_blocks, q)
+    return q.astype(np.uint8)
 
 
 def _np(t):
@@ -502,7 +558,7 @@ class CompressionModel:
 
     # ------------------------------------------------------------------ block loops
     def encode_block_range(self, sess, blocks, resolution, with_normals=False, opt_metrics=('d1_mse',),
-                           max_deltas=(np.inf,), fixed_threshold=False, debug=False, count_scale=None, count_search=None):
+                           max_deltas=(np.inf,), fixed_threshold=False, debug=False, count_scale=None, count_search=None, latent_step=None):
         """The per-block part of compress_blocks (model_types.py:192-212) for a list of blocks: returns
         (strings per block, best-threshold list per block, candidate point lists per block, metric names,
         debug).  This is the unit that shards across GPUs (sharded_blocks.py).
@@ -514,10 +570,15 @@ class CompressionModel:
         scored exactly on the GPU (ops.d1_count_stats / d12_count_stats) and chosen per metric name by the threshold search's own
         decision rule (model_opt.decide_counts_from_tallies).  The candidate of a name is ops.topk_compact(x_hat, its k).  A block's
         strings are then the y/z strings followed by ONE COUNT STRING PER METRIC NAME, in the order of the returned names
-        (compress_blocks keeps the one of each output), and the threshold byte is the fixed one."""
+        (compress_blocks keeps the one of each output), and the threshold byte is the fixed one.
+        latent_step = q or one q per block (V2 only): block b's y is quantised with the step model_syntax.latent_step(q[b])
+        and coded under the scales divided by it; every block carries one more string, directly behind the y/z strings, the byte q[b].
+        Everything behind the transform sees only another x_hat."""
         dhw = self._spatial(self.x_shape)
         ladder = check_count_search(count_search, count_scale, fixed_threshold, self.lossless, 1, self.search_ties, opt_metrics,
                                     lambda: d2_on_gpu(self.d2_search, 'pick'), dhw)
+        steps = check_latent_step(latent_step, None, self.codec_abi, self.precision, 1, self.lossless, count_scale, count_search,
+                                  self.entropy_coder, len(blocks))
         ctx = self._ctx(sess)
         check_count_scale(count_scale, fixed_threshold, self.lossless)
         counted = count_scale is not None
@@ -533,7 +594,8 @@ class CompressionModel:
         for c0 in range(0, len(blocks), self.batch_size):
             chunk = blocks[c0:c0 + self.batch_size]
             x = self._voxelize(ctx, chunk, dhw)
-            enc = self._encode_batch(ctx, x, debug, thr=self._thr_tensor(ctx, [half] * len(chunk)) if fixed_threshold else None)
+            stepped = {} if steps is None else {'steps': torch.from_numpy(steps[c0:c0 + len(chunk)]).to(ctx.device)}
+            enc = self._encode_batch(ctx, x, debug, thr=self._thr_tensor(ctx, [half] * len(chunk)) if fixed_threshold else None, **stepped)
             # the occupancy layer: the chunk's dense input under the x_hat the decoder will compute (same bits: the numerics tag); the
             # threshold search below neither sees nor changes it
             occ_job = ops.occ_encode_launch(ctx, enc['x_hat'], x) if self.lossless else None
@@ -541,6 +603,8 @@ class CompressionModel:
                 ks = [block_count(len(b), count_scale, int(np.prod(dhw))) for b in chunk]
                 enc['xyz'], enc['counts'] = ops.topk_compact(ctx, enc['x_hat'], torch.tensor(ks, dtype=torch.int32).to(ctx.device, non_blocking=True))
             strings = enc['finish']()
+            if steps is not None:       # model strings, then the step string (then any later layer string: none yet)
+                strings = [tuple(ss) + (step_to_bytes(q),) for ss, q in zip(strings, steps[c0:c0 + len(chunk)].tolist())]
             if ladder is not None:
                 rows = count_rows(chunk, ladder, int(np.prod(dhw)))
                 tallies = count_tallies_gpu(ctx, chunk, enc['x_hat'], rows, d2=want_d2, hausdorff=wants_hausdorff(opt_metrics))
@@ -574,7 +638,8 @@ class CompressionModel:
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
-                        need_points=True, metrics_device='host', d2_ties='pick', count_scale=None, count_search=None):
+                        need_points=True, metrics_device='host', d2_ties='pick', count_scale=None, count_search=None, latent_step=None,
+                        target_bpp=None):
         """Uses the compression model to compress a point cloud (model_types.py:184-218).  Under torch.distributed (one
         process per GPU) the block list is sharded (sharded_blocks.py): rank 0 returns the complete result, the other ranks
         return (None, metadata without point lists, local debug list).  `need_points=False` skips the gather of the
@@ -582,10 +647,15 @@ class CompressionModel:
         (single process only) computes the whole-cloud metrics on the GPU and builds no KD-tree.  d2_ties='mean' (single process
         only): the whole-cloud D2 averages over all equidistant nearest points; the per-block threshold search is not affected.
         count_scale, count_search (single process only): see encode_block_range; under count_search the data of output m carries, as every
-        block's last string, the count chosen for that output's metric name."""
+        block's last string, the count chosen for that output's metric name.
+        latent_step (V2, single process only): see encode_block_range.  target_bpp = R (instead of latent_step): the finest uniform step
+        whose predicted container holds at most R * len(points) / 8 bytes (`choose_latent_step`; analysis and hyper run twice).  Under
+        either, every metadata dict carries 'latent_step' (q, or the list of them) and, under a target, 'rate_target'."""
         from . import sharding
         from .utils.pc_metric import check_ties
         rank, world = sharding.world_info()
+        check_latent_step(latent_step, target_bpp, self.codec_abi, self.precision, world, self.lossless, count_scale, count_search,
+                          self.entropy_coder, len(blocks))
         check_ties(d2_ties, world)
         if self.lossless and world > 1:
             raise AssertionError('lossless is single-process only: the sharded path moves the y/z strings alone')
@@ -607,10 +677,14 @@ class CompressionModel:
             from .sharded_blocks import compress_blocks_sharded
             return compress_blocks_sharded(self, sess, blocks, binstr, points, resolution, level, with_normals, opt_metrics,
                                            max_deltas, fixed_threshold, debug, need_points, tree_future)
+        rate_target = None
         try:
+            if target_bpp is not None:
+                latent_step, rate_target = self.choose_latent_step(sess, blocks, binstr, len(points), target_bpp)
             strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
                 sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug,
-                **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}))
+                **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}),
+                **({} if latent_step is None else {'latent_step': latent_step}))
         finally:
             tree = tree_future.result() if tree_future is not None else None
         # block -> opt metric to opt metric -> block
@@ -624,7 +698,16 @@ class CompressionModel:
             data_list = [[(tuple(ss[:n]) + (ss[n + x['idx']],), t) for ss, t in zip(strings_list, threshold_list[x['idx']])] for x in metadata]
         else:
             data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
+        if latent_step is not None:
+            q = np.asarray(latent_step)
+            for x in metadata:
+                x['latent_step'] = int(q) if q.ndim == 0 else [int(v) for v in q]
+                if rate_target is not None:
+                    x['rate_target'] = dict(rate_target)
         return data_list, metadata, debug_t_list
+
+    def choose_latent_step(self, sess, blocks, binstr, n_points, target_bpp):
+        raise AssertionError('target_bpp needs a hyperprior model (c3p and its siblings), drop --target_bpp')
 
     def roundtrip_stream(self, sess, dense_chunks, thr_idx=None, gather=True):
         """Streams chunks of dense occupancy grids (each (b,D,H,W) float32 on the GPU) through the compress
@@ -739,9 +822,12 @@ class CompressionModel:
         against x_hat and returns the exact input voxels, the threshold byte is ignored; 'base' is the lossy decode of the same stream,
         as if the layer were not there.  A stream without the layer decodes the same under both.  'count' reads the extra string as the
         block's point count k ("cnt1") and returns the k highest-scoring voxels of x_hat; 'base' on such a stream is the
-        decode by the threshold byte."""
+        decode by the threshold byte.  'step' reads the string behind the y/z strings as the block's latent step ("qs1", DESIGN.md 4.21;
+        single process only): the stream cannot be decoded without it, so there is no 'base' form of it."""
         from . import sharding
-        assert layers in ('all', 'base', 'count'), f"layers: 'all', 'base' or 'count', not {layers!r}"
+        assert layers in ('all', 'base', 'count', 'step'), f"layers: 'all', 'base', 'count' or 'step', not {layers!r}"
+        if layers == 'step' and sharding.world_info()[1] > 1:
+            raise AssertionError('a stepped stream (qs1) is decoded by one process: the sharded path moves the y/z strings alone, run on one GPU')
         if sharding.world_info()[1] > 1:
             from .sharded_blocks import decompress_blocks_sharded
             return decompress_blocks_sharded(self, sess, blocks, x_shape, debug, layers)
@@ -756,11 +842,14 @@ class CompressionModel:
         n_base = self.n_strings
         exact = layers == 'all' and len(blocks) > 0 and len(blocks[0][0]) == n_base + 1
         ks = self._block_counts(blocks, int(np.prod(dhw))) if layers == 'count' else None
+        qs = self._block_steps(blocks) if layers == 'step' else None            # (read and checked before anything is launched)
         state = [None] * len(chunks)
         results = [None] * len(chunks)
         for k in range(len(chunks) + 1):
             if k < len(chunks):
-                state[k] = self._decode_phase_a(ctx, [s for s, _ in chunks[k]], dhw)
+                c0 = k * self.batch_size
+                stepped = {} if qs is None else {'steps': torch.from_numpy(qs[c0:c0 + len(chunks[k])]).to(ctx.device)}
+                state[k] = self._decode_phase_a(ctx, [s for s, _ in chunks[k]], dhw, **stepped)
             if k >= 1 and exact:
                 B = len(chunks[k - 1])
                 dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=None)
@@ -800,6 +889,19 @@ class CompressionModel:
             ks.append(min(k, n_voxels))
         return ks
 
+    def _block_steps(self, blocks):
+        """The step strings of a "qs1" stream (the string directly behind the model's y/z strings of every block) -> uint8 q per block, read
+        before anything is launched.  A block without one, a string that is not one byte or a q beyond the ladder is a RuntimeError that
+        names the block."""
+        if self.codec_abi != 2:
+            raise RuntimeError('the stream carries latent steps (qs1): only the hyperprior models (c3p and its siblings) read them')
+        qs = np.zeros(len(blocks), np.uint8)
+        for b, (strings, _) in enumerate(blocks):
+            if len(strings) != self.n_strings + 1:
+                raise RuntimeError(f'block {b}: {len(strings)} strings, a stepped stream (qs1) carries {self.n_strings + 1} per block')
+            qs[b] = step_from_bytes(strings[self.n_strings], b)
+        return qs
+
     # ------------------------------------------------------------------ batched graph.  With a pcc_codec_desc (`_codec`) the GPU part
     # of each phase is ONE ABI call; otherwise the same steps run layer by layer.  Both leave the same tensors under the same names.
     def _synthesis_layerwise(self, ctx, t, thr, clip):
@@ -808,11 +910,16 @@ class CompressionModel:
         if thr is not None:
             t['xyz'], t['counts'] = ops.threshold_compact(ctx, t['x_hat'], thr, clip=clip)
 
-    def _encode_batch(self, ctx, x, debug, thr=None, slot=0):
+    def _analysis_stepped(self, ctx, x, steps, stg):
+        raise AssertionError('latent_step needs a hyperprior model (c3p and its siblings), drop --latent_step')
+
+    def _encode_batch(self, ctx, x, debug, thr=None, slot=0, steps=None):
         """The compress graph of a chunk x (B,D,H,W): returns x_hat (and, with `thr`, the encoder-side points xyz / counts), the per-block
-        debug dicts and finish() -> the strings per block, which waits for the symbols and codes them."""
+        debug dicts and finish() -> the strings per block, which waits for the symbols and codes them.
+        steps: (B,) uint8 device tensor of ladder indexes -- the stepped chunk path, layer by layer with the stepped
+        kernels, which stage the symbols themselves."""
         B, dhw = x.shape[0], x.shape[1:4]
-        codec = self._codec(ctx)
+        codec = self._codec(ctx) if steps is None else None
         ready = None
         rans = self.entropy_coder == 'rans'
         stg = None if rans else self._staging(ctx, slot, B, [v // 8 for v in dhw], [v // 16 for v in dhw] if self.n_strings == 2 else None)
@@ -821,10 +928,12 @@ class CompressionModel:
             ready.record(side_stream(ctx, '_idx_stream'))            # creates the handle (on a stream that is idle now: a record costs the
                                                                      # main queue a few microseconds); re-recorded by the library on the main stream
             t = ops.codec_encode(ctx, codec, x.contiguous(), thr, symbols_ready=ready, staging=stg)
+        elif steps is not None:
+            t = self._analysis_stepped(ctx, x, steps, stg)
         else:
             t = self._analysis_layerwise(ctx, x)
         jobs = self._string_jobs(t)
-        if codec is None and not rans:
+        if codec is None and not rans and steps is None:
             stg.pack(ctx, *(t[k] for k in ('symbols', 'z_symbols', 'indexes') if k in t))
         # what crosses PCIe: ONE buffer per chunk -- symbols as int16, the 64 scale rows as uint8 (8.5 -> 3.3 MB per 32-block
         # chunk), packed in stream order by the library before `ready`, plus the per-tile max|symbol| that tells the host
@@ -871,7 +980,13 @@ class CompressionModel:
         else:
             ysym, packed = None, symbols_to_device(ctx, *(self._decode_phase_b_host(st) if host is None else host))
         codec = self._codec(ctx)
-        if codec is not None:                      # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
+        if st.get('steps') is not None:            # stepped stream: y_hat = float(symbol) * step of the block, then the layer-wise synthesis
+            yshape = (len(st['strings']),) + tuple(v // 8 for v in dhw) + (self.num_filters,)
+            sym, y_hat = ops.unpack_dequantize_step(ctx, ysym if rans else packed, yshape, not rans and self.data_format == 'channels_first',
+                                                    st['steps'], self._y_medians(ctx))
+            t = dict(symbols=sym, y_hat=y_hat)
+            self._synthesis_layerwise(ctx, t, thr, clip=False)
+        elif codec is not None:                    # unpack -> dequantise -> synthesis (-> threshold + compaction) in one ABI call
             t = ops.codec_decode_main(ctx, codec, ysym, dhw, thr, packed=packed, channels_first=self.data_format == 'channels_first')
         else:
             if not rans:
@@ -1043,11 +1158,81 @@ class CompressionModelV2(CompressionModel):
     def _string_jobs(self, t):
         return [('y', self.conditional_bottleneck.table, t['symbols'], t['indexes']), ('z', self.entropy_bottleneck.table, t['z_symbols'], None)]
 
-    def _hyper_decode(self, ctx, dhw, zsym=None, zpacked=None, idx_packed=None):
-        """z symbols (int32 on the device) or `zpacked` (stream-order symbols as the host->device copy delivered them) -> z_hat,
-        sigma_hat, indexes; idx_packed: device tensor that also receives the indexes in stream order, for the host coder."""
-        codec = self._codec(ctx)
+    # ---- the latent step: y / step and sigma / step per block; z is quantised as ever
+    def _analysis_hyper(self, ctx, x):
+        """x -A-> y -HA-> z -> z symbols, z_hat -HS-> sigma_hat, layer by layer: what both passes of a rate target and the stepped encode share"""
+        med = self._dev(ctx, 'medians', self.entropy_bottleneck.medians)
+        y = self.analysis_transform.forward_ndhwc(ctx, x.unsqueeze(-1))
+        z = self.hyper_analysis_transform.forward_ndhwc(ctx, y)
+        zsym, z_hat = ops.quantize(ctx, z, med, self.round_mode)
+        return dict(y=y, z=z, z_symbols=zsym, z_hat=z_hat, sigma_hat=self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat))
+
+    @staticmethod
+    def _step_dst(stg, name):
+        """(device address, bytes per element) the stepped kernels pack tensor `name` to: the staging buffer, or -- under rans, which codes
+        from the int32 tensors on the device -- no packed copy at all"""
+        if stg is None:
+            return None, 4
+        return stg.dev_ptr(name), ops._ITEM[stg.idx_dtype if name == 'idx' else stg.sym_dtype]
+
+    def _analysis_stepped(self, ctx, x, steps, stg):
+        t = self._analysis_hyper(ctx, x)
         cf = self.data_format == 'channels_first'
+        ptr, nbytes = self._step_dst(stg, 'idx')
+        t['indexes'] = ops.index_pack_step(ctx, t['sigma_hat'], self._scale_table_dev(ctx), cf, ptr, nbytes, steps)
+        ptr, nbytes = self._step_dst(stg, 'ysym')
+        t['symbols'], t['y_hat'] = ops.quantize_step_pack(ctx, t['y'], None, self.round_mode, cf, ptr, nbytes, steps,
+                                                          None if stg is None else stg.dev_ptr('ytm'))
+        if stg is not None:
+            ops.symbols_pack(ctx, t['z_symbols'], cf, stg.dev_ptr('zsym'), ops._ITEM[stg.sym_dtype], stg.dev_ptr('ztm'))
+        return t
+
+    def choose_latent_step(self, sess, blocks, binstr, n_points, target_bpp):
+        """The rate target's first pass: analysis and hyper per chunk, the rate ladder over all 64 steps and the actual z strings.  The
+        predicted container at q = its fixed bytes (header, binstr, per block the threshold byte, three length fields and the step byte)
+        + the z bytes + sum over the blocks of ceil((bits16[b][q] + rate_margin_bits16(bits16[b][q])) / 2^19): the measured margin by
+        which the coder's string exceeds the model's sum, so that the chosen step fits on every stream measured; it is no proven bound.
+        Returns (q, dict(target_bpp, budget_bytes, predicted_bytes, predictions)): q the smallest (finest) whose prediction is at most
+        target_bpp * n_points / 8, else 63 with a warning."""
+        from .model_syntax import LATENT_STEPS, _HEADER, _U16
+        ctx = self._ctx(sess)
+        dhw = self._spatial(self.x_shape)
+        ladder = np.arange(LATENT_STEPS, dtype=np.uint8)
+        ybytes = np.zeros(LATENT_STEPS, np.int64)
+        zbytes = 0
+        for c0 in range(0, len(blocks), self.batch_size):
+            chunk = blocks[c0:c0 + self.batch_size]
+            t = self._analysis_hyper(ctx, self._voxelize(ctx, chunk, dhw))
+            bits = ops.rate_ladder(ctx, t['y'], t['sigma_hat'], ladder, self._scale_table_dev(ctx), self.conditional_bottleneck.table, self.round_mode)
+            zs = self._to_stream_order(t['z_symbols']).cpu().numpy().reshape(len(chunk), -1)
+            rows, mod = self._eb_rows(zs.shape[1], self.num_filters)
+            zbytes += sum(len(s) for s in ops.range_encode_batch(self.entropy_bottleneck.table, zs, rows, mod, self.coder_threads))
+            bits = bits.cpu().numpy()
+            ybytes += ((bits + rate_margin_bits16(bits) + ((1 << 19) - 1)) >> 19).sum(0)
+        fixed = _HEADER.size + len(binstr) + len(blocks) * (1 + (self.n_strings + 1) * _U16.size + 1)
+        pred = fixed + zbytes + ybytes
+        budget = float(target_bpp) * n_points / 8.0
+        fits = np.flatnonzero(pred <= budget)
+        q = int(fits[0]) if fits.size else LATENT_STEPS - 1
+        if not fits.size:
+            logger.warning('target_bpp %g (%d bytes for %d points) is out of reach: the coarsest step (q = %d, step %g) predicts %d bytes',
+                           target_bpp, int(budget), n_points, q, latent_step_size(q), int(pred[q]))
+        return q, dict(target_bpp=float(target_bpp), budget_bytes=budget, predicted_bytes=int(pred[q]), predictions=[int(v) for v in pred])
+
+    def _hyper_decode(self, ctx, dhw, zsym=None, zpacked=None, idx_packed=None, steps=None):
+        """z symbols (int32 on the device) or `zpacked` (stream-order symbols as the host->device copy delivered them) -> z_hat,
+        sigma_hat, indexes; idx_packed: device tensor that also receives the indexes in stream order, for the host coder.
+        steps: the blocks' ladder indexes (uint8, device): the rows are those of sigma_hat / step, layer by layer as the stepped encoder."""
+        codec = self._codec(ctx) if steps is None else None
+        cf = self.data_format == 'channels_first'
+        if steps is not None:
+            if zpacked is not None:
+                zsym = self._unpack(ctx, zpacked, [v // 16 for v in dhw])
+            z_hat = ops.dequantize(ctx, zsym, self._dev(ctx, 'medians', self.entropy_bottleneck.medians))
+            sigma = self.hyper_synthesis_transform.forward_ndhwc(ctx, z_hat)
+            idx = ops.index_pack_step(ctx, sigma, self._scale_table_dev(ctx), cf, None if idx_packed is None else idx_packed.data_ptr(),
+                                      4 if idx_packed is None else idx_packed.element_size(), steps)
+            return dict(z_hat=z_hat, sigma_hat=sigma, indexes=idx, z_symbols=zsym)
         if codec is not None:                      # unpack z -> dequantise -> hyper-synthesis -> indexes -> pack, one ABI call
             return ops.codec_decode_hyper(ctx, codec, zsym, dhw, packed=zpacked, channels_first=cf, idx_packed=idx_packed)
         if zpacked is not None:
@@ -1057,26 +1242,28 @@ class CompressionModelV2(CompressionModel):
             ops.symbols_pack(ctx, t['indexes'], cf, idx_packed.data_ptr(), idx_packed.element_size())
         return t
 
-    def _decode_phase_a(self, ctx, strings, dhw):
-        """z_string -EB.decompress-> z_hat -HS-> sigma -> indexes (async D2H)."""
+    def _decode_phase_a(self, ctx, strings, dhw, steps=None):
+        """z_string -EB.decompress-> z_hat -HS-> sigma -> indexes (async D2H).  steps: the ladder indexes of a stepped stream's blocks
+        (uint8, device), kept in the state for phase b."""
         B, F = len(strings), self.num_filters
         zstrings = [s[1] for s in strings]
+        stepped = {} if steps is None else {'steps': steps}
         if self.entropy_coder == 'rans':
             zsym, zstatus = self._rans_decode(ctx, self.entropy_bottleneck.table, zstrings, (B,) + tuple(v // 16 for v in dhw) + (F,))
-            t = self._hyper_decode(ctx, dhw, zsym)
+            t = self._hyper_decode(ctx, dhw, zsym, **stepped)
             # the CDF rows stay on the device: phase b decodes the y strings there
-            return dict(strings=strings, z_hat=t['z_hat'], sigma_hat=t['sigma_hat'], indexes=t['indexes'], zstatus=zstatus, device=ctx.device)
+            return dict(strings=strings, z_hat=t['z_hat'], sigma_hat=t['sigma_hat'], indexes=t['indexes'], zstatus=zstatus, device=ctx.device, **stepped)
         zsym_h, zsym_release = self._range_decode_eb('dec_zsym', zstrings, self._stream_shape(B, [v // 16 for v in dhw], F))
         zpacked = symbols_to_device(ctx, zsym_h, zsym_release)
         # the 64 scale rows leave in stream order, one byte each
         row_t = _host_dtypes(len(self.scale_table))[1]
         idx_s = torch.empty(self._stream_shape(B, [v // 8 for v in dhw], F), dtype=row_t, device=ctx.device)
-        t = self._hyper_decode(ctx, dhw, zpacked=zpacked, idx_packed=idx_s)
+        t = self._hyper_decode(ctx, dhw, zpacked=zpacked, idx_packed=idx_s, **stepped)
         # (the host reads idx_h synchronously in phase b, long before the ring comes round: no release event needed)
         idx_h, _ = self._pinned.ring('dec_idx', idx_s.shape, row_t)
         ev = indexes_to_host(ctx, idx_s, idx_h)
         return dict(strings=strings, idx_h=idx_h, ev=ev, z_hat=t['z_hat'], sigma_hat=t['sigma_hat'], indexes=t['indexes'], zsym_h=zsym_h,
-                    device=ctx.device)
+                    device=ctx.device, **stepped)
 
     def _decode_phase_b_host(self, st):
         """Wait for the CDF-row indexes, range-decode the y strings into a pinned buffer (the coder is sequential per stream: 2 ms per

@@ -10,7 +10,8 @@ from .conv import (  # noqa: F401
     mfma_supported)
 from .codec import (  # noqa: F401
     codec_desc, _ITEM, SymbolStaging, symbols_pack, symbols_unpack, _out, quantize_pack, index_pack, unpack_dequantize,
-    codec_encode, _packed_io, codec_decode_hyper, codec_decode_main, quantize, dequantize, scale_to_index, threshold_compact, topk_compact, voxelize)
+    codec_encode, _packed_io, codec_decode_hyper, codec_decode_main, quantize, dequantize, scale_to_index, threshold_compact, topk_compact, voxelize,
+    quantize_step_pack, index_pack_step, unpack_dequantize_step, cost16_table, device_cost_table, rate_ladder)
 from .training import (  # noqa: F401
     focal_loss, focal_loss_grad, relu_backward, dual_desc, conv_repack_map, conv_repack_device, conv_wgrad_slices, conv3d_wgrad,
     histogram_limits, _f32_flat, histogram_unpack, tensor_histograms_launch, tensor_histograms, tensor_histogram, occupancy_scores_launch,

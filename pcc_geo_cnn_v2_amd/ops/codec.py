@@ -148,6 +148,97 @@ def unpack_dequantize(ctx, src, ndhwc_shape, channels_first, medians=None, sym=N
     return sym, deq
 
 
+# ---- the latent step: the stepped twins of the three fused kernels and the rate ladder.  q: (N,) uint8 device tensor,
+# one ladder index (model_syntax.latent_step) per block; the caller has checked q <= 63.
+def _steps(ctx, q, N):
+    assert q.dtype == torch.uint8 and q.is_contiguous() and q.device == ctx.device and q.numel() == N, \
+        'latent steps: one uint8 ladder index per block, on the context\'s device'
+    return _ptr(q)
+
+
+def quantize_step_pack(ctx, v, medians, mode, channels_first, dst_ptr, dst_bytes, q, tile_max_ptr=None, want_deq=True, sym=None, deq=None):
+    """quantize_pack on v / step(q[n]) with deq = float(sym) * step(q[n]) (+ medians) (pcc_quantize_step_pack).  dst_ptr None: no packed copy."""
+    assert v.dtype == torch.float32 and v.is_contiguous() and v.device == ctx.device
+    N, Cc = v.shape[0], v.shape[-1]
+    sym = _out(sym, v.shape, torch.int32, v)
+    deq = _out(deq, v.shape, torch.float32, v) if want_deq else None
+    L.check(L.lib().pcc_quantize_step_pack(ctx.handle, _ptr(v), _ptr(medians), _ptr(sym), _ptr(deq), N, v[0].numel() // Cc, Cc, mode,
+                                           int(bool(channels_first)), C.c_void_p(dst_ptr), dst_bytes,
+                                           None if tile_max_ptr is None else C.c_void_p(tile_max_ptr), _steps(ctx, q, N), ctx.stream),
+            'pcc_quantize_step_pack')
+    return sym, deq
+
+
+def index_pack_step(ctx, sigma, table, channels_first, dst_ptr, dst_bytes, q, idx=None):
+    """index_pack on sigma / step(q[n]) (pcc_index_pack_step).  dst_ptr None: no packed copy."""
+    assert sigma.dtype == torch.float32 and sigma.is_contiguous() and sigma.device == ctx.device and table.dtype == torch.float32
+    N, Cc = sigma.shape[0], sigma.shape[-1]
+    idx = _out(idx, sigma.shape, torch.int32, sigma)
+    L.check(L.lib().pcc_index_pack_step(ctx.handle, _ptr(sigma), _ptr(table), table.numel(), _ptr(idx), N, sigma[0].numel() // Cc, Cc,
+                                        int(bool(channels_first)), C.c_void_p(dst_ptr), dst_bytes, _steps(ctx, q, N), ctx.stream),
+            'pcc_index_pack_step')
+    return idx
+
+
+def unpack_dequantize_step(ctx, src, ndhwc_shape, channels_first, q, medians=None, sym=None, deq=None):
+    """unpack_dequantize with deq = float(sym) * step(q[n]) (+ medians) (pcc_unpack_dequantize_step)."""
+    assert src.is_contiguous() and src.device == ctx.device and src.dtype in _ITEM
+    sym = _out(sym, ndhwc_shape, torch.int32, src)
+    deq = _out(deq, ndhwc_shape, torch.float32, src)
+    N, Cc = sym.shape[0], sym.shape[-1]
+    assert src.numel() == sym.numel()
+    L.check(L.lib().pcc_unpack_dequantize_step(ctx.handle, _ptr(src), _ITEM[src.dtype], N, sym[0].numel() // Cc, Cc,
+                                               int(bool(channels_first)), _ptr(sym), _ptr(medians), _ptr(deq), _steps(ctx, q, N), ctx.stream),
+            'pcc_unpack_dequantize_step')
+    return sym, deq
+
+
+def cost16_table(cdf, cdf_size, precision=16):
+    """Host: cost16[row][b] = rint(65536 * (precision - log2(cdf[b + 1] - cdf[b]))) in float64, as uint32 (rows, stride - 1); bins a row
+    does not have stay 0.  A zero frequency is an AssertionError."""
+    cdf, cdf_size = np.asarray(cdf, np.int64), np.asarray(cdf_size, np.int64)
+    assert cdf.ndim == 2 and cdf_size.shape == (cdf.shape[0],) and cdf.shape[1] >= 2
+    cost = np.zeros((cdf.shape[0], cdf.shape[1] - 1), np.uint32)
+    for r, sz in enumerate(cdf_size.tolist()):
+        assert 2 <= sz <= cdf.shape[1], f'cost table: row {r} has cdf_size {sz} for a stride of {cdf.shape[1]}'
+        freq = np.diff(cdf[r, :sz])
+        assert np.all(freq > 0), f'cost table: row {r} has a bin of frequency {int(freq.min())}: its cost would be infinite'
+        cost[r, :sz - 1] = np.rint(65536.0 * (np.float64(precision) - np.log2(freq.astype(np.float64)))).astype(np.uint32)
+    return cost
+
+
+def device_cost_table(ctx, table):
+    """The cost table of a coders.HostCdfTable on the context's device, built and uploaded once per (context, table) and kept -- like the
+    rANS coder keeps its CDF tables; a table whose arrays were rebuilt in place is uploaded again.  -> (cost16, offset, cdf_size)."""
+    cache = ctx.cache('cost16')
+    e = cache.get(id(table))
+    if e is None or e[0] is not table or not (np.array_equal(e[1], table.cdf) and np.array_equal(e[2], table.cdf_size) and np.array_equal(e[3], table.offset)):
+        cost = cost16_table(table.cdf, table.cdf_size, table.struct.precision)
+        dev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device) for a in (cost.view(np.int32), table.offset, table.cdf_size))
+        cache[id(table)] = e = (table, table.cdf.copy(), table.cdf_size.copy(), table.offset.copy(), dev)      # (the table stays alive: its id is the key)
+    return e[4]
+
+
+def rate_ladder(ctx, y, sigma, steps, scale_table, cdf_table, mode=L.PCC_ROUND_FLOOR_HALF, groups_per_block=0):
+    """The exact size of every block's y string under every step of a ladder (pcc_rate_ladder): y, sigma (N, ..., C) float32 on the device,
+    steps: 1 to 64 ladder indexes (host), scale_table: float32 device tensor, cdf_table: the coders.HostCdfTable whose rows the scale
+    table selects.  -> int64 (N, J) device tensor in units of 2^-16 bit.  groups_per_block: launch geometry, no effect on the result."""
+    assert y.dtype == torch.float32 and y.is_contiguous() and y.device == ctx.device and sigma.dtype == torch.float32 and sigma.is_contiguous()
+    assert sigma.shape == y.shape and sigma.device == ctx.device and scale_table.dtype == torch.float32
+    steps = np.ascontiguousarray(np.asarray(steps).reshape(-1))
+    assert 1 <= steps.size <= 64 and np.issubdtype(steps.dtype, np.integer) and steps.min() >= 0 and steps.max() <= 63, \
+        'rate_ladder: a ladder of 1 to 64 indexes in [0, 63]'
+    steps = steps.astype(np.uint8)
+    assert cdf_table.cdf.shape[0] == scale_table.numel(), 'rate_ladder: one CDF row per scale table entry'
+    cost, offset, size = device_cost_table(ctx, cdf_table)
+    N, Cc = y.shape[0], y.shape[-1]
+    out = torch.empty((N, steps.size), dtype=torch.int64, device=ctx.device)
+    L.check(L.lib().pcc_rate_ladder(ctx.handle, _ptr(y), _ptr(sigma), N, y[0].numel() // Cc, Cc, _ptr(scale_table), scale_table.numel(), mode,
+                                    steps.ctypes.data_as(C.c_void_p), steps.size, _ptr(cost), cost.shape[1], _ptr(offset), _ptr(size),
+                                    cdf_table.struct.overflow_width, int(groups_per_block), _ptr(out), ctx.stream), 'pcc_rate_ladder')
+    return out
+
+
 def _threshold_outputs(ctx, t, thr, cap, scratch, N, D, H, W):
     """What a codec call that also thresholds and compacts needs (`thr` (N,) float32 given): the point lists xyz (N,cap,3) and counts
     (N,), entered into the result dict t, and the compaction scratch, the caller's or a fresh one.  Returns (xyz, counts, cap,
