@@ -92,63 +92,6 @@ def _plan(args):
     return clouds, with_normals
 
 
-def _join_process_group():
-    """-> (rank, world, local device index).  Under torch.distributed.run the blocks are sharded over the ranks."""
-    import torch
-    from . import sharding
-    local = int(os.environ.get('LOCAL_RANK', '0'))
-    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        import torch.distributed as dist
-        # PCC_DIST_BACKEND=gloo + PCC_DIST_SAME_GPU=1: every rank on GPU 0 with host-side collectives -- lets a 1-GPU box run the
-        # sharded path end to end (tests/test_cli_gpu.py); the default is one GPU per rank over RCCL
-        if os.environ.get('PCC_DIST_SAME_GPU'):
-            local = 0
-        torch.cuda.set_device(local)
-        if os.environ.get('PCC_DIST_BACKEND', 'nccl') == 'gloo':
-            dist.init_process_group('gloo')
-        else:
-            dist.init_process_group('nccl', device_id=torch.device('cuda', local))
-    rank, world = sharding.world_info()
-    return rank, world, local
-
-
-def check_metrics_device(metrics_device, world):
-    """--metrics_device gpu runs the whole-cloud metrics of one process; the sharded (world > 1) metric path stays on the host."""
-    if metrics_device not in ('host', 'gpu'):
-        raise AssertionError(f'--metrics_device must be host or gpu, got {metrics_device!r}')
-    if metrics_device == 'gpu' and world > 1:
-        raise AssertionError(f'--metrics_device gpu is single-process only (world size {world}): the sharded metric path runs on the '
-                             'host, drop the flag or run on one GPU')
-
-
-def check_lossless(lossless, world):
-    """--lossless codes the occupancy layer in one process; the sharded path moves the y/z strings alone."""
-    if lossless and world > 1:
-        raise AssertionError(f'--lossless is single-process only (world size {world}): the sharded path does not carry the occupancy '
-                             'strings, drop the flag or run on one GPU')
-
-
-def check_count_threshold(args, world):
-    """--count_threshold replaces the threshold search and its tie rules, and codes in one process; the sharded path moves the y/z strings
-    alone.  From the parsed arguments, before the process group and the GPU are touched."""
-    rho = getattr(args, 'count_threshold', None)
-    if rho is None:
-        return
-    if not (np.isfinite(rho) and rho > 0):
-        raise AssertionError(f'--count_threshold: the scale must be a finite number above 0, got {rho}')
-    if getattr(args, 'fixed_threshold', False):
-        raise AssertionError('--count_threshold and --fixed_threshold are two policies for the same decision, drop one of the two flags')
-    if getattr(args, 'lossless', False):
-        raise AssertionError('--count_threshold and --lossless: a stream carries the point counts or the occupancy layer, drop one of the two flags')
-    if getattr(args, 'search_ties', 'pick') == 'mean':
-        raise AssertionError('--count_threshold runs no threshold search, drop --search_ties mean')
-    if getattr(args, 'd2_search', None) == 'gpu':
-        raise AssertionError('--count_threshold runs no threshold search, drop --d2_search gpu')
-    if world > 1:
-        raise AssertionError(f'--count_threshold is single-process only (world size {world}): the sharded path does not carry the count '
-                             'strings, drop the flag or run on one GPU')
-
-
 COUNT_SEARCH_DEFAULT = (0.5, 2.0, 33)      # a design choice (half to twice the input count, 33 geometric steps), not a tuned value
 
 
@@ -168,74 +111,26 @@ def count_search_of(args):
     return lo, hi, int(steps)
 
 
-def check_count_search(args, world):
-    """--count_search replaces the threshold search by the search over point counts: one process, the GPU engines with
-    their 'pick' tie rule, block grids up to 128^3.  From the parsed arguments, before the process group and the GPU are touched."""
-    ladder = count_search_of(args)
-    if ladder is None:
-        return
-    from .model_opt import count_ladder
-    try:
-        count_ladder(*ladder)
-    except AssertionError as e:
-        raise AssertionError(f'--count_search: {e}') from None
-    if getattr(args, 'count_threshold', None) is not None:
-        raise AssertionError('--count_search and --count_threshold are two policies for the same decision, drop one of the two flags')
-    if getattr(args, 'fixed_threshold', False):
-        raise AssertionError('--count_search and --fixed_threshold are two policies for the same decision, drop one of the two flags')
-    if getattr(args, 'lossless', False):
-        raise AssertionError('--count_search and --lossless: a stream carries the point counts or the occupancy layer, drop one of the two flags')
-    if getattr(args, 'search_ties', 'pick') == 'mean':
-        raise AssertionError('--count_search: the tie-averaged D2 engine has no count source, drop --search_ties mean')
-    if any(str(m).startswith('d2_') for m in (getattr(args, 'opt_metrics', None) or ())) and getattr(args, 'd2_search', None) != 'gpu':
-        raise AssertionError('--count_search with a d2_* metric needs --d2_search gpu: the host KD-tree path has no count source')
-    if (int(args.resolution) >> int(args.octree_level)) > 128:
-        raise AssertionError(f'--count_search covers block grids up to 128^3, not {int(args.resolution) >> int(args.octree_level)}^3: raise --octree_level')
-    if world > 1:
-        raise AssertionError(f'--count_search is single-process only (world size {world}): the sharded path does not carry the count '
-                             'strings, drop the flag or run on one GPU')
-
-
-def check_latent_step(args, world):
-    """--latent_step Q / --target_bpp R: a hyperprior model in fp32, one process, no other layer in the stream; the rate
-    target also needs the range coder.  From the parsed arguments, before the process group and the GPU are touched."""
-    q, target = getattr(args, 'latent_step', None), getattr(args, 'target_bpp', None)
-    if q is None and target is None:
-        return
+def check_encode_options(args, world):
+    """What the parsed flags may combine (stream_layers.plan_encode), before the process group and the GPU are touched:
+    returns the plan of the encode; a refusal names the flag in front of its message."""
     from .model_configs import ModelConfigType
-    from .model_types import CompressionModelV2, check_latent_step as check
-    version = 2
-    if args.model_config in ModelConfigType.keys():
-        version = 2 if issubclass(ModelConfigType[args.model_config].value.model_type.value, CompressionModelV2) else 1
-    flag = '--latent_step' if q is not None else '--target_bpp'
+    from .model_types import CompressionModelV2
+    from .stream_layers import plan_encode
     try:
-        check(q, target, version, getattr(args, 'precision', 'fp32'), world, getattr(args, 'lossless', False), getattr(args, 'count_threshold', None),
-              count_search_of(args), getattr(args, 'entropy_coder', 'range'))
+        search = count_search_of(args)
     except AssertionError as e:
-        raise AssertionError(f'{flag}: {e}') from None
-
-
-def check_hausdorff_metrics(args, world):
-    """--opt_metrics with a Hausdorff name (pc_metric.hausdorff_opt_metrics): what the maxima cannot be combined with,
-    refused at argument time with the flag to change (model_opt.check_hausdorff_search).  d2_hausdorff* reads the GPU's D2 statistics:
-    it needs --d2_search gpu on the command line.  --fixed_threshold runs no search: nothing to refuse."""
-    from .model_opt import check_hausdorff_search
-    if getattr(args, 'fixed_threshold', False):
-        return
-    try:
-        check_hausdorff_search(getattr(args, 'opt_metrics', None) or (), getattr(args, 'search_ties', 'pick'),
-                               getattr(args, 'd2_search', None) == 'gpu', world)
-    except AssertionError as e:
-        raise AssertionError(f'--opt_metrics: {e}') from None
-
-
-def check_d2_ties(d2_ties, world):
-    """--d2_ties mean averages the whole-cloud D2 over all equidistant nearest points in one process; tie sets are not sharded."""
-    from .utils.pc_metric import check_ties
-    try:
-        check_ties(d2_ties, world)
-    except AssertionError as e:
-        raise AssertionError(f'--d2_ties: {e}') from None
+        search = e      # (plan_encode raises it where the rules of the count search stand)
+    config = ModelConfigType[args.model_config] if args.model_config in ModelConfigType.keys() else None      # (unknown: _plan's to refuse)
+    return plan_encode(
+        entry='cli', world=world, count_scale=getattr(args, 'count_threshold', None), count_search=search,
+        fixed_threshold=getattr(args, 'fixed_threshold', False), lossless=getattr(args, 'lossless', False),
+        latent_step=getattr(args, 'latent_step', None), target_bpp=getattr(args, 'target_bpp', None),
+        version=1 if config is not None and not issubclass(config.value.model_type.value, CompressionModelV2) else 2,
+        precision=getattr(args, 'precision', 'fp32'), entropy_coder=getattr(args, 'entropy_coder', 'range'),
+        search_ties=getattr(args, 'search_ties', 'pick'), opt_metrics=getattr(args, 'opt_metrics', None) or (),
+        d2_gpu=getattr(args, 'd2_search', None) == 'gpu', dhw=(int(args.resolution) >> int(args.octree_level),) * 3 if isinstance(search, tuple) else None,
+        metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'))
 
 
 def check_search_ties(search_ties, opt_metrics, with_normals, fixed_threshold=False):
@@ -262,7 +157,8 @@ def _block_grid(resolution, level, data_format):
 def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks, debug_t_list):
     """The files of one rate point: <target> (gzip'd container), <target>.enc.metric.json, optionally the decoded cloud and the
     --debug dumps (/root/reference/src/compress_octree.py:109-125 lists them)."""
-    from .model_syntax import save_compressed_file, write_tagged_gzip
+    from .model_syntax import save_compressed_file, split_stream_tag, write_tagged_gzip
+    from .stream_layers import latent_step as step_size, split_strings
     from .utils import pc_io
     folder = os.path.dirname(target)
     if folder:
@@ -279,16 +175,16 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
             record['d2_ties'] = args.d2_ties
         if getattr(args, 'search_ties', 'pick') != 'pick':
             record['search_ties'] = args.search_ties
+        # the bytes of the stream's layers, by name (the tag names them; what stands in front of them are the model's y/z strings)
+        layers = split_stream_tag(info['numerics_tag'])[2]
+        split = [split_strings(strings, len(strings) - len(layers), layers, b) for b, (strings, _) in enumerate(streams)] if layers else []
         if getattr(args, 'count_threshold', None) is not None:
-            record['threshold_policy'] = 'count'
-            record['count_scale'] = float(args.count_threshold)
-            record['count_bytes'] = sum(len(strings[-1]) for strings, _ in streams)      # (4 per block)
+            record.update(threshold_policy='count', count_scale=float(args.count_threshold))
         if count_search_of(args) is not None:
-            record['threshold_policy'] = 'count_search'
-            record['count_ladder'] = list(count_search_of(args))
-            record['count_bytes'] = sum(len(strings[-1]) for strings, _ in streams)      # (4 per block)
+            record.update(threshold_policy='count_search', count_ladder=list(count_search_of(args)))
+        if 'threshold_policy' in record:
+            record['count_bytes'] = sum(len(extra['cnt1']) for _, extra in split)      # (4 per block)
         if 'latent_step' in info:
-            from .model_syntax import latent_step as step_size
             q = info['latent_step']
             record['latent_step'] = q
             record['latent_step_size'] = step_size(q) if isinstance(q, int) else [step_size(v) for v in q]
@@ -297,11 +193,11 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
                 record['predicted_bytes'] = info['rate_target']['predicted_bytes']
                 record['container_bytes'] = len(payload)
         if getattr(args, 'lossless', False):
-            # the last string of every block is the occupancy layer; the rate of the exact cloud counts the whole file as written
+            # the rate of the exact cloud counts the whole file as written
             n_points = sum(len(b) for b in blocks)
             record['lossless'] = True
-            record['base_bytes'] = sum(len(x) for strings, _ in streams for x in strings[:-1])
-            record['occ_bytes'] = sum(len(strings[-1]) for strings, _ in streams)
+            record['base_bytes'] = sum(len(x) for base, _ in split for x in base)
+            record['occ_bytes'] = sum(len(extra['occ1']) for _, extra in split)
             record['bits_per_input_point_lossless'] = 8.0 * os.path.getsize(target) / max(n_points, 1)
         json.dump(record, fh, sort_keys=True, indent=4)
     if decoded_path is not None:
@@ -314,30 +210,44 @@ def _write_rate_point(target, decoded_path, binstr, streams, info, args, blocks,
         np.savez_compressed(target + '.enc.data.npz', data=np.array(streams, dtype=object), debug_t_list=np.array(debug_t_list, dtype=object))
 
 
+def encode_cloud(args, model, sess, cloud, blocks, binstr, points, plan, with_normals, want_points, write=True):
+    """One cloud of the command line: compress_blocks on its blocks under the parsed options, then -- where `write` (rank 0: the other
+    ranks only take part in the collectives) -- the files of every rate point, tagged with the layers of `plan`."""
+    from .model_syntax import stream_tag
+    from .utils import cli_timing as T
+    logger.info(f'Starting {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
+    streams, infos, debug_t_list = model.compress_blocks(
+        sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
+        max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
+        metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'),
+        count_scale=getattr(args, 'count_threshold', None), count_search=count_search_of(args), latent_step=getattr(args, 'latent_step', None),
+        target_bpp=getattr(args, 'target_bpp', None))
+    T.mark('compress_blocks', sess.device)
+    if write:
+        if len(streams) != len(cloud.targets):
+            raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
+        tag = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, layers=plan.layers)
+        for n, target in enumerate(cloud.targets):
+            infos[n]['numerics_tag'] = tag
+            _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
+        logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
+    T.mark('container_gzip_write')
+
+
 def compress(args):
     from .utils import cli_timing as T
     T.mark('process_start_to_main')
     import torch
     from . import ops
     from .model_configs import ModelConfigType
-    from .model_syntax import stream_tag
+    from .sharding import join_process_group
     from .utils import pc_io
     from .utils.octree_coding import partition_octree
     T.mark('imports')
 
-    check_count_threshold(args, int(os.environ.get('WORLD_SIZE', '1')))     # (first: its message names the flag, not what _plan meets)
-    check_count_search(args, int(os.environ.get('WORLD_SIZE', '1')))
-    check_hausdorff_metrics(args, int(os.environ.get('WORLD_SIZE', '1')))
-    check_latent_step(args, int(os.environ.get('WORLD_SIZE', '1')))
-    latent_step, target_bpp = getattr(args, 'latent_step', None), getattr(args, 'target_bpp', None)
+    plan = check_encode_options(args, int(os.environ.get('WORLD_SIZE', '1')))      # (first: its messages name the flags, not what _plan meets)
     clouds, with_normals = _plan(args)
-    lossless = getattr(args, 'lossless', False)
-    count_scale = getattr(args, 'count_threshold', None)
-    count_search = count_search_of(args)
-    check_lossless(lossless, int(os.environ.get('WORLD_SIZE', '1')))      # (before the process group and the GPU are touched)
-    rank, world, local = _join_process_group()
-    check_metrics_device(getattr(args, 'metrics_device', 'host'), world)
-    check_d2_ties(getattr(args, 'd2_ties', 'pick'), world)
+    rank, world, local = join_process_group()
     if args.debug and world > 1:
         raise AssertionError('--debug dumps every intermediate of every block: run it on one GPU')
     sess = ops.get_context(torch.device('cuda', local))        # what tf.Session is to the reference (compress_octree.py:84)
@@ -359,7 +269,7 @@ def compress(args):
                 f'{block_shape} and {sum(len(blocks) for blocks, _ in partitions)} blocks')
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision,
-                                                    entropy_coder=getattr(args, 'entropy_coder', 'range'), lossless=lossless)
+                                                    entropy_coder=getattr(args, 'entropy_coder', 'range'), lossless=getattr(args, 'lossless', False))
     model.d2_search = getattr(args, 'd2_search', None)      # per model, not a module global
     model.search_ties = getattr(args, 'search_ties', 'pick')
     model.compress(np.concatenate(((1,), block_shape)))
@@ -369,26 +279,8 @@ def compress(args):
         model._codec(sess)
         T.mark('weights_repack_upload', sess.device)
 
-    want_points = clouds[0].decoded is not None or args.debug
     for cloud, points, (blocks, binstr) in zip(clouds, geometry, partitions):
-        logger.info(f'Starting {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
-        streams, infos, debug_t_list = model.compress_blocks(
-            sess, blocks, binstr, points, args.resolution, args.octree_level, with_normals=with_normals, opt_metrics=args.opt_metrics,
-            max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=args.debug, need_points=want_points,
-            metrics_device=getattr(args, 'metrics_device', 'host'), d2_ties=getattr(args, 'd2_ties', 'pick'),
-            **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}),
-            **({} if latent_step is None else {'latent_step': latent_step}), **({} if target_bpp is None else {'target_bpp': target_bpp}))
-        T.mark('compress_blocks', sess.device)
-        if rank == 0:       # the other ranks only took part in the collectives
-            if len(streams) != len(cloud.targets):
-                raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
-            for n, target in enumerate(cloud.targets):
-                infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, model.lossless,
-                                                        count_scale is not None or count_search is not None,
-                                                        **({'step': True} if 'latent_step' in infos[n] else {}))
-                _write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks, debug_t_list)
-            logger.info(f'Finished {cloud.source} to {", ".join(cloud.targets)} with {len(blocks)} blocks')
-        T.mark('container_gzip_write')
+        encode_cloud(args, model, sess, cloud, blocks, binstr, points, plan, with_normals, clouds[0].decoded is not None or args.debug, write=rank == 0)
     T.dump()
     if world > 1:
         import torch.distributed as dist

@@ -36,6 +36,7 @@ def decompress(args):
     from . import ops, sharding
     from .model_configs import ModelConfigType
     from .model_syntax import load_compressed_file, read_gzip_tag, stream_layers
+    from .stream_layers import decode_mode
     from .utils import pc_io
     from .utils.octree_coding import departition_octree
     T.mark('imports')
@@ -44,36 +45,20 @@ def decompress(args):
     assert len(args.input_files) == len(args.output_files)
     assert args.model_config in ModelConfigType.keys()
 
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    local_rank = int(os.environ.get('LOCAL_RANK', '0'))
-    if world > 1:
-        import torch.distributed as dist
-        # PCC_DIST_BACKEND=gloo + PCC_DIST_SAME_GPU=1: every rank on GPU 0 with host-side collectives -- lets a 1-GPU box run the
-        # sharded path end to end (tests/test_cli_gpu.py); the default is one GPU per rank over RCCL
-        if os.environ.get('PCC_DIST_SAME_GPU'):
-            local_rank = 0
-        torch.cuda.set_device(local_rank)
-        if os.environ.get('PCC_DIST_BACKEND', 'nccl') == 'gloo':
-            dist.init_process_group('gloo')
-        else:
-            dist.init_process_group('nccl', device_id=torch.device('cuda', local_rank))
-    rank, world = sharding.world_info()
+    rank, world, local_rank = sharding.join_process_group()
     assert not (args.debug and world > 1), '--debug checks every intermediate of every block: run it on one GPU'
     sess = ops.get_context(torch.device('cuda', local_rank))
     T.mark('context', sess.device)
 
     model = ModelConfigType[args.model_config].build(data_format=args.data_format, batch_size=args.batch_size, precision=args.precision)
-    compressed_data, coders, counted, stepped = [], [], [], []
+    compressed_data, coders, modes = [], [], []
     base_only = getattr(args, 'base_only', False)
     for file in args.input_files:
         # the stream names its entropy coder and its layers (tag suffixes); the rest of the tag is compared as before
         coder, layers = stream_layers(read_gzip_tag(file), sess.numerics_tag(args.precision), getattr(args, 'entropy_coder', None),
                                       ignore=args.ignore_numerics_tag)
         coders.append(coder)
-        counted.append('cnt1' in layers)
-        stepped.append('qs1' in layers)      # the latent steps (compress_octree --latent_step / --target_bpp): part of the base decode itself
-        if base_only and (not layers or stepped[-1]):
-            logger.warning('--base_only has no effect on %s: the stream carries no occupancy layer', file)
+        modes.append(decode_mode(layers, base_only, file))
         if args.debug and 'occ1' in layers and not base_only:
             raise AssertionError(f'--debug compares the decoded blocks with the encoder dumps, which hold the lossy candidate: pass --base_only '
                                  f'to check {file}')
@@ -92,8 +77,7 @@ def decompress(args):
         logger.info(f'{i}/{len(args.input_files)} - Writing {ori_file} to {output_file} with {len(blocks)} blocks')
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
         model.entropy_coder = coders[i]
-        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug,
-                                                          layers='step' if stepped[i] else 'base' if base_only else 'count' if counted[i] else 'all')
+        dec_blocks, debug_t_list = model.decompress_blocks(sess, blocks, x_shape, debug=args.debug, layers=modes[i])
         T.mark('decompress_blocks', sess.device)
         if args.debug and rank == 0:
             dec_blocks_enc = read_pcs(len(blocks), ori_file + '.enc.blocks')

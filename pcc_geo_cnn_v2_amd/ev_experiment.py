@@ -178,7 +178,6 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
             fixed_threshold, metrics_device, d2_ties, batch_size, count_threshold=None, count_search=None, latent_step=None, target_bpp=None):
     """compress_octree.compress for one cloud on the resident state: the same arguments, the same plan, the same writer."""
     from . import compress_octree as CO
-    from .model_syntax import stream_tag
     from .utils.pc_metric import hausdorff_opt_metrics
     argv = ['--input_files', original.input_pc, '--output_files', *enc_pcs, '--checkpoint_dir', model_dir, '--model_config', model_config,
             '--opt_metrics', *opt_metrics, '--max_deltas', *[str(d) for d in max_deltas], '--resolution', str(resolution),
@@ -204,40 +203,21 @@ def _encode(res, original, enc_pcs, dec_pcs, model_dir, model_config, resolution
     if target_bpp is not None:
         argv += ['--target_bpp', repr(float(target_bpp))]
     args = CO.build_parser().parse_args(argv)
-    CO.check_count_threshold(args, 1)
-    CO.check_count_search(args, 1)
-    CO.check_hausdorff_metrics(args, 1)
-    CO.check_latent_step(args, 1)
+    plan = CO.check_encode_options(args, 1)
     clouds, with_normals = CO._plan(args)
-    CO.check_metrics_device(args.metrics_device, 1)
-    CO.check_d2_ties(args.d2_ties, 1)
-    sess = res.ctx
     box, block_shape = CO._block_grid(args.resolution, args.octree_level, args.data_format)
     blocks, binstr = original.partition(box, args.octree_level)
     model = res.model('enc', model_config, model_dir, args.batch_size, args.precision, block_shape)
     model.entropy_coder = args.entropy_coder
     model.d2_search = args.d2_search
     model.search_ties = args.search_ties
-    cloud = clouds[0]
-    streams, infos, debug_t_list = model.compress_blocks(
-        sess, blocks, binstr, original.geometry, args.resolution, args.octree_level, with_normals=with_normals,
-        opt_metrics=args.opt_metrics, max_deltas=args.max_deltas, fixed_threshold=args.fixed_threshold, debug=False,
-        need_points=cloud.decoded is not None, metrics_device=args.metrics_device, d2_ties=args.d2_ties,
-        **({} if args.count_threshold is None else {'count_scale': args.count_threshold}),
-        **({} if CO.count_search_of(args) is None else {'count_search': CO.count_search_of(args)}),
-        **({} if args.latent_step is None else {'latent_step': args.latent_step}), **({} if args.target_bpp is None else {'target_bpp': args.target_bpp}))
-    if len(streams) != len(cloud.targets):
-        raise AssertionError(f'{len(streams)} rate points for {len(cloud.targets)} output files')
-    for n, target in enumerate(cloud.targets):
-        infos[n]['numerics_tag'] = stream_tag(sess.numerics_tag(args.precision), model.entropy_coder, count=args.count_threshold is not None or CO.count_search_of(args) is not None,
-                                              **({'step': True} if 'latent_step' in infos[n] else {}))
-        CO._write_rate_point(target, None if cloud.decoded is None else cloud.decoded[n], binstr, streams[n], infos[n], args, blocks,
-                             debug_t_list)
+    CO.encode_cloud(args, model, res.ctx, clouds[0], blocks, binstr, original.geometry, plan, with_normals, clouds[0].decoded is not None)
 
 
 def _decode(res, enc_pcs, dec_pcs, model_dir, model_config, batch_size, precision='fp32'):
     """decompress_octree.decompress for some files on the resident state."""
     from .model_syntax import load_compressed_file, read_gzip_tag, stream_layers
+    from .stream_layers import decode_mode
     from .utils import pc_io
     from .utils.octree_coding import departition_octree
     sess = res.ctx
@@ -247,7 +227,7 @@ def _decode(res, enc_pcs, dec_pcs, model_dir, model_config, batch_size, precisio
         with gzip.open(enc, 'rb') as f:
             resolution, level, binstr, blocks = load_compressed_file(f)
         x_shape = np.array([resolution, resolution, resolution], dtype=np.uint32) // (2 ** level)
-        dec_blocks, _ = model.decompress_blocks(sess, blocks, x_shape, debug=False, layers='step' if 'qs1' in layers else 'count' if 'cnt1' in layers else 'all')
+        dec_blocks, _ = model.decompress_blocks(sess, blocks, x_shape, debug=False, layers=decode_mode(layers))
         dec_blocks = departition_octree(dec_blocks, binstr, [0, 0, 0], x_shape * (2 ** level), level)
         pa = np.vstack(dec_blocks) if len(dec_blocks) else np.zeros((0, 3))
         pc_io.write_df(dec, pc_io.pa_to_df(pa))

@@ -160,84 +160,9 @@ def split_coder_tag(tag):
                        f'{sorted(k for k in CODER_SUFFIX.values() if k)} and the untagged range coder')
 
 
-# layers on top of the y/z strings -> the final part of the tag that names them; a stream carries at most one
-LAYER_SUFFIX = {'occ1': 'occ1', 'cnt1': 'cnt1'}
-
-_COUNT = struct.Struct('<I')             # the "cnt1" string of a block: how many voxels the decoder keeps
-
-
-def count_to_bytes(k):
-    return _COUNT.pack(int(k))
-
-
-def count_from_bytes(payload):
-    """The count string of a block -> k, or None when it is not exactly 4 bytes long."""
-    return _COUNT.unpack(payload)[0] if len(payload) == _COUNT.size else None
-
-
-# ---- the latent step (DESIGN.md 4.21): one ladder index q per block, one byte, the string directly behind the model's y/z strings ------
-STEP_SUFFIX = 'qs1'                      # the part of the tag that names the step strings: behind the coder part, before any later layer
-LATENT_STEPS = 64
-
-
-def latent_step(q):
-    """Step size of ladder index q in [0, 63]: (8 + (q & 7)) * 2^((q >> 3) - 5) -- 0.25 ... 60, latent_step(16) = 1; integer times a
-    power of two, so every value is exact in float32 (and no libm is involved)."""
-    if not (isinstance(q, (int, np.integer)) and not isinstance(q, bool) and 0 <= q < LATENT_STEPS):
-        raise AssertionError(f'latent_step: the ladder index is an integer in [0, {LATENT_STEPS - 1}], got {q!r}')
-    q = int(q)
-    e = (q >> 3) - 5
-    return float(8 + (q & 7)) * (float(1 << e) if e >= 0 else 1.0 / float(1 << -e))
-
-
-def step_to_bytes(q):
-    latent_step(q)
-    return bytes([int(q)])
-
-
-def step_from_bytes(payload, block):
-    """The step string of block `block` -> q.  A string that is not one byte, or a q beyond the ladder, is a RuntimeError."""
-    if len(payload) != 1:
-        raise RuntimeError(f'block {block}: the step string holds {len(payload)} bytes, a "{STEP_SUFFIX}" stream carries one byte per block')
-    if payload[0] >= LATENT_STEPS:
-        raise RuntimeError(f'block {block}: step index {payload[0]} is beyond the ladder (0 to {LATENT_STEPS - 1})')
-    return payload[0]
-
-
-def stream_tag(tag, entropy_coder, lossless=False, count=False, step=False):
-    """The numerics tag of a stream written with `entropy_coder`, with its layer named as a final part: '/occ1' the occupancy layer,
-    '/cnt1' the per-block point counts, '/qs1' the per-block latent steps (behind the coder part; not beside another layer yet)."""
-    assert not (lossless and count), 'a stream carries the occupancy layer or the point counts, not both'
-    assert not (step and (lossless or count)), 'a stepped stream (qs1) carries neither the occupancy layer nor the point counts'
-    tag = coder_tag(tag, entropy_coder)
-    return f'{tag}/occ1' if lossless else f'{tag}/cnt1' if count else f'{tag}/{STEP_SUFFIX}' if step else tag
-
-
-def split_stream_tag(tag):
-    """(numerics tag without coder and layer parts, entropy coder, tuple of layers) of a stream's tag; (tag, None, ()) for a stream
-    without a tag of ours.  Unknown parts are refused like split_coder_tag refuses them.  The order of the parts is fixed: coder, 'qs1',
-    then a later layer -- and 'qs1' beside 'occ1' / 'cnt1' is refused: no build writes it."""
-    if tag is None or not tag.startswith('pcc_geo_cnn_v2_amd/'):
-        return tag, None, ()
-    parts = tag.split('/')
-    layers = ()
-    if len(parts) > 4 and parts[-1] in LAYER_SUFFIX:
-        layers, parts = (LAYER_SUFFIX[parts[-1]],), parts[:-1]
-    if len(parts) > 4 and parts[-1] == STEP_SUFFIX:
-        if layers:
-            raise RuntimeError(f'the stream carries the latent steps ({STEP_SUFFIX}) beside the layer {layers[0]!r} ({tag}); this build reads '
-                               f'{STEP_SUFFIX} streams without another layer')
-        layers, parts = (STEP_SUFFIX,), parts[:-1]
-    base, coder = split_coder_tag('/'.join(parts))
-    return base, coder, layers
-
-
-def stream_layers(tag, expected, override=None, ignore=False):
-    """Decoder side: (entropy coder, layers) the stream names; the rest of the tag is compared as stream_coder does."""
-    base, coder, layers = split_stream_tag(tag)
-    if coder is None:
-        return stream_coder(tag, expected, override, ignore), layers
-    return stream_coder(coder_tag(base, coder), expected, override, ignore), layers
+# the layers on top of the y/z strings live in stream_layers.py; their names stay importable from here
+from .stream_layers import (LATENT_STEPS, count_from_bytes, count_to_bytes, latent_step, split_stream_tag, step_from_bytes,  # noqa: E402,F401
+                            step_to_bytes, stream_layers, stream_tag)
 
 
 def stream_coder(tag, expected, override=None, ignore=False):

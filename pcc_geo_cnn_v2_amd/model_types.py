@@ -13,7 +13,8 @@ MI355X-first differences (results identical):
 `sess` in the reference's signatures is an `ops.Context` here (None = the default GPU context).
 Here: the whole-cloud selection, the models, their batch graph and the block loops of one process.  Beside it: _stream_io.py (pinned
 buffers, copy streams and the copies on them), block_search.py (the schedule of the adaptive threshold search), sharded_blocks.py (the
-block loops over the ranks of torch.distributed).
+block loops over the ranks of torch.distributed), stream_layers.py (the layers a stream carries behind the y/z strings and their place
+in a block's strings; which options of an encode exclude each other: `plan_encode`, asked by both encoder entry points).
 """
 import logging
 import os
@@ -32,8 +33,8 @@ from . import ops
 from .entropy_models import EntropyBottleneck, GaussianConditional, scale_table
 from ._stream_io import _Immediate, _Pinned, _host_dtypes, gather_points, indexes_to_host, on_side_stream, ship, side_stream, symbols_to_device, to_host
 from .block_search import SearchSchedule
-from .model_opt import check_hausdorff_search, count_rows, count_tallies_gpu, d2_on_gpu, decide_counts_from_tallies
-from .model_syntax import count_from_bytes, count_to_bytes, latent_step as latent_step_size, step_from_bytes, step_to_bytes
+from . import stream_layers as SL
+from .model_opt import count_rows, count_tallies_gpu, d2_on_gpu, decide_counts_from_tallies
 from .model_transforms import TransformType
 from .utils.octree_coding import departition_octree
 from .utils.pc_metric import cloud_metrics_batch, cloud_metrics_batch_gpu, wants_hausdorff
@@ -76,9 +77,6 @@ def rank_candidates(names, cand_metrics, opt_groups=('d1', 'd2')):
     return picks
 
 
-METRICS_DEVICES = ('host', 'gpu')      # where the encoder's whole-cloud metrics run (compress_octree --metrics_device)
-
-
 def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, resolution, with_normals,
                                opt_groups=('d1', 'd2'), tree=None, metrics_device='host', ctx=None, d2_ties='pick', hausdorff=False):
     """Per optimisation group, which candidate reconstruction of the whole cloud to keep (the reference's function of the same
@@ -90,8 +88,8 @@ def select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics, points, r
     hausdorff=True (a Hausdorff opt metric was named; single process): every 'metrics' also carries pc_metric.hausdorff_table's keys, from
     the 9-slot whole-cloud tally of the same engine (cloud_tallies_gpu / cloud_tally_host: the same neighbour links, so the other keys
     keep their values); the ranking is unchanged."""
-    if metrics_device not in METRICS_DEVICES:
-        raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
+    if metrics_device not in SL.METRICS_DEVICES:
+        raise AssertionError(f'metrics_device must be one of {SL.METRICS_DEVICES}, got {metrics_device!r}')
     assert len(opt_metrics) == len(x_hat_list), f'lengths of opt_metrics {len(opt_metrics)} and x_hat_list' + \
                                                 f' {len(x_hat_list)} should be equal'
     grouped = [m for m, n in enumerate(opt_metrics) if any(n.startswith(g) for g in opt_groups)]
@@ -133,49 +131,6 @@ def block_count(n_rows, count_scale, n_voxels):
     return int(min(np.float64(n_voxels), np.floor(np.float64(count_scale) * np.float64(n_rows) + 0.5)))
 
 
-def check_count_scale(count_scale, fixed_threshold, lossless, world=1):
-    """What count-matched thresholding excludes; None (off) passes."""
-    if count_scale is None:
-        return
-    if not (isinstance(count_scale, (int, float, np.floating)) and np.isfinite(count_scale) and count_scale > 0):
-        raise AssertionError(f'count_scale must be a finite float above 0, got {count_scale!r}')
-    if fixed_threshold:
-        raise AssertionError('count_scale and fixed_threshold are two policies for the same decision: pick one')
-    if lossless:
-        raise AssertionError('count_scale and lossless: a stream carries the point counts or the occupancy layer, not both')
-    if world > 1:
-        raise AssertionError('count_scale is single-process only: the sharded path moves the y/z strings alone')
-
-
-def check_count_search(count_search, count_scale=None, fixed_threshold=False, lossless=False, world=1, search_ties='pick', opt_metrics=(),
-                       d2_gpu=None, dhw=None):
-    """What the count search (count_search = (lo, hi, steps)) excludes; None (off) passes.  Returns the ladder of count
-    scales (model_opt.count_ladder).  d2_gpu: whether the D2 statistics of the search come from the GPU -- a callable is asked only when a
-    d2_* metric is requested; dhw: the block grid, when known."""
-    if count_search is None:
-        return None
-    from .model_opt import count_ladder, gpu_search_supported
-    if not (isinstance(count_search, (tuple, list)) and len(count_search) == 3):
-        raise AssertionError(f'count_search must be (lo, hi, steps), got {count_search!r}')
-    ladder = count_ladder(*count_search)
-    if count_scale is not None:
-        raise AssertionError('count_search and count_scale are two policies for the same decision: pick one')
-    if fixed_threshold:
-        raise AssertionError('count_search and fixed_threshold are two policies for the same decision: pick one')
-    if lossless:
-        raise AssertionError('count_search and lossless: a stream carries the point counts or the occupancy layer, not both')
-    if world > 1:
-        raise AssertionError('count_search is single-process only: the sharded path moves the y/z strings alone')
-    if search_ties == 'mean':
-        raise AssertionError("count_search with search_ties 'mean': the tie-averaged D2 engine has no count source")
-    if any(m.startswith('d2_') for m in opt_metrics) and not (d2_gpu() if callable(d2_gpu) else d2_gpu):
-        raise AssertionError("count_search with a d2_* metric needs the D2 statistics from the GPU (d2_search 'gpu'): the host KD-tree "
-                             'path has no count source')
-    if dhw is not None and not gpu_search_supported(opt_metrics, dhw):
-        raise AssertionError(f'count_search covers block grids up to 128^3 (the GPU search engines), not {tuple(dhw)}')
-    return ladder
-
-
 # The margin of the rate target's prediction (DESIGN.md 4.21), in units of 2^-16 bit.  The host range coder's string is longer than the
 # cost model's sum: it never writes fewer than two bytes and its termination depends on the final range state (16.000 bits measured on a
 # one-symbol stream, plus 8), and its interval arithmetic truncates, which costs in proportion to the bits coded (largest ratio measured:
@@ -188,48 +143,6 @@ RATE_MARGIN_PPM = 939
 def rate_margin_bits16(bits16):
     """What choose_latent_step adds to a block's predicted y bits before it rounds them up to bytes (int64 array or int, units of 2^-16 bit)."""
     return (RATE_MARGIN_FIXED_BITS << 16) + (bits16 * RATE_MARGIN_PPM + 999999) // 1000000
-
-
-def check_latent_step(latent_step=None, target_bpp=None, version=2, precision='fp32', world=1, lossless=False, count_scale=None,
-                      count_search=None, entropy_coder='range', n_blocks=None):
-    """What the latent step and the rate target on top of it exclude; both None (off) passes.  latent_step: a ladder index
-    (model_syntax.latent_step) or one per block; target_bpp: bits per input point of the container.  Returns the steps as a uint8 array
-    (n_blocks entries when n_blocks is known and a step was given), None otherwise.  Every message names the flag to drop."""
-    if latent_step is None and target_bpp is None:
-        return None
-    what = 'latent_step' if latent_step is not None else 'target_bpp'
-    if latent_step is not None and target_bpp is not None:
-        raise AssertionError('latent_step and target_bpp: the rate target chooses the step itself, drop --latent_step or --target_bpp')
-    if version != 2:
-        raise AssertionError(f'{what} needs a hyperprior model (c3p and its siblings): the factorized prior of a V1 model has no parametric '
-                             f'rescale, drop --{what}')
-    if precision == 'fp16':
-        raise AssertionError(f'{what} is built on the fp32 layer-wise path, drop --precision fp16 (or --{what})')
-    if world > 1:
-        raise AssertionError(f'{what} is single-process only (world size {world}): the sharded path moves the y/z strings alone, drop --{what} '
-                             'or run on one GPU')
-    if lossless:
-        raise AssertionError(f'{what} and lossless: a stepped stream carries no occupancy layer yet, drop --lossless (or --{what})')
-    if count_scale is not None:
-        raise AssertionError(f'{what} and count_scale: a stepped stream carries no point counts yet, drop --count_threshold (or --{what})')
-    if count_search is not None:
-        raise AssertionError(f'{what} and count_search: a stepped stream carries no point counts yet, drop --count_search (or --{what})')
-    if target_bpp is not None:
-        if not (isinstance(target_bpp, (int, float, np.floating, np.integer)) and not isinstance(target_bpp, bool) and np.isfinite(target_bpp) and target_bpp > 0):
-            raise AssertionError(f'target_bpp must be a finite number above 0, got {target_bpp!r}')
-        if entropy_coder == 'rans':
-            raise AssertionError('target_bpp predicts the size of range-coded strings, the escapes of the rANS coder cost otherwise: drop '
-                                 '--entropy_coder rans (or --target_bpp)')
-        return None
-    from .model_syntax import LATENT_STEPS
-    q = np.asarray(latent_step)
-    if not (np.issubdtype(q.dtype, np.integer) and q.ndim <= 1 and q.size and q.min() >= 0 and q.max() < LATENT_STEPS):
-        raise AssertionError(f'latent_step is a ladder index in [0, {LATENT_STEPS - 1}] or one per block, got {latent_step!r}')
-    if q.ndim == 1 and n_blocks is not None and q.size != n_blocks:
-        raise AssertionError(f'latent_step: {q.size} ladder indexes for {n_blocks} blocks')
-    if q.ndim == 0 and n_blocks is not None:
-        q = np.full(n_blocks, q)
-    return q.astype(np.uint8)
 
 
 def _np(t):
@@ -559,29 +472,24 @@ class CompressionModel:
     # ------------------------------------------------------------------ block loops
     def encode_block_range(self, sess, blocks, resolution, with_normals=False, opt_metrics=('d1_mse',),
                            max_deltas=(np.inf,), fixed_threshold=False, debug=False, count_scale=None, count_search=None, latent_step=None):
-        """The per-block part of compress_blocks (model_types.py:192-212) for a list of blocks: returns
-        (strings per block, best-threshold list per block, candidate point lists per block, metric names,
-        debug).  This is the unit that shards across GPUs (sharded_blocks.py).
-        count_scale = rho: count-matched thresholding instead of the search: every block carries one more string, LAST,
-        with k = block_count(its input rows, rho, voxels); its candidate is the k highest-scoring voxels of x_hat (ops.topk_compact) and
-        its threshold byte the fixed one.
-        count_search = (lo, hi, steps): the count search.  The chunk is encoded as under count_scale; the candidates of a
-        block are the top-k sets for k = block_count(its input rows, rho_j, voxels) over the ladder model_opt.count_ladder(lo, hi, steps),
-        scored exactly on the GPU (ops.d1_count_stats / d12_count_stats) and chosen per metric name by the threshold search's own
-        decision rule (model_opt.decide_counts_from_tallies).  The candidate of a name is ops.topk_compact(x_hat, its k).  A block's
-        strings are then the y/z strings followed by ONE COUNT STRING PER METRIC NAME, in the order of the returned names
-        (compress_blocks keeps the one of each output), and the threshold byte is the fixed one.
-        latent_step = q or one q per block (V2 only): block b's y is quantised with the step model_syntax.latent_step(q[b])
-        and coded under the scales divided by it; every block carries one more string, directly behind the y/z strings, the byte q[b].
-        Everything behind the transform sees only another x_hat."""
+        """The per-block part of compress_blocks (model_types.py:192-212) for a list of blocks: returns (strings per block, best-threshold
+        list per block, candidate point lists per block, metric names, debug).  This is the unit that shards across GPUs
+        (sharded_blocks.py).  A block's strings are the model's y/z strings, then those of the layers, in the order of stream_layers.LAYERS.
+        count_scale = rho: count-matched thresholding instead of the search: the block's candidate is the k =
+        block_count(its input rows, rho, voxels) highest-scoring voxels of x_hat (ops.topk_compact), its threshold byte the fixed one, and
+        k its cnt1 string.
+        count_search = (lo, hi, steps): the count search: the candidates of a block are the top-k sets for k =
+        block_count(its input rows, rho_j, voxels) over model_opt.count_ladder(lo, hi, steps), scored exactly on the GPU (ops.d1_count_stats
+        / d12_count_stats) and chosen per metric name by the threshold search's own decision rule (model_opt.decide_counts_from_tallies).
+        In the cnt1 place stands ONE COUNT STRING PER METRIC NAME, in the order of the returned names (compress_blocks keeps the one of
+        each output); the threshold byte is the fixed one.
+        latent_step = q or one q per block (V2 only): block b's y is quantised with the step stream_layers.latent_step(q[b])
+        and coded under the scales divided by it, and the byte q[b] is its qs1 string.  Everything behind the transform sees only another
+        x_hat."""
         dhw = self._spatial(self.x_shape)
-        ladder = check_count_search(count_search, count_scale, fixed_threshold, self.lossless, 1, self.search_ties, opt_metrics,
-                                    lambda: d2_on_gpu(self.d2_search, 'pick'), dhw)
-        steps = check_latent_step(latent_step, None, self.codec_abi, self.precision, 1, self.lossless, count_scale, count_search,
-                                  self.entropy_coder, len(blocks))
+        plan = self._plan_encode('encode_block_range', 1, len(blocks), dhw, opt_metrics, fixed_threshold=fixed_threshold, count_scale=count_scale,
+                                 count_search=count_search, latent_step=latent_step)
         ctx = self._ctx(sess)
-        check_count_scale(count_scale, fixed_threshold, self.lossless)
-        counted = count_scale is not None
         want_d2 = any(m.startswith('d2_') for m in opt_metrics)
         if not fixed_threshold:
             # once per call what the reference asserts per block (model_opt.py:22-24): unknown metric names, d2_* without normals
@@ -590,51 +498,75 @@ class CompressionModel:
         strings_list, debug_t_list = [], []
         # adaptive search (model_opt.py:33-73): every chunk's x_hat goes to the schedule, the decisions come a few chunks later
         search = SearchSchedule(self, ctx, dhw, len(blocks), resolution, with_normals, opt_metrics, max_deltas)
-        half = len(self.thresholds) // 2
-        for c0 in range(0, len(blocks), self.batch_size):
-            chunk = blocks[c0:c0 + self.batch_size]
-            x = self._voxelize(ctx, chunk, dhw)
-            stepped = {} if steps is None else {'steps': torch.from_numpy(steps[c0:c0 + len(chunk)]).to(ctx.device)}
-            enc = self._encode_batch(ctx, x, debug, thr=self._thr_tensor(ctx, [half] * len(chunk)) if fixed_threshold else None, **stepped)
-            # the occupancy layer: the chunk's dense input under the x_hat the decoder will compute (same bits: the numerics tag); the
-            # threshold search below neither sees nor changes it
-            occ_job = ops.occ_encode_launch(ctx, enc['x_hat'], x) if self.lossless else None
-            if counted:
-                ks = [block_count(len(b), count_scale, int(np.prod(dhw))) for b in chunk]
-                enc['xyz'], enc['counts'] = ops.topk_compact(ctx, enc['x_hat'], torch.tensor(ks, dtype=torch.int32).to(ctx.device, non_blocking=True))
-            strings = enc['finish']()
-            if steps is not None:       # model strings, then the step string (then any later layer string: none yet)
-                strings = [tuple(ss) + (step_to_bytes(q),) for ss, q in zip(strings, steps[c0:c0 + len(chunk)].tolist())]
-            if ladder is not None:
-                rows = count_rows(chunk, ladder, int(np.prod(dhw)))
+        half, n_voxels = len(self.thresholds) // 2, int(np.prod(dhw))
+
+        def topk(x_hat, ks):
+            return ops.topk_compact(ctx, x_hat, torch.tensor(ks, dtype=torch.int32).to(ctx.device, non_blocking=True))
+
+        def one_candidate(xyz, counts, extra=None):
+            # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 and the same points for every metric name
+            n_m = len(max_deltas) * len(opt_metrics)
+            for pts in self._gather_points(xyz, counts):
+                search.thresholds.append([half] * n_m)
+                search.points.append([pts] * n_m)
+            return extra
+
+        # The four candidate policies.  Each is called once the chunk's occupancy launch is queued, launches what it can before the host
+        # codes the strings, and returns decide(): called after enc['finish'](), it leaves the chunk's thresholds and candidate points
+        # with `search` and returns the layer strings the policy adds ({layer: one entry per block}), if any.
+        def searched(chunk, enc):
+            return lambda: search.add(chunk, enc['x_hat'])
+
+        def fixed(chunk, enc):
+            return lambda: one_candidate(enc['xyz'], enc['counts'])
+
+        def counted(chunk, enc):      # the candidate is the top-k one, the byte the fixed one
+            ks = [block_count(len(b), count_scale, n_voxels) for b in chunk]
+            xyz, counts = topk(enc['x_hat'], ks)
+            return lambda: one_candidate(xyz, counts, {'cnt1': [SL.count_to_bytes(k) for k in ks]})
+
+        def count_searched(chunk, enc):
+            def decide():
+                rows = count_rows(chunk, plan.ladder, n_voxels)
                 tallies = count_tallies_gpu(ctx, chunk, enc['x_hat'], rows, d2=want_d2, hausdorff=wants_hausdorff(opt_metrics))
                 search.names, ks_m, _ = decide_counts_from_tallies(chunk, tallies, rows, resolution, opt_metrics, max_deltas, with_normals=want_d2)
-                per_name = []
-                for m in range(len(search.names)):
-                    xyz, cnt = ops.topk_compact(ctx, enc['x_hat'], torch.tensor([k[m] for k in ks_m], dtype=torch.int32).to(ctx.device, non_blocking=True))
-                    per_name.append(self._gather_points(xyz, cnt))
+                per_name = [self._gather_points(*topk(enc['x_hat'], [k[m] for k in ks_m])) for m in range(len(search.names))]
                 for j in range(len(chunk)):
                     search.thresholds.append([half] * len(search.names))
                     search.points.append([pts_m[j] for pts_m in per_name])
-                strings = [tuple(ss) + tuple(count_to_bytes(k) for k in ks) for ss, ks in zip(strings, ks_m)]
-            elif fixed_threshold or counted:
-                # compute_optimal_thresholds' fixed branch (model_opt.py:27-31): index len//2 for every metric; under count_scale the
-                # byte is the same and the candidate is the top-k one
-                n_m = len(max_deltas) * len(opt_metrics)
-                pts = self._gather_points(enc['xyz'], enc['counts'])
-                for j in range(len(chunk)):
-                    search.thresholds.append([half] * n_m)
-                    search.points.append([pts[j]] * n_m)
-            else:
-                search.add(chunk, enc['x_hat'])
+                return {'cnt1': [[SL.count_to_bytes(k) for k in ks] for ks in ks_m]}      # one count string per metric name
+            return decide
+
+        policy = {'search': searched, 'fixed': fixed, 'count': counted, 'count_search': count_searched}[plan.policy]
+        for c0 in range(0, len(blocks), self.batch_size):
+            chunk = blocks[c0:c0 + self.batch_size]
+            x = self._voxelize(ctx, chunk, dhw)
+            q = None if plan.steps is None else plan.steps[c0:c0 + len(chunk)]
+            # (`steps` only where there are some: tests/test_round6_gpu.py and two tools replace _encode_batch by doubles without the keyword)
+            stepped = {} if q is None else {'steps': torch.from_numpy(q).to(ctx.device)}
+            enc = self._encode_batch(ctx, x, debug, thr=self._thr_tensor(ctx, [half] * len(chunk)) if plan.policy == 'fixed' else None, **stepped)
+            # the occupancy layer: the chunk's dense input under the x_hat the decoder will compute (same bits: the numerics tag); the
+            # policy neither sees nor changes it
+            occ_job = ops.occ_encode_launch(ctx, enc['x_hat'], x) if self.lossless else None
+            decide = policy(chunk, enc)
+            strings = enc['finish']()
+            extra = decide() or {}
+            if q is not None:
+                extra['qs1'] = [SL.step_to_bytes(v) for v in q.tolist()]
             if occ_job is not None:
-                strings = [tuple(ss) + (o,) for ss, o in zip(strings, ops.occ_encode_fetch(*occ_job))]
-            if counted:
-                strings = [tuple(ss) + (count_to_bytes(k),) for ss, k in zip(strings, ks)]
+                extra['occ1'] = ops.occ_encode_fetch(*occ_job)
+            if extra:
+                strings = [SL.compose_strings(ss, **{name: per_block[j] for name, per_block in extra.items()}) for j, ss in enumerate(strings)]
             strings_list.extend(strings)
             debug_t_list.extend(enc['debug'])
         search.drain()
         return strings_list, search.thresholds, search.points, search.names, debug_t_list
+
+    def _plan_encode(self, entry, world, n_blocks, dhw, opt_metrics, **options):
+        """stream_layers.plan_encode with what the model itself fixes (version, precision, coder, occupancy layer, search settings)"""
+        return SL.plan_encode(entry=entry, world=world, n_blocks=n_blocks, dhw=dhw, opt_metrics=opt_metrics, version=self.codec_abi,
+                              precision=self.precision, entropy_coder=self.entropy_coder, lossless=self.lossless, search_ties=self.search_ties,
+                              d2_gpu=lambda: d2_on_gpu(self.d2_search, 'pick'), **options)
 
     def compress_blocks(self, sess, blocks, binstr, points, resolution, level, with_normals=False,
                         opt_metrics=('d1_mse',), max_deltas=(np.inf,), fixed_threshold=False, debug=False,
@@ -652,22 +584,10 @@ class CompressionModel:
         whose predicted container holds at most R * len(points) / 8 bytes (`choose_latent_step`; analysis and hyper run twice).  Under
         either, every metadata dict carries 'latent_step' (q, or the list of them) and, under a target, 'rate_target'."""
         from . import sharding
-        from .utils.pc_metric import check_ties
         rank, world = sharding.world_info()
-        check_latent_step(latent_step, target_bpp, self.codec_abi, self.precision, world, self.lossless, count_scale, count_search,
-                          self.entropy_coder, len(blocks))
-        check_ties(d2_ties, world)
-        if self.lossless and world > 1:
-            raise AssertionError('lossless is single-process only: the sharded path moves the y/z strings alone')
-        check_count_scale(count_scale, fixed_threshold, self.lossless, world)
-        check_count_search(count_search, count_scale, fixed_threshold, self.lossless, world, self.search_ties, opt_metrics,
-                           lambda: d2_on_gpu(self.d2_search, 'pick'), None if count_search is None else self._spatial(self.x_shape))
-        if not fixed_threshold:
-            check_hausdorff_search(opt_metrics, self.search_ties, lambda: d2_on_gpu(self.d2_search, 'pick'), world)
-        if metrics_device not in METRICS_DEVICES:
-            raise AssertionError(f'metrics_device must be one of {METRICS_DEVICES}, got {metrics_device!r}')
-        if metrics_device == 'gpu' and world > 1:
-            raise AssertionError('metrics_device gpu is single-process only: the sharded metric path runs on the host')
+        plan = self._plan_encode('compress_blocks', world, len(blocks), None if count_search is None else self._spatial(self.x_shape), opt_metrics,
+                                 fixed_threshold=fixed_threshold, count_scale=count_scale, count_search=count_search, latent_step=latent_step,
+                                 target_bpp=target_bpp, metrics_device=metrics_device, d2_ties=d2_ties)
         # The KD-tree over the ORIGINAL cloud (the whole-cloud metrics of every candidate query it: pc_metric.py:80) does not depend on the
         # encode: it is built on a helper thread while the GPU codes the blocks (0.11 s of a 614 k-point cloud's 0.30 s; scipy builds
         # without the GIL).  Same constructor call as before: the same tree, the same neighbour picks.  The GPU metrics need no tree.
@@ -681,10 +601,10 @@ class CompressionModel:
         try:
             if target_bpp is not None:
                 latent_step, rate_target = self.choose_latent_step(sess, blocks, binstr, len(points), target_bpp)
+            # (only the options that are set: tests/_shard_worker.py replaces encode_block_range by doubles without these keywords)
+            options = {k: v for k, v in (('count_scale', count_scale), ('count_search', count_search), ('latent_step', latent_step)) if v is not None}
             strings_list, threshold_list, x_hat_list, opt_metrics_ret, debug_t_list = self.encode_block_range(
-                sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug,
-                **({} if count_scale is None else {'count_scale': count_scale}), **({} if count_search is None else {'count_search': count_search}),
-                **({} if latent_step is None else {'latent_step': latent_step}))
+                sess, blocks, resolution, with_normals, opt_metrics, max_deltas, fixed_threshold, debug, **options)
         finally:
             tree = tree_future.result() if tree_future is not None else None
         # block -> opt metric to opt metric -> block
@@ -692,12 +612,13 @@ class CompressionModel:
         x_hat_list = list(zip(*x_hat_list))
         metadata = select_best_per_opt_metric(binstr, x_hat_list, level, opt_metrics_ret, points, resolution, with_normals, tree=tree,
                                               metrics_device=metrics_device, ctx=None if host_metrics else self._ctx(sess),
-                                              d2_ties=d2_ties, **({'hausdorff': True} if wants_hausdorff(opt_metrics) and not fixed_threshold else {}))
-        if count_search is not None:      # y/z strings + one count string per metric name: output m keeps its own
-            n = self.n_strings
-            data_list = [[(tuple(ss[:n]) + (ss[n + x['idx']],), t) for ss, t in zip(strings_list, threshold_list[x['idx']])] for x in metadata]
-        else:
-            data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
+                                              d2_ties=d2_ties, hausdorff=wants_hausdorff(opt_metrics) and not fixed_threshold)
+        data_list = [list(zip(strings_list, threshold_list[x['idx']])) for x in metadata]
+        if plan.policy == 'count_search':      # every block holds one count string per metric name: output m keeps its own
+            def keep(strings, m):
+                base, extra = SL.split_strings(strings, self.n_strings, plan.layers, candidates=len(opt_metrics_ret))
+                return SL.compose_strings(base, **{**extra, 'cnt1': extra['cnt1'][m]})
+            data_list = [[(keep(ss, x['idx']), t) for ss, t in data] for x, data in zip(metadata, data_list)]
         if latent_step is not None:
             q = np.asarray(latent_step)
             for x in metadata:
@@ -836,71 +757,51 @@ class CompressionModel:
     def decompress_block_range(self, sess, blocks, x_shape, debug=False, layers='all'):
         """decompress_blocks for a list of blocks on this process' GPU: the unit that shards across GPUs.
         Software pipeline over chunks: the host range decoder of chunk k overlaps the synthesis of k-1."""
-        ctx = self._ctx(sess)
         dhw = self._spatial(x_shape)
         chunks = [blocks[c0:c0 + self.batch_size] for c0 in range(0, len(blocks), self.batch_size)]
-        n_base = self.n_strings
-        exact = layers == 'all' and len(blocks) > 0 and len(blocks[0][0]) == n_base + 1
-        ks = self._block_counts(blocks, int(np.prod(dhw))) if layers == 'count' else None
-        qs = self._block_steps(blocks) if layers == 'step' else None            # (read and checked before anything is launched)
-        state = [None] * len(chunks)
-        results = [None] * len(chunks)
+        # the layer to read and its values, read and checked before anything is launched
+        carried = SL.carried_layer(layers, blocks, self.n_strings)
+        if carried == 'qs1' and self.codec_abi != 2:
+            raise RuntimeError('the stream carries latent steps (qs1): only the hyperprior models (c3p and its siblings) read them')
+        values = None if carried is None else SL.layer_values(carried, blocks, self.n_strings)
+        ctx = self._ctx(sess)
+        if carried == 'qs1':
+            values = np.array(values, np.uint8)
+
+        def of_chunk(k):
+            return values[k * self.batch_size:k * self.batch_size + len(chunks[k])]
+
+        # how the points of chunk k come out of x_hat, chosen once; by the threshold byte it is phase b's own last step
+        by_threshold = carried in (None, 'qs1')
+        if carried == 'occ1':
+            def points(k, dec):
+                B = len(chunks[k])
+                occ, status = ops.occ_decode_batch(ctx, dec['x_hat'], of_chunk(k), check=False)
+                out = ops.threshold_compact(ctx, occ, self._dev(ctx, ('thr_occ', B), np.full(B, 0.5, np.float32)), clip=False)
+                ops.occ_check_status(status)                            # (after the chunk's launches)
+                return out
+        elif carried == 'cnt1':
+            def points(k, dec):      # the stream is not trusted: a count above the block's voxels is the same request as all of them
+                ks = [min(v, int(np.prod(dhw))) for v in of_chunk(k)]
+                return ops.topk_compact(ctx, dec['x_hat'], torch.tensor(ks, dtype=torch.int32).to(ctx.device, non_blocking=True))
+        else:
+            def points(k, dec):
+                return dec['xyz'], dec['counts']                        # the decoder does not clip (:232-233)
+        state, results = [None] * len(chunks), [None] * len(chunks)
         for k in range(len(chunks) + 1):
             if k < len(chunks):
-                c0 = k * self.batch_size
-                stepped = {} if qs is None else {'steps': torch.from_numpy(qs[c0:c0 + len(chunks[k])]).to(ctx.device)}
+                stepped = {} if carried != 'qs1' else {'steps': torch.from_numpy(of_chunk(k)).to(ctx.device)}      # (V1 has no such keyword)
                 state[k] = self._decode_phase_a(ctx, [s for s, _ in chunks[k]], dhw, **stepped)
-            if k >= 1 and exact:
-                B = len(chunks[k - 1])
-                dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=None)
-                occ, status = ops.occ_decode_batch(ctx, dec['x_hat'], [s[n_base] for s, _ in chunks[k - 1]], check=False)
-                xyz, counts = ops.threshold_compact(ctx, occ, self._dev(ctx, ('thr_occ', B), np.full(B, 0.5, np.float32)), clip=False)
-                ops.occ_check_status(status)                            # (after the chunk's launches)
-                results[k - 1] = (xyz, counts, dec['debug'])
-                state[k - 1] = None
-            elif k >= 1 and ks is not None:
-                c0 = (k - 1) * self.batch_size
-                dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=None)
-                kt = torch.tensor(ks[c0:c0 + len(chunks[k - 1])], dtype=torch.int32).to(ctx.device, non_blocking=True)
-                xyz, counts = ops.topk_compact(ctx, dec['x_hat'], kt)
-                results[k - 1] = (xyz, counts, dec['debug'])
-                state[k - 1] = None
-            elif k >= 1:
-                thr_idx = [int(t) for _, t in chunks[k - 1]]
-                dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=self._thr_tensor(ctx, thr_idx))
-                xyz, counts = dec['xyz'], dec['counts']                 # the decoder does not clip (:232-233)
-                results[k - 1] = (xyz, counts, dec['debug'])
+            if k >= 1:
+                thr = self._thr_tensor(ctx, [int(t) for _, t in chunks[k - 1]]) if by_threshold else None
+                dec = self._decode_phase_b(ctx, state[k - 1], dhw, debug, thr=thr)
+                results[k - 1] = points(k - 1, dec) + (dec['debug'],)
                 state[k - 1] = None
         dec_blocks, debug_t_list = [], []
         for xyz, counts, dbg in results:
             dec_blocks.extend(self._gather_points(xyz, counts))
             debug_t_list.extend(dbg)
         return dec_blocks, debug_t_list
-
-    def _block_counts(self, blocks, n_voxels):
-        """The count strings of a "cnt1" stream (the string behind the model's y/z strings of every block) -> k per block, read before
-        anything is launched.  The stream is not trusted: a count above the block's voxels is the same request as all of them."""
-        ks = []
-        for b, (strings, _) in enumerate(blocks):
-            k = count_from_bytes(strings[self.n_strings]) if len(strings) == self.n_strings + 1 else None
-            if k is None:
-                raise L.PccError(f'block {b}: {len(strings)} strings, the last of {len(strings[-1]) if len(strings) else 0} bytes: a count stream '
-                                 f'carries {self.n_strings + 1} strings per block, the last of 4 bytes (status {L.PCC_ERR_CORRUPT})')
-            ks.append(min(k, n_voxels))
-        return ks
-
-    def _block_steps(self, blocks):
-        """The step strings of a "qs1" stream (the string directly behind the model's y/z strings of every block) -> uint8 q per block, read
-        before anything is launched.  A block without one, a string that is not one byte or a q beyond the ladder is a RuntimeError that
-        names the block."""
-        if self.codec_abi != 2:
-            raise RuntimeError('the stream carries latent steps (qs1): only the hyperprior models (c3p and its siblings) read them')
-        qs = np.zeros(len(blocks), np.uint8)
-        for b, (strings, _) in enumerate(blocks):
-            if len(strings) != self.n_strings + 1:
-                raise RuntimeError(f'block {b}: {len(strings)} strings, a stepped stream (qs1) carries {self.n_strings + 1} per block')
-            qs[b] = step_from_bytes(strings[self.n_strings], b)
-        return qs
 
     # ------------------------------------------------------------------ batched graph.  With a pcc_codec_desc (`_codec`) the GPU part
     # of each phase is ONE ABI call; otherwise the same steps run layer by layer.  Both leave the same tensors under the same names.
@@ -1194,7 +1095,8 @@ class CompressionModelV2(CompressionModel):
         which the coder's string exceeds the model's sum, so that the chosen step fits on every stream measured; it is no proven bound.
         Returns (q, dict(target_bpp, budget_bytes, predicted_bytes, predictions)): q the smallest (finest) whose prediction is at most
         target_bpp * n_points / 8, else 63 with a warning."""
-        from .model_syntax import LATENT_STEPS, _HEADER, _U16
+        from .model_syntax import _HEADER, _U16
+        from .stream_layers import LATENT_STEPS
         ctx = self._ctx(sess)
         dhw = self._spatial(self.x_shape)
         ladder = np.arange(LATENT_STEPS, dtype=np.uint8)
@@ -1209,14 +1111,15 @@ class CompressionModelV2(CompressionModel):
             zbytes += sum(len(s) for s in ops.range_encode_batch(self.entropy_bottleneck.table, zs, rows, mod, self.coder_threads))
             bits = bits.cpu().numpy()
             ybytes += ((bits + rate_margin_bits16(bits) + ((1 << 19) - 1)) >> 19).sum(0)
-        fixed = _HEADER.size + len(binstr) + len(blocks) * (1 + (self.n_strings + 1) * _U16.size + 1)
+        layers = ('qs1',)         # per block: the threshold byte, a length field per string, the step byte
+        fixed = _HEADER.size + len(binstr) + len(blocks) * (1 + (self.n_strings + len(layers)) * _U16.size + sum(SL.BY_NAME[n].size for n in layers))
         pred = fixed + zbytes + ybytes
         budget = float(target_bpp) * n_points / 8.0
         fits = np.flatnonzero(pred <= budget)
         q = int(fits[0]) if fits.size else LATENT_STEPS - 1
         if not fits.size:
             logger.warning('target_bpp %g (%d bytes for %d points) is out of reach: the coarsest step (q = %d, step %g) predicts %d bytes',
-                           target_bpp, int(budget), n_points, q, latent_step_size(q), int(pred[q]))
+                           target_bpp, int(budget), n_points, q, SL.latent_step(q), int(pred[q]))
         return q, dict(target_bpp=float(target_bpp), budget_bytes=budget, predicted_bytes=int(pred[q]), predictions=[int(v) for v in pred])
 
     def _hyper_decode(self, ctx, dhw, zsym=None, zpacked=None, idx_packed=None, steps=None):

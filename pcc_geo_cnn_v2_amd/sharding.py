@@ -82,6 +82,25 @@ def world_info():
     return (d.get_rank(), d.get_world_size()) if d is not None else (0, 1)
 
 
+def join_process_group():
+    """What the CLIs do first -> (rank, world, local device index).  Under torch.distributed.run the blocks are sharded over the ranks."""
+    import os
+    local = int(os.environ.get('LOCAL_RANK', '0'))
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        import torch.distributed as dist
+        # PCC_DIST_BACKEND=gloo + PCC_DIST_SAME_GPU=1: every rank on GPU 0 with host-side collectives -- lets a 1-GPU box run the
+        # sharded path end to end (tests/test_cli_gpu.py); the default is one GPU per rank over RCCL
+        if os.environ.get('PCC_DIST_SAME_GPU'):
+            local = 0
+        torch.cuda.set_device(local)
+        if os.environ.get('PCC_DIST_BACKEND', 'nccl') == 'gloo':
+            dist.init_process_group('gloo')
+        else:
+            dist.init_process_group('nccl', device_id=torch.device('cuda', local))
+    rank, world = world_info()
+    return rank, world, local
+
+
 def _device(d, device=None):
     if device is not None:
         return device

@@ -138,6 +138,15 @@ STREAMS = {
     'c3p_16_fp16_range': ('c3p', 16, 'fp16', 'range', False), 'c3p_32_fp16_range': ('c3p', 32, 'fp16', 'range', False),
     'c3p_16_fp32_rans': ('c3p', 16, 'fp32', 'rans', False), 'c1_32_fp32_rans': ('c1', 32, 'fp32', 'rans', False),
     'c3p_32_fp32_range_occ': ('c3p', 32, 'fp32', 'range', True), 'c1_16_fp32_rans_occ': ('c1', 16, 'fp32', 'rans', True),
+    'c3p_16_fp32_range_cnt': ('c3p', 16, 'fp32', 'range', False), 'c3p_32_fp32_range_cntsearch': ('c3p', 32, 'fp32', 'range', False),
+    'c3p_16_fp32_range_qs21': ('c3p', 16, 'fp32', 'range', False), 'c3p_16_fp32_range_bpp': ('c3p', 16, 'fp32', 'range', False),
+}
+# name -> the encoder's threshold policy and layer flags where they are not the plain --fixed_threshold; the listing records them.
+# --target_bpp 6.0: 769.5 bytes for the 1026 points of the 16^3 cloud; the predictions of the recording build are 848 bytes at q = 12 and
+# 729 at q = 13 (2122 at q = 0, 177 from q = 26 on), so the target selects the interior step 13
+STREAM_FLAGS = {
+    'c3p_16_fp32_range_cnt': ['--count_threshold', '1.0'], 'c3p_32_fp32_range_cntsearch': ['--count_search', '0.5', '2.0', '5'],
+    'c3p_16_fp32_range_qs21': ['--fixed_threshold', '--latent_step', '21'], 'c3p_16_fp32_range_bpp': ['--fixed_threshold', '--target_bpp', '6.0'],
 }
 LEVEL = 1
 
@@ -170,8 +179,8 @@ def cli_encode(name, ck, src, out, dec_file):
     cfg, res, prec, coder, lossless = STREAMS[name]
     compress_octree.compress(compress_octree.build_parser().parse_args(
         ['--input_files', src, '--output_files', out, '--dec_files', dec_file, '--checkpoint_dir', ck, '--model_config', cfg,
-         '--resolution', str(2 * res), '--octree_level', str(LEVEL), '--opt_metrics', 'd1_mse', '--fixed_threshold', '--batch_size', '2',
-         '--precision', prec, '--entropy_coder', coder] + (['--lossless'] if lossless else [])))
+         '--resolution', str(2 * res), '--octree_level', str(LEVEL), '--opt_metrics', 'd1_mse', '--batch_size', '2',
+         '--precision', prec, '--entropy_coder', coder] + STREAM_FLAGS.get(name, ['--fixed_threshold']) + (['--lossless'] if lossless else [])))
 
 
 def cli_decode(cfg, prec, ck, inp, out):

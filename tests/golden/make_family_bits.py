@@ -122,7 +122,7 @@ def record_streams(folder, family):
             shutil.copyfile(out, os.path.join(folder, name + '.bin'))
             listing[name] = dict(file=name + '.bin', model=cfg, resolution=2 * res, octree_level=CP.LEVEL, precision=prec, coder=coder,
                                  lossless=lossless, tag=tag, bytes=os.path.getsize(out), input_points=len(pts), points=len(got),
-                                 point_digest=BR.digest(got))
+                                 point_digest=BR.digest(got), **({'flags': CP.STREAM_FLAGS[name]} if name in CP.STREAM_FLAGS else {}))
             print(name, listing[name]['bytes'], 'bytes', len(got), 'points', tag, flush=True)
     with open(os.path.join(folder, 'streams.json'), 'w') as fh:
         json.dump(dict(family=family, streams=listing), fh, indent=1, sort_keys=True)

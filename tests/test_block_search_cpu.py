@@ -110,7 +110,9 @@ def test_n_strings_is_the_number_of_strings_per_block_in_the_committed_streams()
     for e in listing['streams'].values():
         path = os.path.join(CP.streams_dir(listing['family']), e['file'])
         blocks = model_syntax.load_compressed_file(io.BytesIO(CP.payload_of(path)))[3]
-        per_model.setdefault(e['model'], set()).update(len(strings) - int(e['lossless']) for strings, _ in blocks)
+        layers = model_syntax.split_stream_tag(e['tag'])[2]       # (the tag names what stands behind the model's strings)
+        assert ('occ1' in layers) == e['lossless']
+        per_model.setdefault(e['model'], set()).update(len(strings) - len(layers) for strings, _ in blocks)
     assert per_model == {'c1': {1}, 'c3p': {2}}
     by_type = {ModelType.v1.value: per_model['c1'], ModelType.v2.value: per_model['c3p']}      # (c2, c3: the model class of c3p)
     for cfg in ModelConfigType:

@@ -45,10 +45,10 @@ def test_compress_octree_metrics_device_flag():
     assert _args('--metrics_device', 'gpu').metrics_device == 'gpu'
     with pytest.raises(SystemExit):
         _args('--metrics_device', 'cpu')
-    compress_octree.check_metrics_device('gpu', 1)
-    compress_octree.check_metrics_device('host', 4)
+    compress_octree.check_encode_options(_args('--metrics_device', 'gpu'), 1)
+    compress_octree.check_encode_options(_args(), 4)
     with pytest.raises(AssertionError, match='single-process only'):
-        compress_octree.check_metrics_device('gpu', 2)
+        compress_octree.check_encode_options(_args('--metrics_device', 'gpu'), 2)
 
 
 def test_compress_blocks_refuses_gpu_metrics_under_a_sharded_run(monkeypatch):

@@ -10,6 +10,7 @@ import _topk_ref as T
 from pcc_geo_cnn_v2_amd import _lib as L
 from pcc_geo_cnn_v2_amd import model_opt as MO
 from pcc_geo_cnn_v2_amd import model_types as MT
+from pcc_geo_cnn_v2_amd.stream_layers import plan_encode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = [s for s in T.SHAPES if np.prod(s) <= 4096]
@@ -145,24 +146,28 @@ def test_count_threshold_refusals_are_unchanged(monkeypatch):
             compress_octree.compress(_parse('--count_threshold', *extra))
     for bad in [dict(count_scale=0.0), dict(count_scale=1.0, fixed_threshold=True), dict(count_scale=1.0, lossless=True), dict(count_scale=1.0, world=2)]:
         with pytest.raises(AssertionError, match='count_scale'):
-            MT.check_count_scale(bad.pop('count_scale'), bad.pop('fixed_threshold', False), bad.pop('lossless', False), **bad)
-    assert MT.check_count_scale(None, True, True, 4) is None
+            plan_encode(**bad)
+    assert plan_encode(entry='encode_block_range', count_scale=None, fixed_threshold=True, lossless=True, world=4).policy == 'fixed'      # off
 
 
 def test_model_refuses_count_search_with_what_it_excludes(monkeypatch):
     ok = dict(count_search=(0.5, 2.0, 5))
-    assert MT.check_count_search(None, 1.0, True, True, 4, 'mean', ('d2_mse',), False, (256,) * 3) is None
-    assert np.array_equal(MT.check_count_search((0.5, 2.0, 5), opt_metrics=('d1_mse',), dhw=(64,) * 3), MO.count_ladder(0.5, 2.0, 5))
-    assert MT.check_count_search((0.5, 2.0, 5), opt_metrics=('d1_mse', 'd2_mse'), d2_gpu=lambda: True, dhw=(128,) * 3) is not None
+    def ladder(count_search, **kw):
+        return plan_encode(count_search=count_search, **kw).ladder
+    # off: its rules refuse nothing (what count_scale excludes on its own is test_count_threshold_refusals_are_unchanged's)
+    assert ladder(None, world=4, search_ties='mean', opt_metrics=('d2_mse',), d2_gpu=False, dhw=(256,) * 3) is None
+    assert ladder(None, entry='encode_block_range', count_scale=1.0, search_ties='mean', opt_metrics=('d2_mse',), d2_gpu=False, dhw=(256,) * 3) is None
+    assert np.array_equal(ladder((0.5, 2.0, 5), opt_metrics=('d1_mse',), dhw=(64,) * 3), MO.count_ladder(0.5, 2.0, 5))
+    assert ladder((0.5, 2.0, 5), opt_metrics=('d1_mse', 'd2_mse'), d2_gpu=lambda: True, dhw=(128,) * 3) is not None
     for kw, match in [(dict(count_scale=1.0), 'count_scale'), (dict(fixed_threshold=True), 'fixed_threshold'), (dict(lossless=True), 'lossless'),
                       (dict(world=2), 'single-process'), (dict(search_ties='mean'), "search_ties 'mean'"),
                       (dict(opt_metrics=('d1_mse', 'd2_mse'), d2_gpu=False), "d2_search 'gpu'"),
                       (dict(opt_metrics=('d2_mse',), d2_gpu=lambda: False), "d2_search 'gpu'"), (dict(dhw=(256, 64, 64)), '128')]:
         with pytest.raises(AssertionError, match=f'count_search.*{match}'):
-            MT.check_count_search((0.5, 2.0, 5), **kw)
+            ladder((0.5, 2.0, 5), **kw)
     for bad in [(0.5, 2.0), 1.0, (2.0, 0.5, 5), (0.5, 2.0, 0)]:
         with pytest.raises(AssertionError, match='count_search'):
-            MT.check_count_search(bad)
+            ladder(bad)
     # the model's own entry points refuse before a context is made: no GPU here, and sess = None would create the default one
     from pcc_geo_cnn_v2_amd import ops, sharding
     from pcc_geo_cnn_v2_amd.model_configs import ModelConfigType

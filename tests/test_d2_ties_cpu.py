@@ -120,6 +120,11 @@ def test_metric_tables_take_the_rule():
         pc_metric.cloud_tally_host(A, B, n, ties='min')
 
 
+def _ties_args(rule):
+    return compress_octree.build_parser().parse_args(['--input_files', 'a.ply', '--output_files', 'a.bin', '--checkpoint_dir', 'ck',
+                                                      '--model_config', 'c3p', '--opt_metrics', 'd1_mse', '--d2_ties', rule])
+
+
 def test_mean_is_refused_across_ranks():
     class TwoRanks(pc_metric.SingleProcess):
         world = 2
@@ -127,9 +132,9 @@ def test_mean_is_refused_across_ranks():
     with pytest.raises(AssertionError, match='single-process'):
         pc_metric.cloud_metrics_batch(a.astype(np.float64), [b.astype(np.float64)], 1023, n, comm=TwoRanks(), ties='mean')
     with pytest.raises(AssertionError, match='--d2_ties.*single-process'):
-        compress_octree.check_d2_ties('mean', 2)
-    compress_octree.check_d2_ties('mean', 1)
-    compress_octree.check_d2_ties('pick', 4)
+        compress_octree.check_encode_options(_ties_args('mean'), 2)
+    compress_octree.check_encode_options(_ties_args('mean'), 1)
+    compress_octree.check_encode_options(_ties_args('pick'), 4)
     with pytest.raises(AssertionError, match='ties'):
         model_types.select_best_per_opt_metric([], [], 1, [], np.zeros((0, 3)), 64, False, d2_ties='max')
 

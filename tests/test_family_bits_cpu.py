@@ -100,12 +100,15 @@ def test_committed_streams_match_their_listing():
     listing = CP.load_listing(g['family'])
     assert listing['family'] == g['family'] and sorted(listing['streams']) == sorted(CP.STREAMS)
     assert sorted(os.listdir(folder)) == sorted([e['file'] for e in listing['streams'].values()] + ['streams.json'])
-    assert len(listing['streams']) <= 12
+    assert len(listing['streams']) <= 16
     for name, e in listing['streams'].items():
         path = os.path.join(folder, e['file'])
         tag = model_syntax.read_gzip_tag(path)
         assert tag == e['tag'] and tag.startswith(f"pcc_geo_cnn_v2_amd/k{g['family']}/"), name
         assert tag.split('/')[3] == e['precision'] and ('rans1' in tag.split('/')) == (e['coder'] == 'rans') and tag.endswith('/occ1') == e['lossless']
         assert os.path.getsize(path) == e['bytes'] < 16384 and e['points'] > 0 and len(e['point_digest']) == 32
+        flags = CP.STREAM_FLAGS.get(name, [])       # (the layer a flag asks for is the one the tag names)
+        assert e.get('flags', []) == flags and tag.endswith('/cnt1') == any(f.startswith('--count_') for f in flags)
+        assert tag.endswith('/qs1') == bool({'--latent_step', '--target_bpp'} & set(flags))
         resolution, level, _, blocks = model_syntax.load_compressed_file(__import__('io').BytesIO(CP.payload_of(path)))
         assert (resolution, level, len(blocks)) == (e['resolution'], e['octree_level'], CP.B), name

@@ -146,6 +146,22 @@ def test_committed_stream_decodes_to_its_recorded_points(golden, checkpoints, tm
         assert np.array_equal(got, CP.rows(CP.cloud_of(res)))
 
 
+@pytest.mark.parametrize('name', list(CP.STREAMS))
+def test_todays_encoder_writes_the_committed_stream(golden, checkpoints, tmp_path, name):
+    """The encoder CLI's own entry point on the cloud and flags of the listing writes the committed file again, byte for byte: tag, container,
+    every string of every layer (plain, occ1, cnt1 by a scale and by the count search, qs1 by a step and by a rate target)."""
+    from pcc_geo_cnn_v2_amd.utils import pc_io
+    family = golden['family']
+    entry = CP.load_listing(family)['streams'][name]
+    cfg, res, prec, coder, lossless = CP.STREAMS[name]
+    assert entry.get('flags') == CP.STREAM_FLAGS.get(name)
+    src, out = str(tmp_path / 'in.ply'), str(tmp_path / 'out.bin')
+    pc_io.write_df(src, pc_io.pa_to_df(CP.cloud_of(res)))
+    CP.cli_encode(name, checkpoints(cfg), src, out, str(tmp_path / 'enc.ply'))
+    with open(out, 'rb') as a, open(os.path.join(CP.streams_dir(family), entry['file']), 'rb') as b:
+        assert a.read() == b.read(), f'{name}: today\'s encoder writes another file than the committed one'
+
+
 def test_stream_of_another_kernel_family_is_refused(golden, checkpoints, tmp_path):
     """The same payload under the tag of the family before this one: refused with the "codec numerics" error, nothing written.  After
     a bump of PCC_KERNEL_FAMILY the directory of the old family stays in the tree and takes the place of this retagged copy."""

@@ -194,17 +194,17 @@ def test_cli_refuses_at_argument_time():
     base = ['--input_files', 'a.ply', '--checkpoint_dir', 'x', '--model_config', 'c3p', '--input_normals', 'a.n.ply']
     parse = lambda *extra: CO.build_parser().parse_args(base + list(extra))
     two = ['--output_files', 'o1', 'o2', '--opt_metrics', 'd1_hausdorff', 'd2_hausdorff']
-    CO.check_hausdorff_metrics(parse(*two, '--d2_search', 'gpu'), 1)
-    CO.check_hausdorff_metrics(parse('--output_files', 'o1', '--opt_metrics', 'd1_hausdorff'), 1)
-    CO.check_hausdorff_metrics(parse(*two, '--fixed_threshold'), 1)              # no search runs
+    CO.check_encode_options(parse(*two, '--d2_search', 'gpu'), 1)
+    CO.check_encode_options(parse('--output_files', 'o1', '--opt_metrics', 'd1_hausdorff'), 1)
+    CO.check_encode_options(parse(*two, '--fixed_threshold'), 1)              # no search runs
     with pytest.raises(AssertionError, match=r'--opt_metrics: opt metric d2_hausdorff.*--d2_search gpu'):
-        CO.check_hausdorff_metrics(parse(*two), 1)
+        CO.check_encode_options(parse(*two), 1)
     with pytest.raises(AssertionError, match=r'--d2_search gpu'):
-        CO.check_hausdorff_metrics(parse(*two, '--d2_search', 'kdtree'), 1)
+        CO.check_encode_options(parse(*two, '--d2_search', 'kdtree'), 1)
     with pytest.raises(AssertionError, match=r'--opt_metrics: opt metric d1_hausdorff.*--search_ties mean'):
-        CO.check_hausdorff_metrics(parse(*two, '--d2_search', 'gpu', '--search_ties', 'mean'), 1)
+        CO.check_encode_options(parse(*two, '--d2_search', 'gpu', '--search_ties', 'mean'), 1)
     with pytest.raises(AssertionError, match=r'world size 2.*--gpus 1'):
-        CO.check_hausdorff_metrics(parse('--output_files', 'o1', '--opt_metrics', 'd1_hausdorff'), 2)
+        CO.check_encode_options(parse('--output_files', 'o1', '--opt_metrics', 'd1_hausdorff'), 2)
     help_text = CO.build_parser().format_help().replace('\n', ' ')
     help_text = re.sub(r'\s+', ' ', help_text)
     assert help_text.index("'d2_mse']") < help_text.index("'d1_hausdorff_AB'")      # the new names follow the existing ones

@@ -12,6 +12,7 @@ from pcc_geo_cnn_v2_amd import _lib as L
 from pcc_geo_cnn_v2_amd import model_syntax as MS
 from pcc_geo_cnn_v2_amd import model_types as MT
 from pcc_geo_cnn_v2_amd import ops
+from pcc_geo_cnn_v2_amd import stream_layers as SL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BASE = 'pcc_geo_cnn_v2_amd/k6/sw0000/fp32'
@@ -88,17 +89,20 @@ def test_container_round_trip_with_the_step_string_and_malformed_ones():
     assert (res, level, binstr.tolist()) == (128, 1, [1, 0, 1])
     assert [(tuple(s), t) for s, t in back] == [(tuple(s), t) for s, t in blocks]
     m = _model()
-    assert m._block_steps(back).tolist() == qs and m._block_steps(back).dtype == np.uint8
+    read = SL.layer_values('qs1', back, m.n_strings)
+    assert read == qs and all(type(q) is int for q in read) and np.array(read, np.uint8).tolist() == qs      # (one byte each: uint8 holds them)
     assert [MS.step_from_bytes(MS.step_to_bytes(q), 0) for q in range(64)] == list(range(64))
     for bad, match in [(b'', 'block 2.*0 bytes'), (b'\x10\x10', 'block 2.*2 bytes'), (bytes([64]), 'block 2.*64'), (bytes([255]), 'block 2.*255')]:
         broken = list(back)
         broken[2] = ((back[2][0][0], back[2][0][1], bad), back[2][1])
         with pytest.raises(RuntimeError, match=match):
-            m._block_steps(broken)
+            SL.layer_values('qs1', broken, m.n_strings)
+        with pytest.raises(RuntimeError, match=match):                          # ... which is how the decoder reads them, before a context is made
+            m.decompress_block_range(None, broken, [64, 64, 64], layers='step')
     with pytest.raises(RuntimeError, match='block 1.*2 strings'):
-        m._block_steps([back[0], (back[1][0][:2], 0)])
+        SL.layer_values('qs1', [back[0], (back[1][0][:2], 0)], m.n_strings)
     with pytest.raises(RuntimeError, match='hyperprior'):
-        _model('c1')._block_steps(back)
+        _model('c1').decompress_block_range(None, back, [64, 64, 64], layers='step')
     with pytest.raises(AssertionError, match='latent_step'):
         MS.step_to_bytes(64)
 
@@ -153,29 +157,32 @@ def test_cli_refuses_the_target_with_rans_or_a_step_and_bad_values(monkeypatch):
 
 def test_model_refuses_before_a_context_is_made(monkeypatch):
     from pcc_geo_cnn_v2_amd import sharding
-    assert MT.check_latent_step() is None
-    assert MT.check_latent_step(None, None, 1, 'fp16', 4, True, 1.0, (0.5, 2.0, 3), 'rans') is None            # off: nothing to refuse
-    assert MT.check_latent_step(16, n_blocks=3).tolist() == [16, 16, 16] and MT.check_latent_step(16, n_blocks=3).dtype == np.uint8
-    assert MT.check_latent_step([0, 16, 37], n_blocks=3).tolist() == [0, 16, 37]
-    assert MT.check_latent_step(None, 1.5) is None and MT.check_latent_step(16, entropy_coder='rans') is not None
+    def steps(latent_step=None, target_bpp=None, **kw):
+        return SL.plan_encode(latent_step=latent_step, target_bpp=target_bpp, **kw).steps
+    assert steps() is None
+    assert steps(None, None, version=1, precision='fp16', world=4, entropy_coder='rans') is None            # off: nothing to refuse
+    assert steps(None, None, entry='encode_block_range', version=1, precision='fp16', lossless=True, fixed_threshold=True, entropy_coder='rans') is None
+    assert steps(16, n_blocks=3).tolist() == [16, 16, 16] and steps(16, n_blocks=3).dtype == np.uint8
+    assert steps([0, 16, 37], n_blocks=3).tolist() == [0, 16, 37]
+    assert steps(None, 1.5) is None and steps(16, entropy_coder='rans') is not None
     for kw, match in [(dict(version=1), 'hyperprior'), (dict(precision='fp16'), '--precision fp16'), (dict(world=2), 'single-process'),
                       (dict(lossless=True), '--lossless'), (dict(count_scale=1.0), '--count_threshold'), (dict(count_search=(0.5, 2.0, 3)), '--count_search')]:
         with pytest.raises(AssertionError, match=f'latent_step.*{match}'):
-            MT.check_latent_step(16, **kw)
+            steps(16, **kw)
         with pytest.raises(AssertionError, match=f'target_bpp.*{match}'):
-            MT.check_latent_step(None, 1.0, **kw)
+            steps(None, 1.0, **kw)
     with pytest.raises(AssertionError, match='target_bpp.*--entropy_coder rans'):
-        MT.check_latent_step(None, 1.0, entropy_coder='rans')
+        steps(None, 1.0, entropy_coder='rans')
     with pytest.raises(AssertionError, match='--latent_step or --target_bpp'):
-        MT.check_latent_step(16, 1.0)
+        steps(16, 1.0)
     for bad in (64, -1, 1.5, [16, 64], [[16]], []):
         with pytest.raises(AssertionError, match='latent_step'):
-            MT.check_latent_step(bad, n_blocks=2)
+            steps(bad, n_blocks=2)
     with pytest.raises(AssertionError, match='3 ladder indexes for 2 blocks'):
-        MT.check_latent_step([1, 2, 3], n_blocks=2)
+        steps([1, 2, 3], n_blocks=2)
     for bad in (0, -1.0, np.inf, np.nan, 'x', True):
         with pytest.raises(AssertionError, match='target_bpp'):
-            MT.check_latent_step(None, bad)
+            steps(None, bad)
     # the model's own entry points refuse before a context is made: no GPU here, and sess = None would create the default one
     monkeypatch.setattr(ops, 'get_context', lambda *a, **k: pytest.fail('a context was asked for'))
     blocks = [np.zeros((4, 3), np.float32)]
@@ -226,7 +233,7 @@ def test_rate_point_record_carries_the_step_and_the_target(tmp_path):
     assert rec['target_bpp'] == 0.75 and rec['predicted_bytes'] == 77 and rec['container_bytes'] == len(payload)
     assert rec['d1_psnr'] == 40.5 and 'predictions' not in rec
     assert MS.read_gzip_tag(out) == tag and MS.stream_layers(MS.read_gzip_tag(out), BASE) == ('range', ('qs1',))
-    assert _model()._block_steps(MS.load_compressed_file(io.BytesIO(payload))[3]).tolist() == [21, 21]
+    assert SL.layer_values('qs1', MS.load_compressed_file(io.BytesIO(payload))[3], _model().n_strings) == [21, 21]
     # a plain step: no target keys; per-block steps: lists; no step: none of the keys
     info2 = dict(metrics={'d1_psnr': 40.5}, numerics_tag=tag, latent_step=[0, 37])
     CO._write_rate_point(out, None, [1], streams, info2, _parse(), blocks, [])

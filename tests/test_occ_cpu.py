@@ -140,11 +140,12 @@ def test_parsers_carry_the_flags_and_lossless_is_single_process():
     assert decompress_octree.build_parser().parse_args(common).base_only is False
     assert decompress_octree.build_parser().parse_args(common + ['--base_only']).base_only is True
     assert 'base' in compress_octree.build_parser().format_help().split('--dec_files')[2].split('--checkpoint_dir')[0]
-    compress_octree.check_lossless(False, 1)
-    compress_octree.check_lossless(False, 8)
-    compress_octree.check_lossless(True, 1)
+    parse = compress_octree.build_parser().parse_args
+    compress_octree.check_encode_options(parse(common), 1)
+    compress_octree.check_encode_options(parse(common), 8)
+    assert compress_octree.check_encode_options(parse(common + ['--lossless']), 1).layers == ('occ1',)
     with pytest.raises(AssertionError, match='single-process'):
-        compress_octree.check_lossless(True, 2)
+        compress_octree.check_encode_options(parse(common + ['--lossless']), 2)
 
 
 def test_model_keyword():

@@ -8,6 +8,7 @@ import pytest
 import _topk_ref as T
 from pcc_geo_cnn_v2_amd import _lib as L
 from pcc_geo_cnn_v2_amd import model_syntax as MS
+from pcc_geo_cnn_v2_amd import stream_layers as SL
 
 BASE = 'pcc_geo_cnn_v2_amd/abi4/fp32/default'
 
@@ -55,7 +56,7 @@ def test_stream_tag_names_the_count_layer_and_refuses_both_layers():
         MS.stream_tag(BASE, 'range', lossless=True, count=True)
     with pytest.raises(RuntimeError):
         MS.split_stream_tag(BASE + '/cnt2')
-    assert MS.LAYER_SUFFIX['cnt1'] == 'cnt1' and MS.LAYER_SUFFIX['occ1'] == 'occ1'
+    assert SL.BY_NAME['cnt1'].name == 'cnt1' and SL.BY_NAME['occ1'].name == 'occ1' and [layer.name for layer in SL.LAYERS] == ['qs1', 'occ1', 'cnt1']
 
 
 def test_container_roundtrips_blocks_with_the_count_string():
@@ -70,7 +71,10 @@ def test_container_roundtrips_blocks_with_the_count_string():
 
 
 def test_count_arithmetic_matches_hand_worked_values():
-    from pcc_geo_cnn_v2_amd.model_types import block_count, check_count_scale
+    from pcc_geo_cnn_v2_amd.model_types import block_count
+
+    def check_count_scale(count_scale, fixed_threshold, lossless, world=1, entry='compress_blocks'):
+        SL.plan_encode(count_scale=count_scale, fixed_threshold=fixed_threshold, lossless=lossless, world=world, entry=entry)
     n = 64 ** 3
     table = [  # (rho, N, n, k)
         (1.0, 0, n, 0), (1.0, 1, n, 1), (1.0, 4321, n, 4321), (1.0, n, n, n),
@@ -81,7 +85,7 @@ def test_count_arithmetic_matches_hand_worked_values():
     for rho, N, nv, k in table:
         assert block_count(N, rho, nv) == k, (rho, N, nv)
         assert isinstance(block_count(N, rho, nv), int)
-    check_count_scale(None, True, True, 8)
+    check_count_scale(None, True, True, 8, entry='encode_block_range')      # off: its rules refuse nothing
     check_count_scale(0.5, False, False)
     for bad in (0.0, -1.0, float('nan'), float('inf'), '1.0'):
         with pytest.raises(AssertionError, match='count_scale'):
