@@ -328,7 +328,8 @@ __global__ void __launch_bounds__((Cout1M<T>::NT)) conv_cout1_mfma_kernel(ConvAr
     const float bias = (a.flags & PCC_CONV_BIAS) ? a.bias[0] : 0.f;
     const size_t out_plane = (size_t)a.OH * a.OW;
     float* ob = a.out + ((size_t)n * a.OD * out_plane + (size_t)(y0 + oy) * a.OW + x0 + ox) * a.ocs + a.oco;
-    const float* rb = (a.flags & PCC_CONV_ADD) ? a.res + (size_t)n * a.OD * out_plane + (size_t)(y0 + oy) * a.OW + x0 + ox : nullptr;
+    // (a column past H x W has no residual either: on the last plane of the last image its row would lie behind the end of the tensor)
+    const float* rb = ((a.flags & PCC_CONV_ADD) && col_ok) ? a.res + (size_t)n * a.OD * out_plane + (size_t)(y0 + oy) * a.OW + x0 + ox : nullptr;
 
     float thr_n = 0.f;
     unsigned short* mrow = nullptr;        // this lane's row of the bit mask (meaningful on the first lane of each T-lane group)

@@ -41,28 +41,31 @@ def geom_id(g):
 IDS = [geom_id(g) for g in GEOMS]
 
 
-@functools.lru_cache(maxsize=None)
-def _inputs(i):
-    g = GEOMS[i]
+def make_inputs(g, seed):
+    """the inputs of one geometry dict (family, case, shape, cout, transposed, res; 'stride' where the family name does not say it); also the
+    generator of the dense cases of the three-piece bf16 kernels (tests/_impulse_cases.py), which add 'tiny_60': block 0 scaled by 2^-60"""
     N, D, H, W, C = g['shape']
     case, cout = g['case'], g['cout']
-    rng = np.random.default_rng(1000 + i)
+    rng = np.random.default_rng(seed)
     x = rng.standard_normal((N, D, H, W, C)).astype(np.float32)
     b0 = np.maximum(x[0], 0)                                   # ReLU-sparse: about half zeros
     hot = np.zeros((D, H, W), bool)
     z0 = min(HOT_Z, D - 1)
     if case.startswith('hot_voxel'):
         R = int(case.rsplit('_', 1)[1])
-        b0[z0, 15:17, 15:17, :] = (np.abs(x[0, z0, 15:17, 15:17, :]) + np.float32(0.5)) * np.float32(2.0 ** R)
-        hot[z0, 15:17, 15:17] = True
+        py, px = (15 if H >= 16 else H // 2 - 1), (15 if W >= 16 else W // 2 - 1)      # grids below 16: the middle 2 x 2 patch
+        b0[z0, py:py + 2, px:px + 2, :] = (np.abs(x[0, z0, py:py + 2, px:px + 2, :]) + np.float32(0.5)) * np.float32(2.0 ** R)
+        hot[z0, py:py + 2, px:px + 2] = True
     elif case.startswith('hot_channel'):
         b0[..., 3] *= np.float32(2.0 ** int(case.rsplit('_', 1)[1]))
     elif case == 'sparse_bias':
         b0[rng.random(b0.shape) < 0.8] = 0                     # 50 % x 20 % survive: 90 % zeros
     elif case == 'tiny_block':
         b0 = b0 * np.float32(2.0 ** -100)
+    elif case == 'tiny_60':
+        b0 = b0 * np.float32(2.0 ** -60)
     x[0] = b0
-    stride = 2 if g['family'] == 'tr2m' else 1
+    stride = g.get('stride', 2 if g['family'] == 'tr2m' else 1)
     wshape = (3, 3, 3, cout, C) if g['transposed'] else (3, 3, 3, C, cout)
     fan = 27 * C / (8 if stride == 2 else 1)
     w = (rng.standard_normal(wshape) / np.sqrt(fan)).astype(np.float32)
@@ -72,16 +75,23 @@ def _inputs(i):
     if case == 'sparse_bias':
         bias = rng.uniform(0.5, 1.5, cout).astype(np.float32)
         relu = True
-    elif case == 'tiny_block':
+    elif case in ('tiny_block', 'tiny_60'):
         bias = rng.uniform(-1, 1, cout).astype(np.float32)
     oshape = (N, D * stride, H * stride, W * stride, cout)
     res = rng.standard_normal(oshape).astype(np.float32) if g['res'] else None
     if res is not None and case == 'tiny_block':
         res[0] *= np.float32(2.0 ** -100)
+    if res is not None and case == 'tiny_60':
+        res[0] *= np.float32(2.0 ** -60)
     for a in (x, w, bias, res):
         if a is not None:
             a.setflags(write=False)
     return dict(g, x=x, w=w, bias=bias, relu=relu, res=res, stride=stride, hot=hot)
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(i):
+    return make_inputs(GEOMS[i], 1000 + i)
 
 
 def inputs(i):
