@@ -42,13 +42,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg)
     auto ldsr = [&](unsigned off) -> f32x4 { return *reinterpret_cast<const f32x4*>(smem + off); };
     auto ldsw = [&](unsigned off, const f32x4& v) { *reinterpret_cast<f32x4*>(smem + off) = v; };
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int cog = wg % a.nco; wg /= a.nco;       // cout group: neighbours in the grid share their input planes in L2
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const WinoTile wt = wino_tile(a, nwg);
+    const int cog = wt.cog, n = wt.n, X0 = wt.X0, Y0 = wt.Y0, zb = wt.zb;
     const int nsteps = a.zlen + 2;             // input planes zb-1 .. zb+zlen
     const size_t HW = (size_t)a.H * a.W;
     const unsigned HWI = (unsigned)(HW * a.ics * 4), HWR = (unsigned)(HW * a.rcs * 4);      // bytes per z-plane
@@ -169,7 +164,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg)
         for (int j = 0; j < 12; ++j) {
             const int dz = 2 - (j >> 2), py = j & 3;
             const int as = (PH + 2 - dz) % 3;
-            const bool active = MODE == M_ALL || (MODE == M_S0 && dz == 0) || ((MODE == M_S1 || MODE == M_S1O) && dz <= 1);
+            const bool active = row_active(MODE, dz);
             // (1) U fragments of the next row (wraps to the first active row of the next step: step 1 starts at its dz = 1 rows)
             if (active) {
                 const int jn = (j == 11 && MODE == M_S0) ? 4 : (j + 1) % 12, dzn = 2 - (jn >> 2), pyn = jn & 3;
@@ -219,6 +214,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg)
             if (j >= 5 && j <= 8) {
                 // A^T along x on row r of the finished plane, accumulate A^T along y
                 const int r = j - 5;
+                // (reduce_at_row and keep_store_data of wino_common.h are written out in this kernel: as calls they change the scalar
+                // register assignment of the <*, false, false> instantiations, profiles/wino_skeleton_isa.md)
                 const f32x4 m0 = acc_read(acc[AF][r * 4 + 0]), m1 = acc_read(acc[AF][r * 4 + 1]), m2 = acc_read(acc[AF][r * 4 + 2]), m3 = acc_read(acc[AF][r * 4 + 3]);
                 const f32x4 r0 = add4(add4(m0, m1), m2), r1 = sub4(sub4(m1, m2), m3);
                 if (r == 0) { S[0][0] = r0; S[0][1] = r1; }
@@ -227,29 +224,13 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg)
                 else { S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
             }
             if (j == 8 || j == 9) {
-                // epilogue of output row oy = j - 8 (complete after reduction row 2 resp. 3): ReLU, residual, clip, float4 stores
-                // (the bias is already inside, see the dz = 0 rows)
+                // epilogue of output row oy = j - 8 (complete after reduction row 2 resp. 3), float4 stores
 #pragma unroll
-                for (int q = 2 * (j - 8); q < 2 * (j - 8) + 2; ++q) {
-                    f32x4 o = S[q >> 1][q & 1];
-                    if (PRE) o = add4(o, prev[q]);
-                    // one v_maximum3_f32 per element: fmaxf on the result of the inline-asm packed add costs a second v_max (NaN quieting)
-                    if (RELU) o = __builtin_elementwise_maximum(o, zero4);
-                    o = add4(o, resv[q]);     // zeros without PCC_CONV_ADD (zero-sized buffer)
-                    if (CLIP) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) o[c] = fminf(fmaxf(o[c], 0.f), 1.f);
-                    }
-                    ost[q] = o;
-                }
-                // gfx950: a buffer_store_dwordx4 reads its data registers late; a VALU write to them in the next issue
-                // slots corrupts the last dword of the last lanes (seen as out[q].w <- out[q+1].w).  The compiler only
-                // guards the immediate-soffset form with one wait state, so the data registers are kept live (and
-                // therefore unwritten) until the next slot.
+                for (int q = 2 * (j - 8); q < 2 * (j - 8) + 2; ++q) ost[q] = epilogue_voxel<RELU, CLIP, PRE>(S[q >> 1][q & 1], prev[q], resv[q]);
 #pragma unroll
                 for (int q = 2 * (j - 8); q < 2 * (j - 8) + 2; ++q) buf_store4(rout, ost[q], ovo[q], 0);
             }
-            if (j == 9 || j == 10) {
+            if (j == 9 || j == 10) {      // the store data registers stay unwritten for one more slot (keep_store_data)
 #pragma unroll
                 for (int q = 2 * (j - 9); q < 2 * (j - 9) + 2; ++q) asm volatile("" ::"v"(ost[q]));
             }
@@ -267,32 +248,24 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_kernel(WinoArgs a, int nwg)
             __syncthreads();     // plane s+2 is published; nobody still reads plane s+1
         }
     };
-    using P0 = std::integral_constant<int, 0>;
-    using P1 = std::integral_constant<int, 1>;
-    using P2 = std::integral_constant<int, 2>;
-    using MAll = std::integral_constant<int, M_ALL>;
-    using MFin = std::integral_constant<int, M_FIN>;
-
-    if (first_zero) step(P1{}, 1, std::integral_constant<int, M_S1O>{});
+    if (first_zero) step(PH1{}, 1, MS1O{});
     else {
-        step(P0{}, 0, std::integral_constant<int, M_S0>{});
-        step(P1{}, 1, std::integral_constant<int, M_S1>{});
+        step(PH0{}, 0, MS0{});
+        step(PH1{}, 1, MS1{});
     }
     const int nloop = nsteps - (last_zero ? 1 : 0);
     for (int s = 2; s < nloop; s += 3) {
-        step(P2{}, s, MAll{});
-        if (s + 1 < nloop) step(P0{}, s + 1, MAll{});
-        if (s + 2 < nloop) step(P1{}, s + 2, MAll{});
+        step(PH2{}, s, MAll{});
+        if (s + 1 < nloop) step(PH0{}, s + 1, MAll{});
+        if (s + 2 < nloop) step(PH1{}, s + 2, MAll{});
     }
     if (last_zero) {
         const int sl = nsteps - 1, ph = sl % 3;
-        if (ph == 0) step(P0{}, sl, MFin{});
-        else if (ph == 1) step(P1{}, sl, MFin{});
-        else step(P2{}, sl, MFin{});
+        if (ph == 0) step(PH0{}, sl, MFin{});
+        else if (ph == 1) step(PH1{}, sl, MFin{});
+        else step(PH2{}, sl, MFin{});
     }
 }
-
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Cin = Cout = 16 G, G in {2, 4}: the cin groups INSIDE the z march (round 3).
@@ -325,13 +298,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
     const int t = lane & 15, g = lane >> 4;
     auto ldsr = [&](unsigned off) -> f32x4 { return *reinterpret_cast<const f32x4*>(smem + off); };
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int cog = wg % a.nco; wg /= a.nco;
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const WinoTile wt = wino_tile(a, nwg);
+    const int cog = wt.cog, n = wt.n, X0 = wt.X0, Y0 = wt.Y0, zb = wt.zb;
     const int nsteps = a.zlen + 2;
     const size_t HW = (size_t)a.H * a.W;
     const unsigned HWI = (unsigned)(HW * a.ics * 4), HWR = (unsigned)(HW * a.rcs * 4), HWO = (unsigned)(HW * a.ocs * 4);
@@ -438,25 +406,19 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
     // one micro-step.  PH = s mod 3 (accumulator rotation), FIRST / FIN = first / last cin group of the plane: all compile
     // time -- wave-uniform run-time branches around the slot pieces were measured at ~1000 cycles per micro-step (12 % of it:
     // every taken branch restarts the instruction fetch), more than the epilogue they skip.
-    // The two head planes of a slab run only the MFMA rows that feed ITS output planes (ROWS below): plane 0 (zb - 1) its dz = 0 rows,
-    // plane 1 its dz = 1 and dz = 0 rows (the rest of the step -- staging, input transform -- is unchanged): 10 -> 9 plane-equivalents
-    // per 8-plane slab (64 -> 64 @16^3), 34 -> 33 (32 -> 32 @32^3).  The mirror image for the plane behind the slab (ROWS 3 / 5) is a
-    // tail peeled off the loop, one variant per accumulator phase; earlier attempts that kept it inside the loop structure made the
-    // allocator spill 90 - 780 registers, and a run-time row mask cost the 32-channel layer more (+7 % wave cycles, 12 scalar branches
-    // per micro-step) than the plane saves.
-    auto step = [&](auto ph_tag, auto first_tag, auto fin_tag, auto rows_tag) __attribute__((always_inline)) {
+    // The two head planes of a slab run only the MFMA rows that feed ITS output planes (MODE, wino_common.h: M_S0, then M_S1 / M_S1O;
+    // the rest of the step -- staging, input transform -- is unchanged): 10 -> 9 plane-equivalents per 8-plane slab (64 -> 64 @16^3),
+    // 34 -> 33 (32 -> 32 @32^3).  The mirror image for the plane behind the slab (M_FIN: only its LAST micro-step runs, no input work
+    // either / M_TAIL) is a tail peeled off the loop, one variant per accumulator phase; earlier attempts that kept it inside the loop
+    // structure made the allocator spill 90 - 780 registers, and a run-time row mask cost the 32-channel layer more (+7 % wave cycles,
+    // 12 scalar branches per micro-step) than the plane saves.
+    auto step = [&](auto ph_tag, auto first_tag, auto fin_tag, auto mode_tag) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_tag)::value;
         constexpr int AF = PH;
         constexpr bool first = decltype(first_tag)::value, fin = decltype(fin_tag)::value;
-        // ROWS: 0 = all 12 MFMA rows; 1 = plane 0 of the slab (zb - 1): dz = 0 rows only; 2 = plane 1: dz = 1 and dz = 0 rows (its
-        // dz = 2 rows would finish output plane zb - 1, which belongs to the slab below and is never stored); 3 = the plane behind a
-        // slab that ends at z = D (zero padding): no matrix work, no input work -- only its LAST micro-step runs, to reduce and store
-        // output plane D - 1
-        constexpr int ROWS = decltype(rows_tag)::value;
-        // 4 = plane 1 of a slab that starts at z = 0 (plane 0 skipped): as 2, and its dz = 1 rows OPEN their accumulators
-        // 5 = the plane behind a slab INSIDE the volume (zb + zlen): only its dz = 2 rows feed this slab (output plane zb + zlen - 1)
-        constexpr int J_OWN = ROWS == 1 ? 8 : (ROWS == 2 || ROWS == 4) ? 4 : 0;  // first active row of this plane's micro-steps
-        constexpr int J_FIRST_NEXT = !fin ? J_OWN : ROWS == 1 ? 4 : 0;           // ... of the NEXT micro-step (plane 0 -> plane 1 -> full planes)
+        constexpr int MODE = decltype(mode_tag)::value;
+        // first active row of the NEXT micro-step (the same plane's next cin group, or the first one of the next plane)
+        constexpr int J_FIRST_NEXT = first_row(fin ? next_mode(MODE) : MODE);
         const bool zo_ok = s >= 2;
         const __amdgpu_buffer_rsrc_t rres = make_rsrc((const void*)(zo_ok ? res_pl : (unsigned long long)res_n), zo_ok && has_res && fin ? HWR : 0u);
         const __amdgpu_buffer_rsrc_t rout = make_rsrc((const void*)(zo_ok ? out_pl : (unsigned long long)out_n), zo_ok && fin ? HWO : 0u);
@@ -476,11 +438,11 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
             //     MFMAs of slots 4..8 that could cover it (in the one-group kernel every slot has one) -- at 16 registers for U.
             //     The dz = 0 rows open a new output plane in the FIRST cin group (from 0; point (1,1) enters all four outputs
             //     with weight +1 and carries the bias) and continue it in the others.
-            const bool active = ROWS == 0 || (ROWS == 1 && dz == 0) || ((ROWS == 2 || ROWS == 4) && dz <= 1) || (ROWS == 5 && dz == 2);
-            constexpr int J_LAST = ROWS == 5 ? 3 : 11;       // last active row: its U prefetch is the next micro-step's first row
+            const bool active = row_active(MODE, dz);
+            constexpr int J_LAST = MODE == M_TAIL ? 3 : 11;  // last active row: its U prefetch is the next micro-step's first row
             const int jn = j == J_LAST ? J_FIRST_NEXT : j + 1, dzn = 2 - (jn >> 2), pyn = jn & 3;
             const unsigned urow = (j == J_LAST ? (ua ^ UTOG) : ua) + (unsigned)((dzn * 4 + pyn) * 4 * 1024);
-            const bool INIT = first && (dz == 0 || (ROWS == 4 && dz == 1));      // (folds: first is a constant, dz follows from the unrolled j)
+            const bool INIT = first && (dz == 0 || (MODE == M_S1O && dz == 1));     // (folds: first is a constant, dz follows from the unrolled j)
             auto half = [&](auto h_tag) __attribute__((always_inline)) {
                 constexpr int PX0 = decltype(h_tag)::value * 2;
 #pragma unroll
@@ -511,7 +473,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
             }
             __builtin_amdgcn_sched_barrier(0);
             // (3) everything else, as one block behind the MFMAs of the slot
-            if (ROWS == 3) {
+            if (MODE == M_FIN) {
             } else if (j == 0) transform_y_row(Vc, Vn, 3);
             else if (j == 1) {
                 stage_tile(wr_off, s2, c2, tile_pl);
@@ -519,7 +481,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
                 for (int i = 0; i < 16; ++i) Vn[i] = ldsr(ra[i]);
             } else if (j == 2) transform_x_rows(Vn, 0, 2);
             else if (j == 3) transform_x_rows(Vn, 2, 4);
-            if (STREAM && ROWS != 3) {        // U[cn] -> the idle buffer: pieces 0..11 of this wave in slots 0, 2..4
+            if (STREAM && MODE != M_FIN) {        // U[cn] -> the idle buffer: pieces 0..11 of this wave in slots 0, 2..4
                 // (all 12 pieces are on their way by slot 4: the last ones then have 8 slots to land before the closing barrier waits for them)
                 if (j == 0) { stage_u(ub_next, cn, 0); stage_u(ub_next, cn, 1); stage_u(ub_next, cn, 2); }
                 else if (j >= 2 && j <= 4) { stage_u(ub_next, cn, 3 * j - 3); stage_u(ub_next, cn, 3 * j - 2); stage_u(ub_next, cn, 3 * j - 1); }
@@ -532,28 +494,17 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
                 if (j >= 5 && j <= 8) {
                     const int r = j - 5;
                     const f32x4 m0 = acc_read(acc[AF][r * 4 + 0]), m1 = acc_read(acc[AF][r * 4 + 1]), m2 = acc_read(acc[AF][r * 4 + 2]), m3 = acc_read(acc[AF][r * 4 + 3]);
-                    const f32x4 r0 = add4(add4(m0, m1), m2), r1 = sub4(sub4(m1, m2), m3);
-                    if (r == 0) { S[0][0] = r0; S[0][1] = r1; }
-                    else if (r == 1) { S[0][0] = add4(S[0][0], r0); S[0][1] = add4(S[0][1], r1); S[1][0] = r0; S[1][1] = r1; }
-                    else if (r == 2) { S[0][0] = add4(S[0][0], r0); S[0][1] = add4(S[0][1], r1); S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
-                    else { S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
+                    reduce_at_row(S, r, m0, m1, m2, m3);
                 }
                 if (j == 8 || j == 9) {
 #pragma unroll
-                    for (int q = 2 * (j - 8); q < 2 * (j - 8) + 2; ++q) {
-                        f32x4 o = S[q >> 1][q & 1];
-                        if (RELU) o = __builtin_elementwise_maximum(o, zero4);
-                        ost[q] = add4(o, resv[q]);     // zeros without PCC_CONV_ADD (zero-sized buffer)
-                    }
+                    for (int q = 2 * (j - 8); q < 2 * (j - 8) + 2; ++q) ost[q] = epilogue_voxel<RELU, false, false>(S[q >> 1][q & 1], zero4, resv[q]);
 #pragma unroll
                     for (int q = 2 * (j - 8); q < 2 * (j - 8) + 2; ++q) buf_store4(rout, ost[q], ovo[q], 0);
                 }
-                if (j == 9 || j == 10) {      // store data registers stay unwritten for one more slot (see conv16_wino_kernel)
-#pragma unroll
-                    for (int q = 2 * (j - 9); q < 2 * (j - 9) + 2; ++q) asm volatile("" ::"v"(ost[q]));
-                }
+                if (j == 9 || j == 10) keep_store_data(ost, j - 9);
             }
-            if (ROWS == 3) {
+            if (MODE == M_FIN) {
             } else if (j == 9) transform_y_row(Vc, Vn, 0);
             else if (j == 10) {
                 transform_y_row(Vc, Vn, 1);
@@ -568,7 +519,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
         }
         // tile m+2 (slot 1) and the U pieces (slots 0..7) must have landed before the barrier publishes them; the only younger
         // memory operations are the four stores of a final micro-step
-        if (ROWS == 3) return;                            // (the last thing this workgroup does)
+        if (MODE == M_FIN) return;                            // (the last thing this workgroup does)
         if (fin) __builtin_amdgcn_s_waitcnt(0x0F74);      // vmcnt(4)
         else __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0)
         __syncthreads();
@@ -590,19 +541,18 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
     };
 
     // one input plane = G micro-steps: first, (G - 2 middle ones: one body, looped), last
-    auto plane = [&](auto ph_tag, auto rows_tag) __attribute__((always_inline)) {
-        step(ph_tag, std::true_type{}, std::false_type{}, rows_tag);
+    auto plane = [&](auto ph_tag, auto mode_tag) __attribute__((always_inline)) {
+        step(ph_tag, std::true_type{}, std::false_type{}, mode_tag);
         if (G > 2) {
 #pragma nounroll
-            for (int k = 0; k < G - 2; ++k) step(ph_tag, std::false_type{}, std::false_type{}, rows_tag);
+            for (int k = 0; k < G - 2; ++k) step(ph_tag, std::false_type{}, std::false_type{}, mode_tag);
         }
-        step(ph_tag, std::false_type{}, std::true_type{}, rows_tag);
+        step(ph_tag, std::false_type{}, std::true_type{}, mode_tag);
     };
-    using R0 = std::integral_constant<int, 0>;
-    if (first_zero) plane(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});      // plane s = 1 opens everything
+    if (first_zero) plane(PH1{}, MS1O{});      // plane s = 1 opens everything
     else {
-        plane(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});      // plane s = 0 (z = zb - 1): dz = 0 rows only
-        plane(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});      // plane s = 1: dz = 1, 0 rows
+        plane(PH0{}, MS0{});      // plane s = 0 (z = zb - 1): dz = 0 rows only
+        plane(PH1{}, MS1{});      // plane s = 1: dz = 1, 0 rows
     }
     // The plane behind the slab is peeled off the loop: behind the volume (z = D, zero padding) only the reduction + store of output
     // plane D - 1 is left of it; inside the volume only its dz = 2 rows feed this slab.  Wave-uniform, decided outside the MFMA stream.
@@ -610,21 +560,19 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_cin_kernel(WinoArgs a, int 
     const int nloop = nsteps - 1;
 #pragma nounroll
     for (int sp = 2; sp < nloop; sp += 3) {                                          // planes 2 .. nloop - 1, phase = s mod 3
-        plane(std::integral_constant<int, 2>{}, R0{});
-        if (sp + 1 < nloop) plane(std::integral_constant<int, 0>{}, R0{});
-        if (sp + 2 < nloop) plane(std::integral_constant<int, 1>{}, R0{});
+        plane(PH2{}, MAll{});
+        if (sp + 1 < nloop) plane(PH0{}, MAll{});
+        if (sp + 2 < nloop) plane(PH1{}, MAll{});
     }
-    using R3 = std::integral_constant<int, 3>;
-    using R5 = std::integral_constant<int, 5>;
     const int ph = (nsteps - 1) % 3;
     if (last_zero) {
-        if (ph == 0) step(std::integral_constant<int, 0>{}, std::false_type{}, std::true_type{}, R3{});
-        else if (ph == 1) step(std::integral_constant<int, 1>{}, std::false_type{}, std::true_type{}, R3{});
-        else step(std::integral_constant<int, 2>{}, std::false_type{}, std::true_type{}, R3{});
+        if (ph == 0) step(PH0{}, std::false_type{}, std::true_type{}, MFin{});
+        else if (ph == 1) step(PH1{}, std::false_type{}, std::true_type{}, MFin{});
+        else step(PH2{}, std::false_type{}, std::true_type{}, MFin{});
     } else {
-        if (ph == 0) plane(std::integral_constant<int, 0>{}, R5{});
-        else if (ph == 1) plane(std::integral_constant<int, 1>{}, R5{});
-        else plane(std::integral_constant<int, 2>{}, R5{});
+        if (ph == 0) plane(PH0{}, MTail{});
+        else if (ph == 1) plane(PH1{}, MTail{});
+        else plane(PH2{}, MTail{});
     }
 }
 
@@ -648,21 +596,9 @@ bool pcc_wino_eligible(const pcc_conv_desc* d) {
 int pcc_conv_wino(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* u_packed, const float* bias,
                   const float* residual, float* out, hipStream_t st) {
     PCC_REQUIRE(pcc_wino_eligible(d), "pcc_conv_wino: shape not covered");
-    WinoArgs a;
-    a.in = in; a.bias = bias; a.res = residual; a.out = out;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.nty = d->H / 16; a.ntx = d->W / 16;
-    a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    a.oco = d->out_coffset;
     const int G = d->Cin / 16;
-    a.nco = G; a.ics = d->Cin; a.rcs = d->Cout;
-    // split z so that every CU gets a workgroup (each split pays the 48 KB U load and two halo planes)
-    const int base = d->N * a.nty * a.ntx * G;
-    int zs = 1;
-    const int min_zlen = G >= 2 ? 4 : 8;      // (multi-group layers: 32 -> 32 @16^3 x 32 gets 256 workgroups of 4 planes: 41 us; 128 of 8: 69 us)
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= min_zlen) zs *= 2;
-    a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = base * zs;
+    WinoArgs a = wino_fill_args(ctx, d, G, in, bias, residual, out);
+    const int nwg = wino_num_wg(a);
     typedef void (*kern_t)(WinoArgs, int);
     static const kern_t kerns[8] = {conv16_wino_kernel<false, false, false>, conv16_wino_kernel<true, false, false>,
                                     conv16_wino_kernel<false, true, false>,  conv16_wino_kernel<true, true, false>,
@@ -676,14 +612,9 @@ int pcc_conv_wino(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const f
     if ((G == 2 || G == 4) && !(d->flags & PCC_CONV_CLIP01) && !per_group) {
         static const kern_t ck[4] = {conv16_wino_cin_kernel<false, 2>, conv16_wino_cin_kernel<true, 2>,
                                      conv16_wino_cin_kernel<false, 4>, conv16_wino_cin_kernel<true, 4>};
-        a.u = u_packed; a.ico = 0; a.ncig = G; a.flags = d->flags;
-        const kern_t ckern = ck[(G == 4 ? 2 : 0) + ((d->flags & PCC_CONV_RELU) ? 1 : 0)];
-        { const int rc = pcc_enable_big_lds((const void*)ckern, LDS_BYTES_CIN); if (rc != PCC_OK) return rc; }
-        hipLaunchKernelGGL(ckern, dim3((unsigned)nwg), dim3(NT), LDS_BYTES_CIN, st, a, nwg);
-        PCC_CHECK_HIP(hipGetLastError());
-        return PCC_OK;
+        a.u = u_packed; a.ncig = G;
+        return wino_launch(ck[(G == 4 ? 2 : 0) + ((d->flags & PCC_CONV_RELU) ? 1 : 0)], LDS_BYTES_CIN, nwg, st, a);
     }
-    a.ncig = 1;
     for (int ci = 0; ci < G; ++ci) {
         const bool last = ci == G - 1;
         a.u = u_packed + (size_t)ci * G * (U_BYTES / 4);
@@ -691,9 +622,7 @@ int pcc_conv_wino(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const f
         a.flags = last ? d->flags : 0;
         const bool relu = last && (d->flags & PCC_CONV_RELU), clip = last && (d->flags & PCC_CONV_CLIP01);
         const kern_t kern = kerns[(relu ? 1 : 0) + (clip ? 2 : 0) + (ci > 0 ? 4 : 0)];
-        { const int rc = pcc_enable_big_lds((const void*)kern, LDS_BYTES); if (rc != PCC_OK) return rc; }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), LDS_BYTES, st, a, nwg);
-        PCC_CHECK_HIP(hipGetLastError());
+        { const int rc = wino_launch(kern, LDS_BYTES, nwg, st, a); if (rc != PCC_OK) return rc; }
     }
     return PCC_OK;
 }

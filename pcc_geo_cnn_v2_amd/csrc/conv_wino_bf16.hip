@@ -64,12 +64,6 @@ __device__ __forceinline__ void dot2c_sub16(float (&Y)[16], unsigned p0, unsigne
         : "v"(p0), "v"(p1), "v"(p2), "v"(p3), "v"(p4), "v"(p5), "v"(p6), "v"(p7), "s"(0x0000bf80u), "s"(0xbf800000u));
 }
 
-// B^T along x on one patch row (4 voxels x 4 channels), in place
-__device__ __forceinline__ void transform_x_row(f32x4 (&P)[4]) {
-    const f32x4 d0 = P[0], d1 = P[1], d2 = P[2], d3 = P[3];
-    P[0] = sub4(d0, d2); P[1] = add4(d1, d2); P[2] = sub4(d2, d1); P[3] = sub4(d1, d3);
-}
-
 // Long-lived per-lane constants (addresses) are PARKED in AccVGPRs and read back right before their use: the 128 registers of
 // the V pieces leave the arch VGPRs no room for them (the register allocator otherwise spills into scratch).
 __device__ __forceinline__ unsigned park(unsigned v) {
@@ -102,13 +96,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     auto lds_abs = [&](unsigned addr) -> f32x4 { return *(lds_cf4)(unsigned long long)addr; };     // absolute LDS address
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int cog = wg % a.nco; wg /= a.nco;
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const WinoTile wt = wino_tile(a, nwg);
+    const int cog = wt.cog, n = wt.n, X0 = wt.X0, Y0 = wt.Y0, zb = wt.zb;
     const int nsteps = a.zlen + 2;             // input planes zb-1 .. zb+zlen
     const size_t HW = (size_t)a.H * a.W;
     const unsigned HWI = (unsigned)(HW * a.ics * 4), HWR = (unsigned)(HW * a.rcs * 4), HWO = (unsigned)(HW * a.ocs * 4);
@@ -155,7 +144,6 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     const int wx = wave & 1, wy = wave >> 1;
     const int TX = 4 * wx + (t & 3), TY = 4 * wy + (t >> 2);
     const unsigned pa0 = (unsigned)(64 * (36 * TY + TX) + 16 * (g + 2 * TY));       // patch (dy, dx) = (0, 0) of this lane in ring slot 0
-    auto pa_off = [](int dy, int dx) constexpr -> unsigned { return (unsigned)(64 * (18 * dy + 9 * (dx & 1) + (dx >> 1)) + (dy >= 2 ? 32 : 0)); };
     const unsigned ua = (unsigned)(U_BASE + lane * 16);
 
     // ---- epilogue addressing: lane writes couts 4g..4g+3 of the 2x2 voxels of its tile
@@ -194,14 +182,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     f32x4 resv[4], ost[4];
     // ---- pieces of the schedule.  V row r of a plane: Y = its fp32 values (yrow), then H = cvt(Y), Y -= H, M = cvt(Y), Y -= M,
     //      L = cvt(Y).  The cvts are single VALU ops the compiler sees (fillers between MFMAs); the subtractions are asm blocks.
-    auto yrow = [&](auto r_tag) __attribute__((always_inline)) {
-        constexpr int r = decltype(r_tag)::value;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            const f32x4 y = r == 0 ? sub4(P0[x], P2[x]) : r == 1 ? add4(P1[x], P2[x]) : r == 2 ? sub4(P2[x], P1[x]) : sub4(P1[x], P3[x]);
-            Y[4 * x + 0] = y[0]; Y[4 * x + 1] = y[1]; Y[4 * x + 2] = y[2]; Y[4 * x + 3] = y[3];
-        }
-    };
+    auto yrow = [&](auto r_tag) __attribute__((always_inline)) { transform_y_row_split<decltype(r_tag)::value>(Y, P0, P1, P2, P3); };
     // pair j = (point x = j >> 1, channel pair hf = j & 1) of row r: stage 0 = h (also into B2), 1 = m, 2 = l
     auto cvt_task = [&](auto r_tag, auto st_tag, auto j_tag) __attribute__((always_inline)) {
         constexpr int r = decltype(r_tag)::value, st = decltype(st_tag)::value, j = decltype(j_tag)::value;
@@ -218,15 +199,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
     };
     auto load_prow = [&](f32x4 (&P)[4], int dy, unsigned slot_off) __attribute__((always_inline)) {
 #pragma unroll
-        for (int x = 0; x < 4; ++x) P[x] = ldsr(pa0 + pa_off(dy, x) + slot_off);
+        for (int x = 0; x < 4; ++x) P[x] = ldsr(pa0 + (unsigned)patch_off_padded(dy, x) + slot_off);
     };
-    using R0 = std::integral_constant<int, 0>;
-    using R1 = std::integral_constant<int, 1>;
-    using R2 = std::integral_constant<int, 2>;
-    using R3 = std::integral_constant<int, 3>;
-    using ST0 = std::integral_constant<int, 0>;
-    using ST1 = std::integral_constant<int, 1>;
-    using ST2 = std::integral_constant<int, 2>;
     // a whole row at once (prologue only)
     auto split_row = [&](auto r_tag) __attribute__((always_inline)) {
         yrow(r_tag);
@@ -325,10 +299,10 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
                 }
                 if constexpr (!FIN) {
                     if constexpr (i < 8 && !(PCC_WB_PROBE & 32)) cvt_task(RS{}, STG{}, i_tag);
-                    if constexpr (q == 0 && i >= 8 && !(PCC_WB_PROBE & 512)) P2[i - 8] = lds_abs(pa_s + pa_off(2, i - 8) + slotN);
-                    if constexpr (q == 1 && i >= 8 && !(PCC_WB_PROBE & 512)) P0[i - 8] = lds_abs(pa_s + pa_off(0, i - 8) + slotN);
-                    if constexpr (q == 4 && i >= 8 && !(PCC_WB_PROBE & 512)) P1[i - 8] = lds_abs(pa_s + pa_off(1, i - 8) + slotN);
-                    if constexpr (q == 9 && i >= 8 && !(PCC_WB_PROBE & 512)) P3[i - 8] = lds_abs(pa_s + pa_off(3, i - 8) + slotN);
+                    if constexpr (q == 0 && i >= 8 && !(PCC_WB_PROBE & 512)) P2[i - 8] = lds_abs(pa_s + (unsigned)patch_off_padded(2, i - 8) + slotN);
+                    if constexpr (q == 1 && i >= 8 && !(PCC_WB_PROBE & 512)) P0[i - 8] = lds_abs(pa_s + (unsigned)patch_off_padded(0, i - 8) + slotN);
+                    if constexpr (q == 4 && i >= 8 && !(PCC_WB_PROBE & 512)) P1[i - 8] = lds_abs(pa_s + (unsigned)patch_off_padded(1, i - 8) + slotN);
+                    if constexpr (q == 9 && i >= 8 && !(PCC_WB_PROBE & 512)) P3[i - 8] = lds_abs(pa_s + (unsigned)patch_off_padded(3, i - 8) + slotN);
                     if constexpr (q == 3 && i >= 6 && !(PCC_WB_PROBE & 2))
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_ptr)(smem + slotW + (wave * 5 + i - 6) * 1024), 16, (int)unpark(rel_p[i - 6]), 0, 0, 0);
                 }
@@ -360,26 +334,13 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
                 // A^T along x on row r of the finished plane, accumulate A^T along y
                 constexpr int r = q / 3;
                 const f32x4 m0 = {Mr[0], Mr[1], Mr[2], Mr[3]}, m1 = {Mr[4], Mr[5], Mr[6], Mr[7]}, m2 = {Mr[8], Mr[9], Mr[10], Mr[11]}, m3 = {Mr[12], Mr[13], Mr[14], Mr[15]};
-                const f32x4 r0 = add4(add4(m0, m1), m2), r1 = sub4(sub4(m1, m2), m3);
-                if (r == 0) { S[0][0] = r0; S[0][1] = r1; }
-                else if (r == 1) { S[0][0] = add4(S[0][0], r0); S[0][1] = add4(S[0][1], r1); S[1][0] = r0; S[1][1] = r1; }
-                else if (r == 2) { S[0][0] = add4(S[0][0], r0); S[0][1] = add4(S[0][1], r1); S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
-                else { S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
+                reduce_at_row(S, r, m0, m1, m2, m3);
             }
             if constexpr ((q == 8 || q == 11) && !(PCC_WB_PROBE & (64 | 4))) {
-                // epilogue of output row oy (complete after reduction row 2 resp. 3): ReLU, residual, clip, float4 stores
+                // epilogue of output row oy (complete after reduction row 2 resp. 3), float4 stores
                 constexpr int oy = q == 8 ? 0 : 1;
 #pragma unroll
-                for (int v = 2 * oy; v < 2 * oy + 2; ++v) {
-                    f32x4 o = S[v >> 1][v & 1];
-                    if (RELU) o = __builtin_elementwise_maximum(o, zero4);
-                    o = add4(o, resv[v]);     // zeros without PCC_CONV_ADD (zero-sized buffer)
-                    if (CLIP) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) o[c] = fminf(fmaxf(o[c], 0.f), 1.f);
-                    }
-                    ost[v] = o;
-                }
+                for (int v = 2 * oy; v < 2 * oy + 2; ++v) ost[v] = epilogue_voxel<RELU, CLIP, false>(S[v >> 1][v & 1], zero4, resv[v]);
 #pragma unroll
                 for (int v = 2 * oy; v < 2 * oy + 2; ++v) buf_store4(rout, ost[v], ovo_s, oso[v]);
             }
@@ -387,9 +348,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
 #pragma unroll
                 for (int v = 2 * (q / 3); v < 2 * (q / 3) + 2; ++v) resv[v] = buf_load4(rres, rvo_s, rso[v]);
             }
-            // gfx950: a buffer_store_dwordx4 reads its data registers late (conv16_wino_kernel): keep them unwritten for one more slot
-            if constexpr (q == 9) { asm volatile("" ::"v"(ost[0])); asm volatile("" ::"v"(ost[1])); }
-            if constexpr (q == 0) { asm volatile("" ::"v"(ost[2])); asm volatile("" ::"v"(ost[3])); }
+            if constexpr (q == 9) keep_store_data(ost, 0);
+            if constexpr (q == 0) keep_store_data(ost, 1);
             __builtin_amdgcn_sched_barrier(0);
         });
         // the LDS-direct loads of plane s+2 (F(3)) must have landed before the barrier publishes them; younger: the residual loads of
@@ -399,32 +359,24 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_bf16_kernel(WinoArgs a, int
             __syncthreads();
         }
     };
-    using P0t = std::integral_constant<int, 0>;
-    using P1t = std::integral_constant<int, 1>;
-    using P2t = std::integral_constant<int, 2>;
-    using MAll = std::integral_constant<int, M_ALL>;
-    using MFin = std::integral_constant<int, M_FIN>;
-
-    if (first_zero) step(P1t{}, 1, std::integral_constant<int, M_S1O>{});
+    if (first_zero) step(PH1{}, 1, MS1O{});
     else {
-        step(P0t{}, 0, std::integral_constant<int, M_S0>{});
-        step(P1t{}, 1, std::integral_constant<int, M_S1>{});
+        step(PH0{}, 0, MS0{});
+        step(PH1{}, 1, MS1{});
     }
     const int nloop = nsteps - (last_zero ? 1 : 0);
     for (int s = 2; s < nloop; s += 3) {
-        step(P2t{}, s, MAll{});
-        if (s + 1 < nloop) step(P0t{}, s + 1, MAll{});
-        if (s + 2 < nloop) step(P1t{}, s + 2, MAll{});
+        step(PH2{}, s, MAll{});
+        if (s + 1 < nloop) step(PH0{}, s + 1, MAll{});
+        if (s + 2 < nloop) step(PH1{}, s + 2, MAll{});
     }
     if (last_zero) {
         const int sl = nsteps - 1, ph = sl % 3;
-        if (ph == 0) step(P0t{}, sl, MFin{});
-        else if (ph == 1) step(P1t{}, sl, MFin{});
-        else step(P2t{}, sl, MFin{});
+        if (ph == 0) step(PH0{}, sl, MFin{});
+        else if (ph == 1) step(PH1{}, sl, MFin{});
+        else step(PH2{}, sl, MFin{});
     }
 }
-
-
 
 }  // namespace pccwino
 
@@ -444,7 +396,7 @@ void pcc_wino_bf16_pack(int ngroups, const float* u_f32, float* out) {
                     const float x = u_f32[(((size_t)pair * 48 + row) * 64 + lane) * 4 + c];
                     bf16_split3(x, h[c], m[c], l[c]);
                 }
-                const int dz = row / 16, py = (row / 4) % 4, px = row % 4, orow = (3 * py + 2 - dz) * 4 + px;
+                const int orow = wino_row_slot(row);
                 unsigned short* a1 = o + ((((size_t)pair * 48 + orow) * 2 + 0) * 64 + lane) * 8;
                 unsigned short* a2 = o + ((((size_t)pair * 48 + orow) * 2 + 1) * 64 + lane) * 8;
                 for (int c = 0; c < 4; ++c) { a1[c] = h[c]; a1[4 + c] = m[c]; a2[c] = l[c]; a2[4 + c] = h[c]; }
@@ -454,25 +406,11 @@ void pcc_wino_bf16_pack(int ngroups, const float* u_f32, float* out) {
 int pcc_conv_wino_bf16(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, const float* ub_packed, const float* bias,
                        const float* residual, float* out, hipStream_t st) {
     PCC_REQUIRE(pcc_wino_eligible(d) && d->Cin == 16, "pcc_conv_wino_bf16: shape not covered");
-    WinoArgs a;
-    a.in = in; a.bias = bias; a.res = residual; a.out = out;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.nty = d->H / 16; a.ntx = d->W / 16;
-    a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    a.oco = d->out_coffset;
-    a.nco = 1; a.ics = d->Cin; a.rcs = d->Cout; a.ico = 0; a.ncig = 1;
-    a.u = ub_packed; a.flags = d->flags;
-    const int base = d->N * a.nty * a.ntx;
-    int zs = 1;
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= 8) zs *= 2;
-    a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = base * zs;
+    WinoArgs a = wino_fill_args(ctx, d, 1, in, bias, residual, out);
+    a.u = ub_packed;
     typedef void (*kern_t)(WinoArgs, int);
     static const kern_t kerns[4] = {conv16_wino_bf16_kernel<false, false>, conv16_wino_bf16_kernel<true, false>,
                                     conv16_wino_bf16_kernel<false, true>, conv16_wino_bf16_kernel<true, true>};
     const kern_t kern = kerns[((d->flags & PCC_CONV_RELU) ? 1 : 0) + ((d->flags & PCC_CONV_CLIP01) ? 2 : 0)];
-    { const int rc = pcc_enable_big_lds((const void*)kern, LDS_BYTES_B); if (rc != PCC_OK) return rc; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), LDS_BYTES_B, st, a, nwg);
-    PCC_CHECK_HIP(hipGetLastError());
-    return PCC_OK;
+    return wino_launch(kern, LDS_BYTES_B, wino_num_wg(a), st, a);
 }

@@ -152,13 +152,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     typedef __attribute__((address_space(3))) void* lds_ptr;
     const unsigned lds0 = (unsigned)(unsigned long long)(lds_ptr)smem;       // absolute LDS address of the dynamic segment
 
-    int wg = xcd_remap(blockIdx.x, nwg);
-    const int cog = wg % a.nco; wg /= a.nco;
-    const int tx_ = wg % a.ntx; wg /= a.ntx;
-    const int ty_ = wg % a.nty; wg /= a.nty;
-    const int zs = wg % a.zsplit;
-    const int n = wg / a.zsplit;
-    const int X0 = tx_ * 16, Y0 = ty_ * 16, zb = zs * a.zlen;
+    const WinoTile wt = wino_tile(a, nwg);
+    const int cog = wt.cog, n = wt.n, X0 = wt.X0, Y0 = wt.Y0, zb = wt.zb;
     const int nsteps = a.zlen + 2;             // input planes zb-1 .. zb+zlen
     const size_t HW = (size_t)a.H * a.W;
     const unsigned HWI = (unsigned)(HW * a.ics * 4), HWR = (unsigned)(HW * a.rcs * 4), HWO = (unsigned)(HW * a.ocs * 4);
@@ -209,7 +204,6 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     const int wx = wave & 1, wy = wave >> 1;
     const int TX = 4 * wx + (t & 3), TY = 4 * wy + (t >> 2);
     const unsigned pa0 = lds0 + (unsigned)(64 * (36 * TY + TX) + 16 * (g + 2 * TY));
-    constexpr auto pa_off = [](int dy, int dx) constexpr -> int { return 64 * (18 * dy + 9 * (dx & 1) + (dx >> 1)) + (dy >= 2 ? 32 : 0); };
     unsigned ua[G];
 #pragma unroll
     for (int c = 0; c < G; ++c) ua[c] = lds0 + (unsigned)(U_BASE + c * UG_BYTES + lane * UL_LANE_BYTES);
@@ -252,14 +246,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     f32x4 resv[4], ost[4], prev[PRE ? 4 : 1];
     float mx = 0.f;             // max |stored value| of this lane (amax_out)
     // ---- pieces of the schedule.  V row r of a tile: Y = its fp32 values (yrow), H = cvt_pk(Y), L = fma_mix(Y - H).
-    auto yrow = [&](auto r_tag) __attribute__((always_inline)) {
-        constexpr int r = decltype(r_tag)::value;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-            const f32x4 y = r == 0 ? sub4(P0[x], P2[x]) : r == 1 ? add4(P1[x], P2[x]) : r == 2 ? sub4(P2[x], P1[x]) : sub4(P1[x], P3[x]);
-            Y[4 * x + 0] = y[0]; Y[4 * x + 1] = y[1]; Y[4 * x + 2] = y[2]; Y[4 * x + 3] = y[3];
-        }
-    };
+    auto yrow = [&](auto r_tag) __attribute__((always_inline)) { transform_y_row_split<decltype(r_tag)::value>(Y, P0, P1, P2, P3); };
     // pair j = (point x = j >> 1, channel pair hf = j & 1) of row r: stage 0 = h, 1 = l
     auto cvt_task = [&](auto r_tag, auto st_tag, auto j_tag) __attribute__((always_inline)) {
         constexpr int r = decltype(r_tag)::value, st = decltype(st_tag)::value, j = decltype(j_tag)::value;
@@ -269,12 +256,6 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
         else if constexpr (st == 1)
             B[r * 4 + x][2 + hf] = mix_low_pair(B[r * 4 + x][hf], Y[4 * x + 2 * hf], Y[4 * x + 2 * hf + 1]);
     };
-    using R0 = std::integral_constant<int, 0>;
-    using R1 = std::integral_constant<int, 1>;
-    using R2 = std::integral_constant<int, 2>;
-    using R3 = std::integral_constant<int, 3>;
-    using ST0 = std::integral_constant<int, 0>;
-    using ST1 = std::integral_constant<int, 1>;
     // a whole row at once (prologue only)
     auto split_row = [&](auto r_tag) __attribute__((always_inline)) {
         yrow(r_tag);
@@ -290,7 +271,7 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
     // patch row dy of the tile in ring slot SLOT: piece x
     auto load_p = [&](f32x4 (&P)[4], auto dy_tag, auto x_tag, auto slot_tag) __attribute__((always_inline)) {
         constexpr int dy = decltype(dy_tag)::value, x = decltype(x_tag)::value, SLOT = decltype(slot_tag)::value;
-        P[x] = lds_read128<pa_off(dy, x) + SLOT * PLANE_BYTES>(pa0);
+        P[x] = lds_read128<patch_off_padded(dy, x) + SLOT * PLANE_BYTES>(pa0);
     };
     auto prologue = [&](auto slot_tag, auto first_slot_tag) __attribute__((always_inline)) {
         static_for<0, 4>([&](auto x) __attribute__((always_inline)) {
@@ -413,32 +394,17 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
                 // A^T along x on row r of the finished plane, accumulate A^T along y
                 constexpr int r = q / 3;
                 const f32x4 m0 = {Mr[0], Mr[1], Mr[2], Mr[3]}, m1 = {Mr[4], Mr[5], Mr[6], Mr[7]}, m2 = {Mr[8], Mr[9], Mr[10], Mr[11]}, m3 = {Mr[12], Mr[13], Mr[14], Mr[15]};
-                const f32x4 r0 = add4(add4(m0, m1), m2), r1 = sub4(sub4(m1, m2), m3);
-                if (r == 0) { S[0][0] = r0; S[0][1] = r1; }
-                else if (r == 1) { S[0][0] = add4(S[0][0], r0); S[0][1] = add4(S[0][1], r1); S[1][0] = r0; S[1][1] = r1; }
-                else if (r == 2) { S[0][0] = add4(S[0][0], r0); S[0][1] = add4(S[0][1], r1); S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
-                else { S[1][0] = sub4(S[1][0], r0); S[1][1] = sub4(S[1][1], r1); }
+                reduce_at_row(S, r, m0, m1, m2, m3);
             }
             if constexpr (LAST && (q == 8 || q == 11) && !(PCC_WH_PROBE & (64 | 4))) {
-                // epilogue of output row oy (complete after reduction row 2 resp. 3): ReLU, un-scale + residual (one packed fma), clip, stores
+                // epilogue of output row oy (complete after reduction row 2 resp. 3); the un-scale is one packed fma with the first thing
+                // added (PRE: the partial sums of the first launch, else the residual); stores
                 constexpr int oy = q == 8 ? 0 : 1;
 #pragma unroll
                 for (int v = 2 * oy; v < 2 * oy + 2; ++v) {
-                    f32x4 o = S[v >> 1][v & 1];
-                    if constexpr (PRE) {
-                        o = fma4s(o, inv2, prev[v]);     // + the partial sums of the first launch, then ReLU, then the residual
-                        if (RELU) o = __builtin_elementwise_maximum(o, zero4);
-                        o = add4(o, resv[v]);
-                    } else {
-                        if (RELU) o = __builtin_elementwise_maximum(o, zero4);
-                        o = fma4s(o, inv2, resv[v]);     // zeros without PCC_CONV_ADD (zero-sized buffer)
-                    }
-                    if (CLIP) {
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) o[c] = fminf(fmaxf(o[c], 0.f), 1.f);
-                    }
-                    ost[v] = o;
-                    if constexpr (ZO) amax4(mx, o);
+                    ost[v] = epilogue_voxel<RELU, CLIP, PRE>(S[v >> 1][v & 1], prev[PRE ? v : 0], resv[v],
+                                                             [&](const f32x4& o, const f32x4& x) __attribute__((always_inline)) { return fma4s(o, inv2, x); });
+                    if constexpr (ZO) amax4(mx, ost[v]);
                 }
 #pragma unroll
                 for (int v = 2 * oy; v < 2 * oy + 2; ++v) buf_store4(rout, ost[v], ovo0, oso[v]);
@@ -450,9 +416,8 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
                     if constexpr (PRE) prev[v] = buf_load4(rout, ovo0, oso[v]);
                 }
             }
-            // gfx950: a buffer_store_dwordx4 reads its data registers late (conv16_wino_kernel): keep them unwritten for one more slot
-            if constexpr (LAST && q == 9) { asm volatile("" ::"v"(ost[0])); asm volatile("" ::"v"(ost[1])); }
-            if constexpr (LAST && q == 0) { asm volatile("" ::"v"(ost[2])); asm volatile("" ::"v"(ost[3])); }
+            if constexpr (LAST && q == 9) keep_store_data(ost, 0);
+            if constexpr (LAST && q == 0) keep_store_data(ost, 1);
             __builtin_amdgcn_sched_barrier(0);
         });
         // the LDS-direct loads of tile m+2 (F(3)) must have landed before the barrier publishes them; younger (last cin group only):
@@ -464,34 +429,29 @@ __global__ void __launch_bounds__(NT, 1) conv16_wino_f16s_kernel(WinoArgs a, int
             __syncthreads();
         }
     };
-    using P0t = std::integral_constant<int, 0>;
-    using P1t = std::integral_constant<int, 1>;
-    using P2t = std::integral_constant<int, 2>;
-    using MAll = std::integral_constant<int, M_ALL>;
-    using MFin = std::integral_constant<int, M_FIN>;
     // one input plane = G micro-steps
     auto plane = [&](auto ph_tag, int s, auto mode_tag) __attribute__((always_inline)) {
         static_for<0, G>([&](auto c_tag) __attribute__((always_inline)) { step(ph_tag, c_tag, s, mode_tag); });
     };
     using CL = std::integral_constant<int, G - 1>;
 
-    if (first_zero) plane(P1t{}, 1, std::integral_constant<int, M_S1O>{});
+    if (first_zero) plane(PH1{}, 1, MS1O{});
     else {
-        plane(P0t{}, 0, std::integral_constant<int, M_S0>{});
-        plane(P1t{}, 1, std::integral_constant<int, M_S1>{});
+        plane(PH0{}, 0, MS0{});
+        plane(PH1{}, 1, MS1{});
     }
     const int nloop = nsteps - (last_zero ? 1 : 0);
     for (int s = 2; s < nloop; s += 3) {
-        plane(P2t{}, s, MAll{});
-        if (s + 1 < nloop) plane(P0t{}, s + 1, MAll{});
-        if (s + 2 < nloop) plane(P1t{}, s + 2, MAll{});
+        plane(PH2{}, s, MAll{});
+        if (s + 1 < nloop) plane(PH0{}, s + 1, MAll{});
+        if (s + 2 < nloop) plane(PH1{}, s + 2, MAll{});
     }
     if (last_zero) {
         // the padding plane behind the volume: no matrix work; its last micro-step reduces and stores output plane D - 1
         const int sl = nsteps - 1, ph = sl % 3;
-        if (ph == 0) step(P0t{}, CL{}, sl, MFin{});
-        else if (ph == 1) step(P1t{}, CL{}, sl, MFin{});
-        else step(P2t{}, CL{}, sl, MFin{});
+        if (ph == 0) step(PH0{}, CL{}, sl, MFin{});
+        else if (ph == 1) step(PH1{}, CL{}, sl, MFin{});
+        else step(PH2{}, CL{}, sl, MFin{});
     }
     // ---- max |out| of block n for the next layer's pre-scale (order-independent: atomicMax on non-negative fp32 bit patterns)
     if (a.amax_out != nullptr) pcc_amax_record(a.amax_out + (size_t)n * PCC_AMAX_SLOTS, mx, (int)blockIdx.x * 4 + wave);
@@ -543,8 +503,7 @@ void pcc_wino_f16s_pack(int ngroups, const float* u_f32, float* out) {
         for (int cog = 0; cog < ngroups; ++cog)
             for (int row = 0; row < 48; ++row)
                 for (int lane = 0; lane < 64; ++lane) {
-                    const int dz = row / 16, py = (row / 4) % 4, px = row % 4, q = 3 * py + 2 - dz;
-                    unsigned short* d = o + ((size_t)(cog * ngroups + cig) * UG_BYTES + (size_t)lane * UL_LANE_BYTES + (size_t)(q * 4 + px) * 16) / 2;
+                    unsigned short* d = o + ((size_t)(cog * ngroups + cig) * UG_BYTES + (size_t)lane * UL_LANE_BYTES + (size_t)wino_row_slot(row) * 16) / 2;
                     for (int c = 0; c < 4; ++c) {
                         const float x = u_f32[((((size_t)cig * ngroups + cog) * 48 + row) * 64 + lane) * 4 + c] * su;      // exact
                         d[c] = f16_bits(x);
@@ -564,14 +523,8 @@ int pcc_conv_wino_f16s(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
     PCC_REQUIRE(pcc_wino_eligible(d) && pcc_wino_f16s_covers(d), "pcc_conv_wino_f16s: shape not covered");
     const int NG = d->Cin / 16, G = NG >= 2 ? 2 : 1;
     PCC_REQUIRE(NG == 1 || !(d->flags & PCC_CONV_CLIP01), "pcc_conv_wino_f16s: the multi-group kernels do not clip");
-    WinoArgs a;
-    a.in = in; a.bias = bias; a.res = residual; a.out = out;
-    a.N = d->N; a.D = d->D; a.H = d->H; a.W = d->W;
-    a.nty = d->H / 16; a.ntx = d->W / 16;
-    a.ocs = d->out_cstride ? d->out_cstride : d->Cout;
-    a.oco = d->out_coffset;
-    a.nco = NG; a.ics = d->Cin; a.rcs = d->Cout; a.ico = 0; a.ncig = NG; a.ig0 = 0;
-    a.u = uh_packed; a.flags = d->flags;
+    WinoArgs a = wino_fill_args(ctx, d, NG, in, bias, residual, out);
+    a.u = uh_packed; a.ncig = NG;
     a.utail = uh_packed + (size_t)NG * NG * PCC_WINO_UH_FLOATS;
     a.amax_out = ext ? ext->out_amax : nullptr;
     if (ext) ext->out_recorded = ext->out_amax != nullptr;
@@ -582,21 +535,9 @@ int pcc_conv_wino_f16s(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, co
         { const int rc = pcc_block_amax(ctx, in, d->N, (size_t)d->D * d->H * d->W * d->Cin, am, st); if (rc != PCC_OK) return rc; }
         a.amax_in = am;
     }
-    const int base = d->N * a.nty * a.ntx * NG;
-    int zs = 1;
-    const int min_zlen = NG >= 2 ? 4 : 8;
-    while (base * zs < ctx->num_cu && d->D % (zs * 2) == 0 && d->D / (zs * 2) >= min_zlen) zs *= 2;
-    a.zsplit = zs; a.zlen = d->D / zs;
-    const int nwg = base * zs;
     typedef void (*kern_t)(WinoArgs, int);
     const bool relu = (d->flags & PCC_CONV_RELU) != 0;
-    const int lds = f16s_lds_bytes(G);
-    auto launch1 = [&](kern_t kern, const WinoArgs& aa) -> int {
-        { const int rc = pcc_enable_big_lds((const void*)kern, lds); if (rc != PCC_OK) return rc; }
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NT), lds, st, aa, nwg);
-        PCC_CHECK_HIP(hipGetLastError());
-        return PCC_OK;
-    };
+    auto launch1 = [&](kern_t kern, const WinoArgs& aa) { return wino_launch(kern, f16s_lds_bytes(G), wino_num_wg(aa), st, aa); };
     if (NG == 1) {
         static const kern_t k1[4] = {conv16_wino_f16s_kernel<false, false, 1>, conv16_wino_f16s_kernel<true, false, 1>,
                                      conv16_wino_f16s_kernel<false, true, 1>, conv16_wino_f16s_kernel<true, true, 1>};

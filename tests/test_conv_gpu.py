@@ -438,6 +438,77 @@ def test_winograd_cin_groups_inside_the_march(ctx, monkeypatch, C, N, D, H, W, t
     assert (a - b).abs().max().item() <= 2e-5 * scale and (a - d).abs().max().item() <= 2e-5 * scale
 
 
+# Instantiations of the four Winograd kernels that no other test selects (profiles/wino_skeleton_isa.md has the whole table):
+# kernel<template arguments>, the family pcc_conv_kernel_family must name, numerics switches, channels, relu, clip, tolerance.
+# The launcher's choice follows from these: 16 channels under no_split take conv16_wino_kernel; 32 / 64 channels under no_split take
+# conv16_wino_cin_kernel<RELU, channels / 16>, or, with wino_per_group or a clip, one launch of conv16_wino_kernel per cin group (the
+# later ones PRE, the last one with the epilogue); no_f16s on 16 channels takes the bf16 kernel; 64 channels by default take two
+# launches of the two-group fp16 kernel, the second one PRE.
+WINO_INSTANCE_CASES = [
+    ('conv16_wino_kernel<false, true, false>', 'conv16_wino (', dict(no_split=True), 16, False, True, TOL),
+    ('conv16_wino_kernel<true, true, false>', 'conv16_wino (', dict(no_split=True), 16, True, True, TOL),
+    ('conv16_wino_kernel<false, false, true>', 'conv16_wino (', dict(no_split=True, wino_per_group=True), 32, False, False, TOL),
+    ('conv16_wino_kernel<true, false, true>', 'conv16_wino (', dict(no_split=True, wino_per_group=True), 32, True, False, TOL),
+    ('conv16_wino_kernel<false, true, true>', 'conv16_wino (', dict(no_split=True), 32, False, True, TOL),
+    ('conv16_wino_kernel<true, true, true>', 'conv16_wino (', dict(no_split=True), 64, True, True, TOL),
+    ('conv16_wino_cin_kernel<false, 2>', 'conv16_wino (', dict(no_split=True), 32, False, False, TOL),
+    ('conv16_wino_cin_kernel<false, 4>', 'conv16_wino (', dict(no_split=True), 64, False, False, TOL),
+    ('conv16_wino_cin_kernel<true, 4>', 'conv16_wino (', dict(no_split=True), 64, True, False, TOL),
+    ('conv16_wino_bf16_kernel<false, true>', 'conv16_wino_bf16', dict(no_f16s=True), 16, False, True, 8e-6),
+    ('conv16_wino_bf16_kernel<true, true>', 'conv16_wino_bf16', dict(no_f16s=True), 16, True, True, 8e-6),
+    ('conv16_wino_f16s_kernel<false, true, 1>', 'conv16_wino_f16s', {}, 16, False, True, 8e-6),
+    ('conv16_wino_f16s_kernel<true, true, 1>', 'conv16_wino_f16s', {}, 16, True, True, 8e-6),
+    ('conv16_wino_f16s_kernel<false, false, 2, true>', 'conv16_wino_f16s', {}, 64, False, False, 8e-6),
+]
+_WINO_INSTANCE_REFS = {}
+
+
+def _wino_instance_ref(O, ch, D):
+    """x, w, b, r and the oracle's conv + bias (no ReLU, no residual) of one 16 x 16 tile, shared by every case of (ch, D) and never
+    written to.  The input scale is 1: with unit-variance inputs, bias and residual and weights of variance 1 / fan-in the unclipped
+    result spreads over (-inf, 0), [0, 1] and (1, inf) as the clip cases assert below."""
+    if (ch, D) not in _WINO_INSTANCE_REFS:
+        rng = np.random.default_rng(1000 * ch + D)
+        x = rng.standard_normal((1, D, 16, 16, ch)).astype(np.float32)
+        w = (rng.standard_normal((3, 3, 3, ch, ch)) / np.sqrt(27 * ch)).astype(np.float32)
+        b = rng.standard_normal(ch).astype(np.float32)
+        r = rng.standard_normal((1, D, 16, 16, ch)).astype(np.float32)
+        _WINO_INSTANCE_REFS[(ch, D)] = (x, w, b, r, O.conv3d(x, w, b, 1, False))
+    return _WINO_INSTANCE_REFS[(ch, D)]
+
+
+@pytest.mark.parametrize('zcase', ['D3', 'D4', 'D5', 'split'])
+@pytest.mark.parametrize('case', WINO_INSTANCE_CASES, ids=[c[0] for c in WINO_INSTANCE_CASES])
+def test_every_winograd_instantiation_matches_oracle(ctx, oracle, case, zcase):
+    """One launch per kernel instantiation that the other tests leave out, bias + residual, at the tolerances of this file (exact fp32:
+    TOL, split operands: 8e-6).  D = 3, 4, 5: one slab over the whole volume whose last step (M_FIN: reduction and store only) falls
+    into accumulator phase 1, 2, 0.  `split`: D = 16 (one cin group) or 8 (two, four): two slabs per column, so one starts and one ends
+    inside the volume (M_S0 / M_S1, and the peeled tail of the cin kernel).  Clip cases: the UNCLIPPED oracle has at least a tenth of
+    its values below 0, above 1 and in between, so a clip that is missing, or applied before the residual, fails the comparison."""
+    name, family, switches, ch, relu, clip, tol = case
+    D = {'D3': 3, 'D4': 4, 'D5': 5, 'split': 16 if ch == 16 else 8}[zcase]
+    x, w, b, r, conv = _wino_instance_ref(oracle, ch, D)
+    ref = (np.maximum(conv, 0) if relu else conv) + r
+    if clip:
+        below, above = (ref < 0).mean(), (ref > 1).mean()
+        assert below >= 0.1 and above >= 0.1 and 1 - below - above >= 0.1, (below, above)
+        ref = np.clip(ref, 0, 1)
+    layer = ops.ConvLayer(w, b, 1, False, relu)
+    flags = L.PCC_CONV_CLIP01 if clip else 0
+    with ctx.numerics_override(**switches):
+        buf = ctypes.create_string_buffer(96)
+        d = layer.desc(1, D, 16, 16, flags | L.PCC_CONV_ADD, L.PCC_IMPL_WINOGRAD, 0, 0)
+        L.check(L.lib().pcc_conv_kernel_family(ctx.handle, ctypes.byref(d), buf, 96), 'pcc_conv_kernel_family')
+        assert buf.value.decode().startswith(family), (name, buf.value.decode())
+        out = ops.conv3d(ctx, torch.from_numpy(x).to(ctx.device), layer, residual=torch.from_numpy(r).to(ctx.device),
+                         impl=L.PCC_IMPL_WINOGRAD, flags=flags)
+        torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    err, bound = np.abs(got - ref).max(), tol * (1 + np.abs(ref).max())
+    print(f'{name} D={D}: max err {err:.3e}, bound {bound:.3e}')
+    assert err <= bound, f'{name}: max err {err} > {bound}; first bad {np.argwhere(np.abs(got - ref) > bound)[:5]}'
+
+
 F16S_CASES = [  # C, N, D, H, W, transposed, residual, out16
     (16, 2, 5, 16, 16, True, False, True), (16, 1, 9, 32, 48, False, True, True), (16, 2, 6, 16, 32, True, True, False),
     (32, 1, 5, 16, 16, True, False, True), (32, 2, 7, 32, 16, False, True, False), (16, 3, 32, 32, 32, True, True, True),
