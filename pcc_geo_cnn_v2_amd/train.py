@@ -106,6 +106,8 @@ class _ConvFn(torch.autograd.Function):
 
 def dgrad(pctx, layer, d, g, x):
     """Input gradient of layer descriptor d: pcc_conv3d on the dual descriptor with the same Keras array."""
+    # a stride-2 Conv3D on an odd grid has no dual: a Conv3DTranspose writes 2 O voxels per axis, one more than x has
+    assert d.transposed or d.stride == 1 or not (d.D | d.H | d.W) & 1, 'dgrad: stride-2 Conv3D on an odd grid'
     dd = ops.dual_desc(d)
     dx = torch.empty_like(x)
     L.check(L.lib().pcc_conv3d(pctx.handle, C.byref(dd), ops._ptr(g), ops._ptr(layer.weight.detach()),

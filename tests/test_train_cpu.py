@@ -1,5 +1,6 @@
 """CPU: the training pieces that need no GPU -- tfc 1.3 entropy-model formulas, lower_bound gradients, aux targets, the exported
-checkpoint's keys and tables, the train / test split and the tr_train command line."""
+checkpoint's keys and tables, the train / test split, the tr_train command line, and the premises of the exact gradient tests of
+test_train_gpu.py (tests/_train_cases.py)."""
 import math
 import os
 import subprocess
@@ -9,8 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+import _train_cases as T
 import _train_ref as R
-from pcc_geo_cnn_v2_amd import train
+from pcc_geo_cnn_v2_amd import _lib as L
+from pcc_geo_cnn_v2_amd import ops, train
 from pcc_geo_cnn_v2_amd.entropy_models import EntropyBottleneck as HostEB
 from pcc_geo_cnn_v2_amd.init_checkpoint import make_synthetic_weights
 from pcc_geo_cnn_v2_amd.model_configs import ModelConfigType
@@ -111,3 +114,92 @@ def test_tr_train_help():
     for flag in ('--model_config', '--resolution', '--batch_size', '--lmbda', '--alpha', '--gamma', '--max_steps', '--warm_start',
                  '--seed', '--validation_interval', '--validation_steps', '--data_format'):
         assert flag in r.stdout
+
+
+# ---- the cases of the exact gradient tests (tests/_train_cases.py; the GPU assertions are in test_train_gpu.py) --------------------
+INT_CASES = list(dict.fromkeys(T.slice_cases() + T.valu_cases() + T.small_grids() + T.noncubic_cases() + T.mixed_parity_cases()))
+
+
+def test_every_mfma_entry_has_a_geometry_and_a_slice_grid():
+    assert len(T.TILES) == 8 and set(T.SLICE_GRIDS) == set(T.TILES)
+    assert {T.view(g) for g in T.GEOMS} >= set(T.TILES)
+    assert {T.view(c[0]) for c in T.slice_cases()} == set(T.TILES)
+    # forward and transposed layers of one entry are cases of their own, and every geometry is in one of the two slice sets
+    assert len(T.slice_cases()) + len(T.valu_cases()) == len(T.GEOMS)
+    assert {T.view(c[0]) for c in T.valu_cases()} == {(1, 16, 3, 2), (1, 16, 3, 1), (1, 32, 9, 2)}
+    assert {c[0] for c in T.noncubic_cases()} == {g for g in T.GEOMS if not g[7]}
+    mixed = T.mixed_parity_cases()
+    assert {c[0] for c in mixed} == {g for g in T.GEOMS if not g[4] and g[3] == 2}
+    assert {tuple(n % 2 for n in c[2]) for c in mixed} == {(1, 0, 1), (0, 1, 1)} and all(T.small_dims(c[0], c[2]) == (3, 6, 10) for c in mixed)
+    grids = T.small_grids()
+    assert all(max(c[2]) <= 8 and c[1] == 3 for c in grids)
+    assert {c[2][0] for c in grids} == {1, 2, 4, 8}
+
+
+@pytest.mark.parametrize('case', INT_CASES, ids=T.case_id)
+def test_integer_cases_are_exact_in_any_float32_order(case):
+    """The premise of the exact GPU tests: every gradient element's sum of |terms| is below 2^24, so all its partial sums are integers
+    a float32 holds; torch's float32 conv backward on the CPU (another summation order again) already gives the float64 bits."""
+    g, N, dims = case
+    layer, x, dout = T.int_case(g, N, dims, T.SEED)
+    for a in (layer.kernel, x, dout):
+        assert np.array_equal(a, np.rint(a)) and np.abs(a).max() <= 2
+    assert np.count_nonzero(x) < .5 * x.size or x.size < 100                   # ReLU-sparse
+    ref = T.int_reference(g, N, dims, T.SEED)
+    tot = T.grads(layer, x, dout, absolute=True, dx=not g[7])
+    f32 = T.grads(layer, x, dout, dtype=torch.float32, dx=not g[7])
+    assert (ref[2] is None) == bool(g[7])
+    for name, r, a, f in zip(('dW', 'dB', 'dX'), ref, tot, f32):
+        if r is None:
+            continue
+        assert a.max() < 2 ** 24, (name, a.max())
+        assert np.all(np.abs(r) <= a) and np.array_equal(r, np.rint(r)), name
+        assert f.dtype == np.float32 and np.array_equal(f.astype(np.float64), r), name
+
+
+@pytest.mark.parametrize('case', T.slice_cases() + T.valu_cases(), ids=T.case_id)
+def test_slice_grids_split_unevenly_and_end_in_partial_tiles(case):
+    g, N, dims = case
+    n = T.units(g, N, dims)
+    S, chain = T.slices(g, N, dims)
+    assert ops.conv_wgrad_slices(T.desc(g, N, dims)) == (S, chain)            # host-only: TILES is the library's tiling
+    assert S < n and n % S != 0, (S, n)
+    o = T.small_dims(g, dims)
+    if T.view(g) in T.TILES:
+        tile = T.TILES[T.view(g)]
+        assert o == T.SLICE_GRIDS[T.view(g)][1] and N == T.SLICE_GRIDS[T.view(g)][0]
+        assert chain == -(-n // S) * int(np.prod(tile))
+        assert all(a % t != 0 for a, t in zip(o, tile) if t > 1), (o, tile)
+    else:
+        assert S == 1024 and n == N * int(np.prod(o)) and len(set(o)) == 3
+    if not g[4] and g[3] == 2:
+        assert all(d == 2 * a - 1 for d, a in zip(dims, o))                      # the odd large grid
+
+
+def test_slice_grids_have_the_tile_and_slice_counts_of_the_plan():
+    """(slices, tiles) per entry, worked out by hand from S = min(1024, 2^25 / (k^3 cu cz), tiles)."""
+    want = {(16, 16, 3, 1): (1024, 1254), (32, 32, 3, 1): (1024, 1254), (64, 64, 3, 1): (303, 378), (16, 32, 3, 2): (1024, 1134),
+            (32, 32, 3, 2): (1024, 1134), (32, 64, 3, 2): (606, 630), (64, 64, 3, 2): (303, 375), (32, 32, 5, 2): (262, 315)}
+    for g, N, dims in T.slice_cases():
+        assert (T.slices(g, N, dims)[0], T.units(g, N, dims)) == want[T.view(g)], g
+
+
+@pytest.mark.parametrize('case', list({T.view(c[0]): c for c in reversed(T.slice_cases())}.values()), ids=T.case_id)
+def test_reference_dw_moves_by_an_integer_with_one_edge_voxel_and_with_a_shifted_dout(case):
+    """Exact equality cannot pass a kernel that drops the last column of a partial tile or misplaces dout by a voxel: either change
+    moves an element of the float64 dW by at least 1."""
+    g, N, dims = case
+    layer, x, dout = T.int_case(g, N, dims, T.SEED)
+    ref = T.int_reference(g, N, dims, T.SEED)[0]
+    n, z, y, _ = np.argwhere(x[:, :, :, -1, :] != 0)[-1]                        # a voxel of the last x column, in a partial tile
+    x2 = x.copy()
+    x2[n, z, y, -1, :] = 0
+    for what, xs, gs in (('edge voxel', x2, dout), ('shift', x, np.roll(dout, 1, axis=3))):
+        diff = T.grads(layer, xs, gs, dx=False)[0] - ref
+        assert np.array_equal(diff, np.rint(diff)) and np.abs(diff).max() >= 1, what
+
+
+def test_dgrad_refuses_a_stride_2_conv_on_an_odd_grid():
+    for dims in ((5, 6, 6), (6, 6, 7)):
+        with pytest.raises(AssertionError, match='odd grid'):
+            train.dgrad(None, None, L.ConvDesc(1, *dims, 16, 32, 3, 2, 0, 0, L.PCC_IMPL_AUTO, 0, 0), None, None)

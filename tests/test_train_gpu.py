@@ -1,5 +1,6 @@
-"""GPU: training -- weight / input gradients of every conv geometry of c1, c2, c3 and c3p against float64 autograd, determinism,
-the device repack of the packed weight images, the focal-loss gradient, whole-model gradients, and tr_train end to end."""
+"""GPU: training -- weight / input gradients of every conv geometry of c1, c2, c3 and c3p against float64 autograd (with a bound
+on Gaussian data, bit for bit on the integer cases of tests/_train_cases.py: partial tiles, uneven slices, the trainer's small grids,
+non-cubic grids), the ReLU mask bitwise, packed images after in-place weight updates, determinism, the device repack of the packed weight images, the focal-loss gradient, whole-model gradients, and tr_train end to end."""
 import ctypes as C
 import os
 import subprocess
@@ -9,7 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+import _train_cases as T
 import _train_ref as R
+from _train_cases import GEOMS, _layer
 from pcc_geo_cnn_v2_amd import _lib as L
 from pcc_geo_cnn_v2_amd import model_transforms as MT
 from pcc_geo_cnn_v2_amd import ops, train
@@ -21,35 +24,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -24
 
 
-def _geometries():
-    """Distinct (cin, cout, k, stride, transposed, relu, bias, first) of the conv layers of c1, c2, c3, c3p; `first`: the layer
-    reads the network input (no input gradient needed)."""
-    out = set()
-    for cfg in ('c1', 'c2', 'c3', 'c3p'):
-        m = ModelConfigType[cfg].build()
-        m.compress([1, 1, 64, 64, 64])
-        for prefix, tr, _ in m._transforms():
-            for i, c in enumerate(tr.conv_layers()):
-                l = c.layer
-                out.add((l.cin, l.cout, l.k, l.stride, int(l.transposed), int(l.relu), int(l.bias is not None),
-                         int(prefix == 'analysis' and i == 0)))
-    return sorted(out)
-
-
-GEOMS = _geometries()
-
-
 @pytest.fixture(scope='module')
 def pctx():
     return train.training_context(torch.device('cuda', 0))
-
-
-def _layer(g, rng):
-    cin, cout, k, s, tr, relu, bias, _ = g
-    shape = (k, k, k) + ((cout, cin) if tr else (cin, cout))
-    w = rng.uniform(-1, 1, shape).astype(np.float32) / np.sqrt(k ** 3 * cin)
-    b = rng.normal(0, .1, cout).astype(np.float32) if bias else None
-    return ops.ConvLayer(w, b, s, tr, relu)
 
 
 def _grid(g):
@@ -57,17 +34,29 @@ def _grid(g):
     return 8 if k == 9 else 16
 
 
-def _wgrad_case(pctx, g, n, D, seed):
-    rng = np.random.default_rng(seed)
-    layer = _layer(g, rng)
-    x = np.maximum(rng.normal(0, 1, (n, D, D, D, layer.cin)), 0).astype(np.float32)      # ReLU-sparse input
-    oshape = ops.conv_out_shape(layer, x.shape)
-    dout = rng.normal(0, 1, oshape).astype(np.float32)
-    d = layer.desc(n, D, D, D)
+def _wgrad(pctx, layer, x, dout):
+    """(descriptor, dW, dB) of pcc_conv3d_wgrad on host arrays x and dout."""
+    d = layer.desc(*x.shape[:4])
     xd, gd = torch.from_numpy(x).cuda(), torch.from_numpy(dout).cuda()
     dw = torch.empty(layer.kernel.shape, dtype=torch.float32, device='cuda')
     db = torch.empty(layer.cout, dtype=torch.float32, device='cuda')
     ops.conv3d_wgrad(pctx, d, xd, gd, dw, db)
+    return d, dw, db
+
+
+def _gauss_case(g, n, dims, seed):
+    """Layer of geometry g, ReLU-sparse Gaussian x on an n x dims grid (dims: one extent for a cube, or three) and Gaussian dout."""
+    rng = np.random.default_rng(seed)
+    layer = _layer(g, rng)
+    dims = (dims,) * 3 if isinstance(dims, int) else tuple(dims)
+    x = np.maximum(rng.normal(0, 1, (n,) + dims + (layer.cin,)), 0).astype(np.float32)      # ReLU-sparse input
+    dout = rng.normal(0, 1, ops.conv_out_shape(layer, x.shape)).astype(np.float32)
+    return layer, x, dout
+
+
+def _wgrad_case(pctx, g, n, D, seed):
+    layer, x, dout = _gauss_case(g, n, D, seed)
+    d, dw, db = _wgrad(pctx, layer, x, dout)
     return layer, x, dout, d, dw, db
 
 
@@ -119,12 +108,13 @@ def test_wgrad_is_bitwise_deterministic(pctx, g):
 
 @pytest.mark.parametrize('g', [g for g in GEOMS if not g[7]], ids=[f'{g[0]}-{g[1]}-k{g[2]}s{g[3]}{"T" if g[4] else ""}' for g in GEOMS if not g[7]])
 def test_dgrad_through_the_dual_descriptor(pctx, g):
-    rng = np.random.default_rng(4)
-    layer = _layer(g, rng)
-    D = _grid(g)
-    x = np.maximum(rng.normal(0, 1, (2, D, D, D, layer.cin)), 0).astype(np.float32)
-    dout = rng.normal(0, 1, ops.conv_out_shape(layer, x.shape)).astype(np.float32)
-    dd = ops.dual_desc(layer.desc(2, D, D, D))
+    layer, x, dout = _gauss_case(g, 2, _grid(g), 4)
+    _check_dgrad(layer, x, dout, _dgrad(pctx, layer, x, dout))
+
+
+def _dgrad(pctx, layer, x, dout):
+    """dX of host arrays: pcc_conv3d on the dual descriptor with the Keras array and its device-repacked image."""
+    dd = ops.dual_desc(layer.desc(*x.shape[:4]))
     m = ops.conv_repack_map(dd)
     wd = torch.from_numpy(layer.kernel).cuda()
     pk = None
@@ -133,6 +123,10 @@ def test_dgrad_through_the_dual_descriptor(pctx, g):
     dx = torch.empty(x.shape, dtype=torch.float32, device='cuda')
     L.check(L.lib().pcc_conv3d(pctx.handle, C.byref(dd), ops._ptr(torch.from_numpy(dout).cuda()), ops._ptr(wd), ops._ptr(pk),
                                None, None, ops._ptr(dx), pctx.stream), 'dgrad')
+    return dx
+
+
+def _check_dgrad(layer, x, dout, dx):
     ref = []
     for xs, gs, ws in ((x, dout, layer.kernel), (x, np.abs(dout), np.abs(layer.kernel))):
         xt = torch.from_numpy(xs).double().requires_grad_()
@@ -184,6 +178,174 @@ def test_device_repack_equals_host_pack_on_the_training_segments(pctx, cfg):
                     assert sel.sum() >= w.size
                     assert np.array_equal(dev[sel].view(np.uint32), host[sel].view(np.uint32)), (cfg, prefix, fam)
                 D = ops.conv_out_shape(l, (2, D, D, D, l.cin))[1]
+
+
+# ---- exact gradients on small integers (tests/_train_cases.py): every partial sum is an integer below 2^24, so any slice split,
+#      MFMA chain or summation order gives the float64 value bit for bit
+SEED = T.SEED
+
+
+def _assert_exact(what, got, want64, k=None):
+    """got (device float32) equals the float64 reference; dW (k given) names the first bad (tap, cu, cz)."""
+    want = want64.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), want64), f'{what}: the reference is not a float32'
+    got = got.cpu().numpy()
+    assert got.shape == want.shape
+    bad = np.argwhere(~(got == want))
+    if len(bad):
+        i = tuple(int(v) for v in bad[0])
+        where = f'(tap {(i[0] * k + i[1]) * k + i[2]}, cu {i[3]}, cz {i[4]})' if k else str(i)
+        raise AssertionError(f'{what}: {len(bad)} of {got.size} differ, first at {where}: got - want = {got[i] - want[i]:g}')
+
+
+def _exact_wgrad(pctx, case):
+    g, N, dims = case
+    layer, x, dout = T.int_case(g, N, dims, SEED)
+    d, dw, db = _wgrad(pctx, layer, x, dout)
+    rdw, rdb, _ = T.int_reference(g, N, dims, SEED)
+    _assert_exact('dW', dw, rdw, layer.k)
+    _assert_exact('dB', db, rdb)
+    return layer, x, dout, d
+
+
+def _uneven_slices(case):
+    """The preconditions of the slice tests: what the library plans is what TILES predicts, more units than slices, uneven split."""
+    g, N, dims = case
+    n = T.units(g, N, dims)
+    S, chain = T.slices(g, N, dims)
+    assert ops.conv_wgrad_slices(T.desc(g, N, dims)) == (S, chain)
+    assert S < n and n % S != 0, (S, n)
+    return S, n
+
+
+@pytest.mark.parametrize('case', T.slice_cases(), ids=T.case_id)
+def test_wgrad_is_exact_on_integers_with_partial_tiles_and_uneven_slices(pctx, case):
+    g, N, dims = case
+    S, ntiles = _uneven_slices(case)
+    tile, o = T.TILES[T.view(g)], T.small_dims(g, dims)
+    assert all(a % t != 0 for a, t in zip(o, tile) if t > 1), (o, tile)
+    _exact_wgrad(pctx, case)
+
+
+@pytest.mark.parametrize('case', T.valu_cases(), ids=T.case_id)
+def test_wgrad_valu_and_bias_are_exact_with_uneven_voxel_slices(pctx, case):
+    S, nvox = _uneven_slices(case)
+    assert S == 1024 and nvox == case[1] * int(np.prod(T.small_dims(case[0], case[2])))
+    layer, x, dout, d = _exact_wgrad(pctx, case)
+    assert int(np.prod(dout.shape[:4])) % 1024 != 0            # the bias slices are uneven too
+
+
+def _train_conv(layer):
+    """The trainer's layer object over an ops.ConvLayer."""
+    class _Conv:
+        pass
+    c = _Conv()
+    c.layer = layer
+    return train.TrainConv(c, torch.device('cuda', 0))
+
+
+@pytest.mark.parametrize('case', T.small_grids(), ids=T.case_id)
+def test_gradients_are_exact_on_the_small_grids_the_trainer_runs(pctx, case):
+    g, N, dims = case
+    layer, x, dout, d = _exact_wgrad(pctx, case)
+    if g[7]:
+        return
+    assert _family(pctx, ops.dual_desc(d)) in TRAINING_FAMILIES
+    tc = _train_conv(layer)
+    xd = torch.from_numpy(x).cuda()
+    dx = train.dgrad(pctx, tc, d, torch.from_numpy(dout).cuda(), xd)
+    _assert_exact('dX', dx, T.int_reference(g, N, dims, SEED)[2])
+
+
+@pytest.mark.parametrize('case', T.noncubic_cases(), ids=T.case_id)
+def test_gradients_on_a_non_cubic_grid(pctx, case):
+    g, N, dims = case
+    assert len(set(dims)) == 3 and len(set(T.small_dims(g, dims))) == 3
+    tile = T.TILES.get(T.view(g), (1, 1, 1))
+    assert all(a % t != 0 for a, t in zip(T.small_dims(g, dims), tile) if t > 1)
+    layer, x, dout, d = _exact_wgrad(pctx, case)
+    assert _family(pctx, ops.dual_desc(d)) in TRAINING_FAMILIES
+    _assert_exact('dX', _dgrad(pctx, layer, x, dout), T.int_reference(g, N, dims, SEED)[2])
+    layer, x, dout = _gauss_case(g, N, dims, 12)
+    d, dw, db = _wgrad(pctx, layer, x, dout)
+    _check_wgrad(layer, d, x, dout, dw, db)
+    _check_dgrad(layer, x, dout, _dgrad(pctx, layer, x, dout))
+
+
+@pytest.mark.parametrize('case', T.mixed_parity_cases(), ids=T.case_id)
+def test_wgrad_is_exact_on_large_grids_of_mixed_parity(pctx, case):
+    assert len({n % 2 for n in case[2]}) == 2
+    _exact_wgrad(pctx, case)
+
+
+@pytest.mark.parametrize('n', [1, 255, 257, None], ids=['1', '255', '257', 'second-pass'])
+def test_relu_backward_masks_by_act_greater_than_zero(pctx, n):
+    if n is None:
+        n = pctx.num_cu * 32 * 256 + 5           # a few elements past one pass of the largest grid pcc_relu_backward launches
+    rng = np.random.default_rng(13)
+    special = np.array([0, 0x80000000, 1, 0x80000001, 0x3f800000, 0xbf800000, 0x7f800000, 0xff800000, 0x7fc00000], np.uint32)
+    # +0, -0, the smallest denormal, its negative, 1, -1, inf, -inf, NaN
+    act = rng.normal(0, 1, n).astype(np.float32)
+    grad = rng.normal(0, 1, n).astype(np.float32)
+    gspecial = np.array([np.inf, -np.inf, np.nan, -0.0, 1e-45], np.float32)
+    pos = rng.permutation(n)
+    if n >= 64:                                  # every act special under a finite, an inf and a NaN gradient
+        k = len(special)
+        for j in range(3):
+            act[pos[j * k:(j + 1) * k]] = special.view(np.float32)
+        grad[pos[k:2 * k]] = np.inf
+        grad[pos[2 * k:3 * k]] = np.nan
+        grad[pos[3 * k:3 * k + len(gspecial)]] = gspecial
+        act[-1], grad[-1] = np.float32(1e-45), -np.inf           # the last element of the last pass
+    else:
+        act[0], grad[0] = np.float32(1e-45), np.nan
+    a = act.view(np.uint32)
+    keep = (a > 0) & (a <= 0x7f800000)           # act > 0 on the bits: positive, denormals and +inf included, NaN and zeros not
+    assert np.array_equal(keep, act > 0)
+    want = np.where(keep, grad.view(np.uint32), np.uint32(0))
+    got = ops.relu_backward(pctx, torch.from_numpy(grad.copy()).cuda(), torch.from_numpy(act).cuda()).cpu().numpy().view(np.uint32)
+    bad = np.flatnonzero(got != want)
+    assert len(bad) == 0, (f'{len(bad)} of {n} differ, first at {bad[0]}: act {a[bad[0]]:#010x} grad '
+                           f'{grad.view(np.uint32)[bad[0]]:#010x} got {got[bad[0]]:#010x} want {want[bad[0]]:#010x}')
+
+
+def _step(pctx, tc, x, dout):
+    """One forward and backward of train.conv: (y, dX, dW), the parameter gradients cleared first."""
+    tc.weight.grad = None
+    xd = torch.from_numpy(x).cuda().requires_grad_()
+    y = train.conv(pctx, tc, xd)
+    y.backward(torch.from_numpy(dout).cuda())
+    return y.detach().clone(), xd.grad.clone(), tc.weight.grad.clone()
+
+
+def test_packed_images_follow_in_place_weight_updates(pctx):
+    g = (16, 16, 3, 1, 1, 1, 0, 0)               # 16 -> 16 k3 s1 transposed, ReLU, no bias
+    assert T.view(g) in T.TILES
+    N, dims = 2, (8, 8, 8)
+    layer, x, dout = T.int_case(g, N, dims, SEED)
+    tc = _train_conv(layer)
+    d = tc.desc(N, *dims)
+    assert tc.packed(pctx, d) is not None and tc.packed(pctx, ops.dual_desc(d)) is not None      # both read a packed image
+    y1, dx1, dw1 = _step(pctx, tc, x, dout)
+    assert bool((y1 != 0).any()) and bool((dx1 != 0).any())
+    with torch.no_grad():
+        tc.weight.mul_(2)
+    y2, dx2, dw2 = _step(pctx, tc, x, dout)
+    assert torch.equal(y2, 2 * y1) and torch.equal(dx2, 2 * dx1) and torch.equal(dw2, dw1)
+    # an optimizer step (weights no longer integers): the forward and dX are those of the new weights
+    tc.weight.grad = dw2
+    torch.optim.SGD([tc.weight], lr=1e-3).step()
+    y3, dx3, _ = _step(pctx, tc, x, dout)
+    assert not torch.equal(y3, y2)
+    w = tc.weight.detach().cpu().numpy()
+    assert not np.array_equal(w, 2 * layer.kernel)
+    ref = [R.layer(torch.from_numpy(x).double(), torch.from_numpy(ws).double(), None, 1, True, relu).numpy()
+           for ws, relu in ((w, True), (np.abs(w), False))]
+    # one output is a sum of at most k^3 Cin products accumulated in fp32 (any order), the bound of the dual's dgrad
+    bound = 2 * 27 * 16 * EPS * ref[1] + 1e-30
+    err = np.abs(y3.cpu().numpy().astype(np.float64) - ref[0])
+    assert np.all(err <= bound), f'forward after the step: max err/bound {np.max(err / bound):.3g}'
+    _check_dgrad(ops.ConvLayer(w, None, 1, True, True), x, dout * (y3.cpu().numpy() > 0), dx3)      # under the mask the kernel used
 
 
 def test_focal_gradient_matches_float64_autograd(pctx):
