@@ -160,6 +160,8 @@ def _flags(case, L):
         f |= L.PCC_CONV_OUT16
     if case['res']:
         f |= L.PCC_CONV_ADD
+    if case.get('clip'):        # rows of tests/_direct_cases.py
+        f |= L.PCC_CONV_CLIP01
     return f
 
 
