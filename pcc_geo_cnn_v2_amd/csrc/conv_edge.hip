@@ -513,6 +513,8 @@ int pcc_conv_cout1_mfma(pcc_ctx* ctx, const pcc_conv_desc* d, const float* in, c
     const bool t16 = ctx->num(PCC_NUM_COUT1_T16);
     typedef void (*kern_t)(ConvArgs);
     const bool in16 = (d->flags & PCC_CONV_IN16) != 0;
+    // the kernel reads `residual` as fp32 whatever the input type, and pcc_conv3d lets an fp16-input layer have an fp16 residual only
+    PCC_REQUIRE(!(in16 && (d->flags & PCC_CONV_ADD)), "pcc_conv3d: the 16 -> 1 layer with fp16 input (PCC_CONV_IN16) takes no residual");
     // the occupancy bits ride along when the caller asked for them and whole T-voxel rows map to whole mask pieces
     const bool thr = fuse != nullptr && a.ocs == 1 && a.oco == 0 && a.W % 16 == 0 && ((size_t)a.H * a.W) % 32 == 0;
     if (thr) { a.thr = fuse->thr; a.mask = (unsigned short*)fuse->mask; a.thr_clip = fuse->clip; }

@@ -1,14 +1,19 @@
-"""The table of the direct exact-fp32 conv kernels and their fp16-MFMA twins (tests/test_direct_cases_cpu.py,
-tests/test_direct_exact_gpu.py): one row per kernel instantiation that launch_fwd, launch_tr2, pcc_conv_cin1, pcc_conv_cout1_mfma,
-pcc_conv_cout1, pcc_conv_tr2m and the generic kernel can select without fp16 input (IN16 / RES16) and without the threshold-fusing
-epilogue, on the smallest grid that gives the instantiation a partial tile; the launchers' choices restated as plain Python
-(`select`); integer inputs on which every fp32 summation order gives the float64 value bit for bit; and the references.
+"""The table of the direct exact-fp32 conv kernels, their fp16-MFMA twins and the fp16-storage kernels (tests/test_direct_cases_cpu.py,
+tests/test_direct_exact_gpu.py): one row per kernel instantiation that launch_fwd, launch_tr2, pcc_conv_cin1, pcc_conv_cout1_mfma (fp32
+and fp16 input), pcc_conv_cout1, pcc_conv_tr2m, pcc_conv_f16, pcc_conv_tr2m_f16 and the generic kernel can select, on the smallest grid
+that gives the instantiation a partial tile or, for the kernels that march whole columns along z, its edges in z (SAME padding, slab
+seams); the launchers' choices restated as plain Python (`select`); integer inputs on which every fp32 summation order gives the
+float64 value bit for bit; and the references.  The four instantiations of conv_cout1_mfma_kernel with the threshold-fusing epilogue
+are listed here (INSTANCES, `select` with flags['thr']) and launched through the codec graph by tests/test_thr_fuse_gpu.py on the cases
+of tests/_thr_ref.py: pcc_thr_fuse has no export of its own.
 
 Exactness.  Set A (fp32 rows): x integers of [-3, 3], w and bias integers of [-2, 2] times 2^e per OUTPUT channel (e in [-6, 6]),
 residual integers of [-3, 3].  Every term of one output carries the same power of two, so each product and partial sum is an integer
-multiple of 2^min(e, 0) and, while the sum of |terms| in those units stays below 2^24, a float32.  Set B (fp16-MFMA rows): x in
-{0, 1}, w and bias in {-1, 0, 1}: exact in fp16, the products accumulate in fp32; with an fp16 output the results must stay within
-+-2048, where fp16 holds every integer.  tests/test_direct_cases_cpu.py asserts both per row.
+multiple of 2^min(e, 0) and, while the sum of |terms| in those units stays below 2^24, a float32.  Set B (fp16-MFMA and fp16-storage
+rows): x in {0, 1}, w and bias in {-1, 0, 1}, residual integers of [-2, 2]: exact in fp16, the products accumulate in fp32; with an
+fp16 output the results must stay within +-2048, where fp16 holds every integer (at most 27 x 64 + 1 + 2 = 1731), and so must the raw
+fp16 partial sums that the first launch of a 64-channel conv_f16 layer leaves for the second (at most 27 x 32 = 864).
+tests/test_direct_cases_cpu.py asserts all of these per row.
 
 Importing this module needs numpy only.
 """
@@ -61,6 +66,21 @@ _COUT1M = 'conv_cout1_mfma_kernel<false,16,false> conv_cout1_mfma_kernel<false,3
 # conv_cout1_kernel<16,3,1,4,8,8> is compiled and unreachable: make_plan sends Cin = 16 to conv_cout1_mfma_kernel
 _COUT1 = 'conv_cout1_kernel<32,3,1,4,8,8> conv_cout1_kernel<32,9,2,2,8,8>'
 _GENERIC = 'conv_fwd_generic conv_tr_generic'
+# ---- fp16 storage (csrc/conv_f16.hip, conv_tr2m_f16.hip) and the IN16 / THR variants of the 16 -> 1 layer (conv_edge.hip).
+# conv_f16_kernel<C,OUT32,SUB>: <32,.,true> is the 64-channel layer, two launches with raw fp16 partial sums in between;
+# conv_tr2m_f16_kernel<NG,RELU>; conv_cout1_mfma_kernel<IN16,T,THR>
+_F16 = """
+conv_f16_kernel<16,false,false> conv_f16_kernel<16,true,false> conv_f16_kernel<32,false,false> conv_f16_kernel<32,true,false>
+conv_f16_kernel<32,false,true> conv_f16_kernel<32,true,true>
+"""
+_TR2M_F16 = 'conv_tr2m_f16_kernel<1,true> conv_tr2m_f16_kernel<1,false> conv_tr2m_f16_kernel<2,true> conv_tr2m_f16_kernel<2,false>'
+_COUT1M_IN16 = 'conv_cout1_mfma_kernel<true,16,false> conv_cout1_mfma_kernel<true,32,false>'
+# the threshold-fusing epilogue exists inside the codec graph only (pcc_thr_fuse has no export): its rows are the cases of
+# tests/_thr_ref.py, launched by tests/test_thr_fuse_gpu.py through ops.codec_encode / ops.codec_decode_main
+_COUT1M_THR = """
+conv_cout1_mfma_kernel<false,16,true> conv_cout1_mfma_kernel<false,32,true> conv_cout1_mfma_kernel<true,16,true>
+conv_cout1_mfma_kernel<true,32,true>
+"""
 
 
 def _twin(name):
@@ -81,11 +101,16 @@ INSTANCES = {
     'pcc_conv_cout1_mfma': _COUT1M.split(),
     'pcc_conv_cout1': _COUT1.split(),
     'pcc_conv3d_generic': _GENERIC.split(),
+    'pcc_conv_f16': _F16.split(),
+    'pcc_conv_tr2m_f16': _TR2M_F16.split(),
+    'pcc_conv_cout1_mfma (PCC_CONV_IN16)': _COUT1M_IN16.split(),
+    'pcc_conv_cout1_mfma (pcc_thr_fuse)': _COUT1M_THR.split(),
 }
+GRAPH_ONLY = INSTANCES['pcc_conv_cout1_mfma (pcc_thr_fuse)']      # no row here: the cases of tests/_thr_ref.py
 UNREACHABLE = ['conv_cout1_kernel<16,3,1,4,8,8>']
 ALL_INSTANCES = [n for block in INSTANCES.values() for n in block]
 assert len(set(ALL_INSTANCES)) == len(ALL_INSTANCES)
-assert [len(v) for v in INSTANCES.values()] == [26, 25, 31, 39, 4, 4, 2, 2, 2]
+assert [len(v) for v in INSTANCES.values()] == [26, 25, 31, 39, 4, 4, 2, 2, 2, 6, 4, 2, 4] and len(ALL_INSTANCES) == 135 + 16
 
 CPU_NUM_CU = 256          # what the CPU tests restate the launchers for: the MI355X
 
@@ -97,7 +122,8 @@ def _cdiv(a, b):
 
 def flags_of(row):
     m = row['mode']
-    return dict(f16=m != 'fp32', out16=m == 'out16', res=bool(row['res']), clip=bool(row.get('clip')))
+    return dict(f16=m != 'fp32', in16=m.startswith('in16'), out16=m in ('out16', 'in16-out16'), res=bool(row['res']),
+                clip=bool(row.get('clip')), thr=bool(row.get('thr')))
 
 
 def out_dims(geo):
@@ -136,23 +162,53 @@ def select(desc, flags, switches, num_cu):
     if not tr and cin == 1:                                            # conv_route.hip:28 make_plan -> K_CIN1; conv_edge.hip:503
         assert s == 2 and k in (3, 9) and cout in (16, 32) and ow % 16 == 0 and not (D % 2 or H % 2 or W % 2)
         return _sel('conv_cin1_kernel<%d,%d,2,8,4>' % (cout, k), (2, 8, 16))
+    in16 = bool(flags.get('in16'))
     if tr and cout == 1:
-        if s == 1 and k == 3 and cin == 16:                            # conv_route.hip:33 -> K_COUT1M
+        if s == 1 and k == 3 and cin == 16:                            # conv_route.hip:33 -> K_COUT1M (:252: also with fp16 input)
             t16 = sw('cout1_t16')                                      # conv_edge.hip:513
+            # conv_edge.hip:515-517: fp16 input; the occupancy bits ride along when the caller asked for them (pcc_thr_fuse), the
+            # output is dense and whole 16-voxel rows map to whole mask pieces
+            thr = bool(flags.get('thr')) and not desc.get('ocs') and W % 16 == 0 and (H * W) % 32 == 0
+            name = 'conv_cout1_mfma_kernel<%s,%%d,%s>' % ('true' if in16 else 'false', 'true' if thr else 'false')
             if not t16 and H % 32 == 0 and W % 32 == 0:                # conv_edge.hip:520
                 base, zsp = N * (H // 32) * (W // 32), 1
                 while base * zsp < num_cu and D // (zsp * 2) >= 16:    # conv_edge.hip:523
                     zsp *= 2
                 if base * zsp >= num_cu:                               # conv_edge.hip:524
-                    return _sel('conv_cout1_mfma_kernel<false,32,false>', (D, 32, 32), zsp=zsp)
-            return _sel('conv_cout1_mfma_kernel<false,16,false>', (D, 16, 16), zsp=1)       # conv_edge.hip:532
+                    return _sel(name % 32, (D, 32, 32), zsp=zsp, fused=thr)                 # conv_edge.hip:527-529
+            return _sel(name % 16, (D, 16, 16), zsp=1, fused=thr)                           # conv_edge.hip:532-536
+        assert not in16, 'conv_route.hip:252: fp16 input on a 32 -> 1 layer goes to pcc_conv_f16, which refuses it'
         assert cin == 32 and W % 8 == 0 and (k, s) in ((3, 1), (9, 2))          # conv_route.hip:34-35 -> K_COUT1
         return _sel('conv_cout1_kernel<32,%d,%d,%s>' % (k, s, '4,8,8' if s == 1 else '2,8,8'), (4, 8, 8) if s == 1 else (2, 8, 8))
     bw = W if tr else ow                                               # conv_route.hip:17 base_w
     assert bw % 16 == 0 or bw in (8, 4)
     tx = 16 if bw % 16 == 0 else bw                                    # conv_route.hip:41
     nct = cout // 16
+    if in16:
+        # conv_route.hip:252 -> PCC_FAM_F16, :328 and pcc_f16_eligible (conv_f16.hip:287-294): k3 stride 1 (a transposed layer through
+        # flipped taps), Cin = Cout in {16, 32, 64}, H and W multiples of 16, a dense output; pcc_conv3d admits fp16 storage under AUTO only
+        assert desc['impl'] == 'AUTO' and s == 1 and k == 3 and cin == cout and cin in (16, 32, 64) and H % 16 == 0 and W % 16 == 0
+        assert not desc.get('ocs') and not desc.get('oco')
+        sub = cin == 64                                                # conv_f16.hip:335: two launches of the 32-channel kernel
+        C = 32 if sub else cin                                         # conv_f16.hip:355-366
+        ty = 16 if cin == 16 else 8                                    # conv_f16.hip:339
+        base, zs = N * (H // ty) * (W // 16) * (2 if sub else 1), 1    # conv_f16.hip:342
+        while base * zs < num_cu and D % (zs * 2) == 0 and D // (zs * 2) >= 4:              # conv_f16.hip:346
+            zs *= 2
+        while base * zs < 2 * num_cu and D % (zs * 2) == 0 and D // (zs * 2) >= 8:          # conv_f16.hip:347
+            zs *= 2
+        return _sel('conv_f16_kernel<%d,%s,%s>' % (C, 'false' if out16 else 'true', 'true' if sub else 'false'), (D // zs, ty, 16),
+                    zsplit=zs, zlen=D // zs, nwg=base * zs, launches=2 if sub else 1)       # conv_f16.hip:348-349
     if tr and s == 2:
+        # conv_route.hip:260-261 and pcc_tr2m_f16_covers (conv_tr2m_f16.hip:237-241, tr2m_shape_ok of tr2m_common.h:134-143): under AUTO
+        # the fp16 mode with fp16 hand-over marches along z unless no_tr2m is set; bias / ReLU only, offsets in multiples of 4
+        if (k == 3 and desc['impl'] == 'AUTO' and not sw('no_tr2m') and f16 and out16 and plain and (cin, cout) in ((32, 16), (64, 32))
+                and H % 16 == 0 and W % 16 == 0 and (desc.get('ocs') or cout) % 4 == 0 and (desc.get('oco') or 0) % 4 == 0):
+            base, zs = N * (H // 16) * (W // 16) * nct, 1              # tr2m_common.h:105-110
+            while base * zs < num_cu and D % (zs * 2) == 0 and D // (zs * 2) >= 4:
+                zs *= 2
+            return _sel('conv_tr2m_f16_kernel<%d,%s>' % (cin // 32, 'true' if desc['relu'] else 'false'), (D // zs, 16, 16),
+                        zsplit=zs, zlen=D // zs)                       # conv_tr2m_f16.hip:249-254
         # conv_route.hip:257-270: the z march where it is eligible and wanted, else the tiled kernels
         march = (k == 3 and not sw('no_tr2m') and not f16 and plain and (cin, cout) in ((32, 16), (64, 32)) and H % 16 == 0
                  and W % 16 == 0 and (sw('tr2m') or cin == 32 or D >= 32))
@@ -221,6 +277,7 @@ BARE = dict(bias=False, relu=False, res=False, clip=False)
 NORES = dict(bias=True, relu=True, res=False, clip=False)
 FULL = dict(bias=True, relu=True, res=True, clip=False)
 FULLCLIP = dict(bias=True, relu=True, res=True, clip=True)
+NORESCLIP = dict(bias=True, relu=True, res=False, clip=True)
 
 
 def _row(rid, fam, kernel, geo, impl, switches, mode, epi, off, group='base', oco=8):
@@ -337,6 +394,34 @@ def _base_rows():
     rows.append(_row('cout1-k3s1', 'cout1', 'conv_cout1_kernel<32,3,1,4,8,8>', (N_BASE, 5, 10, 8, 32, 1, 3, 1, 1), 'AUTO', {}, 'fp32', FULL, True,
                      oco=3))
     rows.append(_row('cout1-k9s2', 'cout1', 'conv_cout1_kernel<32,9,2,2,8,8>', (N_BASE, 5, 10, 8, 32, 1, 9, 2, 1), 'AUTO', {}, 'fp32', BARE, False))
+    # ---- pcc_conv_cout1_mfma with fp16 input, T = 16: the same two shapes; the layer takes no fp16 residual (it reads `residual` as fp32)
+    rows.append(_row('cout1m-t16-w24-in16', 'cout1_mfma', 'conv_cout1_mfma_kernel<true,16,false>', (N_BASE, 5, 10, 24, 16, 1, 3, 1, 1), 'AUTO', {},
+                     'in16-out32', BARE, False))
+    rows.append(_row('cout1m-t16-w5-in16', 'cout1_mfma', 'conv_cout1_mfma_kernel<true,16,false>', (N_BASE, 4, 6, 5, 16, 1, 3, 1, 1), 'AUTO', {},
+                     'in16-out32', NORESCLIP, True, oco=3))
+    # ---- pcc_conv_f16: H and W are multiples of 16 and the tiles (16 x 16 at C = 16, 8 x 16 at C = 32 / 64) divide them, so the edges
+    # are in z: SAME padding and the slab seams.  Every instantiation at D = 5 (odd: one slab) and at D = 16, where N = 2 leaves so few
+    # workgroups that the first loop of the launcher ends at its smallest slab of 4 planes; two tiles in x (C = 16) or y (C = 32 / 64).
+    # No channel offset: pcc_f16_eligible refuses one.
+    i = 0
+    for C in (16, 32, 64):
+        for out32 in (False, True):
+            for D, zsplit in ((5, 1), (16, 4)):
+                epi = (BARE, NORES, FULL)[i % 3]
+                tr = i % 4 in (1, 2)
+                name = 'conv_f16_kernel<%d,%s,%s>' % (min(C, 32), 'true' if out32 else 'false', 'true' if C == 64 else 'false')
+                geo = (N_BASE, D, 16, 32 if C == 16 else 16, C, C, 3, 1, int(tr))
+                r = _row(f'f16-{C}-{"out32" if out32 else "out16"}{"T" if tr else ""}-d{D}', 'conv_f16', name, geo, 'AUTO', {},
+                         'in16-out32' if out32 else 'in16-out16', epi, False)
+                r['zsplit'] = zsplit
+                rows.append(r)
+                i += 1
+    # ---- pcc_conv_tr2m_f16: the four grids of the pcc_conv_tr2m rows above, fp16 hand-over; bias / ReLU epilogues only
+    for j, (geo, relu) in enumerate((((1, 1, 16, 16, 32, 16, 3, 2, 1), True), ((2, 5, 16, 32, 64, 32, 3, 2, 1), False),
+                                     ((1, 9, 32, 16, 64, 32, 3, 2, 1), True), ((2, 32, 16, 16, 32, 16, 3, 2, 1), False))):
+        name = 'conv_tr2m_f16_kernel<%d,%s>' % (geo[4] // 32, 'true' if relu else 'false')
+        rows.append(_row(f'tr2mf16-{geo[4]}-{geo[5]}-d{geo[1]}', 'tr2m_f16', name, geo, 'AUTO', {}, 'out16',
+                         dict(bias=j != 3, relu=relu, res=False, clip=False), j % 2 == 1))
     # ---- the generic kernels: the odd shapes of GENERIC_CASES (tests/test_conv_gpu.py)
     rows.append(_row('generic-fwd', 'generic', 'conv_fwd_generic', (N_BASE, 7, 9, 6, 3, 5, 3, 2, 0), 'GENERIC', {}, 'fp32', FULLCLIP, True, oco=3))
     rows.append(_row('generic-tr', 'generic', 'conv_tr_generic', (N_BASE, 5, 4, 6, 4, 3, 3, 2, 1), 'GENERIC', {}, 'fp32', BARE, False))
@@ -359,7 +444,8 @@ def _window_n(per_image, slots):
 def windowed_rows(num_cu):
     """The rows whose kernel or loop depends on the voxel count against the CU count; N follows num_cu.  Groups: 'big' (the 2 x 8 x 16
     tile of 64 -> 64), 'pers' and 'tr2g' (persistent loops: more tiles than slots, no multiple of them, partial tiles in z and y),
-    'cout1' (32 x 32 columns, one and two z slabs, and the same layer under cout1_t16)."""
+    'cout1' (32 x 32 columns with one, two, four and eight z slabs, each with fp32 and with fp16 input, and the one-slab layer under
+    cout1_t16; every row carries the slab count it means as 'zsp')."""
     rows = []
     def big(n):        # conv_fwd.hip:486-494
         row = dict(geo=(n, 15, 20, 32, 64, 64, 3, 1, 0), impl='MFMA')
@@ -390,6 +476,18 @@ def windowed_rows(num_cu):
                               ('cout1m-t32-zsp2', (num_cu // 2, 33, 32, 32, 16, 1, 3, 1, 1), {}, 'conv_cout1_mfma_kernel<false,32,false>'),
                               ('cout1m-t16-forced', (num_cu, 3, 32, 32, 16, 1, 3, 1, 1), {'cout1_t16': True}, 'conv_cout1_mfma_kernel<false,16,false>')):
         rows.append(_row(rid, 'cout1_mfma', name, g, 'AUTO', sws, 'fp32', FULL, False, 'cout1'))
+    # four and eight slabs of 16 planes (the 64^3 and 128^3 batches of the benchmark): every seam has 16 planes on either side.  The
+    # launcher splits only while a slab keeps 16 planes and only until every CU has a workgroup, so N x D cannot be smaller than
+    # 16 planes per CU: these rows have the voxel count of cout1m-t32-zsp2.  Then every slab count again with fp16 input (no residual).
+    for zsp, D in ((4, 64), (8, 128)):
+        rows.append(_row(f'cout1m-t32-zsp{zsp}', 'cout1_mfma', 'conv_cout1_mfma_kernel<false,32,false>', (num_cu // zsp, D, 32, 32, 16, 1, 3, 1, 1),
+                         'AUTO', {}, 'fp32', FULL, False, 'cout1'))
+    for r in [r for r in rows if r['group'] == 'cout1' and not r['switches']]:
+        rows.append(_row(r['id'] + '-in16', 'cout1_mfma', 'conv_cout1_mfma_kernel<true,32,false>', r['geo'], 'AUTO', {}, 'in16-out32', NORES, False,
+                         'cout1'))
+    for r in rows:
+        if r['group'] == 'cout1':
+            r['zsp'] = 1 if r['switches'] else int(r['id'].split('zsp')[1].split('-')[0])
     return rows
 
 
@@ -478,6 +576,29 @@ def magnitude_bound(row):
     if row['set'] == 'A':
         return (k ** 3 * cin * 3 * 2 + 2 + 3) * 64
     return k ** 3 * cin + 1 + 2
+
+
+def is_sub(row):
+    """The 64-channel layer of conv_f16.hip: two launches of conv_f16_kernel<32,.,true> with raw fp16 partial sums in between."""
+    return row['kernel'].startswith('conv_f16_kernel') and row['kernel'].endswith(',true>')
+
+
+def partial_bound(row):
+    """An upper bound of |raw partial sum| that the launch of input half 0 of a SUB row leaves in fp16: taps x 32 channels x max |x| x
+    max |w|; no bias, no residual (conv_f16.hip:150-159: `raw`)."""
+    assert is_sub(row) and row['set'] == 'B'
+    return row['geo'][6] ** 3 * 32
+
+
+def partial_reference(row, absolute=False):
+    """float64: the partial sums of input channels 0 .. 31 of a SUB row (a.ico = 0, the cig = 0 images of pcc_f16_pack), bare."""
+    from oracle import oracle as O
+    assert is_sub(row)
+    x, w, _, _, _ = _arrays(row['geo'], row['set'])
+    f = np.abs if absolute else (lambda a: a)
+    x0 = np.ascontiguousarray(f(x[..., :32]))
+    w0 = np.ascontiguousarray(f(w[..., :32] if row['geo'][8] else w[:, :, :, :32, :]))
+    return np.asarray((O.conv3d_transpose if row['geo'][8] else O.conv3d)(x0, w0, None, row['geo'][7], False), np.float64)
 
 
 def explain(row, got, want, tile, limit=5):

@@ -28,9 +28,17 @@ def test_inputs_keep_the_row_exact(oracle, row):
     mag = DC.reference(row, absolute=True) * np.exp2(-np.minimum(DC.exponents(row), 0))        # per output channel, in its unit
     assert mag.max() < 2 ** 24, (row['id'], mag.max())
     assert mag.max() <= DC.magnitude_bound(row)                   # the closed form the windowed rows are held to
-    if row['mode'] == 'out16':
+    if row['mode'] in ('out16', 'in16-out16'):
         ref = DC.reference(row)
         assert np.abs(ref).max() <= 2048 and np.array_equal(ref, np.round(ref)), row['id']
+    if row['kernel'].startswith(('conv_f16_kernel', 'conv_tr2m_f16_kernel', 'conv_cout1_mfma_kernel<true')):
+        assert row['set'] == 'B' and DC.magnitude_bound(row) <= 27 * 64 + 1 + 2 < 2048
+    if DC.is_sub(row):
+        # the raw fp16 partial sums of input half 0, which the second launch reads back: integers that fp16 holds
+        part, mag = DC.partial_reference(row), DC.partial_reference(row, absolute=True)
+        assert mag.max() <= DC.partial_bound(row) == 864 < 2048 and np.abs(part).max() <= mag.max(), row['id']
+        assert np.array_equal(part, np.round(part)) and np.array_equal(part.astype(np.float16).astype(np.float64), part), row['id']
+        assert part.any(), row['id']
     x, w, b, r = DC.inputs(row)
     e = DC.exponents(row)
     for a in (x, r):
@@ -59,8 +67,13 @@ def test_every_instantiation_has_a_row():
         assert sel['kernel'] == row['kernel'], (row['id'], sel['kernel'], row['kernel'])
         assert row['kernel'] in DC.ALL_INSTANCES, row['id']
         chosen.setdefault(row['kernel'], []).append(row['id'])
-    missing = [n for n in DC.ALL_INSTANCES if n not in chosen]
+    missing = [n for n in DC.ALL_INSTANCES if n not in chosen and n not in DC.GRAPH_ONLY]
     assert not missing, missing
+    # the threshold-fusing instantiations have no row: the codec graph launches them (tests/_thr_ref.py names the cases)
+    assert len(DC.ALL_INSTANCES) == 151 and len(DC.GRAPH_ONLY) == 4 and not set(DC.GRAPH_ONLY) & set(chosen)
+    import _thr_ref as TR
+    graph = {TR.last_layer(c, p, DC.CPU_NUM_CU)['kernel'] for c in TR.cases(DC.CPU_NUM_CU) for p in ('fp32', 'fp16')}
+    assert set(DC.GRAPH_ONLY) <= graph, sorted(set(DC.GRAPH_ONLY) - graph)
     assert not set(DC.UNREACHABLE) & set(chosen)
     for name in ('tr2_old', 'p16', 'cout1_t16'):
         assert any(r['switches'].get(name) for r in ALL), name
@@ -82,13 +95,19 @@ def test_windowed_rows_at_256_cus():
     assert DC.select(by['cout1m-t32-zsp1'], DC.flags_of(by['cout1m-t32-zsp1']), {}, 256)['zsp'] == 1
     assert DC.select(by['cout1m-t32-zsp2'], DC.flags_of(by['cout1m-t32-zsp2']), {}, 256)['zsp'] == 2
     assert by['cout1m-t32-zsp2']['geo'][1] == 33                  # slabs of 17 and 16 planes
+    cout1 = [r for r in WINDOWED if r['group'] == 'cout1']
+    assert sorted((r['zsp'], r['mode']) for r in cout1 if not r['switches']) == [(z, m) for z in (1, 2, 4, 8) for m in ('fp32', 'in16-out32')]
+    for r in cout1:
+        assert DC.select(r, DC.flags_of(r), r['switches'], 256)['zsp'] == r['zsp'], r['id']
+        assert not (r['mode'] == 'in16-out32' and r['res']), 'the 16 -> 1 layer reads its residual as fp32'
+    assert by['cout1m-t32-zsp4']['geo'][:2] == (64, 64) and by['cout1m-t32-zsp8']['geo'][:2] == (32, 128)     # slabs of 16 planes
 
 
 def test_every_tiled_row_has_a_partial_tile():
     for row in ALL:
         tile = DC.select(row, DC.flags_of(row), row['switches'], DC.CPU_NUM_CU)['tile']
-        if tile is None or row['group'] == 'cout1' or row['kernel'].startswith('conv_tr2m_kernel'):
-            continue              # whole 16 x 16 / 32 x 32 columns marched along z: the shape rules admit no partial column
+        if tile is None or row['group'] == 'cout1' or row['kernel'].startswith(('conv_tr2m_kernel', 'conv_tr2m_f16_kernel', 'conv_f16_kernel')):
+            continue              # whole 16 x 16 / 8 x 16 / 32 x 32 columns marched along z: the shape rules admit no partial column
         ext = DC.base_dims(row['geo'])
         partial = [e % t != 0 for e, t in zip(ext, tile)]
         assert any(partial), (row['id'], ext, tile)
@@ -101,7 +120,8 @@ def test_every_tiled_row_has_a_partial_tile():
 def test_base_rows_alternate_direction_epilogue_and_offset():
     s1 = [r for r in DC.ROWS if r['kernel'].startswith(('conv_fwd_kernel', 'conv16_pers')) and r['geo'][7] == 1]
     assert {r['geo'][8] for r in s1} == {0, 1}
-    assert sum(1 for r in DC.ROWS if r['ocs']) >= len(DC.ROWS) // 2 - 4
+    takes_offset = [r for r in DC.ROWS if not r['kernel'].startswith('conv_f16_kernel')]      # pcc_f16_eligible refuses an offset
+    assert sum(1 for r in takes_offset if r['ocs']) >= len(takes_offset) // 2 - 4
     assert any(r.get('clip') for r in DC.ROWS) and any(not r['bias'] for r in DC.ROWS) and any(r['res'] for r in DC.ROWS)
     for r in DC.ROWS:
         if r['ocs']:
@@ -114,6 +134,37 @@ def test_the_plan_covers_the_row(row):
     d = L.ConvDesc(N, D, H, W, cin, cout, k, s, tr, DC.FC._flags(row, L), getattr(L, 'PCC_IMPL_' + row['impl']), row['ocs'], row['oco'])
     want = 0 if row['id'] == 'generic-tr' or row['id'] == 'generic-fwd' else 1
     assert L.lib().pcc_conv_mfma_supported(C.byref(d)) == want
+
+
+def test_fp16_storage_rows_sit_on_their_edges_in_z():
+    """conv_f16_kernel: every instantiation with one slab (odd D) and with the smallest slab of the launcher's first loop (4 planes),
+    more than one tile in x or y, a residual on both output types, both orientations per channel count; conv_tr2m_f16_kernel: D = 1,
+    odd, and z-split, ReLU on and off, two channel-offset outputs."""
+    f16 = [r for r in DC.ROWS if r['kernel'].startswith('conv_f16_kernel')]
+    assert len(f16) == 12
+    for name in DC.INSTANCES['pcc_conv_f16']:
+        got = {}
+        for r in f16:
+            if r['kernel'] == name:
+                sel = DC.select(r, DC.flags_of(r), r['switches'], DC.CPU_NUM_CU)
+                assert sel['zsplit'] == r['zsplit'] and r['geo'][0] == 2, r['id']
+                assert (r['geo'][2] // sel['tile'][1]) * (r['geo'][3] // 16) > 1, r['id']
+                got[sel['zsplit']] = sel['zlen']
+        assert got == {1: 5, 4: 4}, (name, got)
+    for out in ('in16-out16', 'in16-out32'):
+        assert any(r['res'] for r in f16 if r['mode'] == out)
+        assert {e for r in f16 if r['mode'] == out for e in [(r['bias'], r['res'])]} == {(False, False), (True, False), (True, True)}
+    for C in (16, 32, 64):
+        assert {r['geo'][8] for r in f16 if r['geo'][4] == C} == {0, 1}
+    assert all(any(r['res'] for r in f16 if r['kernel'] == n) for n in DC.INSTANCES['pcc_conv_f16'][4:])      # both SUB instantiations
+    tm = [r for r in DC.ROWS if r['kernel'].startswith('conv_tr2m_f16_kernel')]
+    assert sorted(r['geo'][1] for r in tm) == [1, 5, 9, 32] and sum(1 for r in tm if r['ocs']) == 2
+    assert {r['kernel'] for r in tm} == set(DC.INSTANCES['pcc_conv_tr2m_f16'])
+    assert DC.select(tm[3], DC.flags_of(tm[3]), {}, DC.CPU_NUM_CU)['zsplit'] == 8
+    # the tiled rows of the same layers keep their kernels: no_tr2m holds the fp16 hand-over off the march (conv_route.hip:261)
+    for r in DC.ROWS:
+        if r['mode'] == 'out16' and r['geo'][7] == 2 and r['geo'][8] and r['switches'].get('no_tr2m'):
+            assert r['kernel'].startswith(('conv_tr2_kernel', 'conv_tr2g_kernel')), r['id']
 
 
 def _doc_switches():

@@ -1,7 +1,8 @@
-"""Every instantiation of the direct conv kernels (conv_fwd.hip, conv_tr2.hip, conv_edge.hip, conv_tr2m.hip, conv_generic.hip) and of
-their fp16-MFMA twins, launched through pcc_conv3d on integer operands (tests/_direct_cases.py) and compared with the float64
-reference by equality, per output: on these inputs every correct fp32 kernel returns the float64 value bit for bit, whatever its tile,
-summation order or MFMA chain.  No tolerance appears in this file."""
+"""Every instantiation of the direct conv kernels (conv_fwd.hip, conv_tr2.hip, conv_edge.hip, conv_tr2m.hip, conv_generic.hip), of
+their fp16-MFMA twins and of the fp16-storage kernels (conv_f16.hip, conv_tr2m_f16.hip, the fp16-input 16 -> 1 layer), launched through
+pcc_conv3d on integer operands (tests/_direct_cases.py) and compared with the float64 reference by equality, per output: on these
+inputs every correct kernel returns the float64 value bit for bit, whatever its tile, slab, summation order or MFMA chain, and
+whether it stores fp32 or fp16.  No tolerance appears in this file."""
 import numpy as np
 import pytest
 import torch
@@ -19,6 +20,8 @@ def _check(ctx, row, want=None):
     # 1. the launchers' choice on THIS machine's CU count still names the row's kernel (fail, never skip)
     sel = DC.select(row, DC.flags_of(row), row['switches'], ctx.num_cu)
     assert sel['kernel'] == row['kernel'], f'{row["id"]}: with {ctx.num_cu} CUs the launcher takes {sel["kernel"]}, the row means {row["kernel"]}'
+    for key in ('zsplit', 'zsp'):             # ... and the number of z slabs the row means
+        assert key not in row or sel[key] == row[key], f'{row["id"]}: with {ctx.num_cu} CUs the launcher takes {key} = {sel[key]}, the row means {row[key]}'
     arrays = DC.inputs(row)
     if want is None:
         want = DC.reference(row)
@@ -100,13 +103,38 @@ def test_tr2g_walks_more_tiles_than_slots(ctx, oracle, rid):
 
 
 def test_cout1_mfma_32_wide_columns_one_and_two_slabs(ctx, oracle):
-    """conv_cout1_mfma_kernel<false, 32, false> with one z slab and with slabs of 17 and 16 planes; the same layer under cout1_t16
-    (16 x 16 columns), which the numerics tag treats as the same bits."""
+    """conv_cout1_mfma_kernel<false, 32, false> with one z slab, with slabs of 17 and 16 planes, and with four and eight slabs of 16
+    planes (the seams of the 64^3 and 128^3 batches); the one-slab layer under cout1_t16 (16 x 16 columns), which the numerics tag
+    treats as the same bits."""
     rows = {r['id']: r for r in _windowed(ctx, 'cout1')}
-    for rid, zsp in (('cout1m-t32-zsp1', 1), ('cout1m-t32-zsp2', 2)):
-        assert DC.select(rows[rid], DC.flags_of(rows[rid]), {}, ctx.num_cu)['zsp'] == zsp
+    for rid, zsp in (('cout1m-t32-zsp1', 1), ('cout1m-t32-zsp2', 2), ('cout1m-t32-zsp4', 4), ('cout1m-t32-zsp8', 8)):
+        assert rows[rid]['zsp'] == zsp and DC.select(rows[rid], DC.flags_of(rows[rid]), {}, ctx.num_cu)['zsp'] == zsp
     _pin_torch_oracle(oracle, rows['cout1m-t32-zsp2'])
     a = _check(ctx, rows['cout1m-t32-zsp1'])
     b = _check(ctx, rows['cout1m-t16-forced'])
     assert np.array_equal(a, b)
     _check(ctx, rows['cout1m-t32-zsp2'])
+    _check(ctx, rows['cout1m-t32-zsp4'])
+    _check(ctx, rows['cout1m-t32-zsp8'])
+
+
+@pytest.mark.parametrize('zsp', [1, 2, 4, 8])
+def test_cout1_mfma_32_wide_columns_fp16_input(ctx, oracle, zsp):
+    """conv_cout1_mfma_kernel<true, 32, false>: the same four slab counts with an fp16 input tensor (one fp16 MFMA per tap tile)."""
+    (row,) = [r for r in _windowed(ctx, 'cout1') if r['id'] == f'cout1m-t32-zsp{zsp}-in16']
+    assert row['zsp'] == zsp and row['kernel'] == 'conv_cout1_mfma_kernel<true,32,false>'
+    if zsp == 2:
+        _pin_torch_oracle(oracle, row)
+    _check(ctx, row)
+
+
+def test_cout1_mfma_with_fp16_input_refuses_a_residual(ctx):
+    """The 16 -> 1 kernel reads its residual as fp32.  pcc_conv3d accepts an fp16-input layer only with an fp16 residual
+    (PCC_CONV_RES16), so the launcher refuses the combination before anything is launched instead of reading a half-sized tensor as
+    fp32."""
+    row = dict(DC.BY_ID['cout1m-t16-w24-in16'], res=True)
+    out = torch.zeros(1, device=ctx.device)
+    with pytest.raises((AssertionError, L.PccError), match='takes no residual'):
+        FC.run(ctx, row, DC.inputs(row))
+    torch.cuda.synchronize()
+    assert float(out.item()) == 0.0
