@@ -357,8 +357,14 @@ int pcc_rate_ladder(pcc_ctx* ctx, const float* y, const float* sigma, int32_t N,
  * src/model_opt.py:12,29).  x: B blocks of D*H*W float32; thr[b] is the float32 threshold of
  * block b (device array); clip!=0 applies np.clip(x,0,1) first (encoder, model_types.py:202).
  * xyz: B * cap * 3 float32, block b's points at xyz + b*cap*3 in C order (x slowest, z fastest),
- * counts[b] = number of points of block b (may exceed cap: then only the first cap are written).
- * `scratch` must hold B * ceil(D*H*W/4096) int32.  Bit-exact with the numpy expression.         */
+ * counts[b] = number of points of block b (may exceed cap: then only the first cap are written;
+ * rows from min(counts[b], cap) on are left untouched).  thr[b] may be any float: a negative one
+ * or -inf takes voxels at or below 0, +inf and NaN take none.  A NaN voxel is never a point,
+ * clipped or not (np.clip keeps NaN, and NaN > thr is false).  x needs float alignment only; the
+ * 16-byte loads are used when D*H*W % 4 == 0 and x is 16-byte aligned.  B <= 65535.
+ * `scratch` must hold pcc_threshold_scratch_ints(B, D, H, W) int32 (the fused occupancy-bit path
+ * of the codec graphs shares it, so this is more than the B * ceil(D*H*W/4096) chunk counts).
+ * Bit-exact with the numpy expression.                                                          */
 int pcc_threshold_compact(pcc_ctx* ctx, const float* x, int32_t B, int32_t D, int32_t H,
                           int32_t W, const float* thr, int32_t clip, float* xyz, int32_t* counts,
                           int64_t cap, int32_t* scratch, void* stream);

@@ -51,6 +51,8 @@ def lib():
             fn.argtypes = [f32p, f32p, f32p, f32p] + [C.c_int] * 9
         L.pcc_oracle_focal_loss.restype = C.c_double
         L.pcc_oracle_focal_loss.argtypes = [f32p, f32p, C.c_size_t, C.c_float, C.c_float]
+        L.pcc_oracle_focal_terms.restype = None
+        L.pcc_oracle_focal_terms.argtypes = [f32p, f32p, C.c_size_t, C.c_float, C.c_float, f32p, f32p]
         L.pcc_oracle_threshold_argwhere.restype = C.c_long
         L.pcc_oracle_threshold_argwhere.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_float, f32p, C.c_long]
         L.pcc_oracle_clip01.restype = None
@@ -121,6 +123,16 @@ def focal_loss(y_true, y_pred, gamma=2.0, alpha=0.9):
     yp, ypp = _f(y_pred)
     assert yt.size == yp.size
     return lib().pcc_oracle_focal_loss(ytp, ypp, yt.size, gamma, alpha)
+
+
+def focal_terms(y_true, y_pred, gamma=2.0, alpha=0.9):
+    """(term1, term0) float32 per element: the terms focal_loss sums, focal_loss = -sum(term1) - sum(term0)"""
+    yt, ytp = _f(y_true)
+    yp, ypp = _f(y_pred)
+    assert yt.size == yp.size
+    t1, t0 = np.empty(yt.size, np.float32), np.empty(yt.size, np.float32)
+    lib().pcc_oracle_focal_terms(ytp, ypp, yt.size, gamma, alpha, t1.ctypes.data_as(f32p), t0.ctypes.data_as(f32p))
+    return t1, t0
 
 
 def threshold_argwhere(x_hat, thr):

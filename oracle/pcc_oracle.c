@@ -160,6 +160,20 @@ PCC_API double pcc_oracle_focal_loss(const float* y_true, const float* y_pred, s
     return -s1 - s0;
 }
 
+/* The float terms pcc_oracle_focal_loss sums, one pair per element: the loss is -sum(term1) - sum(term0).  Tests measure the
+ * float32 error of a single term with it. */
+PCC_API void pcc_oracle_focal_terms(const float* y_true, const float* y_pred, size_t n, float gamma, float alpha,
+                                    float* term1, float* term0) {
+    for (size_t i = 0; i < n; ++i) {
+        float pt1 = (y_true[i] == 1.f) ? y_pred[i] : 1.f;
+        float pt0 = (y_true[i] == 0.f) ? y_pred[i] : 0.f;
+        pt1 = fminf(fmaxf(pt1, 1e-3f), .999f);
+        pt0 = fminf(fmaxf(pt0, 1e-3f), .999f);
+        term1[i] = alpha * powf(1.f - pt1, gamma) * logf(pt1);
+        term0[i] = (1.f - alpha) * powf(pt0, gamma) * logf(1.f - pt0);
+    }
+}
+
 /* x_hat > threshold then np.argwhere: C-order (x slowest, z fastest) index list as float32 triples.
  * src/model_types.py:209,233-234; src/model_opt.py:12,29.  The comparison is done in float32 with
  * the threshold rounded to float32 (numpy 1.18 value-based casting).

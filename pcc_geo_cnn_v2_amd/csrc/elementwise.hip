@@ -345,19 +345,32 @@ __device__ __forceinline__ int block_excl_scan(int v, int* total, int* lds4) {
 // ---- threshold + compaction ----------------------------------------------------------------
 constexpr int kChunk = 4096;  // voxels per workgroup (4 passes of 256 threads x 4 voxels)
 
-__device__ __forceinline__ void load4(const float* __restrict__ xb, size_t idx, size_t nvox, bool vec, float (&v)[4]) {
+// the float4 path needs D*H*W % 4 == 0 (every block starts on a multiple of 4 floats) and a 16-byte aligned x
+__device__ __forceinline__ bool vec_ok(const float* x, size_t nvox) {
+    return (nvox % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+}
+
+// returns the mask of the voxels idx + e that exist (bit e): the tail of the last chunk is told apart by index, never by a padding
+// value (-inf is clipped to 0 and passes a negative threshold)
+__device__ __forceinline__ unsigned load4(const float* __restrict__ xb, size_t idx, size_t nvox, bool vec, float (&v)[4]) {
     if (vec && idx + 3 < nvox) {
         const float4 t = *reinterpret_cast<const float4*>(xb + idx);
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (idx + e < nvox) ? xb[idx + e] : -INFINITY;
+        return 15u;
     }
+    unsigned in = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool ok = idx + e < nvox;
+        v[e] = ok ? xb[idx + e] : 0.f;
+        in |= (ok ? 1u : 0u) << e;
+    }
+    return in;
 }
 
-__device__ __forceinline__ bool hit(float v, float thr, int clip) {
-    if (clip) v = fminf(fmaxf(v, 0.f), 1.f);
-    return v > thr;  // float32 compare (numpy 1.18 value-based casting of the float64 threshold)
+__device__ __forceinline__ bool hit(float v, float thr, int clip, unsigned in) {
+    if (clip) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);  // np.clip: NaN stays NaN (fmaxf(NaN, 0) is 0)
+    return (in & 1u) && v > thr;  // float32 compare (numpy 1.18 value-based casting of the float64 threshold)
 }
 
 __global__ void __launch_bounds__(kThreads) k_thr_count(const float* __restrict__ x, const float* __restrict__ thr,
@@ -365,16 +378,16 @@ __global__ void __launch_bounds__(kThreads) k_thr_count(const float* __restrict_
     __shared__ int lds4[4];
     const int b = blockIdx.y, c = blockIdx.x;
     const float* xb = x + (size_t)b * nvox;
-    const bool vec = (nvox % 4) == 0;
+    const bool vec = vec_ok(x, nvox);
     const float t = thr[b];
     int cnt = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const size_t idx = (size_t)c * kChunk + ((size_t)j * kThreads + threadIdx.x) * 4;
         float v[4];
-        load4(xb, idx, nvox, vec, v);
+        const unsigned in = load4(xb, idx, nvox, vec, v);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) cnt += hit(v[e], t, clip) ? 1 : 0;
+        for (int e = 0; e < 4; ++e) cnt += hit(v[e], t, clip, in >> e) ? 1 : 0;
     }
     int total;
     block_excl_scan(cnt, &total, lds4);
@@ -388,7 +401,7 @@ __global__ void __launch_bounds__(kThreads) k_thr_write(const float* __restrict_
     __shared__ int lds4[4];
     const int b = blockIdx.y, c = blockIdx.x;
     const float* xb = x + (size_t)b * nvox;
-    const bool vec = (nvox % 4) == 0;
+    const bool vec = vec_ok(x, nvox);
     const float t = thr[b];
     // offset of this chunk = sum of the counts of the preceding chunks of the same block
     int part = 0;
@@ -401,11 +414,11 @@ __global__ void __launch_bounds__(kThreads) k_thr_write(const float* __restrict_
     for (int j = 0; j < 4; ++j) {
         const size_t idx = (size_t)c * kChunk + ((size_t)j * kThreads + threadIdx.x) * 4;
         float v[4];
-        load4(xb, idx, nvox, vec, v);
+        const unsigned in = load4(xb, idx, nvox, vec, v);
         bool h[4];
         int cnt = 0;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { h[e] = hit(v[e], t, clip); cnt += h[e] ? 1 : 0; }
+        for (int e = 0; e < 4; ++e) { h[e] = hit(v[e], t, clip, in >> e); cnt += h[e] ? 1 : 0; }
         int total;
         int pos = offset + block_excl_scan(cnt, &total, lds4);
 #pragma unroll

@@ -413,9 +413,12 @@ def topk_compact(ctx, x, k, cap=None):
 
 def voxelize(ctx, pts, block_of, B, D, H, W):
     """pts (n,3) int32, block_of (n,) int32 (device) -> dense (B,D,H,W) float32 of {0,1}."""
+    assert pts.dtype == torch.int32 and pts.dim() == 2 and pts.shape[1] == 3, 'voxelize: pts is an (n, 3) int32 tensor'
+    assert pts.is_contiguous() and pts.device == ctx.device, 'voxelize: pts is contiguous and on the context\'s device'
+    assert block_of.dtype == torch.int32 and tuple(block_of.shape) == (pts.shape[0],), 'voxelize: block_of is an (n,) int32 tensor'
+    assert block_of.is_contiguous() and block_of.device == ctx.device, 'voxelize: block_of is contiguous and on the context\'s device'
     dense = torch.zeros((B, D, H, W), dtype=torch.float32, device=ctx.device)
     if pts.numel():
-        assert pts.dtype == torch.int32 and pts.is_contiguous() and block_of.dtype == torch.int32
         L.check(L.lib().pcc_voxelize(ctx.handle, _ptr(pts), _ptr(block_of), pts.shape[0], B, D, H, W, _ptr(dense),
                                      ctx.stream), 'pcc_voxelize')
     return dense
