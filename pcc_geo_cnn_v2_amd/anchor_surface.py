@@ -235,18 +235,21 @@ def vertices(points, resolution, node_log2, device='gpu', ctx=None):
     return _model(p, k, device, ctx)[1:]
 
 
-def surface_points(leaf_keys, edge_keys, flags, t, resolution, node_log2, device='gpu', ctx=None):
-    """What the decoder does behind its coder: leaves, edge list and vertices -> the decoded cloud."""
+def surface_points(leaf_keys, edge_keys, flags, t, resolution, node_log2, device='gpu', ctx=None, return_counts=False):
+    """What the decoder does behind its coder: leaves, edge list and vertices -> the decoded cloud.  return_counts (device='gpu'):
+    -> (cloud, pos, total) of ops.surface_reconstruct, the count pass's numbers per leaf."""
     import torch
     from . import ops
     check_device(device)
     resolution, k = check_resolution(resolution), check_node_log2(node_log2)
     leaf_keys, edge_keys = np.ascontiguousarray(leaf_keys, np.uint64), np.ascontiguousarray(edge_keys, np.uint64)
     if device == 'host':
+        if return_counts:
+            raise ValueError('anchor_surface: the host path has no count pass')
         return reconstruct_host(leaf_keys, edge_keys, np.asarray(flags), np.asarray(t), k, resolution)
     ctx = _ctx(ctx)
     dev = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(a.view(np.int64)).to(ctx.device)
-    return ops.surface_reconstruct(ctx, dev(leaf_keys), dev(edge_keys), flags, t, k, resolution)
+    return ops.surface_reconstruct(ctx, dev(leaf_keys), dev(edge_keys), flags, t, k, resolution, return_counts=return_counts)
 
 
 def encode(points, resolution, node_log2, device='gpu', ctx=None):

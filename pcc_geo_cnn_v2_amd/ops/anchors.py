@@ -218,8 +218,10 @@ def surface_vertices(ctx, pkeys, k, edge_keys):
     return out[0], out[1]
 
 
-def surface_reconstruct(ctx, leaf_keys, edge_keys, flags, t, k, resolution):
-    """Leaves, edge list (device int64) and the vertices (numpy uint8 per edge) -> the decoded (n,3) int32 cloud (numpy), in Morton order."""
+def surface_reconstruct(ctx, leaf_keys, edge_keys, flags, t, k, resolution, return_counts=False):
+    """Leaves, edge list (device int64) and the vertices (numpy uint8 per edge) -> the decoded (n,3) int32 cloud (numpy), in Morton order.
+    return_counts: -> (cloud, pos, total) with the count pass's pos (numpy int64: the first voxel of each leaf, before the clip and the
+    final unique) and its total."""
     dev = ctx.device
     nleaves, nedges = int(leaf_keys.shape[0]), int(edge_keys.shape[0])
     flags, t = _u8(flags), _u8(t)
@@ -239,7 +241,8 @@ def surface_reconstruct(ctx, leaf_keys, edge_keys, flags, t, k, resolution):
     n = int(hdr.cpu()[0])
     if not 1 <= n <= total:
         raise L.PccError(f'surface_reconstruct: {n} distinct voxels of {total}')
-    return pts[:n].cpu().numpy()
+    out = pts[:n].cpu().numpy()
+    return (out, pos.cpu().numpy(), total) if return_counts else out
 
 
 # ---------------------------------------------------------------------------------------------

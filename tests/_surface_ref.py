@@ -20,7 +20,7 @@ from _normals_ref import shell
 
 def morton(c):
     k = 0
-    for b in range(21):
+    for b in range(int(max(c[0], c[1], c[2])).bit_length()):                  # at most 21; the bits above are 0
         k |= ((c[0] >> b) & 1) << (3 * b + 2) | ((c[1] >> b) & 1) << (3 * b + 1) | ((c[2] >> b) & 1) << (3 * b)
     return k
 
@@ -33,22 +33,35 @@ def cross(ax, ay, bx, by):
     return ax * by - ay * bx
 
 
+def leaf_edges(b):
+    """The 12 edges (key, corner, axis) of leaf b, edge e = 4 a + 2 du + dv at place e."""
+    out = []
+    for a in range(3):
+        u, v = others(a)
+        for du in (0, 1):
+            for dv in (0, 1):
+                c = list(b)
+                c[u] += du
+                c[v] += dv
+                out.append((morton(c) << 2 | a, tuple(c), a))
+    return out
+
+
+def edge_list(leaves):
+    """-> [(key, corner, axis)] of the distinct edges of all leaves, ascending by key: the coded order."""
+    edge_set = {}
+    for b in leaves:
+        for key, c, a in leaf_edges(b):
+            edge_set[key] = (c, a)
+    return [(key,) + edge_set[key] for key in sorted(edge_set)]
+
+
 def model(points, k):
     """-> (distinct points, leaves [b], edges [(key, corner, axis)], flags, ts), leaves and edges in their coded order."""
     W = 1 << k
     cloud = set(tuple(int(v) for v in p) for p in points)
     leaves = sorted(set((x >> k, y >> k, z >> k) for x, y, z in cloud), key=morton)
-    edge_set = {}
-    for b in leaves:
-        for a in range(3):
-            u, v = others(a)
-            for du in (0, 1):
-                for dv in (0, 1):
-                    c = list(b)
-                    c[u] += du
-                    c[v] += dv
-                    edge_set[morton(c) << 2 | a] = (tuple(c), a)
-    edges = [(key,) + edge_set[key] for key in sorted(edge_set)]
+    edges = edge_list(leaves)
     flags, ts = [], []
     for key, c, a in edges:
         u, v = others(a)
@@ -75,7 +88,17 @@ def half(x, y):
 
 
 def leaf_voxels(rs, W):
-    """Vertices relative to the origin, in edge-key order -> the set of voxels of the leaf, relative to its origin."""
+    """Vertices relative to the origin, in edge-key order -> the set of voxels of the leaf, relative to its origin.  A pure function
+    of its arguments: the last few hundred results are kept, for the leaves that several cases of one block share."""
+    return _kept_leaf_voxels(tuple(tuple(r) for r in rs), W)
+
+
+@functools.lru_cache(maxsize=256)
+def _kept_leaf_voxels(rs, W):
+    return frozenset(_leaf_voxels(rs, W))
+
+
+def _leaf_voxels(rs, W):
     m = len(rs)
     if m == 0:
         return {(W // 2, W // 2, W // 2)}
@@ -136,18 +159,12 @@ def reconstruction(leaves, edges, flags, ts, k, resolution, per_leaf=False):
     cloud, leafwise = set(), []
     for b in leaves:
         mine = []
-        for a in range(3):
-            u, v = others(a)
-            for du in (0, 1):
-                for dv in (0, 1):
-                    c = list(b)
-                    c[u] += du
-                    c[v] += dv
-                    n = where[morton(c) << 2 | a]
-                    if flags[n]:
-                        r = [W * (c[x] - b[x]) for x in range(3)]
-                        r[a] += ts[n]
-                        mine.append((n, r))
+        for key, c, a in leaf_edges(b):
+            n = where[key]
+            if flags[n]:
+                r = [W * (c[x] - b[x]) for x in range(3)]
+                r[a] += ts[n]
+                mine.append((n, r))
         rel = leaf_voxels([r for _, r in sorted(mine)], W)
         leafwise.append(rel)
         for vox in rel:
@@ -171,10 +188,8 @@ def payload(edges, flags, ts, k):
     return e.finish()
 
 
-@functools.lru_cache(maxsize=None)
-def coded(name, k):
-    """-> dict(stream, decoded, leaf_keys, edge_keys, flags, t, leaves, leafwise) of a small cloud: computed once, shared, read only."""
-    points, resolution = small_clouds()[name]
+def coded_points(points, resolution, k):
+    """-> dict(stream, decoded, leaf_keys, edge_keys, flags, t, leaves, edges, leafwise) of a cloud, by the restatement alone."""
     W = 1 << k
     ndistinct, leaves, edges, flags, ts = model(points, k)
     blocks = np.array(leaves, np.int64)
@@ -182,9 +197,16 @@ def coded(name, k):
     head = struct.pack('<4sBIBIIIII', b'PCSA', 1, resolution, k, len(leaves), len(edges), sum(flags), ndistinct, len(octree))
     decoded, leafwise = reconstruction(leaves, edges, flags, ts, k, resolution, per_leaf=True)
     decoded.setflags(write=False)
-    return dict(stream=head + octree + payload(edges, flags, ts, k), decoded=decoded, leaves=leaves, leafwise=leafwise,
+    return dict(stream=head + octree + payload(edges, flags, ts, k), decoded=decoded, leaves=leaves, edges=edges, leafwise=leafwise,
                 leaf_keys=np.array([morton(b) for b in leaves], np.uint64), edge_keys=np.array([e[0] for e in edges], np.uint64),
                 flags=np.array(flags, np.uint8), t=np.array(ts, np.uint8))
+
+
+@functools.lru_cache(maxsize=None)
+def coded(name, k):
+    """coded_points of a small cloud: computed once, shared, read only."""
+    points, resolution = small_clouds()[name]
+    return coded_points(points, resolution, k)
 
 
 @functools.lru_cache(maxsize=None)

@@ -58,12 +58,15 @@ def test_codec_equal_on_both_devices_and_to_the_restatement(ctx, name):
 
 @pytest.mark.parametrize('k', [5, 6])
 def test_the_large_blocks_equal_the_host_path(ctx, k):
-    """k = 5 and 6 take the four-wave kernel with the largest voxel maps; the host path stands in for the restatement."""
+    """k = 5 and 6 take the four-wave kernel with the largest voxel maps: against the host path and against the restatement."""
     for name in ('shell128', 'res100'):
         points, resolution = R.small_clouds()[name]
         gpu = S.encode(points, resolution, k, device='gpu', ctx=ctx)
         assert gpu == S.encode(points, resolution, k, device='host')
-        assert np.array_equal(S.decode(gpu, device='gpu', ctx=ctx), S.reconstruct(points, resolution, k))
+        dec = S.decode(gpu, device='gpu', ctx=ctx)
+        assert np.array_equal(dec, S.reconstruct(points, resolution, k))
+        ref = R.coded(name, k)                                             # R.coded_points, once per (cloud, k)
+        assert gpu == ref['stream'] and dec.dtype == np.int32 and np.array_equal(dec, ref['decoded'])
 
 
 @pytest.mark.parametrize('k', [2, 4])
